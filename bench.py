@@ -15,8 +15,13 @@ inputs already resident in HBM.  Weights: seeded synthetic checkpoint with the r
 
 Prints ONE JSON line (rank 0) with the driver's contract fields plus
   roofline     the dominant phase by time, the decode step (HBM-bound): algorithmic bytes / step time, + PMC traffic per step
+and, with --full only (each takes GPU or CPU runs of its own beyond the timed steps):
   roofline_gemm  the dominant family by FLOPs (dense GEMMs of encoder + prefill, MFMA-bound), HIP events on the engine's stream
+  reference_semantics, pcie_inclusive, alt_modes, pipelined, north_star_b64, configs3  supplementary passes and workloads
   cpu_baseline the oracle (op-for-op CPU port of the reference: no KV cache) timed on a bounded sample (N = 1 only)
+
+--dump-outputs DIR writes what the last timed step returned (tokens.npy, lengths.npy; float32) for output-for-output comparisons
+of two builds: the weights and inputs are seeded, so the same arguments give the same inputs on every run.
 """
 from __future__ import annotations
 
@@ -92,6 +97,22 @@ def committed_pmc(fname: str, precision: str, key: str):
         return None, (f"profiles/{fname} was measured on other kernel sources (sha {pj.get('source_sha16')} != "
                       f"{kernel_source_sha16()}): not printed; regenerate with tools/collect_profiles.sh")
     return round(pj[key]), f"bytes (memory-side, PMC, profiles/{fname}, same kernel sources)"
+
+
+DUMP_TOKENS_MAX_BYTES = 32 << 20
+
+
+def dump_outputs(out_dir: str, tokens: np.ndarray, lengths: np.ndarray):
+    """The arrays a caller of the timed path receives -- token ids [rows, steps] (-1 past a row's end) and lengths [rows] --
+    as float32 .npy (ids < 2^24: exact).  Above 32 MB of tokens a fixed, seeded sample of rows is written instead, the same rows
+    on every run with the same arguments."""
+    os.makedirs(out_dir, exist_ok=True)
+    rows = np.arange(tokens.shape[0])
+    max_rows = max(1, DUMP_TOKENS_MAX_BYTES // (4 * max(1, tokens.shape[1])))
+    if rows.size > max_rows:
+        rows = np.sort(np.random.default_rng(0).choice(rows.size, max_rows, replace=False))
+    np.save(os.path.join(out_dir, "tokens.npy"), tokens[rows].astype(np.float32))
+    np.save(os.path.join(out_dir, "lengths.npy"), np.asarray(lengths)[rows].astype(np.float32))
 
 
 def decode_algorithmic_bytes(B: int, L: int, T0: int = 389) -> float:
@@ -345,6 +366,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=32, help="examples per GPU")
     ap.add_argument("--max-len", type=int, default=64)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's timed steps, also run the supplementary measurements (reference-semantics and "
+                         "PCIe-inclusive passes, the event-profiled pass behind roofline_gemm, the other numeric modes, pipelined "
+                         "contexts, batch 64, configs[3], the CPU baseline); the --no-* and --inflight options below select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (tokens.npy, lengths.npy; float32) to DIR")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--precision", choices=("f32", "fp8", "f32x3"), default="f32x3",
                     help="f32x3 (default: fp32-accurate GEMMs as exact 3-way bf16 splits on the bf16 MFMA pipe; passes the whole "
@@ -365,6 +392,8 @@ def main():
                     help="engine option (mellow_engine_set_option; repeatable): a non-default configuration is printed in the line's "
                          "`engine` object and the line says so -- the library itself reads no environment variable")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     try:
         engine_options = {kv.split("=", 1)[0]: int(kv.split("=", 1)[1], 0) for kv in args.option}
     except (IndexError, ValueError):
@@ -427,11 +456,12 @@ def main():
     n_crops = 1 if args.clip_seconds <= 10 else 7
 
     def step():
+        """one pass of the timed path -> (first_token_ms, token ids, lengths): what its caller receives (gathered under DP)"""
         toks, lens, steps, ftm = eng.generate(a1d, a2d, idsd, max_len=L, top_p=0.8, temperature=1.0, stop_id=0,
                                               ignore_stop=True)
         if use_dist:   # the path's single exchange: all-gather of the token ids over RCCL/xGMI
-            mdist.gather_tokens(toks, lens, world * B, L, device=comm_dev)
-        return ftm
+            toks, lens = mdist.gather_tokens(toks, lens, world * B, L, device=comm_dev)
+        return ftm, toks, lens
 
     _progress("engine ready; warm-up")
     for _ in range(args.warmup):
@@ -441,7 +471,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    ftms = [step() for _ in range(args.steps)]
+    results = [step() for _ in range(args.steps)]
     torch.cuda.synchronize()
     if use_dist:
         dist.barrier()
@@ -451,63 +481,56 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     phases = eng.last_phase_ms()
+    ftms = [r[0] for r in results]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, results[-1][1], results[-1][2])
 
-    # ---- reference-semantics mode (SURVEY 8d ii): the stop id is honoured, the loop ends when every row has produced it
-    #      (reference wrapper.py:247-249).  With the synthetic checkpoint no row emits id 0, so all max_len steps run plus the
-    #      host-side check every 8 steps; reported next to the fixed-length headline, never instead of it.
-    _progress("leg: ref_sem")
-    ref_sem = None
-    if rank == 0 and world == 1:
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        n_ref = max(1, min(3, args.steps))
-        steps_run = 0
-        for _ in range(n_ref):
-            _, _, steps_run, _ = eng.generate(a1d, a2d, idsd, max_len=L, top_p=0.8, temperature=1.0, stop_id=0, ignore_stop=False)
-        torch.cuda.synchronize()
-        ref_sem = {"value": round(n_ref * B / (time.perf_counter() - t1), 2), "unit": "responses/s", "passes": n_ref,
-                   "steps_run": int(steps_run), "steps_enqueued": eng.last_steps_enqueued(), "note": "stop id honoured (reference loop exit rule); synthetic weights never emit it"}
+    ref_sem = pcie = rep = None
+    if args.full:
+        # ---- reference-semantics mode (SURVEY 8d ii): the stop id is honoured, the loop ends when every row has produced it
+        #      (reference wrapper.py:247-249).  With the synthetic checkpoint no row emits id 0, so all max_len steps run plus the
+        #      host-side check every 8 steps; reported next to the fixed-length headline, never instead of it.
+        _progress("leg: ref_sem")
+        if rank == 0 and world == 1:
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            n_ref = max(1, min(3, args.steps))
+            steps_run = 0
+            for _ in range(n_ref):
+                _, _, steps_run, _ = eng.generate(a1d, a2d, idsd, max_len=L, top_p=0.8, temperature=1.0, stop_id=0, ignore_stop=False)
+            torch.cuda.synchronize()
+            ref_sem = {"value": round(n_ref * B / (time.perf_counter() - t1), 2), "unit": "responses/s", "passes": n_ref,
+                       "steps_run": int(steps_run), "steps_enqueued": eng.last_steps_enqueued(), "note": "stop id honoured (reference loop exit rule); synthetic weights never emit it"}
 
-    # ---- PCIe-inclusive rate: the same pass with the waveforms and prompt ids starting in (pageable) host memory ----
-    _progress("leg: pcie")
-    pcie = None
-    if rank == 0 and world == 1:
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        n_p = max(1, min(3, args.steps))
-        ft_host = []
-        for _ in range(n_p):
-            eng.generate(a1, a2, ids, max_len=L, top_p=0.8, temperature=1.0, stop_id=0, ignore_stop=True)
-            ft_host.append(eng.last_first_token_host_ms)
-        torch.cuda.synchronize()
-        pcie = {"value": round(n_p * B / (time.perf_counter() - t1), 2), "unit": "responses/s", "passes": n_p,
-                "first_token_ms_p50": round(statistics.median(ft_host), 2),
-                "note": f"inputs start in pageable HOST memory: host->device copy of 2 x {B} x 1.28 MB waveforms + ids inside the "
-                        f"timed region (never the headline); first_token_ms_p50 here is SURVEY 8d's latency definition"}
+        # ---- PCIe-inclusive rate: the same pass with the waveforms and prompt ids starting in (pageable) host memory ----
+        _progress("leg: pcie")
+        if rank == 0 and world == 1:
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            n_p = max(1, min(3, args.steps))
+            ft_host = []
+            for _ in range(n_p):
+                eng.generate(a1, a2, ids, max_len=L, top_p=0.8, temperature=1.0, stop_id=0, ignore_stop=True)
+                ft_host.append(eng.last_first_token_host_ms)
+            torch.cuda.synchronize()
+            pcie = {"value": round(n_p * B / (time.perf_counter() - t1), 2), "unit": "responses/s", "passes": n_p,
+                    "first_token_ms_p50": round(statistics.median(ft_host), 2),
+                    "note": f"inputs start in pageable HOST memory: host->device copy of 2 x {B} x 1.28 MB waveforms + ids inside the "
+                            f"timed region (never the headline); first_token_ms_p50 here is SURVEY 8d's latency definition"}
 
-    # ---- roofline of the dominant kernel family, HIP events on the engine's stream over one more step ----
-    _progress("leg: eng.prof_enable(True)")
-    eng.prof_enable(True)
-    eng.prof_reset()
-    step()
-    rep = eng.prof_report()
-    eng.prof_enable(False)
+        # ---- roofline of the dominant kernel family, HIP events on the engine's stream over one more step ----
+        _progress("leg: eng.prof_enable(True)")
+        eng.prof_enable(True)
+        eng.prof_reset()
+        step()
+        rep = eng.prof_report()
+        eng.prof_enable(False)
 
     if rank == 0:
-        traffic, traffic_note = committed_pmc(PMC_TRAFFIC_FILE.replace(".json", "_fp8.json") if args.precision == "fp8" else PMC_TRAFFIC_FILE,
-                                              args.precision, "traffic_bytes_per_launch")
         dec_traffic, dec_traffic_note = committed_pmc(PMC_DECODE_FILE, args.precision, "traffic_bytes_per_step")
         total = n_gpus * B * args.steps
         value = total / elapsed
         ms_per_step = elapsed / args.steps * 1e3
-        g = rep["gemm_f32_mfma"]
-        # ALGORITHMIC flops: the STFT is priced as the FFT it could be (0.051 GF/clip), not as the dense DFT
-        # GEMM the kernel runs (2 x frames x 1024 x 1026 flops per clip); the dense figure is kept beside it
-        # (when the engine runs the STFT as an FFT -- f32x3 mode -- its own count already is the algorithmic one)
-        dense_dft = 0.0 if eng.stft_is_fft() else 2.0 * (2 * B) * 1001 * 1024 * 1026
-        flops_alg = g["flops"] - dense_dft + ((2 * B) * FFT_GFLOP_PER_CLIP * 1e9 if dense_dft else 0.0)
-        tf = flops_alg / (g["ms"] * 1e-3) / 1e12 if g["ms"] > 0 else 0.0
-        tf_dense = g["flops"] / (g["ms"] * 1e-3) / 1e12 if g["ms"] > 0 else 0.0
         dec_bytes = decode_algorithmic_bytes(B, L)
         if args.precision == "fp8":
             # the fp8 mode is priced on ITS OWN bytes (e4m3 weights 134.5 MB per step; K/V as the mode stores them):
@@ -546,30 +569,10 @@ def main():
             "prefill_parts": eng.prefill_parts(),      # measured by the engine: 2 = two half-batch chains on streams that overlap
             "first_token_ms_p50": round(statistics.median(ftms), 2),
             "phase_ms": {k: round(v, 2) for k, v in phases.items()},
-            "roofline_gemm": {"kernel": ("gemm_mx8_kernel (v_mfma_scale_f32_32x32x64_f8f6f4: the block-scaled K = 64 form, the pipe the 5 PF peak refers to; MXFP8 activations emitted by their producers, e4m3 weights per output channel) + the standalone quantiser where no producer emits AMX + the fp32 GEMMs left (front-end mel, lm_forward head)"
-                                    if fp8 else "gemm_x3q_kernel (LM prefill, Swin stages 2-3) + gemm_x3w_kernel (stage-0 qkv / fc1) + gemm_x3p_kernel (rest of the encoder): 6 x v_mfma_f32_32x32x16_bf16 per fp32 product; "
-                                    "mel on gemm_x3p_kernel too, the STFT as an FFT (stft_fft_power_kernel, counted in this family); peak = 2.5 PF dense bf16 / 6" if args.precision == "f32x3"
-                                    else "gemm_f32_kernel (v_mfma_f32_32x32x2_f32: encoder + LM prefill GEMMs)"),
-                         "bound": "mfma", "achieved": round(tf, 2), "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(tf / peak, 4), "traffic": traffic,
-                         "traffic_unit": traffic_note,
-                         "launches": g["launches"], "avg_launch_us": round(g["ms"] * 1e3 / max(1, g["launches"]), 2),
-                         "flops_per_step": flops_alg,
-                         "profiled_with_single_chain": True,
-                         "profiled_schedule_note": "the per-family HIP events need one launch at a time: this figure comes from one extra pass with the "
-                                                   "LM prefill as ONE chain (the timed passes of `value` run it as `prefill_parts` half-batch chains "
-                                                   "on overlapping streams, which shortens the prefill phase but not a kernel's own time)",
-                         "achieved_dense_dft": round(tf_dense, 2),
-                         "gemm_plus_norm_ms": round(g["ms"] + rep["norm"]["ms"], 3),
-                         "gemm_plus_norm_note": "family time + the normalisation launches beside it: since round 4 the LM prefill's RMSNorms live in "
-                                                "the GEMM epilogues (round 3: 19.6 + 2.37 ms), so this sum is the like-for-like figure across rounds",
-                         "note": "achieved = algorithmic flops (STFT priced as an FFT, SURVEY 8d) / family time measured live with "
-                                 "HIP events on the engine's stream; achieved_dense_dft counts the DFT GEMM's own flops"},
             "roofline": None,
             "path_roofline": {"t_roof_ms_per_step": round(t_roof * 1e3, 3),
                               "frac": round(t_roof * 1e3 / ms_per_step, 4),
                               "definition": "F_dense/P_mfma(dtype) + Bytes_decode/8TB/s per response x batch (SURVEY 8d)"},
-            "kernel_families_ms": {k: round(v["ms"], 3) for k, v in rep.items()},
         }
         # the dominant part of the pass by time is the decode phase (hipGraph replays of one step = one "launch" of 124 kernels):
         # HBM-bound, priced by the ALGORITHMIC bytes of SURVEY 8d; `traffic` = what the memory side actually moved per step (PMC)
@@ -587,25 +590,56 @@ def main():
                     "/ average step time, HIP events around the decode phase of the timed pass on the engine's stream",
         }
         out["roofline_decode"] = out["roofline"]                 # the name earlier rounds used
-        if ref_sem is not None:
-            out["reference_semantics"] = ref_sem
-        if pcie is not None:
-            out["pcie_inclusive"] = pcie
-        std = args.clip_seconds == 10        # the supplementary legs below are defined on the 10 s workload
-        if n_gpus == 1 and args.precision != "fp8" and not args.no_alt_modes and std:
-            _progress("leg: alt_modes")
-            out["alt_modes"] = alt_modes(B, L, args.precision)
-        if n_gpus == 1 and args.inflight > 1 and std:
-            out["pipelined"] = pipelined(args.inflight, B, L, max(args.steps, 2 * args.inflight), args.precision)
-        if n_gpus == 1 and args.precision != "fp8" and not args.no_b64 and B != 64 and std:
-            _progress("leg: north_star_b64")
-            out["north_star_b64"] = north_star_b64(L, args.precision)
-        if n_gpus == 1 and args.precision != "fp8" and not args.no_configs3 and args.preset != "configs3":
-            _progress("leg: configs3")
-            out["configs3"] = configs3_leg(args.precision)
-        if n_gpus == 1 and not args.no_cpu_baseline:
-            _progress("leg: cpu_baseline")
-            out["cpu_baseline"] = cpu_baseline(L)
+        if args.full:
+            traffic, traffic_note = committed_pmc(PMC_TRAFFIC_FILE.replace(".json", "_fp8.json") if fp8 else PMC_TRAFFIC_FILE,
+                                                  args.precision, "traffic_bytes_per_launch")
+            g = rep["gemm_f32_mfma"]
+            # ALGORITHMIC flops: the STFT is priced as the FFT it could be (0.051 GF/clip), not as the dense DFT
+            # GEMM the kernel runs (2 x frames x 1024 x 1026 flops per clip); the dense figure is kept beside it
+            # (when the engine runs the STFT as an FFT -- f32x3 mode -- its own count already is the algorithmic one)
+            dense_dft = 0.0 if eng.stft_is_fft() else 2.0 * (2 * B) * 1001 * 1024 * 1026
+            flops_alg = g["flops"] - dense_dft + ((2 * B) * FFT_GFLOP_PER_CLIP * 1e9 if dense_dft else 0.0)
+            tf = flops_alg / (g["ms"] * 1e-3) / 1e12 if g["ms"] > 0 else 0.0
+            tf_dense = g["flops"] / (g["ms"] * 1e-3) / 1e12 if g["ms"] > 0 else 0.0
+            out["roofline_gemm"] = {"kernel": ("gemm_mx8_kernel (v_mfma_scale_f32_32x32x64_f8f6f4: the block-scaled K = 64 form, the pipe the 5 PF peak refers to; MXFP8 activations emitted by their producers, e4m3 weights per output channel) + the standalone quantiser where no producer emits AMX + the fp32 GEMMs left (front-end mel, lm_forward head)"
+                                          if fp8 else "gemm_x3q_kernel (LM prefill, Swin stages 2-3) + gemm_x3w_kernel (stage-0 qkv / fc1) + gemm_x3p_kernel (rest of the encoder): 6 x v_mfma_f32_32x32x16_bf16 per fp32 product; "
+                                          "mel on gemm_x3p_kernel too, the STFT as an FFT (stft_fft_power_kernel, counted in this family); peak = 2.5 PF dense bf16 / 6" if args.precision == "f32x3"
+                                          else "gemm_f32_kernel (v_mfma_f32_32x32x2_f32: encoder + LM prefill GEMMs)"),
+                               "bound": "mfma", "achieved": round(tf, 2), "peak": peak, "unit": "TFLOP/s",
+                               "frac": round(tf / peak, 4), "traffic": traffic,
+                               "traffic_unit": traffic_note,
+                               "launches": g["launches"], "avg_launch_us": round(g["ms"] * 1e3 / max(1, g["launches"]), 2),
+                               "flops_per_step": flops_alg,
+                               "profiled_with_single_chain": True,
+                               "profiled_schedule_note": "the per-family HIP events need one launch at a time: this figure comes from one extra pass with the "
+                                                         "LM prefill as ONE chain (the timed passes of `value` run it as `prefill_parts` half-batch chains "
+                                                         "on overlapping streams, which shortens the prefill phase but not a kernel's own time)",
+                               "achieved_dense_dft": round(tf_dense, 2),
+                               "gemm_plus_norm_ms": round(g["ms"] + rep["norm"]["ms"], 3),
+                               "gemm_plus_norm_note": "family time + the normalisation launches beside it: since round 4 the LM prefill's RMSNorms live in "
+                                                      "the GEMM epilogues (round 3: 19.6 + 2.37 ms), so this sum is the like-for-like figure across rounds",
+                               "note": "achieved = algorithmic flops (STFT priced as an FFT, SURVEY 8d) / family time measured live with "
+                                       "HIP events on the engine's stream; achieved_dense_dft counts the DFT GEMM's own flops"}
+            out["kernel_families_ms"] = {k: round(v["ms"], 3) for k, v in rep.items()}
+            if ref_sem is not None:
+                out["reference_semantics"] = ref_sem
+            if pcie is not None:
+                out["pcie_inclusive"] = pcie
+            std = args.clip_seconds == 10        # the supplementary legs below are defined on the 10 s workload
+            if n_gpus == 1 and args.precision != "fp8" and not args.no_alt_modes and std:
+                _progress("leg: alt_modes")
+                out["alt_modes"] = alt_modes(B, L, args.precision)
+            if n_gpus == 1 and args.inflight > 1 and std:
+                out["pipelined"] = pipelined(args.inflight, B, L, max(args.steps, 2 * args.inflight), args.precision)
+            if n_gpus == 1 and args.precision != "fp8" and not args.no_b64 and B != 64 and std:
+                _progress("leg: north_star_b64")
+                out["north_star_b64"] = north_star_b64(L, args.precision)
+            if n_gpus == 1 and args.precision != "fp8" and not args.no_configs3 and args.preset != "configs3":
+                _progress("leg: configs3")
+                out["configs3"] = configs3_leg(args.precision)
+            if n_gpus == 1 and not args.no_cpu_baseline:
+                _progress("leg: cpu_baseline")
+                out["cpu_baseline"] = cpu_baseline(L)
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.destroy_process_group()

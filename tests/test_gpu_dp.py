@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -172,22 +173,26 @@ def test_gather_runs_on_rccl_with_one_rank(tmp_path):
     assert "rccl ok" in r.stdout
 
 
-def test_bench_runs_end_to_end_on_rccl_with_one_rank():
+def test_bench_runs_end_to_end_on_rccl_with_one_rank(tmp_path):
     """8-GPU readiness on a 1-GPU box: `bench.py` under the driver's launcher (`torch.distributed.run`) with the DEFAULT backend
     ("nccl" = RCCL) and one rank -- process-group init with `device_id`, the barrier, the MAX all-reduce of the elapsed time and
     the token all-gather of mellow_amd.dist all execute on RCCL with device buffers, and `ranks_seen` comes from
     `dist.get_world_size()`.  (MELLOW_BENCH_FORCE_DIST=1: the launcher gives WORLD_SIZE=1, for which bench.py would otherwise
-    skip the group.)  The supplementary legs of the N = 1 line are switched off to keep the run short."""
+    skip the group.)  The supplementary legs of the N = 1 line are switched off to keep the run short.  --dump-outputs writes the
+    gathered token ids of the last timed step."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29751", HSA_ENABLE_IPC_MODE_LEGACY="0", MELLOW_BENCH_FORCE_DIST="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29751", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "8",
-           "--no-cpu-baseline", "--no-alt-modes", "--no-b64", "--no-configs3", "--inflight", "0"]
+           "--no-cpu-baseline", "--no-alt-modes", "--no-b64", "--no-configs3", "--inflight", "0", "--dump-outputs", str(tmp_path / "out")]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, lines
     out = json.loads(lines[0])
     assert out["n_gpus"] == 1 and out["ranks_seen"] == 1 and out["dist_backend"] == "nccl" and out["value"] > 0
+    toks, lens = np.load(tmp_path / "out" / "tokens.npy"), np.load(tmp_path / "out" / "lengths.npy")
+    assert toks.dtype == np.float32 and toks.shape == (8, 64) and lens.tolist() == [64] * 8
+    assert (toks >= 0).all() and (toks < 49152).all() and (toks == np.round(toks)).all()
 
 
 _LOAD_WORKER = r"""

@@ -63,10 +63,17 @@ def test_resample_44k_to_32k_length_and_tone():
     assert audio.resample(x, 32000, 32000) is x               # no-op at the model rate
 
 
-def test_reference_fixture_wavs_load():
-    p = "/root/reference/resource/1.wav"
-    if not os.path.exists(p):
-        pytest.skip("reference fixtures are only present in the build container")
+def test_reference_fixture_wavs_load(tmp_path):
+    """resource/1.wav of the reference, rebuilt byte for byte from its decoded PCM (tests/golden/example.npz): a canonical
+    44-byte-header mono 16-bit file, so the header is fixed by rate, channels and length; the hash is the original file's."""
+    import hashlib
+    import wave
+    g = np.load(os.path.join(ROOT, "tests", "golden", "example.npz"))
+    p = str(tmp_path / "1.wav")
+    with wave.open(p, "wb") as w:
+        w.setnchannels(1); w.setsampwidth(2); w.setframerate(int(g["sr1"])); w.writeframes(g["pcm1"].astype("<i2").tobytes())
+    with open(p, "rb") as f:
+        assert hashlib.sha256(f.read()).hexdigest() == "67f626c4141f263970975ace059447c0044434ad71dd8f6fd14acc0c29d00855"
     y = audio.load_audio_into_tensor(p, 10, 32000)
     assert y.shape == (320000,)
     w, sr = audio.load_wav(p)
@@ -219,7 +226,8 @@ def test_bench_cli_contract_flags():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--precision", "--inflight", "--no-cpu-baseline", "--preset", "configs3", "--clip-seconds"):
+    for flag in ("--gpus", "--steps", "--warmup", "--precision", "--inflight", "--no-cpu-baseline", "--preset", "configs3", "--clip-seconds",
+                 "--full", "--dump-outputs"):
         assert flag in r.stdout
 
 
