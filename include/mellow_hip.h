@@ -47,8 +47,9 @@ extern "C" {
  *  2: mellow_prefill_parts (round 5).
  *  3: mellow_engine_set_option / mellow_engine_describe (round 6): the library no longer reads ANY environment variable; every
  *     switch it has is a named option, and the resolved configuration can be printed.  mellow_debug_gemm_f32 modes 6 / 9 are gone
- *     (the pre-split debug kernel was removed; 16 / 17 are the engine's own f32x3 kernels). */
-#define MELLOW_ABI_MINOR 3
+ *     (the pre-split debug kernel was removed; 16 / 17 are the engine's own f32x3 kernels).
+ *  4: opt-in seeded nucleus sampling: mellow_generate_sampled and mellow_sample_logits.  mellow_generate is unchanged (greedy). */
+#define MELLOW_ABI_MINOR 4
 
 typedef struct mellow_engine mellow_engine_t;
 
@@ -119,7 +120,8 @@ const char* mellow_engine_required_key(int i);
  * input_ids     : dev i32 [B][text_len]   (preprocess_text's input_ids, wrapper.py:181-195)
  * max_len       : entry_length of the loop (wrapper.py:200)
  * top_p, temperature : accepted for API parity; the reference's filter never removes the arg-max
- *                 (wrapper.py:220-232) so the result is greedy for every value
+ *                 (wrapper.py:220-232) so the result is greedy for every value;
+ *                 mellow_generate_sampled is the opt-in sampling form
  * stop_id       : tokenizer.encode(stop_token)[0] (wrapper.py:208)
  * ignore_stop   : 0 = reference semantics (loop ends when every row has produced stop_id,
  *                 wrapper.py:247-249); 1 = always run max_len steps (fixed-work benchmark mode)
@@ -138,6 +140,29 @@ int  mellow_generate(mellow_engine_t* e, const float* audio1, const float* audio
                      const int32_t* input_ids, int B, int max_len, float top_p, float temperature,
                      int stop_id, int ignore_stop, int32_t* out_tokens, int32_t* out_len,
                      int32_t* out_steps, float* first_token_ms);
+/* Opt-in seeded nucleus (top-p) / temperature sampling: mellow_generate with the arg-max of every step (the prefill's token
+ * included) replaced by a draw, inside the same captured decode step.  The default call above stays greedy and
+ * reference-identical.  For a row with fp32 logits l[0..vocab), global row index r and step t (the column of out_tokens):
+ *   1. z_i = l_i / temperature in fp32; temperature must be finite and > 0 (else an error).
+ *   2. Nucleus (the reference's rule, wrapper.py:219-226): order the tokens by (z desc, index asc), p = softmax(z); token i is
+ *      kept iff the mass of the tokens strictly before it in that order is <= top_p.  The first token is always kept:
+ *      top_p <= 0 keeps exactly the arg-max, top_p >= 1 every token; top_p NaN is an error.  Masses are fixed-point
+ *      integers (2^-31 of the row maximum's weight) summed exactly, so the boundary depends on no summation order.
+ *   3. Draw (Gumbel-max): the token is argmax over kept i of (z_i + g_i), ties to the lowest index, g_i = -log(-log(u_i)),
+ *      u_i = (2 * (x >> 9) + 1) * 2^-24 with x = word (i & 3) of Philox4x32-10 at counter (i >> 2, t, r, 0) and key
+ *      (lo32(seed), hi32(seed)).
+ *   4. A row holding a NaN logit yields its first NaN index (the greedy rule).
+ * r = row_offset + the row's index in this call, so a row's stream depends on (seed, r, t) only: not on its batch slot, the
+ * 1024-row passes, row migration or the engine context.  Results are bit-deterministic, graph or eager.  The vocabulary must be
+ * 49152 (the sampler's one-workgroup-per-row tiling). */
+int  mellow_generate_sampled(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples,
+                             const int32_t* input_ids, int B, int max_len, float top_p, float temperature, uint64_t seed,
+                             int32_t row_offset, int stop_id, int ignore_stop, int32_t* out_tokens, int32_t* out_len,
+                             int32_t* out_steps, float* first_token_ms);
+/* The same draw on caller logits, no loop state (numeric tap): logits dev [B][vocab], row_ids dev i32 [B] (global row index
+ * of each row; NULL = 0..B-1), step = t above -> tokens dev i32 [B]. */
+int  mellow_sample_logits(mellow_engine_t* e, const float* logits, int B, const int32_t* row_ids, int step, float top_p,
+                          float temperature, uint64_t seed, int32_t* tokens);
 
 /* ---- parity taps (same kernels as mellow_generate, stage by stage) ------------------------------- */
 /* A1-A3: htsat.py:864-870.  wav dev [n][n_samples] -> out dev [n][frames][64]; apply_bn=0 gives the

@@ -181,6 +181,9 @@ struct mellow_engine {
     unsigned long long* d_progress = nullptr;  // its device alias
     std::map<std::pair<int, int>, float*> resample_banks;   // (orig, new) gcd-reduced -> device polyphase bank [klen][new]
     int32_t h_params[2] = {0, 0};              // staging of d_params {max_len, stop id}
+    uint32_t* d_sparams = nullptr;             // sampling parameter block (kernels.h SMP_*): graph replays serve any seed / top_p / T
+    uint32_t h_sparams[SMP_WORDS] = {0};       // ... its staging
+    bool sample_on = false;                    // run_lm_head draws with dec_sample_kernel instead of the arg-max (mellow_generate_sampled)
     int32_t h_blk[64] = {0};                   // staging of d_blk_left[32] | d_blk_live[32]
     std::vector<int32_t> h_ident;              // staging of d_row_of_slot
     int last_steps_enqueued = 0;               // decode steps (incl. the prefill's token) the last generate call enqueued
@@ -230,6 +233,7 @@ struct mellow_engine {
     hipGraphExec_t step_exec8 = nullptr;      // the same step captured 8 times in a row (the step is position-independent)
     int step_exec_B = -1, step_exec_Tmax = -1;
     const void* graph_out_tok = nullptr;      // the graphs bake buffer addresses in; max_len / stop id travel in d_params
+    int graph_sample = -1;                    // sampling mode the graphs were captured in (the sampler + logits store, or the arg-max)
 
     // profiling
     bool prof_on = false;

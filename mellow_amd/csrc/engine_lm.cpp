@@ -141,8 +141,15 @@ int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec)
       if (e->head8) launch_dec_lm_head(dh(1), e->head8, e->lm_head.KP / 8, e->cfg.vocab_size, e->stream, e->head_sc);
       else launch_dec_lm_head(dh(1), e->lm_head.p, e->lm_head.KP / 8, e->cfg.vocab_size, e->stream); }
     { ProfScope ps(e, PF_MISC, 0, 0);
-      launch_dec_argmax(dh(2), B, NT, e->d_tokens, e->embed, (rec && rec->embed_next) ? 1 : 0, rec ? loop_args(e) : LoopArgs(),
-                        e->stream);
+      if (e->sample_on) {          // mellow_generate_sampled: the head stored the logits (da.logits); draw instead of the arg-max
+          SampleArgs sa;
+          sa.logits = e->da.logits; sa.ld = e->cfg.vocab_size; sa.prm = e->d_sparams;
+          launch_dec_sample(sa, dh(2), B, e->d_tokens, e->embed, (rec && rec->embed_next) ? 1 : 0, rec ? loop_args(e) : LoopArgs(),
+                            e->stream);
+      } else {
+          launch_dec_argmax(dh(2), B, NT, e->d_tokens, e->embed, (rec && rec->embed_next) ? 1 : 0, rec ? loop_args(e) : LoopArgs(),
+                            e->stream);
+      }
       if (rec && e->da.row_of_slot) launch_dec_compact(e->da, B, loop_args(e), e->stream); }
     return 0;
 }
@@ -540,9 +547,21 @@ int mellow_lm_forward_logits(mellow_engine_t* e, const float* embeds, int B, int
     return 0;
 }
 
+// sampling of one call (mellow_generate_sampled); on = false: the greedy arg-max of mellow_generate
+struct SampleCall {
+    bool on = false;
+    float top_p = 0.f, temperature = 1.f;
+    uint64_t seed = 0;
+    int32_t row_offset = 0;
+};
 static int generate_pass(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples,
                          const int32_t* input_ids, int B, int max_len, int stop_id,
-                         int ignore_stop, int32_t* out_tokens, int32_t* out_len, int32_t* out_steps, float* first_token_ms);
+                         int ignore_stop, int32_t* out_tokens, int32_t* out_len, int32_t* out_steps, float* first_token_ms,
+                         const SampleCall& sc);
+static int generate_all(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples,
+                        const int32_t* input_ids, int B, int max_len, int stop_id,
+                        int ignore_stop, int32_t* out_tokens, int32_t* out_len, int32_t* out_steps, float* first_token_ms,
+                        const SampleCall& sc);
 
 // The reference's loop (wrapper.py:216-249) takes any number of examples.  One pass of the engine takes up to 1024 rows (32 row
 // blocks of loop state), so a larger batch runs as consecutive passes of <= 1024 rows on the same pages: examples are
@@ -554,12 +573,62 @@ int mellow_generate(mellow_engine_t* e, const float* audio1, const float* audio2
                     int ignore_stop, int32_t* out_tokens, int32_t* out_len, int32_t* out_steps, float* first_token_ms) {
     (void)top_p;
     (void)temperature;  // the reference's top-p/temperature path never changes the arg-max (wrapper.py:219-232)
+    return generate_all(e, audio1, audio2, n_samples, input_ids, B, max_len, stop_id, ignore_stop, out_tokens, out_len, out_steps,
+                        first_token_ms, SampleCall());
+}
+
+static int check_sampling(mellow_engine_t* e, float top_p, float temperature) {
+    if (e->cfg.vocab_size != SAMPLE_MAX_V) return fail("the sampler is built for a vocabulary of %d (engine: %d)", SAMPLE_MAX_V, e->cfg.vocab_size);
+    if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail("temperature must be finite and > 0 (got %g); greedy is mellow_generate", (double)temperature);
+    if (top_p != top_p) return fail("top_p is NaN");
+    return 0;
+}
+
+static void stage_sampling(mellow_engine_t* e, float top_p, float temperature, uint64_t seed, int32_t row_offset, int step) {
+    uint32_t* w = e->h_sparams;
+    w[SMP_SEED_LO] = (uint32_t)seed; w[SMP_SEED_HI] = (uint32_t)(seed >> 32); w[SMP_ROW_OFF] = (uint32_t)row_offset;
+    memcpy(&w[SMP_TOP_P], &top_p, 4); memcpy(&w[SMP_TEMP], &temperature, 4); w[SMP_STEP] = (uint32_t)step;
+}
+
+int mellow_generate_sampled(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples,
+                            const int32_t* input_ids, int B, int max_len, float top_p, float temperature, uint64_t seed,
+                            int32_t row_offset, int stop_id, int ignore_stop, int32_t* out_tokens, int32_t* out_len,
+                            int32_t* out_steps, float* first_token_ms) {
+    if (!e || !e->finalized) return fail("engine not finalized");
+    CHK(check_sampling(e, top_p, temperature));
+    if (row_offset < 0) return fail("row_offset must be >= 0");
+    SampleCall sc;
+    sc.on = true; sc.top_p = top_p; sc.temperature = temperature; sc.seed = seed; sc.row_offset = row_offset;
+    return generate_all(e, audio1, audio2, n_samples, input_ids, B, max_len, stop_id, ignore_stop, out_tokens, out_len, out_steps,
+                        first_token_ms, sc);
+}
+
+int mellow_sample_logits(mellow_engine_t* e, const float* logits, int B, const int32_t* row_ids, int step, float top_p,
+                         float temperature, uint64_t seed, int32_t* tokens) {
+    if (!e || !e->finalized) return fail("engine not finalized");
+    if (!logits || !tokens || B <= 0) return fail("bad argument");
+    CHK(check_sampling(e, top_p, temperature));
+    HIPCHK(hipSetDevice(e->device));
+    stage_sampling(e, top_p, temperature, seed, 0, step);
+    HIPCHK(hipMemcpyAsync(e->d_sparams, e->h_sparams, sizeof(e->h_sparams), hipMemcpyHostToDevice, e->stream));
+    SampleArgs sa;
+    sa.logits = logits; sa.ld = e->cfg.vocab_size; sa.prm = e->d_sparams; sa.row_ids = row_ids;
+    launch_sample_logits(sa, B, tokens, e->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+static int generate_all(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples,
+                        const int32_t* input_ids, int B, int max_len, int stop_id,
+                        int ignore_stop, int32_t* out_tokens, int32_t* out_len, int32_t* out_steps, float* first_token_ms,
+                        const SampleCall& sc) {
     if (!e || !e->finalized) return fail("engine not finalized");
     if (!audio1 || !audio2 || !input_ids || !out_tokens) return fail("null argument");
     if (B <= 0 || max_len <= 0) return fail("B and max_len must be positive");
     constexpr int kPassRows = 1024;
     if (B <= kPassRows)
-        return generate_pass(e, audio1, audio2, n_samples, input_ids, B, max_len, stop_id, ignore_stop, out_tokens, out_len, out_steps, first_token_ms);
+        return generate_pass(e, audio1, audio2, n_samples, input_ids, B, max_len, stop_id, ignore_stop, out_tokens, out_len, out_steps, first_token_ms, sc);
     int steps_all = 0, enq_all = 0, rep_all = 0;
     float ph[3] = {0.f, 0.f, 0.f};
     std::vector<int> pass_steps;
@@ -567,8 +636,10 @@ int mellow_generate(mellow_engine_t* e, const float* audio1, const float* audio2
         const int nb = B - r0 < kPassRows ? B - r0 : kPassRows;
         int st = 0;
         float ftm = 0.f;
+        SampleCall scp = sc;
+        scp.row_offset = sc.row_offset + r0;           // a row's random stream follows its index in the whole call
         CHK(generate_pass(e, audio1 + (size_t)r0 * n_samples, audio2 + (size_t)r0 * n_samples, n_samples, input_ids + (size_t)r0 * e->cfg.text_len,
-                          nb, max_len, stop_id, ignore_stop, out_tokens + (size_t)r0 * max_len, out_len ? out_len + r0 : nullptr, &st, &ftm));
+                          nb, max_len, stop_id, ignore_stop, out_tokens + (size_t)r0 * max_len, out_len ? out_len + r0 : nullptr, &st, &ftm, scp));
         if (r0 == 0 && first_token_ms) *first_token_ms = ftm;      // the first answers of the call: entry -> first token of the first pass
         pass_steps.push_back(st);
         steps_all = st > steps_all ? st : steps_all;
@@ -597,7 +668,8 @@ int mellow_generate(mellow_engine_t* e, const float* audio1, const float* audio2
 
 static int generate_pass(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples,
                          const int32_t* input_ids, int B, int max_len, int stop_id,
-                         int ignore_stop, int32_t* out_tokens, int32_t* out_len, int32_t* out_steps, float* first_token_ms) {
+                         int ignore_stop, int32_t* out_tokens, int32_t* out_len, int32_t* out_steps, float* first_token_ms,
+                         const SampleCall& sc) {
     const auto t_entry = std::chrono::steady_clock::now();
     HIPCHK(hipSetDevice(e->device));
     hipStream_t s = e->stream;
@@ -621,6 +693,13 @@ static int generate_pass(mellow_engine_t* e, const float* audio1, const float* a
     // stop id, the block's workgroups return at once in every later kernel (its rows' texts are already cut there).  Columns a
     // row never reached are -1 in the token record.
     e->da.logits = nullptr;             // generation needs the arg-max candidates only: no 6 MB logits store per step
+    e->sample_on = sc.on;               // ... unless it samples: the sampler reads the full logits rows
+    struct SampleOff { mellow_engine* e; ~SampleOff() { e->sample_on = false; } } sample_off{e};    // the taps never sample
+    if (sc.on) {
+        e->da.logits = e->dlogits.p;
+        stage_sampling(e, sc.top_p, sc.temperature, sc.seed, sc.row_offset, 0);
+        HIPCHK(hipMemcpyAsync(e->d_sparams, e->h_sparams, sizeof(e->h_sparams), hipMemcpyHostToDevice, s));
+    }
     e->da.blk_live = (!ignore_stop && e->da.RB > 1) ? e->d_blk_live : nullptr;
     e->da.blk_snap = e->d_blk_live + 32;
 #ifdef MELLOW_DEVPROBE
@@ -662,7 +741,7 @@ static int generate_pass(mellow_engine_t* e, const float* audio1, const float* a
     // captured once per (B, page geometry, buffers) and replayed; max_len and the stop id are read from d_params
     const bool graph = e->use_graph && !e->prof_on && max_len > 1;
     if (graph && (!e->step_exec || e->step_exec_B != B || e->step_exec_Tmax != e->kv_Tmax || e->graph_out_tok != e->out_tok.p ||
-                  e->graph_blk != e->da.blk_live || e->graph_rows != e->da.row_of_slot)) {
+                  e->graph_blk != e->da.blk_live || e->graph_rows != e->da.row_of_slot || e->graph_sample != (int)sc.on)) {
         if (e->step_exec) { hipGraphExecDestroy(e->step_exec); e->step_exec = nullptr; }
         if (e->step_exec8) { hipGraphExecDestroy(e->step_exec8); e->step_exec8 = nullptr; }
         hipGraph_t gr = nullptr;
@@ -684,6 +763,7 @@ static int generate_pass(mellow_engine_t* e, const float* audio1, const float* a
         HIPCHK(hipGraphInstantiate(&e->step_exec8, gr, nullptr, nullptr, 0));
         HIPCHK(hipGraphDestroy(gr));
         e->step_exec_B = B; e->step_exec_Tmax = e->kv_Tmax; e->graph_out_tok = e->out_tok.p; e->graph_blk = e->da.blk_live; e->graph_rows = e->da.row_of_slot;
+        e->graph_sample = (int)sc.on;
     }
     int steps_done = 1;   // token 0 came from the prefill
     double first_ms = -1.0;

@@ -251,6 +251,22 @@ struct LoopArgs {
 // write_x it gathers embed[token] as the next step's residual stream
 void launch_dec_argmax(const DecArgs& a, int B, int n_tiles, int32_t* tokens, const float* embed, int write_x,
                        const LoopArgs& loop, hipStream_t s);
+// Seeded nucleus sampling (sample.hip; include/mellow_hip.h mellow_generate_sampled states the exact definition).  The
+// parameters live in a device block the host fills per call, so captured graphs serve any seed / top_p / temperature:
+// prm = {lo32(seed), hi32(seed), row offset, bits of top_p, bits of temperature, step (taps only)}.
+enum { SMP_SEED_LO = 0, SMP_SEED_HI, SMP_ROW_OFF, SMP_TOP_P, SMP_TEMP, SMP_STEP, SMP_WORDS = 8 };
+struct SampleArgs {
+    const float* logits = nullptr;       // [rows][ld] fp32
+    int64_t ld = 0;
+    const uint32_t* prm = nullptr;       // device block of SMP_WORDS words
+    const int32_t* row_ids = nullptr;    // taps: global row index of each row (null: the row's position)
+};
+constexpr int SAMPLE_MAX_V = 49152;      // the vocabulary the sampler is built for: 48 values per thread of one 1024-thread workgroup
+// the decode step's sampler: draws from sa.logits (= DecArgs::logits) and then does exactly the bookkeeping of dec_argmax_kernel
+void launch_dec_sample(const SampleArgs& sa, const DecArgs& a, int B, int32_t* tokens, const float* embed, int write_x,
+                       const LoopArgs& loop, hipStream_t s);
+// the same draw on caller rows, no loop state (mellow_sample_logits)
+void launch_sample_logits(const SampleArgs& sa, int B, int32_t* tokens, hipStream_t s);
 // after the arg-max of a step (early-exit mode only): if the rows that have not produced the stop id yet fit into fewer 32-row
 // blocks than are live, move them (their next-step residual rows) to the lowest slots, rewrite row_of_slot / blk_left / blk_live
 void launch_dec_compact(const DecArgs& a, int B, const LoopArgs& loop, hipStream_t s);

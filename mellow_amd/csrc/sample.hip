@@ -1,0 +1,319 @@
+// Seeded nucleus (top-p) / temperature sampling inside the decode step (include/mellow_hip.h, mellow_generate_sampled).
+//
+// One 1024-thread workgroup per row holds the whole row in registers (48 values per thread, coalesced float4 loads):
+//   1. z = l / T (fp32), row maximum m, first NaN index (a row with a NaN yields it: the greedy rule);
+//   2. every token's softmax mass as a fixed-point integer q = rn(exp(z - m) * 2^31) and the row total S = sum q -- integer
+//      sums, so the nucleus boundary depends on no summation or arrival order;
+//   3. the boundary: token i is kept iff the mass strictly before it in the order (z desc, index asc) is <= top_p * S.  A
+//      mass-weighted radix select over the order-preserving u32 key of z (4 passes of 8 bits, per-wave LDS histograms of
+//      integer mass) finds the boundary key; ties on that key are cut by index with a second select over the index (counts);
+//   4. Gumbel-max over the kept tokens: argmax (z + g), g = -log(-log u), u from Philox4x32-10 keyed by (seed) with counter
+//      (index / 4, step, global row, 0); ties to the lowest index.  Noise is only formed for kept tokens.
+// The loop variant then does exactly the bookkeeping of dec_argmax_kernel (decode.hip), which it replaces in the step.
+#include "common.h"
+#include "kernels.h"
+
+namespace mellow {
+
+namespace {
+
+constexpr int SMP_THREADS = 1024, SMP_WAVES = SMP_THREADS / 64;
+constexpr int SMP_NV4 = SAMPLE_MAX_V / 4 / SMP_THREADS;      // float4 groups per thread (12)
+static_assert(SMP_NV4 * 4 * SMP_THREADS == SAMPLE_MAX_V, "row tiling");
+
+__device__ __forceinline__ int64_t f32_idx(int rb, int K8, int m, int k) {      // decode.hip's F32-layout index
+    return ((int64_t)rb * K8 + (k >> 3)) * 64 + m + 32 * ((k >> 2) & 1);
+}
+
+// order-preserving key: a > b (as floats, no NaN) <=> okey(a) > okey(b); equal keys <=> equal values (z carries no -0)
+__device__ __forceinline__ uint32_t okey(float z) {
+    const uint32_t u = __float_as_uint(z);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// a copy of a register value the compiler cannot see through: keeps per-pass key / mass arithmetic inside the pass loops
+// (hoisted out, the 48 keys, masses and sign masks of a thread's row slice would be live at once: 128-VGPR budget, spills)
+__device__ __forceinline__ float opaque(float x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+
+// Philox4x32-10 (Salmon et al., SC'11; Random123's constants)
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t out[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+struct SelScratch {
+    unsigned long long hist[SMP_WAVES][256];   // per-wave histograms (integer adds: order-free)
+    unsigned long long bin[256];
+    uint32_t digit;
+    unsigned long long above, mass;
+};
+
+// Mass-weighted radix select, descending: among the items whose key matches the prefix found so far, find the key K such
+// that mass(key > K) <= thr < mass(key >= K), walking 8-bit digits from bit shift_hi down (bits above shift_hi + 8 are 0).
+// thr = thr_of(total mass), formed after the first histogram; returns false (nothing selected) when thr >= total.  Then
+// exactly one bin qualifies in every pass.  key_of(k, j, key) says whether element j of float4 group k takes part (and its
+// key); w_of(k, j) is its weight, evaluated only for elements inside the current prefix.  Workgroup-uniform results.
+template <typename KeyF, typename WF, typename ThrF>
+__device__ __forceinline__ bool radix_select(KeyF key_of, WF w_of, ThrF thr_of, int shift_hi, SelScratch& sh, uint32_t& out_key,
+                                             unsigned long long& out_above, unsigned long long& out_mass,
+                                             unsigned long long& out_thr) {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    uint32_t prefix = 0, pmask = shift_hi + 8 >= 32 ? 0u : ~0u << (shift_hi + 8);
+    unsigned long long above = 0, mass = 0, thr = 0;
+    for (int shift = shift_hi; shift >= 0; shift -= 8) {
+        for (int i = tid; i < SMP_WAVES * 256; i += SMP_THREADS) (&sh.hist[0][0])[i] = 0ull;
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < SMP_NV4; ++k)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                uint32_t key;
+                if (key_of(k, j, key) && (key & pmask) == prefix) {
+                    const unsigned long long w = w_of(k, j);
+                    if (w) atomicAdd(&sh.hist[wave][(key >> shift) & 255u], w);
+                }
+            }
+        __syncthreads();
+        if (tid < 256) {
+            unsigned long long s = 0;
+            for (int w = 0; w < SMP_WAVES; ++w) s += sh.hist[w][tid];
+            sh.bin[tid] = s;
+        }
+        __syncthreads();
+        if (shift == shift_hi) {
+            unsigned long long total = 0;
+            for (int i = 0; i < 256; ++i) total += sh.bin[i];        // (LDS broadcast reads)
+            thr = thr_of(total);
+            if (thr >= total) { __syncthreads(); return false; }
+        }
+        if (wave == 0) {
+            // lane l owns digits 255 - 4l .. 252 - 4l (descending key order)
+            unsigned long long v[4], tot = 0;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) { v[s] = sh.bin[255 - 4 * lane - s]; tot += v[s]; }
+            unsigned long long inc = tot;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const unsigned long long o = __shfl_up(inc, off, 64);
+                if (lane >= off) inc += o;
+            }
+            unsigned long long run = above + (inc - tot);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                if (run <= thr && thr < run + v[s]) { sh.digit = 255u - 4u * lane - s; sh.above = run; sh.mass = v[s]; }
+                run += v[s];
+            }
+        }
+        __syncthreads();
+        prefix |= sh.digit << shift;
+        pmask |= 255u << shift;
+        above = sh.above;
+        mass = sh.mass;
+        __syncthreads();            // (sh is rewritten by the next pass)
+    }
+    out_key = prefix; out_above = above; out_mass = mass; out_thr = thr;
+    return true;
+}
+
+template <typename T, typename Op>
+__device__ __forceinline__ T block_reduce(T v, Op op, T* red) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_xor(v, off, 64));
+    if ((tid & 63) == 0) red[tid >> 6] = v;
+    __syncthreads();
+    T r = red[0];
+    for (int w = 1; w < SMP_WAVES; ++w) r = op(r, red[w]);
+    __syncthreads();
+    return r;
+}
+
+// the draw of one row: returns the token (workgroup-uniform)
+__device__ __forceinline__ int sample_row(const float* __restrict__ lrow, const uint32_t* __restrict__ prm, uint32_t grow,
+                                          uint32_t step) {
+    __shared__ SelScratch sh;
+    __shared__ float red_f[SMP_WAVES];
+    __shared__ int red_i[SMP_WAVES];
+    __shared__ uint32_t qtie_s;
+    const int tid = threadIdx.x;
+    const uint32_t seed_lo = prm[SMP_SEED_LO], seed_hi = prm[SMP_SEED_HI];
+    const float top_p = __uint_as_float(prm[SMP_TOP_P]), temp = __uint_as_float(prm[SMP_TEMP]);
+
+    float z[SMP_NV4][4];
+    int nan_idx = 0x7fffffff;
+    float m = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < SMP_NV4; ++k) {
+        const int i4 = k * SMP_THREADS + tid;
+        const float4 v = reinterpret_cast<const float4*>(lrow)[i4];
+        const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float zz = __fdiv_rn(vv[j], temp) + 0.0f;          // (+ 0: -0 becomes +0, so equal values have equal keys)
+            z[k][j] = zz;
+            if (vv[j] != vv[j]) nan_idx = min(nan_idx, 4 * i4 + j);
+            else m = fmaxf(m, zz);
+        }
+    }
+    nan_idx = block_reduce(nan_idx, [](int a, int b) { return min(a, b); }, red_i);
+    if (nan_idx != 0x7fffffff) return nan_idx;          // greedy rule: the first NaN (torch.argmax, dec_argmax_kernel)
+    m = block_reduce(m, [](float a, float b) { return fmaxf(a, b); }, red_f);
+
+    // fixed-point mass q = rn(exp(z - m) * 2^31) <= 2^31, so S < 2^47 is exact in fp64 for the threshold; formed where a
+    // histogram pass needs it (the first pass for every token, the later ones for the few inside the prefix)
+    auto q_of = [&](int k, int j) -> unsigned long long {
+        const float zz = opaque(z[k][j]);
+        const float e = zz == m ? 1.0f : expf(zz - m);                   // (z == m also covers m = +inf)
+        return __float2uint_rn(e * 2147483648.0f);
+    };
+    bool keep_all = !(top_p < 1.0f);
+    uint32_t kstar = 0;                  // boundary key: keys above it are kept
+    int idx_cut = 0x7fffffff;            // tokens ON the boundary key are kept up to this index
+    if (!keep_all) {
+        unsigned long long above, mass, thr;
+        keep_all = !radix_select([&](int k, int j, uint32_t& key) { key = okey(opaque(z[k][j])); return true; }, q_of,
+                                 [&](unsigned long long S) { return top_p > 0.0f ? (unsigned long long)((double)top_p * (double)S) : 0ull; },
+                                 24, sh, kstar, above, mass, thr);
+        if (!keep_all) {
+            // the tokens on kstar all carry the same q (same z): the first c of them by index are kept
+#pragma unroll
+            for (int k = 0; k < SMP_NV4; ++k)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (okey(opaque(z[k][j])) == kstar) qtie_s = (uint32_t)q_of(k, j);   // (every writer stores the same value)
+            __syncthreads();
+            const unsigned long long qt = qtie_s;            // > 0: the boundary bin's mass exceeds thr - above >= 0
+            const unsigned long long n_tie = mass / qt, c = (thr - above) / qt + 1;
+            if (c < n_tie) {
+                uint32_t kidx;
+                unsigned long long a2, m2, t2;
+                radix_select([&](int k, int j, uint32_t& key) {
+                                 key = 0xFFFFu - (uint32_t)(4 * (k * SMP_THREADS + tid) + j);
+                                 return okey(opaque(z[k][j])) == kstar; },
+                             [](int, int) { return 1ull; }, [c](unsigned long long) { return c - 1; }, 8, sh, kidx, a2, m2, t2);
+                idx_cut = (int)(0xFFFFu - kidx);
+            }
+        }
+    }
+
+    // Gumbel-max over the kept tokens
+    float best = -INFINITY;
+    int bidx = 0x7fffffff;
+#pragma unroll
+    for (int k = 0; k < SMP_NV4; ++k) {
+        const int i4 = k * SMP_THREADS + tid;
+        bool kept[4], any = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t key = okey(opaque(z[k][j]));
+            kept[j] = (keep_all || key > kstar || (key == kstar && 4 * i4 + j <= idx_cut));
+            any |= kept[j];
+        }
+        if (any) {
+            uint32_t x[4];
+            philox4x32_10((uint32_t)i4, step, grow, 0u, seed_lo, seed_hi, x);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (kept[j]) {
+                    const float u = (float)(2u * (x[j] >> 9) + 1u) * 0x1p-24f;
+                    const float s = z[k][j] - logf(-logf(u));
+                    const int id = 4 * i4 + j;
+                    if (s > best || (s == best && id < bidx)) { best = s; bidx = id; }
+                }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ob = __shfl_xor(best, off, 64);
+        const int oi = __shfl_xor(bidx, off, 64);
+        if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
+    }
+    if ((tid & 63) == 0) { red_f[tid >> 6] = best; red_i[tid >> 6] = bidx; }
+    __syncthreads();
+    best = red_f[0]; bidx = red_i[0];
+    for (int w = 1; w < SMP_WAVES; ++w)
+        if (red_f[w] > best || (red_f[w] == best && red_i[w] < bidx)) { best = red_f[w]; bidx = red_i[w]; }
+    __syncthreads();
+    return min(max(bidx, 0), SAMPLE_MAX_V - 1);
+}
+
+}  // namespace
+
+// the decode step's sampler: replaces dec_argmax_kernel when sampling is on; after the draw the loop bookkeeping below is
+// dec_argmax_kernel's, line for line (decode.hip: dead-slot rule, token record, stop counts, arrival / publish, embedding gather)
+__global__ __launch_bounds__(SMP_THREADS) void dec_sample_kernel(const SampleArgs sa, const DecArgs a, int32_t* __restrict__ tokens,
+                                                                 const float* __restrict__ embed, int write_x, const LoopArgs lp) {
+    __shared__ int tok_s;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int row = lp.row_of_slot ? lp.row_of_slot[b] : b;         // the example in this slot
+    const bool dead = (lp.blk_snap && lp.blk_snap[b >> 5] == 0) || row < 0;      // workgroup-uniform; written by an EARLIER launch
+    int idx = 0;
+    if (!dead) {
+        const int step = lp.out_tokens ? *a.d_pos - lp.T0 + 1 : (int)sa.prm[SMP_STEP];
+        idx = sample_row(sa.logits + (int64_t)b * sa.ld, sa.prm, sa.prm[SMP_ROW_OFF] + (uint32_t)row, (uint32_t)step);
+    }
+    if (tid == 0) {
+        if (!dead) {
+            tokens[b] = idx;
+            tok_s = idx;
+        }
+        if (lp.out_tokens) {
+            if (!dead) {
+                const int max_len = lp.params[0], stop_id = lp.params[1];
+                const int step = *a.d_pos - lp.T0 + 1;
+                if (step >= 0 && step < max_len) lp.out_tokens[(int64_t)row * max_len + step] = idx;
+                if (idx == stop_id && lp.seen_stop[row] == 0) {
+                    lp.seen_stop[row] = 1;
+                    atomicAdd(lp.n_seen, 1);
+                    if (lp.blk_left && atomicSub(lp.blk_left + (b >> 5), 1) == 1) lp.blk_live[b >> 5] = 0;   // from the NEXT step on
+                }
+            }
+            // publish exactly as dec_argmax_kernel does (its comment gives the ordering argument)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (atomicAdd(lp.arrive, 1) == (int)gridDim.x - 1) {
+                *lp.arrive = 0;
+                const int t = *lp.ticket + 1;
+                *lp.ticket = t;
+                const int ns = atomicAdd(lp.n_seen, 0);
+                __hip_atomic_store(lp.host_progress, ((unsigned long long)(unsigned)t << 32) | (unsigned)ns, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
+    }
+    if (dead) return;
+    if (write_x) {
+        __syncthreads();
+        if (tid < 144) {
+            const float4 e = reinterpret_cast<const float4*>(embed + (int64_t)tok_s * 576)[tid];
+            reinterpret_cast<float4*>(a.xmidF)[f32_idx(b >> 5, 72, b & 31, tid * 4)] = e;
+        }
+    }
+}
+
+__global__ __launch_bounds__(SMP_THREADS) void sample_logits_kernel(const SampleArgs sa, int32_t* __restrict__ tokens) {
+    const int b = blockIdx.x;
+    const uint32_t grow = sa.prm[SMP_ROW_OFF] + (uint32_t)(sa.row_ids ? sa.row_ids[b] : b);
+    const int idx = sample_row(sa.logits + (int64_t)b * sa.ld, sa.prm, grow, sa.prm[SMP_STEP]);
+    if (threadIdx.x == 0) tokens[b] = idx;
+}
+
+void launch_dec_sample(const SampleArgs& sa, const DecArgs& a, int B, int32_t* tokens, const float* embed, int write_x,
+                       const LoopArgs& loop, hipStream_t s) {
+    hipLaunchKernelGGL(dec_sample_kernel, dim3(B), dim3(SMP_THREADS), 0, s, sa, a, tokens, embed, write_x, loop);
+}
+
+void launch_sample_logits(const SampleArgs& sa, int B, int32_t* tokens, hipStream_t s) {
+    hipLaunchKernelGGL(sample_logits_kernel, dim3(B), dim3(SMP_THREADS), 0, s, sa, tokens);
+}
+
+}  // namespace mellow

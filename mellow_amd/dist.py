@@ -100,7 +100,7 @@ def agree_on_examples(sig: bytes) -> None:
             pass
     if any(s != sigs[0] for s in sigs):
         counts = [int.from_bytes(s[:8], "little") for s in sigs]
-        raise ValueError("data_parallel generate(): the ranks were given different `examples` "
+        raise ValueError("data_parallel generate(): the ranks were given different `examples` or sampling arguments "
                          f"(counts {counts}); call it with the same list on every rank, or turn sharding off")
 
 
@@ -134,6 +134,8 @@ def generate_sharded(generate_fn, audio1, audio2, input_ids, max_len: int, devic
     world = dist.get_world_size() if dist.is_initialized() else 1
     lo, hi = shard_range(n, rank, world)
     if hi > lo:
+        if kw.get("do_sample"):
+            kw = dict(kw, row_offset=int(kw.get("row_offset", 0)) + lo)     # the shard's rows keep their global random streams
         res = generate_fn(audio1[lo:hi], audio2[lo:hi], input_ids[lo:hi], max_len=max_len, **kw)
         toks, lens = np.asarray(res[0], dtype=np.int32), np.asarray(res[1], dtype=np.int32)
     else:

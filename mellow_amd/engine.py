@@ -66,6 +66,9 @@ def load_library(path: Optional[str] = None):
         "mellow_engine_num_required": (ci, []),
         "mellow_engine_required_key": (C.c_char_p, [ci]),
         "mellow_generate": (ci, [vp, vp, vp, i64, vp, ci, ci, cf, cf, ci, ci, vp, P(C.c_int32), P(C.c_int32), P(cf)]),
+        "mellow_generate_sampled": (ci, [vp, vp, vp, i64, vp, ci, ci, cf, cf, C.c_uint64, C.c_int32, ci, ci, vp, P(C.c_int32),
+                                         P(C.c_int32), P(cf)]),
+        "mellow_sample_logits": (ci, [vp, vp, ci, vp, ci, cf, cf, C.c_uint64, vp]),
         "mellow_logmel": (ci, [vp, vp, ci, i64, ci, vp]),
         "mellow_encode": (ci, [vp, vp, ci, i64, vp]),
         "mellow_prefix": (ci, [vp, vp, vp, i64, vp, ci, vp]),
@@ -113,7 +116,7 @@ def load_library(path: Optional[str] = None):
 EXPORTED_SYMBOLS = (
     "mellow_abi_version", "mellow_last_error", "mellow_device_count", "mellow_engine_create",
     "mellow_engine_destroy", "mellow_engine_fork", "mellow_engine_load_tensor", "mellow_engine_finalize",
-    "mellow_engine_num_required", "mellow_engine_required_key", "mellow_generate", "mellow_logmel",
+    "mellow_engine_num_required", "mellow_engine_required_key", "mellow_generate", "mellow_generate_sampled", "mellow_sample_logits", "mellow_logmel",
     "mellow_encode", "mellow_prefix", "mellow_lm_prefill", "mellow_lm_decode_step", "mellow_argmax", "mellow_embed_tokens", "mellow_lm_forward_logits",
     "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
     "mellow_prof_num_families", "mellow_prof_family_name", "mellow_prof_get", "mellow_last_phase_ms", "mellow_last_steps_enqueued", "mellow_last_row_repacks", "mellow_stft_is_fft", "mellow_prefill_parts", "mellow_abi_minor",
@@ -128,6 +131,13 @@ def hf_rope_tables(max_pos: int, head_dim: int, theta: float):
     pos = torch.arange(max_pos, dtype=torch.float32)
     freqs = (inv_freq[None, :, None].float() @ pos[None, None, :].float()).transpose(1, 2)[0]
     return freqs.cos().contiguous().numpy(), freqs.sin().contiguous().numpy()
+
+
+def _seed64(seed) -> int:
+    """a sampling seed as the u64 the C ABI takes (any Python int, taken modulo 2^64); None is an error"""
+    if seed is None:
+        raise ValueError("do_sample needs an integer seed")
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
 
 
 def _ptr(t: torch.Tensor) -> C.c_void_p:
@@ -291,10 +301,14 @@ class Engine:
 
     # ---- hot path ----------------------------------------------------------------------------------
     def generate(self, audio1, audio2, input_ids, max_len: int, top_p: float = 0.8, temperature: float = 1.0,
-                 stop_id: int = 0, ignore_stop: bool = False):
+                 stop_id: int = 0, ignore_stop: bool = False, do_sample: bool = False, seed: Optional[int] = None,
+                 row_offset: int = 0):
         """-> (tokens int32 [B, steps] on host, lengths [B], steps, first_token_ms)
         first_token_ms is measured from the C entry (inputs on the device); `last_first_token_host_ms` adds the time this
-        call spent bringing host arrays to the device (latency from audio in HOST memory)."""
+        call spent bringing host arrays to the device (latency from audio in HOST memory).
+        do_sample=False (default): greedy, the reference's result for every top_p / temperature.  do_sample=True: seeded
+        nucleus sampling (include/mellow_hip.h mellow_generate_sampled); row b draws from the stream of global row
+        row_offset + b, so a shard or batch given its first row's offset reproduces the rows of one big call."""
         import time
         t_in = time.perf_counter()
         a1, a2, ids = self._f32(audio1), self._f32(audio2), self._prompt_ids(input_ids)
@@ -306,9 +320,14 @@ class Engine:
         lens = (C.c_int32 * B)()
         steps = C.c_int32(0)
         ftm = C.c_float(0.0)
-        self._chk(self.lib.mellow_generate(self.h, _ptr(a1), _ptr(a2), n, _ptr(ids), B, int(max_len), float(top_p),
-                                           float(temperature), int(stop_id), 1 if ignore_stop else 0, _ptr(out),
-                                           lens, C.byref(steps), C.byref(ftm)))
+        if do_sample:
+            self._chk(self.lib.mellow_generate_sampled(self.h, _ptr(a1), _ptr(a2), n, _ptr(ids), B, int(max_len), float(top_p),
+                                                       float(temperature), _seed64(seed), int(row_offset), int(stop_id),
+                                                       1 if ignore_stop else 0, _ptr(out), lens, C.byref(steps), C.byref(ftm)))
+        else:
+            self._chk(self.lib.mellow_generate(self.h, _ptr(a1), _ptr(a2), n, _ptr(ids), B, int(max_len), float(top_p),
+                                               float(temperature), int(stop_id), 1 if ignore_stop else 0, _ptr(out),
+                                               lens, C.byref(steps), C.byref(ftm)))
         toks = out.cpu().numpy()[:, : steps.value]
         self.last_first_token_host_ms = t_up + float(ftm.value)
         return toks, np.asarray(list(lens), dtype=np.int32), int(steps.value), float(ftm.value)
@@ -413,6 +432,22 @@ class Engine:
         out = torch.empty((l.shape[0],), dtype=torch.int32, device=self.tdev)
         self._sync_inputs()
         self._chk(self.lib.mellow_argmax(self.h, _ptr(l), l.shape[0], _ptr(out)))
+        return out
+
+    def sample_logits(self, logits, top_p: float, temperature: float, seed: int, step: int, row_ids=None) -> torch.Tensor:
+        """The decode step's draw on caller logits (B, vocab) -> tokens int32 (B,) on the device; row_ids (B,) = the global
+        row index of each row (None: 0..B-1), step = the column of the token record the draw stands for."""
+        l = self._f32(logits)
+        if l.dim() != 2 or l.shape[1] != self.lm.vocab_size:
+            raise ValueError(f"logits must be (B, {self.lm.vocab_size}), got {tuple(l.shape)}")
+        B = l.shape[0]
+        out = torch.empty((B,), dtype=torch.int32, device=self.tdev)
+        rid = None if row_ids is None else torch.as_tensor(row_ids).reshape(-1).to(device=self.tdev, dtype=torch.int32).contiguous()
+        if rid is not None and rid.shape[0] != B:
+            raise ValueError(f"row_ids has {rid.shape[0]} entries for {B} rows")
+        self._sync_inputs()
+        self._chk(self.lib.mellow_sample_logits(self.h, _ptr(l), B, None if rid is None else _ptr(rid), int(step), float(top_p),
+                                                float(temperature), _seed64(seed), _ptr(out)))
         return out
 
     def resample(self, wav, orig_freq: int, new_freq: int) -> torch.Tensor:

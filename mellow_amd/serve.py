@@ -59,6 +59,14 @@ class EnginePool:
             return self.engines[slot].generate(a1, a2, ids, **kw)     # ctypes releases the GIL inside the call
 
     def generate_many(self, batches: Sequence, **kw):
-        """batches: sequence of (audio1, audio2, input_ids); returns the per-batch results of Engine.generate, in order."""
-        futs = [self._pool.submit(self._run, i % len(self.engines), b, kw) for i, b in enumerate(batches)]
+        """batches: sequence of (audio1, audio2, input_ids); returns the per-batch results of Engine.generate, in order.
+        With do_sample=True batch k samples as rows row_offset + (rows of the batches before it) of one concatenated list,
+        so the result does not depend on how many contexts run the batches or which one gets which."""
+        kws = [kw] * len(batches)
+        if kw.get("do_sample"):
+            off, kws = int(kw.get("row_offset", 0)), []
+            for b in batches:
+                kws.append(dict(kw, row_offset=off))
+                off += int(len(b[0]))
+        futs = [self._pool.submit(self._run, i % len(self.engines), b, kws[i]) for i, b in enumerate(batches)]
         return [f.result() for f in futs]

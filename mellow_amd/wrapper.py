@@ -13,8 +13,14 @@ What is kept from the reference, quirks included: class attribu
 `ValueError` for an unknown model; `config/<config>.yaml` key layout; strict `state_dict` load with the
 'module.' retry; prompt right-padded with '!' to 129 ids; sep = token 0; pads attended; multi-channel wav
 flattened not mixed; crop start from the unseeded `random` module; sampling parameters accepted but the result
-is greedy for every value (the reference's top-p filter never removes the arg-max, wrapper.py:220-232); the
+is greedy for every value (the reference's top-p filter never removes the arg-max, wrapper.py:220-232) -- the default
+call stays exactly that; the
 loop stops only when every row has produced the stop id; text is cut at the first '<|endoftext|>'.
+Extension (opt-in, keyword-only): `generate(..., do_sample=True, seed=s)` draws every token by seeded nucleus sampling
+inside the captured decode step -- z = logits / temperature, the nucleus of the reference's rule (a token is kept iff the
+softmax mass strictly before it in (z desc, index asc) order is <= top_p), then Gumbel-max with Philox4x32-10 noise keyed by
+(seed, row, step); include/mellow_hip.h mellow_generate_sampled gives the exact definition.  seed=None draws a 63-bit seed from
+`random` (kept as `last_seed`); under data parallelism the seed must be given and equal on every rank.
 Deviations: `tqdm` progress output is not produced; the B>1/steps==1 mis-shape and B==1/steps==1 crash of
 reference wrapper.py:251-253 are not reproduced (one string per example is always returned).
 """
@@ -23,6 +29,7 @@ from __future__ import annotations
 import argparse
 import math
 import os
+import random
 import warnings
 from collections import OrderedDict
 from pathlib import Path
@@ -57,6 +64,7 @@ class MellowWrapper:
 
     model_repo = "soham97/mellow"
     model_name = {"v0": "v0.ckpt", "v0_s": "v0_s.ckpt"}
+    last_seed: Optional[int] = None      # seed of the last generate(do_sample=True) call
 
     def __init__(self, config, model, device, use_cuda=True, *, checkpoint: Optional[str] = None,
                  state_dict: Optional[Dict[str, torch.Tensor]] = None, tokenizer=None, max_positions: Optional[int] = None,
@@ -215,13 +223,13 @@ class MellowWrapper:
             return dist.get_rank(), dist.get_world_size()
         return 0, 1
 
-    def _check_same_examples(self, examples):
+    def _check_same_examples(self, examples, extra: bytes = b""):
         """Sharding is only meaningful when every rank was handed the same list: compare (count, content digest) across ranks and
         raise on every rank otherwise (a silent mismatch would return other ranks' texts, or hang in the gather).  The exchange
         runs over the process group's rendezvous store (mellow_amd.dist.agree_on_examples): the token all-gather is the only
         collective of the call."""
         from . import dist as mdist
-        mdist.agree_on_examples(mdist.examples_signature(examples))
+        mdist.agree_on_examples(mdist.examples_signature(examples) + extra)
 
     def _clamp_max_len(self, entry_length: int) -> int:
         limit = self.model.max_new_tokens_limit()
@@ -233,7 +241,8 @@ class MellowWrapper:
         return entry_length
 
     def _generate_batch(self, audio1, audio2, input_ids, entry_length=300, top_p=0.8, temperature=1.0,
-                        stop_token: str = "<|endoftext|>", n_total: Optional[int] = None):
+                        stop_token: str = "<|endoftext|>", n_total: Optional[int] = None, do_sample: bool = False,
+                        seed: Optional[int] = None, row_offset: int = 0):
         """Tokens for the rows given (this rank's shard under data parallelism), decoded for ALL `n_total` examples:
         the shards' token ids are all-gathered once (mellow_amd.dist, RCCL over xGMI under backend "nccl")."""
         stop_token_index = self.tokenizer.encode(stop_token)[0]
@@ -241,8 +250,9 @@ class MellowWrapper:
         rank, world = self._dp()
         n_local = int(audio1.shape[0])
         if n_local:
+            samp = dict(do_sample=True, seed=seed, row_offset=row_offset) if do_sample else {}
             toks, lens, steps, ftm = self.model.generate(audio1, audio2, input_ids, max_len=entry_length, top_p=top_p,
-                                                         temperature=temperature, stop_id=stop_token_index)
+                                                         temperature=temperature, stop_id=stop_token_index, **samp)
             self.last_first_token_ms = ftm
         else:
             toks, lens = np.zeros((0, 0), dtype=np.int32), np.zeros((0,), dtype=np.int32)
@@ -255,11 +265,13 @@ class MellowWrapper:
         rows = [r[r >= 0] for r in toks]
         return [self.tokenizer.decode(x).split("<|endoftext|>")[0] for x in rows]
 
-    def generate(self, examples, max_len, top_p, temperature, stop_token="<|endoftext|>", audio_resample=True):
+    def generate(self, examples, max_len, top_p, temperature, stop_token="<|endoftext|>", audio_resample=True, *,
+                 do_sample: bool = False, seed: Optional[int] = None):
         r"""Produces text response for the given audio files and text prompts
         examples: (list<list>) each example is [audio path 1, audio path 2, text prompt]
         max_len: (int) maximum length for text generation
-        top_p, temperature: accepted for API parity; decoding is greedy (see module docstring)
+        top_p, temperature: accepted for API parity; decoding is greedy (see module docstring) unless do_sample
+        do_sample, seed: opt-in seeded nucleus sampling (module docstring); seed=None draws one (kept as `last_seed`)
         stop_token: (str) token used to stop text generation
         audio_resample (bool) True for resampling audio. The model supports only 32 kHz
 
@@ -276,10 +288,19 @@ class MellowWrapper:
         n = len(examples)
         if n == 0:          # the reference fails in torch.cat(audio_tensors) (wrapper.py:178) on an empty list
             raise RuntimeError("torch.cat(): expected a non-empty list of Tensors")
+        extra = b""
+        if do_sample:
+            if seed is None:
+                if world > 1:       # every rank raises here: no rank reaches the agreement or the gather
+                    raise ValueError("data_parallel generate(do_sample=True) needs an explicit seed, the same on every rank")
+                seed = random.getrandbits(63)
+            seed = int(seed)
+            self.last_seed = seed
+            extra = repr(("sample", seed, float(top_p), float(temperature))).encode()
         lo, hi = 0, n
         if world > 1:
             from .dist import shard_range
-            self._check_same_examples(examples)
+            self._check_same_examples(examples, extra)      # a sampling mismatch is refused by the same exchange
             lo, hi = shard_range(n, rank, world)
         if hi > lo:
             audio1 = self.preprocess_audio(audio_paths1[lo:hi], resample=audio_resample)
@@ -289,4 +310,5 @@ class MellowWrapper:
             audio1 = audio2 = torch.zeros((0, 1))
             ids = torch.zeros((0, spec.TEXT_LEN), dtype=torch.int64)
         return self._generate_batch(audio1, audio2, ids, entry_length=max_len, top_p=top_p,
-                                    temperature=temperature, stop_token=stop_token, n_total=n)
+                                    temperature=temperature, stop_token=stop_token, n_total=n, do_sample=do_sample,
+                                    seed=seed, row_offset=lo)
