@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """Build libmellow_hip.so for gfx950 with hipcc (cross-compiles without a GPU).
 
-    python mellow_amd/csrc/build.py [--force] [--verbose]
+    python mellow_amd/csrc/build.py [--force] [--verbose] [--out PATH] [--objdir DIR]
 
 Objects are cached under mellow_amd/csrc/build/ (git-ignored) keyed on source mtimes; the shared
-library lands in mellow_amd/lib/ (git-ignored, but shipped to the GPU box by gpurun)."""
+library lands in mellow_amd/lib/ (git-ignored).  A variant for a same-box A/B
+(tools/ab_build.sh, tools/ab_decode.sh) is this build with MELLOW_EXTRA_FLAGS="-D..." and a library path and an object
+directory of its own (--out, --objdir), so that the source list and the per-file flags exist once."""
 from __future__ import annotations
 
 import argparse
@@ -53,16 +55,18 @@ KERNARG_PRELOAD = [] if os.environ.get("MELLOW_KERNARG_PRELOAD", "14") == "0" el
 FILE_FLAGS["decode.hip"] = FILE_FLAGS.get("decode.hip", []) + KERNARG_PRELOAD
 
 
-def build(force=False, verbose=False):
-    os.makedirs(LIBDIR, exist_ok=True)
-    os.makedirs(OBJDIR, exist_ok=True)
+def build(force=False, verbose=False, out=None, objdir=None):
+    lib = os.path.abspath(out) if out else LIB
+    objdir = os.path.abspath(objdir) if objdir else OBJDIR
+    os.makedirs(os.path.dirname(lib), exist_ok=True)
+    os.makedirs(objdir, exist_ok=True)
     hipcc = _hipcc()
     hdrs = [os.path.join(HERE, h) for h in HEADERS] + [os.path.abspath(__file__)]
     jobs = []
     objs = []
     for src in SOURCES:
         sp = os.path.join(HERE, src)
-        op = os.path.join(OBJDIR, src + ".o")
+        op = os.path.join(objdir, src + ".o")
         objs.append(op)
         if force or _stale(op, [sp] + hdrs):
             jobs.append((sp, op))
@@ -82,20 +86,22 @@ def build(force=False, verbose=False):
                 raise RuntimeError(f"hipcc failed on {sp}")
             if verbose and r.stderr.strip():
                 sys.stderr.write(r.stderr)
-    if force or jobs or _stale(LIB, objs):
-        cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", LIB] + objs
+    if force or jobs or _stale(lib, objs):
+        cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", lib] + objs
         if verbose:
             print(" ".join(cmd), flush=True)
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             sys.stderr.write(r.stdout + r.stderr)
             raise RuntimeError("link failed")
-    return LIB
+    return lib
 
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--force", action="store_true")
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--out", metavar="PATH", help="write the library here instead of mellow_amd/lib/libmellow_hip.so")
+    ap.add_argument("--objdir", metavar="DIR", help="object cache of this build instead of mellow_amd/csrc/build/")
     a = ap.parse_args()
-    print(build(a.force, a.verbose))
+    print(build(a.force, a.verbose, a.out, a.objdir))

@@ -25,6 +25,7 @@
 #include <cstdio>
 #include <mutex>
 #include <set>
+#include <type_traits>
 #include <utility>
 
 namespace mellow {
@@ -2143,70 +2144,53 @@ void set_max_dynamic_lds(const void* fn, size_t bytes) {
         if (e != hipSuccess) fprintf(stderr, "mellow: hipFuncSetAttribute(max dynamic LDS %zu) failed: %s\n", bytes, hipGetErrorString(e));
     }
 }
-// BLK = per-row-block early exit compiled in (a.blk_live != null); W8 = e4m3 weights (wscale != null): chosen on the host
-#define MELLOW_LAUNCH_BLK(KERNEL, GRID, BLOCK, ...)                                                               \
-    do {                                                                                                         \
-        if (a.blk_live) hipLaunchKernelGGL((KERNEL<true>), GRID, BLOCK, 0, s, __VA_ARGS__);                       \
-        else hipLaunchKernelGGL((KERNEL<false>), GRID, BLOCK, 0, s, __VA_ARGS__);                                 \
-    } while (0)
+// Every decode kernel is a template over a few switches that the host knows only at run time.  These helpers turn one such value
+// into a compile-time constant (a std::integral_constant) and hand it to a generic lambda, so that a launcher names its kernel, its
+// grid and its arguments once.  A launcher nests them for the LEGAL combinations only: a kernel exists for what is spelled here.
+template <class F> static inline void with_bool(bool v, F&& f) {
+    if (v) f(std::true_type{}); else f(std::false_type{});
+}
+// one value out of a fixed list; the last entry also serves every value that is not listed (the `else` of a ladder)
+template <int V0, int... Vs, class F> static inline void with_int(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V0>{});
+    else if (v == V0) f(std::integral_constant<int, V0>{});
+    else with_int<Vs...>(v, f);
+}
 // weight mode of a launch: 0 fp32, 1 e4m3 weights widened to fp32, 2 e4m3 weights and activations on the fp8 matrix pipe (a.a8)
 static inline int w8_mode(const DecArgs& a, const float* wscale) { return wscale ? (a.a8 ? 2 : 1) : 0; }
-#define MELLOW_LAUNCH_BLK_W8(KERNEL, GRID, BLOCK, ...)                                                            \
-    do {                                                                                                         \
-        const int mode_ = w8_mode(a, wscale);                                                                    \
-        if (a.blk_live && mode_ == 2) hipLaunchKernelGGL((KERNEL<true, 2>), GRID, BLOCK, 0, s, __VA_ARGS__, wscale);    \
-        else if (a.blk_live && mode_ == 1) hipLaunchKernelGGL((KERNEL<true, 1>), GRID, BLOCK, 0, s, __VA_ARGS__, wscale); \
-        else if (a.blk_live) hipLaunchKernelGGL((KERNEL<true, 0>), GRID, BLOCK, 0, s, __VA_ARGS__, wscale);              \
-        else if (mode_ == 2) hipLaunchKernelGGL((KERNEL<false, 2>), GRID, BLOCK, 0, s, __VA_ARGS__, wscale);             \
-        else if (mode_ == 1) hipLaunchKernelGGL((KERNEL<false, 1>), GRID, BLOCK, 0, s, __VA_ARGS__, wscale);             \
-        else hipLaunchKernelGGL((KERNEL<false, 0>), GRID, BLOCK, 0, s, __VA_ARGS__, wscale);                             \
-    } while (0)
+// f(BLK, W8): BLK = per-row-block early exit compiled in (a.blk_live != null); W8 = the weight mode (wscale != null: e4m3 weights)
+template <class F> static inline void with_blk_w8(const DecArgs& a, const float* wscale, F&& f) {
+    with_bool(a.blk_live != nullptr, [&](auto blk) { with_int<2, 1, 0>(w8_mode(a, wscale), [&](auto w8) { f(blk, w8); }); });
+}
 void launch_dec_qkv(const DecArgs& a, const float* Wp, int K8p, int kcd, hipStream_t s, const float* wscale) {
     const dim3 grid(30, DEC_KC_QKV, a.RB);
     // the first qkv launch of a step (a.first) always starts from a materialised x (kcd == 0); later ones sum the down slabs
-#define MELLOW_QKV(KCD, FIRST)                                                                              \
-    do {                                                                                                    \
-        const int mode_ = w8_mode(a, wscale);                                                                \
-        if (a.blk_live && mode_ == 2) hipLaunchKernelGGL((dec_qkv_kernel<KCD, true, FIRST, 2>), grid, dim3(QKV_THREADS), 0, s, Wp, (const float*)a.xmidF, (const float*)a.dslabF, K8p, a, wscale);   \
-        else if (a.blk_live && mode_ == 1) hipLaunchKernelGGL((dec_qkv_kernel<KCD, true, FIRST, 1>), grid, dim3(QKV_THREADS), 0, s, Wp, (const float*)a.xmidF, (const float*)a.dslabF, K8p, a, wscale);   \
-        else if (a.blk_live) hipLaunchKernelGGL((dec_qkv_kernel<KCD, true, FIRST, 0>), grid, dim3(QKV_THREADS), 0, s, Wp, (const float*)a.xmidF, (const float*)a.dslabF, K8p, a, wscale);        \
-        else if (mode_ == 2) hipLaunchKernelGGL((dec_qkv_kernel<KCD, false, FIRST, 2>), grid, dim3(QKV_THREADS), 0, s, Wp, (const float*)a.xmidF, (const float*)a.dslabF, K8p, a, wscale);            \
-        else if (mode_ == 1) hipLaunchKernelGGL((dec_qkv_kernel<KCD, false, FIRST, 1>), grid, dim3(QKV_THREADS), 0, s, Wp, (const float*)a.xmidF, (const float*)a.dslabF, K8p, a, wscale);            \
-        else hipLaunchKernelGGL((dec_qkv_kernel<KCD, false, FIRST, 0>), grid, dim3(QKV_THREADS), 0, s, Wp, (const float*)a.xmidF, (const float*)a.dslabF, K8p, a, wscale);                       \
-    } while (0)
-    if (kcd == 0 && a.first) MELLOW_QKV(0, true);
-    else if (kcd == 0) MELLOW_QKV(0, false);
-    else if (a.first) MELLOW_QKV(DEC_KC_DOWN, true);
-    else MELLOW_QKV(DEC_KC_DOWN, false);
-#undef MELLOW_QKV
+    with_int<0, DEC_KC_DOWN>(kcd, [&](auto kcd_c) { with_bool(a.first != 0, [&](auto first) { with_blk_w8(a, wscale, [&](auto blk, auto w8) {
+        hipLaunchKernelGGL((dec_qkv_kernel<kcd_c.value, blk.value, first.value, w8.value>), grid, dim3(QKV_THREADS), 0, s, Wp, (const float*)a.xmidF,
+                           (const float*)a.dslabF, K8p, a, wscale);
+    }); }); });
 }
 void launch_dec_attn(const DecArgs& a, float* k_cache, float* v_cache, bool fused, hipStream_t s) {
-    const dim3 grid(3, a.rows, a.ts), block(DA_WAVES * 64);
+    const dim3 grid(3, a.rows, a.ts);
     const bool one = a.RB == 1 && !a.blk_live;
     if (a.ts != DEC_TS && (one || a.kv16 || a.ts != DEC_TS_MULTI)) {      // kernels.h dec_key_splits
         fprintf(stderr, "mellow: decode attention launched with %d key splits at RB = %d\n", a.ts, a.RB);
         abort();
     }
-    // bf16 pages, matrix form: MELLOW_DA16_NW physical waves from two row blocks on -- kernel comment at DA_GM
-#define MELLOW_DA(BLKV, FUSEDV, ONEV)                                                                                    \
-    do {                                                                                                                 \
-        constexpr int NW16 = MELLOW_DA16_MFMA && DA_WAVES == 8 && !(ONEV) ? MELLOW_DA16_NW : DA_WAVES;                     \
-        constexpr int TSM = (ONEV) ? DEC_TS : DEC_TS_MULTI;        /* (ONE never meets another split count) */            \
-        if (a.kv16) hipLaunchKernelGGL((dec_attn_kernel<BLKV, FUSEDV, ONEV, true, NW16, DEC_TS>), grid, dim3(NW16 * 64), 0, s, k_cache, v_cache, (const int32_t*)a.d_pos, \
-                                       (const float*)a.pq, (const float*)a.xmidF, a.Tmax, a.gs, a.rows, a);               \
-        else if (a.ts == DEC_TS) hipLaunchKernelGGL((dec_attn_kernel<BLKV, FUSEDV, ONEV, false, DA_WAVES, DEC_TS>), grid, block, 0, s, k_cache, v_cache, (const int32_t*)a.d_pos, \
-                                                    (const float*)a.pq, (const float*)a.xmidF, a.Tmax, a.gs, a.rows, a);  \
-        else hipLaunchKernelGGL((dec_attn_kernel<BLKV, FUSEDV, ONEV, false, DA_WAVES, TSM>), grid, block, 0, s, k_cache, v_cache, (const int32_t*)a.d_pos, \
-                                (const float*)a.pq, (const float*)a.xmidF, a.Tmax, a.gs, a.rows, a);                      \
-    } while (0)
+    auto launch = [&](auto blk, auto one_c) { with_bool(fused, [&](auto fused_c) { with_bool(a.kv16 != 0, [&](auto kv16) {
+        constexpr bool ONE = one_c.value, KV16 = kv16.value;
+        // bf16 pages, matrix form: MELLOW_DA16_NW physical waves from two row blocks on -- kernel comment at DA_GM
+        constexpr int NW = !KV16 ? DA_WAVES : MELLOW_DA16_MFMA && DA_WAVES == 8 && !ONE ? MELLOW_DA16_NW : DA_WAVES;
+        // the split count: ONE never meets another than DEC_TS, and the bf16 pages always run DEC_TS
+        constexpr int TSM = ONE || KV16 ? DEC_TS : DEC_TS_MULTI;
+        with_int<DEC_TS, TSM>(a.ts, [&](auto ts) {
+            hipLaunchKernelGGL((dec_attn_kernel<blk.value, fused_c.value, ONE, KV16, NW, ts.value>), grid, dim3(NW * 64), 0, s, k_cache, v_cache,
+                               (const int32_t*)a.d_pos, (const float*)a.pq, (const float*)a.xmidF, a.Tmax, a.gs, a.rows, a);
+        });
+    }); }); };
     // (the per-block early exit exists only with more than one row block, so <BLK, ONE> never meet)
-    if (one) {
-        if (fused) MELLOW_DA(false, true, true); else MELLOW_DA(false, false, true);
-    } else if (a.blk_live && fused) MELLOW_DA(true, true, false);
-    else if (a.blk_live) MELLOW_DA(true, false, false);
-    else if (fused) MELLOW_DA(false, true, false);
-    else MELLOW_DA(false, false, false);
-#undef MELLOW_DA
+    if (one) launch(std::false_type{}, std::true_type{});
+    else with_bool(a.blk_live != nullptr, [&](auto blk) { launch(blk, std::false_type{}); });
 }
 // fp32 form: Wq2 = [30][Q2_K8] (W' | W' Wd);  e4m3 form (sc_x != null): three separately quantised matrices (kernel comment)
 static void launch_dec_qkv2_any(const DecArgs& a, const float* Wx, int K8x, const float* Wh, int K8h, const float* Wd,
@@ -2219,66 +2203,47 @@ static void launch_dec_qkv2_any(const DecArgs& a, const float* Wx, int K8x, cons
 #else
     bool few = a.RB == 1;
 #endif
-    const int mode = w8_mode(a, sc_x);
     // (activations on the fp8 pipe: a wave's k-slice is the unit of the activation scale, so the wave count must not depend on
     //  the batch size -- a row's tokens would otherwise change with the number of row blocks around it)
-    if (mode == 2) few = false;
-#define MELLOW_Q2(BLKV, WV, MODE) \
-    hipLaunchKernelGGL((dec_qkv2_kernel<BLKV, WV, MODE>), grid, dim3(WV * 64), 0, s, Wx, Wh, Wd, (const float*)a.xmidF, (const float*)a.guF, \
-                       K8x, K8h, a, sc_x, sc_h, sc_d)
-#define MELLOW_Q2_MODES(BLKV, WV)                  \
-    do {                                           \
-        if (mode == 2) MELLOW_Q2(BLKV, WV, 2);     \
-        else if (mode == 1) MELLOW_Q2(BLKV, WV, 1);\
-        else MELLOW_Q2(BLKV, WV, 0);               \
-    } while (0)
-    if (few) {
-        if (a.blk_live) MELLOW_Q2_MODES(true, 4); else MELLOW_Q2_MODES(false, 4);
-    } else {
-        if (a.blk_live) MELLOW_Q2_MODES(true, Q2_WAVES); else MELLOW_Q2_MODES(false, Q2_WAVES);
-    }
-#undef MELLOW_Q2_MODES
-#undef MELLOW_Q2
+    if (w8_mode(a, sc_x) == 2) few = false;
+    with_bool(few, [&](auto few_c) { with_blk_w8(a, sc_x, [&](auto blk, auto w8) {
+        constexpr int WV = few_c.value ? 4 : Q2_WAVES;
+        hipLaunchKernelGGL((dec_qkv2_kernel<blk.value, WV, w8.value>), grid, dim3(WV * 64), 0, s, Wx, Wh, Wd, (const float*)a.xmidF,
+                           (const float*)a.guF, K8x, K8h, a, sc_x, sc_h, sc_d);
+    }); });
 }
-// The launchers raise a kernel's dynamic-LDS limit on first use; a decode step is launched inside a stream capture, so the engine
-// calls this once per device beforehand (ensure_lm): every instantiation that needs more than 64 KiB.
-void dec_prepare_lds_attributes() {
-    const size_t head = (size_t)36 * 3 * 64 * 16, q4 = (size_t)Q3W * 4 * 16 * 64 * 4;
-    set_max_dynamic_lds(reinterpret_cast<const void*>(&dec_head3r_kernel<1, MELLOW_H3R_D1, true>), head);
-    set_max_dynamic_lds(reinterpret_cast<const void*>(&dec_head3r_kernel<1, MELLOW_H3R_D1, false>), head);
-    set_max_dynamic_lds(reinterpret_cast<const void*>(&dec_head3r_kernel<2, MELLOW_H3R_D2, true>), head);
-    set_max_dynamic_lds(reinterpret_cast<const void*>(&dec_head3r_kernel<2, MELLOW_H3R_D2, false>), head);
-    set_max_dynamic_lds(reinterpret_cast<const void*>(&dec_head3r_kernel<4, MELLOW_H3R_D4, true>), head);
-    set_max_dynamic_lds(reinterpret_cast<const void*>(&dec_head3r_kernel<4, MELLOW_H3R_D4, false>), head);
-    set_max_dynamic_lds(reinterpret_cast<const void*>(&dec_qkv2x3_kernel<true, 4>), q4);
-    set_max_dynamic_lds(reinterpret_cast<const void*>(&dec_qkv2x3_kernel<false, 4>), q4);
+// The kernels with dynamic LDS: one function per family states the byte count, and one hands f(kernel, bytes) the instantiation
+// that serves `rb` row blocks (>= 1; RBM / G = 1, 2, or 4 for every larger count) -- to the launcher and to
+// dec_prepare_lds_attributes alike.
+constexpr size_t dec_qkv2x3_lds(int rbm) { return (size_t)Q3W * rbm * 16 * 64 * 4; }
+constexpr size_t dec_gateup3_lds(int rbm) { return (size_t)GU3W * rbm * 8 * 64 * 4; }
+constexpr size_t dec_head3r_lds() { return (size_t)36 * 3 * 64 * 16; }
+template <class F> static inline void with_qkv2x3(int rb, bool blk, F&& f) {
+    with_int<1, 2, 4>(rb, [&](auto rbm) { with_bool(blk, [&](auto b) { f(&dec_qkv2x3_kernel<b.value, rbm.value>, dec_qkv2x3_lds(rbm.value)); }); });
+}
+template <class F> static inline void with_gateup3(int rb, bool blk, F&& f) {
+    with_int<1, 2, 4>(rb, [&](auto rbm) { with_bool(blk, [&](auto b) { f(&dec_gateup3_kernel<b.value, rbm.value>, dec_gateup3_lds(rbm.value)); }); });
+}
+template <class F> static inline void with_head3r(int rb, bool blk, F&& f) {
+    with_int<1, 2, 4>(rb, [&](auto g) { with_bool(blk, [&](auto b) {
+        constexpr int G = g.value, D = G == 1 ? MELLOW_H3R_D1 : G == 2 ? MELLOW_H3R_D2 : MELLOW_H3R_D4;      // weight chunks in flight
+        f(&dec_head3r_kernel<G, D, b.value>, dec_head3r_lds());
+    }); });
 }
 void launch_dec_qkv2x3(const DecArgs& a, const float* Wq2, const float* Wd, hipStream_t s) {
     const float* Wh = Wq2 + (size_t)72 * 64 * 4;
     const i32x4 *x3 = reinterpret_cast<const i32x4*>(a.xmid3_32), *h3 = reinterpret_cast<const i32x4*>(a.h3);
-#define MELLOW_Q3(BLKV, RBMV)                                                                                        \
-    do {                                                                                                             \
-        const size_t lds = (size_t)Q3W * RBMV * 16 * 64 * 4;                                                         \
-        set_max_dynamic_lds(reinterpret_cast<const void*>(&dec_qkv2x3_kernel<BLKV, RBMV>), lds);                             \
-        hipLaunchKernelGGL((dec_qkv2x3_kernel<BLKV, RBMV>), dim3(Q2_BLOCKS), dim3(Q3W * 64), lds, s, Wq2, Wh, Wd, x3, h3, Q2_K8, Q2_K8, a.RB, a); \
-    } while (0)
-    if (a.RB <= 1) { if (a.blk_live) MELLOW_Q3(true, 1); else MELLOW_Q3(false, 1); }
-    else if (a.RB == 2) { if (a.blk_live) MELLOW_Q3(true, 2); else MELLOW_Q3(false, 2); }
-    else { if (a.blk_live) MELLOW_Q3(true, 4); else MELLOW_Q3(false, 4); }
-#undef MELLOW_Q3
+    with_qkv2x3(a.RB, a.blk_live != nullptr, [&](auto* kernel, size_t lds) {
+        set_max_dynamic_lds(reinterpret_cast<const void*>(kernel), lds);
+        hipLaunchKernelGGL(kernel, dim3(Q2_BLOCKS), dim3(Q3W * 64), lds, s, Wq2, Wh, Wd, x3, h3, Q2_K8, Q2_K8, a.RB, a);
+    });
 }
 void launch_dec_gateup3(const DecArgs& a, const float* Wp16, hipStream_t s) {
     const i32x4* x3 = reinterpret_cast<const i32x4*>(a.xmid3_16);
-#define MELLOW_G3(BLKV, RBMV)                                                                                        \
-    do {                                                                                                             \
-        const size_t lds = (size_t)GU3W * RBMV * 8 * 64 * 4;                                                         \
-        set_max_dynamic_lds(reinterpret_cast<const void*>(&dec_gateup3_kernel<BLKV, RBMV>), lds);                            \
-        hipLaunchKernelGGL((dec_gateup3_kernel<BLKV, RBMV>), dim3(192), dim3(GU3W * 64), lds, s, Wp16, x3, (const float*)a.ssq, a.RB, a); \
-    } while (0)
-    if (a.RB <= 1) { if (a.blk_live) MELLOW_G3(true, 1); else MELLOW_G3(false, 1); }
-    else if (a.RB == 2) { if (a.blk_live) MELLOW_G3(true, 2); else MELLOW_G3(false, 2); }
-    else { if (a.blk_live) MELLOW_G3(true, 4); else MELLOW_G3(false, 4); }
-#undef MELLOW_G3
+    with_gateup3(a.RB, a.blk_live != nullptr, [&](auto* kernel, size_t lds) {
+        set_max_dynamic_lds(reinterpret_cast<const void*>(kernel), lds);      // (beyond 64 KiB only with more waves: MELLOW_GU3_WAVES)
+        hipLaunchKernelGGL(kernel, dim3(192), dim3(GU3W * 64), lds, s, Wp16, x3, (const float*)a.ssq, a.RB, a);
+    });
 }
 void launch_dec_qkv2(const DecArgs& a, const float* Wq2, const float* Wd, hipStream_t s) {
     launch_dec_qkv2_any(a, Wq2, Q2_K8, Wq2 + (size_t)72 * 64 * 4, Q2_K8, Wd, nullptr, nullptr, nullptr, s);
@@ -2315,40 +2280,28 @@ void launch_dec_oproj(const DecArgs& a, const float* Wp16, hipStream_t s, const 
 #else
     const int rows = a.RB == 1 ? 8 : 16;
 #endif
-#define MELLOW_OPROJ_L(BLKV, W8V, ROWSV, TSV, PARTSV)                                                                      \
-    hipLaunchKernelGGL((dec_oproj_kernel<BLKV, W8V, ROWSV, TSV>), dim3(36, PARTSV * a.RB), dim3(OP_WAVES * 64), 0, s, Wp16,    \
-                       (const float*)a.attF16, (const float*)a.att_ml, (const float*)a.xnewR, a.RB, a.rows, a, wscale)
-#define MELLOW_OPROJ(BLKV, W8V)                                                                                             \
-    do {                                                                                                                    \
-        if (rows == 8 && a.ts == 1) MELLOW_OPROJ_L(BLKV, W8V, 8, 1, 4);                                                     \
-        else if (rows == 8) MELLOW_OPROJ_L(BLKV, W8V, 8, DEC_TS, 4);                                                        \
-        else if (a.ts == 1) MELLOW_OPROJ_L(BLKV, W8V, 16, 1, 2);                                                            \
-        else MELLOW_OPROJ_L(BLKV, W8V, 16, DEC_TS, 2);                                                                      \
-    } while (0)
-    const int mode = w8_mode(a, wscale);
-    if (a.blk_live && mode == 2) MELLOW_OPROJ(true, 2);
-    else if (a.blk_live && mode == 1) MELLOW_OPROJ(true, 1);
-    else if (a.blk_live) MELLOW_OPROJ(true, 0);
-    else if (mode == 2) MELLOW_OPROJ(false, 2);
-    else if (mode == 1) MELLOW_OPROJ(false, 1);
-    else MELLOW_OPROJ(false, 0);
-#undef MELLOW_OPROJ
-#undef MELLOW_OPROJ_L
+    with_int<8, 16>(rows, [&](auto rows_c) { with_int<1, DEC_TS>(a.ts, [&](auto ts) { with_blk_w8(a, wscale, [&](auto blk, auto w8) {
+        constexpr int ROWS = rows_c.value, PARTS = ROWS == 8 ? 4 : 2;        // the two forms of the kernel: 8 rows x 4 parts, 16 rows x 2 parts
+        hipLaunchKernelGGL((dec_oproj_kernel<blk.value, w8.value, ROWS, ts.value>), dim3(36, PARTS * a.RB), dim3(OP_WAVES * 64), 0, s, Wp16,
+                           (const float*)a.attF16, (const float*)a.att_ml, (const float*)a.xnewR, a.RB, a.rows, a, wscale);
+    }); }); });
 }
 void launch_dec_gateup(const DecArgs& a, const float* Wp16, hipStream_t s, const float* wscale) {
-    MELLOW_LAUNCH_BLK_W8(dec_gateup16_kernel, dim3(192, a.RB), dim3(GU_WAVES * 64), Wp16, a.xmidF16, a.ssq, a);
+    with_blk_w8(a, wscale, [&](auto blk, auto w8) {
+        hipLaunchKernelGGL((dec_gateup16_kernel<blk.value, w8.value>), dim3(192, a.RB), dim3(GU_WAVES * 64), 0, s, Wp16, a.xmidF16, a.ssq, a, wscale);
+    });
 }
 void launch_dec_down(const DecArgs& a, const float* Wp, int K8p, hipStream_t s, const float* wscale) {
-    MELLOW_LAUNCH_BLK_W8(dec_down_kernel, dim3(18, DEC_KC_DOWN, a.RB), dim3(DN_WAVES * 64), Wp, (const float*)a.guF, K8p, a);
+    with_blk_w8(a, wscale, [&](auto blk, auto w8) {
+        hipLaunchKernelGGL((dec_down_kernel<blk.value, w8.value>), dim3(18, DEC_KC_DOWN, a.RB), dim3(DN_WAVES * 64), 0, s, Wp, (const float*)a.guF,
+                           K8p, a, wscale);
+    });
 }
 void launch_dec_final_norm(const DecArgs& a, const float* norm_w, int kcd, hipStream_t s) {
-    if (kcd == 0) {
-        if (a.blk_live) hipLaunchKernelGGL((dec_final_norm_kernel<0, true>), dim3(a.rows), dim3(192), 0, s, norm_w, (const float*)a.xmidF, (const float*)a.dslabF, a.slabF_stride4, a);
-        else hipLaunchKernelGGL((dec_final_norm_kernel<0, false>), dim3(a.rows), dim3(192), 0, s, norm_w, (const float*)a.xmidF, (const float*)a.dslabF, a.slabF_stride4, a);
-    } else {
-        if (a.blk_live) hipLaunchKernelGGL((dec_final_norm_kernel<DEC_KC_DOWN, true>), dim3(a.rows), dim3(192), 0, s, norm_w, (const float*)a.xmidF, (const float*)a.dslabF, a.slabF_stride4, a);
-        else hipLaunchKernelGGL((dec_final_norm_kernel<DEC_KC_DOWN, false>), dim3(a.rows), dim3(192), 0, s, norm_w, (const float*)a.xmidF, (const float*)a.dslabF, a.slabF_stride4, a);
-    }
+    with_int<0, DEC_KC_DOWN>(kcd, [&](auto kcd_c) { with_bool(a.blk_live != nullptr, [&](auto blk) {
+        hipLaunchKernelGGL((dec_final_norm_kernel<kcd_c.value, blk.value>), dim3(a.rows), dim3(192), 0, s, norm_w, (const float*)a.xmidF,
+                           (const float*)a.dslabF, a.slabF_stride4, a);
+    }); });
 }
 // true when the streaming f32x3 lm_head (dec_head3r_kernel) tiles this vocabulary: only then may the final norm hand its output
 // over pre-split (DecArgs::xn3, which aliases xnF) -- engine_lm.cpp: ensure_lm
@@ -2356,29 +2309,30 @@ bool dec_head3r_fits(int vocab) { return vocab % 32 == 0 && (vocab / 32) % H3_NW
 void launch_dec_lm_head(const DecArgs& a, const float* Wp, int K8p, int vocab, hipStream_t s, const float* wscale) {
     if ((a.x3 & DEC_X3_HEAD) && !wscale && a.xn3 && (vocab / 32) % H3_NW == 0) {
         // f32x3 mode, activations pre-split by the final norm: the streaming form (weights read once for every row block)
-        const dim3 grid(vocab / 32 / H3_NW), block(H3_NW * 64);
         const i32x4* X3 = reinterpret_cast<const i32x4*>(a.xn3);
-#define MELLOW_H3R(GV, DV)                                                                                                \
-        do {                                                                                                              \
-            const size_t lds = (size_t)36 * 3 * 64 * 16;                                                                  \
-            if (a.blk_live) { set_max_dynamic_lds(reinterpret_cast<const void*>(&dec_head3r_kernel<GV, DV, true>), lds);  \
-                              hipLaunchKernelGGL((dec_head3r_kernel<GV, DV, true>), grid, block, lds, s, Wp, X3, K8p, vocab, a.RB, a); } \
-            else { set_max_dynamic_lds(reinterpret_cast<const void*>(&dec_head3r_kernel<GV, DV, false>), lds);             \
-                   hipLaunchKernelGGL((dec_head3r_kernel<GV, DV, false>), grid, block, lds, s, Wp, X3, K8p, vocab, a.RB, a); } \
-        } while (0)
-        if (a.RB == 1) MELLOW_H3R(1, MELLOW_H3R_D1); else if (a.RB == 2) MELLOW_H3R(2, MELLOW_H3R_D2); else MELLOW_H3R(4, MELLOW_H3R_D4);
-#undef MELLOW_H3R
+        with_head3r(a.RB, a.blk_live != nullptr, [&](auto* kernel, size_t lds) {
+            set_max_dynamic_lds(reinterpret_cast<const void*>(kernel), lds);
+            hipLaunchKernelGGL(kernel, dim3(vocab / 32 / H3_NW), dim3(H3_NW * 64), lds, s, Wp, X3, K8p, vocab, a.RB, a);
+        });
         return;
     }
     // (fp32 rows in xnF -- taps on caller rows, or a vocabulary the streaming form does not tile: the exact fp32 kernel below)
-    const dim3 grid(vocab / 32, 1, a.RB), block(LM_WAVES * 64);
-    const int mode = w8_mode(a, wscale);
-    if (a.blk_live && mode == 2) hipLaunchKernelGGL((dec_fullk_kernel<OUT_LOGITS, true, 2>), grid, block, 0, s, Wp, (const float*)a.xnF, K8p, vocab, a, wscale);
-    else if (a.blk_live && mode == 1) hipLaunchKernelGGL((dec_fullk_kernel<OUT_LOGITS, true, 1>), grid, block, 0, s, Wp, (const float*)a.xnF, K8p, vocab, a, wscale);
-    else if (a.blk_live) hipLaunchKernelGGL((dec_fullk_kernel<OUT_LOGITS, true, 0>), grid, block, 0, s, Wp, (const float*)a.xnF, K8p, vocab, a, wscale);
-    else if (mode == 2) hipLaunchKernelGGL((dec_fullk_kernel<OUT_LOGITS, false, 2>), grid, block, 0, s, Wp, (const float*)a.xnF, K8p, vocab, a, wscale);
-    else if (mode == 1) hipLaunchKernelGGL((dec_fullk_kernel<OUT_LOGITS, false, 1>), grid, block, 0, s, Wp, (const float*)a.xnF, K8p, vocab, a, wscale);
-    else hipLaunchKernelGGL((dec_fullk_kernel<OUT_LOGITS, false, 0>), grid, block, 0, s, Wp, (const float*)a.xnF, K8p, vocab, a, wscale);
+    with_blk_w8(a, wscale, [&](auto blk, auto w8) {
+        hipLaunchKernelGGL((dec_fullk_kernel<OUT_LOGITS, blk.value, w8.value>), dim3(vocab / 32, 1, a.RB), dim3(LM_WAVES * 64), 0, s, Wp,
+                           (const float*)a.xnF, K8p, vocab, a, wscale);
+    });
+}
+// The launchers raise a kernel's dynamic-LDS limit on first use; a decode step is launched inside a stream capture, so the engine
+// calls this once per device beforehand (ensure_lm): every instantiation the launchers can pick (set_max_dynamic_lds skips those
+// within 64 KiB).
+void dec_prepare_lds_attributes() {
+    const auto raise = [](auto* kernel, size_t lds) { set_max_dynamic_lds(reinterpret_cast<const void*>(kernel), lds); };
+    for (const int rb : {1, 2, 4})
+        for (const bool blk : {false, true}) {
+            with_head3r(rb, blk, raise);
+            with_qkv2x3(rb, blk, raise);
+            with_gateup3(rb, blk, raise);
+        }
 }
 // fp32 packed decode weight (P-layout: 32 rows per tile, or P16: 16 rows per tile; `slots` float4 slots per tile) -> one
 // 4-byte word of four e4m3 values per slot + one scale per packed row (amax / 448): one workgroup per tile

@@ -87,6 +87,10 @@ struct MergeW {
     float *nw, *nb;
     Packed red;
 };
+// one decode GEMM operand as the launchers take it: the e4m3 copy with its row scales when the layer holds one, else fp32
+struct DecW {
+    const float *p, *scale;            // scale == nullptr: fp32 weights
+};
 struct LMLayerW {
     Packed qkv, o, gateup, down;       // prefill (plain weights, P-layout); `down` is also the decode operand
     Packed qkv_f, gateup_f;            // decode: RMSNorm weight folded into the columns (W'[n][k] = W[n][k]*ln[k])
@@ -102,6 +106,10 @@ struct LMLayerW {
     float *qkv8 = nullptr, *qkv_sc = nullptr, *o8 = nullptr, *o_sc = nullptr, *gu8 = nullptr, *gu_sc = nullptr, *dn8 = nullptr,
           *dn_sc = nullptr;
     float *in_ln, *post_ln;
+    DecW qkv_w() const { return qkv8 ? DecW{qkv8, qkv_sc} : DecW{qkv_f.p, nullptr}; }
+    DecW o_w() const { return o8 ? DecW{o8, o_sc} : DecW{o16, nullptr}; }
+    DecW gateup_w() const { return gu8 ? DecW{gu8, gu_sc} : DecW{gu16, nullptr}; }
+    DecW down_w() const { return dn8 ? DecW{dn8, dn_sc} : DecW{down.p, nullptr}; }
 };
 
 struct ProfRec {
@@ -207,6 +215,7 @@ struct mellow_engine {
     bool fp8_attn_bf16 = true;                   // fp8 mode: prefill attention on operands rounded once to bf16 (option "fp8_attn_bf16" = 0: the exact 3-way split)
     bool fp8_prefill = true;                     // fp8 mode: e4m3 GEMMs in encoder + prefill (option "fp8_prefill" = 0: a test isolating the decode weights)
     float *head8 = nullptr, *head_sc = nullptr;  // e4m3 lm_head for the decode step
+    DecW head_w() const { return head8 ? DecW{head8, head_sc} : DecW{lm_head.p, nullptr}; }
     int dec_x3_min_rb = 2;                       // ... and the fewest 32-row blocks at which the layer GEMM launches take their f32x3 forms (option "decode_x3_min_rb")
     int dec_x3 = 0;                              // f32x3 mode: DEC_X3_* mask of the decode GEMM launches on the bf16 pipe (option "decode_x3", developer A/B)
     int f32x3_terms = 0;                         // 0 = off; 6 = fp32 GEMMs on the bf16 pipe by exact 3-way operand splitting (six partial products)

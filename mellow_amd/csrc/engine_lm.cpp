@@ -138,8 +138,8 @@ int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec)
     { ProfScope ps(e, PF_NORM, 0, (double)(pending_kcd + 2) * Bp * 576 * 4);
       launch_dec_final_norm(dh(0), e->final_norm, pending_kcd, e->stream); }
     { ProfScope ps(e, PF_SKINNY, 2.0 * Bp * 576.0 * e->cfg.vocab_size, 576.0 * e->cfg.vocab_size * 4);
-      if (e->head8) launch_dec_lm_head(dh(1), e->head8, e->lm_head.KP / 8, e->cfg.vocab_size, e->stream, e->head_sc);
-      else launch_dec_lm_head(dh(1), e->lm_head.p, e->lm_head.KP / 8, e->cfg.vocab_size, e->stream); }
+      const DecW h = e->head_w();
+      launch_dec_lm_head(dh(1), h.p, e->lm_head.KP / 8, e->cfg.vocab_size, e->stream, h.scale); }
     { ProfScope ps(e, PF_MISC, 0, 0);
       if (e->sample_on) {          // mellow_generate_sampled: the head stored the logits (da.logits); draw instead of the arg-max
           SampleArgs sa;
@@ -328,6 +328,7 @@ int enqueue_decode_layer_range(mellow_engine* e, int B, int l_begin, int l_end, 
 #endif
     for (int l = l_begin; l < l_end; ++l) {
         const LMLayerW& w = e->layers[same_w ? 0 : l];
+        const DecW qkv = w.qkv_w(), o = w.o_w(), gu = w.gateup_w(), dn = w.down_w();      // fp32, or e4m3 + row scales (fp8 mode)
         // (KV16: the bf16 shadow pages; a layer's pages are half as many floats)
         float* kc = e->kv16 ? e->kcache16.p + kv_layer_floats(e) / 2 * (same_kv ? 0 : l) : e->kcache.p + kv_layer_floats(e) * (same_kv ? 0 : l);
         float* vc = e->kv16 ? e->vcache16.p + kv_layer_floats(e) / 2 * (same_kv ? 0 : l) : e->vcache.p + kv_layer_floats(e) * (same_kv ? 0 : l);
@@ -349,20 +350,17 @@ int enqueue_decode_layer_range(mellow_engine* e, int B, int l_begin, int l_end, 
         a.inc_pos = (inc_pos && l == l_begin) ? 1 : 0;     // ... and advances the position word
         if (!(skip & 1) && !fused_in)
         { ProfScope ps(e, PF_SKINNY, 2.0 * Bp * 576.0 * 960.0, 576.0 * 960.0 * 4);
-          if (w.qkv8) launch_dec_qkv(a, w.qkv8, w.qkv_f.KP / 8, kcd, s, w.qkv_sc);
-          else launch_dec_qkv(a, w.qkv_f.p, w.qkv_f.KP / 8, kcd, s); }
+          launch_dec_qkv(a, qkv.p, w.qkv_f.KP / 8, kcd, s, qkv.scale); }
         if (!(skip & 2))
         { ProfScope ps(e, PF_DECODE_ATTN, 4.0 * 64 * 9 * (double)B * (e->cur_pos + 1), 2.0 * (double)B * 3 * 64 * 4 * (e->cur_pos + 1));
           launch_dec_attn(da(1), kc, vc, fused_in, s); }
         if (!(skip & 4))
         { ProfScope ps(e, PF_SKINNY, 2.0 * Bp * 576.0 * 576.0, 576.0 * 576.0 * 4);
-          if (w.o8) launch_dec_oproj(da(2), w.o8, s, w.o_sc);
-          else launch_dec_oproj(da(2), w.o16, s); }
+          launch_dec_oproj(da(2), o.p, s, o.scale); }
         if (!(skip & 8))
         { ProfScope ps(e, PF_SKINNY, 2.0 * Bp * 576.0 * 3072.0, 576.0 * 3072.0 * 4);
-          if (w.gu8) launch_dec_gateup(da(3), w.gu8, s, w.gu_sc);
-          else if (x3l) launch_dec_gateup3(da(3), w.gu16n, s);
-          else launch_dec_gateup(da(3), w.gu16, s); }
+          if (x3l && !w.gu8) launch_dec_gateup3(da(3), w.gu16n, s);      // (the f32x3 form reads fp32 weights only)
+          else launch_dec_gateup(da(3), gu.p, s, gu.scale); }
         const LMLayerW* nx = (l + 1 < l_end && !same_w) ? &e->layers[l + 1] : nullptr;
         if (nx && ((nx->qkv2 && fuse_rb) || nx->q2h8)) {
             // the down projection of this layer and the q/k/v projection of the next one as one launch (decode.hip, dec_qkv2_kernel)
@@ -373,8 +371,7 @@ int enqueue_decode_layer_range(mellow_engine* e, int B, int l_begin, int l_end, 
               else launch_dec_qkv2(da(4), nx->qkv2, w.down.p, s); }
         } else if (!(skip & 16))
         { ProfScope ps(e, PF_SKINNY, 2.0 * Bp * 576.0 * 1536.0, 576.0 * 1536.0 * 4);
-          if (w.dn8) launch_dec_down(da(4), w.dn8, w.down.KP / 8, s, w.dn_sc);
-          else launch_dec_down(da(4), w.down.p, w.down.KP / 8, s); }
+          launch_dec_down(da(4), dn.p, w.down.KP / 8, s, dn.scale); }
     }
     return 0;
 }
@@ -502,8 +499,8 @@ int mellow_debug_dec_head(mellow_engine_t* e, const float* x, int B, int act_fp8
     a.xnF = a.xmidF;                                  // dec_load_rows writes the F32-layout operand there
     a.xn3 = nullptr;                                  // (the f32x3 kernel splits these rows itself)
     launch_dec_load_rows(a, B, x, 576, nullptr, 1, 0, e->stream);
-    if (e->head8) launch_dec_lm_head(a, e->head8, e->lm_head.KP / 8, e->cfg.vocab_size, e->stream, e->head_sc);
-    else launch_dec_lm_head(a, e->lm_head.p, e->lm_head.KP / 8, e->cfg.vocab_size, e->stream);
+    const DecW h = e->head_w();
+    launch_dec_lm_head(a, h.p, e->lm_head.KP / 8, e->cfg.vocab_size, e->stream, h.scale);
     HIPCHK(hipMemcpyAsync(logits, e->dlogits.p, (size_t)B * e->cfg.vocab_size * 4, hipMemcpyDeviceToDevice, e->stream));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(e->stream));

@@ -3,15 +3,11 @@
 # from the release build's cache, mellow_amd/csrc/build/): seconds instead of minutes per variant.
 #   tools/ab_decode.sh nohoist "-DMELLOW_NO_HOIST"   ->  mellow_amd/lib/ab/libmellow_hip_nohoist.so
 # Run `python mellow_amd/csrc/build.py` first.  Use with MELLOW_HIP_LIB=... python tools/decode_probe.py, or tools/ab_run.sh.
+# (build.py on a copy of its object cache without decode.hip.o: the copies keep their times, so nothing else is stale)
 set -e
 cd "$(dirname "$0")/.."
 name=$1; flags=$2
-mkdir -p mellow_amd/lib/ab
-out=mellow_amd/lib/ab/libmellow_hip_$name.so
 tmp=$(mktemp -d)
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -fvisibility=hidden --offload-arch=gfx950 -Wno-unused-function -x hip $flags -mllvm -amdgpu-kernarg-preload-count=14 \
-    -c mellow_amd/csrc/decode.hip -o $tmp/decode.hip.o
-objs=$(ls mellow_amd/csrc/build/*.o | grep -v decode.hip.o)
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o $out $objs $tmp/decode.hip.o
-rm -rf $tmp
-echo $out
+cp -p $(ls mellow_amd/csrc/build/*.o | grep -v decode.hip.o) "$tmp/"
+MELLOW_EXTRA_FLAGS="$flags" python mellow_amd/csrc/build.py --objdir "$tmp" --out "mellow_amd/lib/ab/libmellow_hip_$name.so"
+rm -rf "$tmp"
