@@ -48,7 +48,9 @@ extern "C" {
  *  3: mellow_engine_set_option / mellow_engine_describe (round 6): the library no longer reads ANY environment variable; every
  *     switch it has is a named option, and the resolved configuration can be printed.  mellow_debug_gemm_f32 modes 6 / 9 are gone
  *     (the pre-split debug kernel was removed; 16 / 17 are the engine's own f32x3 kernels).
- *  4: opt-in seeded nucleus sampling: mellow_generate_sampled and mellow_sample_logits.  mellow_generate is unchanged (greedy). */
+ *  4: opt-in seeded nucleus sampling: mellow_generate_sampled and mellow_sample_logits.  mellow_generate is unchanged (greedy).
+ *     The scoring symbols mellow_score and mellow_lm_score were added later under this same minor (no existing symbol or struct
+ *     changed): a binding that must also load an older minor-4 library detects them by symbol lookup (dlsym), not by the number. */
 #define MELLOW_ABI_MINOR 4
 
 typedef struct mellow_engine mellow_engine_t;
@@ -190,6 +192,39 @@ int  mellow_embed_tokens(mellow_engine_t* e, const int32_t* token_ids, int n, fl
  * embedded answer tokens): embeds dev [B][T][hidden] -> logits dev [B][T - from_pos][vocab], the rows of positions
  * t >= from_pos.  Inference arithmetic only (no loss, no gradient); leaves no decode state behind. */
 int  mellow_lm_forward_logits(mellow_engine_t* e, const float* embeds, int B, int T, int from_pos, float* logits);
+
+/* ---- scoring: teacher-forced log-probabilities of given tokens.  The reference has no counterpart as a function; the numbers are
+ *      `log_softmax(model(input_dict).logits, -1)` gathered at the answer ids (Mellow.forward, mellow.py:89-98).  The LM head of these
+ *      two calls is the exact fp32 MFMA GEMM of the logits tap above (in every precision mode) with an epilogue that reduces each
+ *      row's logits to log-softmax statistics instead of storing them: no [rows][vocab] tensor is written, and a row's target logit
+ *      and maximum logit are bit-identical to the entries the logits tap returns.  Results are bit-deterministic run to run.
+ *      The ABI is defined on results only (how much work the candidates of one example share is the engine's business).
+ *
+ * The tap-level twin of the logits tap: embeds dev [B][T][hidden]; element (b, j) of every output describes the logits of position
+ * from_pos + j, scored against targets dev i32 [B][T - from_pos]:
+ *   out_logprob dev f32 [B][T - from_pos]  logit[target] - lse, or 0 for a target of -1 ("not scored")
+ *   out_argmax  dev i32 (may be NULL)      arg-max of the position's logits, first-index ties and NaN rule of the arg-max tap
+ *   out_lse     dev f32 (may be NULL)      log(sum(exp(logits))) = M + log(sum_g s_g exp(m_g - M)) over 64-column groups g, ascending
+ *   out_max     dev f32 (may be NULL)      maximum logit M
+ * A target outside [-1, vocab) is an error (the binding raises IndexError).  Leaves no decode state behind. */
+int  mellow_lm_score(mellow_engine_t* e, const float* embeds, int B, int T, int from_pos, const int32_t* targets,
+                     float* out_logprob, int32_t* out_argmax, float* out_lse, float* out_max);
+/* The end-to-end form: K candidate answers of at most L tokens for each of B examples.  audio1 / audio2 / input_ids as for the
+ * generate call; cand_ids dev i32 [B][K][L] (entries at j >= cand_len are padding: read, never scored; any id in the vocabulary),
+ * cand_len HOST i32 [B][K], each in [1, L]; prefix_len + L <= max_positions.  Front-end, encoder, projection and prefix run once
+ * per example; the LM input [prefix_b | embed(cand_{b,k})] of the B x K rows is built on the device and the all-position forward
+ * runs over them (more than 1024 rows: consecutive passes inside the call).  Token j of a candidate is scored by the logits of
+ * position prefix_len - 1 + j (the last prefix position predicts token 0):
+ *   out_logprob dev f32 [B][K][L]  log_softmax(logits[prefix_len - 1 + j])[cand_ids[b][k][j]] for j < cand_len, exactly 0 beyond
+ *   out_sum     dev f32 [B][K]     sum of out_logprob over j < cand_len, accumulated in ascending j in fp32
+ *   out_argmax  dev i32 [B][K][L]  (may be NULL) arg-max of the logits of every position, padding positions included
+ * A candidate id outside the vocabulary at j < cand_len is an error (IndexError in the binding), as is a cand_len outside [1, L].
+ * A candidate's results do not depend on K, on its slot k, on the other rows or on L in MELLOW_PRECISION_F32 (bit-equal); in the
+ * default mode they agree to the 1e-3 stated under minor 1 above.  Drains the stream before returning; the next generate call is
+ * undisturbed. */
+int  mellow_score(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples, const int32_t* input_ids,
+                  int B, const int32_t* cand_ids, const int32_t* cand_len, int K, int L, float* out_logprob, float* out_sum,
+                  int32_t* out_argmax);
 /* A0 (host harness of the reference, wrapper.py:146 `torchaudio.transforms.Resample(sr, 32000)`) on the device:
  * sinc-interpolation resampling with a Hann window, lowpass_filter_width 6, rolloff 0.99, gcd-reduced polyphase bank.
  * wav dev [n][n_in] -> out dev [n][*n_out], *n_out = ceil(new_freq * n_in / orig_freq); out == NULL only queries *n_out. */

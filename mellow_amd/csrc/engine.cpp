@@ -257,7 +257,7 @@ void mellow_engine_destroy(mellow_engine_t* e) {
     mellow_engine::Buf* bufs[] = {&e->wavcat, &e->wpad, &e->power, &e->logmel, &e->X0, &e->X1, &e->T, &e->QKV, &e->H, &e->ats,
                                   &e->fpx, &e->fpxavg, &e->latv, &e->emb33, &e->e1, &e->gbuf, &e->sbuf, &e->proj33,
                                   &e->lm_x, &e->lm_xn, &e->lm_q, &e->lm_o, &e->lm_h, &e->lm_xn3, &e->lm_o3, &e->lm_h3, &e->lm_ssq, &e->enc_a3, &e->enc_h3, &e->sk_ws, &e->kcache, &e->vcache, &e->kcache16, &e->vcache16, &e->dec,
-                                  &e->dlogits, &e->cand, &e->out_tok};
+                                  &e->dlogits, &e->cand, &e->out_tok, &e->sc_prefix, &e->sc_part, &e->sc_ws};
     for (auto* b : bufs)
         if (b->p) hipFree(b->p);
     for (auto& kv : e->taps)

@@ -54,9 +54,11 @@ static const char* LMK = "caption_decoder.lm.";
 static inline int rup(int x, int m) { return (x + m - 1) / m * m; }
 
 // ---- profiler families --------------------------------------------------------------------------------------
-enum { PF_GEMM = 0, PF_SKINNY, PF_PREFILL_ATTN, PF_DECODE_ATTN, PF_WINDOW_ATTN, PF_NORM, PF_MISC, PF_COUNT };
+// PF_LM_HEAD: the all-position LM head (row gather + final norm + head GEMM), storing (mellow_lm_forward_logits) or fused with the
+// log-softmax statistics and their merge (mellow_score / mellow_lm_score); the generation path never runs it
+enum { PF_GEMM = 0, PF_SKINNY, PF_PREFILL_ATTN, PF_DECODE_ATTN, PF_WINDOW_ATTN, PF_NORM, PF_MISC, PF_LM_HEAD, PF_COUNT };
 static const char* kFamilyNames[PF_COUNT] = {"gemm_f32_mfma", "skinny_gemm_m32", "prefill_attention",
-                                             "decode_attention", "window_attention", "norm", "misc"};
+                                             "decode_attention", "window_attention", "norm", "misc", "lm_head_all_positions"};
 
 struct HostTensor {
     std::vector<char> data;
@@ -177,6 +179,9 @@ struct mellow_engine {
     Buf lm_ssq;                                // ... and the per-row sum-of-squares partials of the residual stream (norm-free chaining)
     Buf dec;                                   // one arena for the decode-step buffers (DecArgs)
     Buf dlogits, cand;
+    // scoring (mellow_score / mellow_lm_score): the B prefixes of a call [B][prefix_len][hidden], the fused head's per-(64-column
+    // group, row) partials (three words per entry), and the small per-row words (targets, target logits, candidate lengths)
+    Buf sc_prefix, sc_part, sc_ws;
     DecArgs da;
     int32_t *d_tokens = nullptr, *d_step = nullptr, *d_pos = nullptr, *d_seen = nullptr, *d_nseen = nullptr;
     int32_t *d_arrive = nullptr, *d_ticket = nullptr, *d_params = nullptr;   // loop bookkeeping words (LoopArgs)
@@ -308,5 +313,8 @@ int enqueue_decode_layer_range(mellow_engine* e, int B, int l_begin, int l_end, 
 int enqueue_decode_layers(mellow_engine* e, int B, const RecordArgs* rec);
 int ensure_prefill_streams(mellow_engine* e);      // creates + probes the split prefill's side streams; may lower e->prefill_parts to 1
 int encode_pair_to_prefix(mellow_engine* e, const float* a1, const float* a2, int64_t n_samples, const int32_t* ids, int B, float* prefix_out);
+// final norm + fused log-softmax head (EPI_LSE + merge) on rows from_pos .. from_pos + n - 1 of the hidden states in lm_x [B][T]
+int run_score_head(mellow_engine* e, int B, int T, int from_pos, int n, const int32_t* targets, float* out_logprob,
+                   int32_t* out_argmax, float* out_lse, float* out_max);
 void clear_bad_id(mellow_engine* e);
 int check_bad_id(mellow_engine* e);

@@ -439,6 +439,45 @@ static int wait_ticket(mellow_engine* e, unsigned want, unsigned* nseen) {
     }
 }
 
+// ---- scoring: teacher-forced log-probs through an LM head that never writes its logits ------------------------------------------
+// The hidden states of every position are in lm_x (run_prefill, all_positions).  The head is the exact fp32 MFMA GEMM of
+// mellow_lm_forward_logits with the EPI_LSE epilogue (gemm_epilogue.h): per (row, 64-column group) one (max, sum of exponentials,
+// arg-max) partial instead of 64 logits -- vocab / 64 x 12 bytes per row -- merged in ascending group order by lse_merge_kernel.
+// Profiled as the family "lm_head_all_positions" (PF_LM_HEAD: gather + final norm + head GEMM + merge).
+// A target (or candidate) id outside the vocabulary is flagged by the kernels in word 2 of the mapped progress block.
+static void clear_bad_target(mellow_engine* e) { __atomic_store_n(e->h_progress + 2, 0ull, __ATOMIC_RELEASE); }
+static int check_bad_target(mellow_engine* e, const char* what, int lo) {
+    const unsigned long long w = __atomic_load_n(e->h_progress + 2, __ATOMIC_ACQUIRE);
+    if (!w) return 0;
+    return fail("index out of range in self: %s id %d of row %u is outside [%d, %d)", what, (int)(unsigned)(w & 0xffffffffu),
+                (unsigned)((w >> 32) & 0x7fffffffu), lo, e->cfg.vocab_size);
+}
+
+int run_score_head(mellow_engine* e, int B, int T, int from_pos, int n, const int32_t* targets, float* out_logprob,
+                   int32_t* out_argmax, float* out_lse, float* out_max) {
+    hipStream_t s = e->stream;
+    const int V = e->cfg.vocab_size, rows = B * n, groups = V / 64;
+    if (V % 64 != 0 || e->lm_head.Nw != V) return fail("the scoring head tiles the vocabulary in groups of 64 columns (vocab %d)", V);
+    const size_t ld = (size_t)rup(rows, 64);
+    CHK(ensure(e, e->sc_part, (size_t)groups * ld * 3));         // (max, sum) pairs, then the arg-max words
+    float2* part_ms = reinterpret_cast<float2*>(e->sc_part.p);
+    int32_t* part_arg = reinterpret_cast<int32_t*>(e->sc_part.p + (size_t)groups * ld * 2);
+    float* tgt_logit = e->sc_ws.p;                               // [rows] (the callers size sc_ws: target logits first)
+    GemmArgs g = lin(e->lm_xn.p, 576, rows, e->lm_head, nullptr, 0, nullptr);
+    g.epi = EPI_LSE;
+    g.lse_target = targets; g.lse_ms = part_ms; g.lse_arg = part_arg; g.lse_tgt = tgt_logit; g.lse_ld = (int64_t)ld;
+    // bytes: the head weight once, the normed rows, and the partials written by the GEMM and read twice by the merge
+    ProfScope ps(e, PF_LM_HEAD, gemm_flops(g), 576.0 * V * 4 + (double)rows * 576 * 4 + 3.0 * rows * groups * 12);
+    // final norm on the scored rows only, as mellow_lm_forward_logits does
+    launch_gather_span(e->lm_x.p, B, T, from_pos, n, e->lm_o.p, s);
+    launch_rmsnorm(e->lm_o.p, e->lm_xn.p, rows, 576, e->final_norm, e->cfg.rms_norm_eps, s);
+    launch_gemm(g, s);
+    launch_lse_merge(part_ms, part_arg, (int64_t)ld, groups, rows, targets, tgt_logit, V, out_logprob, out_argmax, out_lse, out_max,
+                     e->d_progress + 2, s);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 extern "C" {
 
 int mellow_prefix(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples, const int32_t* input_ids,
@@ -535,13 +574,77 @@ int mellow_lm_forward_logits(mellow_engine_t* e, const float* embeds, int B, int
     e->cur_B = 0;                                   // no decode state: a decode step needs a real prefill first
     const int n = T - from_pos;
     // final norm on the selected rows only: gather [B][n][576] out of [B][T][576] into lm_xn, then normalise in place
-    launch_gather_span(e->lm_x.p, B, T, from_pos, n, e->lm_o.p, s);
-    launch_rmsnorm(e->lm_o.p, e->lm_xn.p, B * n, 576, e->final_norm, e->cfg.rms_norm_eps, s);
     GemmArgs g = lin(e->lm_xn.p, 576, B * n, e->lm_head, logits, e->cfg.vocab_size, nullptr);
-    launch_gemm(g, s);
+    { ProfScope ps(e, PF_LM_HEAD, gemm_flops(g), (576.0 + (double)B * n) * e->cfg.vocab_size * 4 + (double)B * n * 576 * 4);
+      launch_gather_span(e->lm_x.p, B, T, from_pos, n, e->lm_o.p, s);
+      launch_rmsnorm(e->lm_o.p, e->lm_xn.p, B * n, 576, e->final_norm, e->cfg.rms_norm_eps, s);
+      launch_gemm(g, s); }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
     return 0;
+}
+
+int mellow_lm_score(mellow_engine_t* e, const float* embeds, int B, int T, int from_pos, const int32_t* targets,
+                    float* out_logprob, int32_t* out_argmax, float* out_lse, float* out_max) {
+    if (!e || !e->finalized) return fail("engine not finalized");
+    if (!embeds || !targets || !out_logprob || B <= 0 || T <= 0 || from_pos < 0 || from_pos >= T) return fail("bad argument");
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    CHK(ensure_lm(e, B, T, T + 1));
+    CHK(ensure(e, e->sc_ws, (size_t)B * (T - from_pos)));
+    clear_bad_target(e);
+    HIPCHK(hipMemcpyAsync(e->lm_x.p, embeds, (size_t)B * T * 576 * 4, hipMemcpyDeviceToDevice, s));
+    CHK(run_prefill(e, B, T, nullptr, true));
+    e->cur_B = 0;                                   // no decode state, like mellow_lm_forward_logits
+    CHK(run_score_head(e, B, T, from_pos, T - from_pos, targets, out_logprob, out_argmax, out_lse, out_max));
+    HIPCHK(hipStreamSynchronize(s));
+    return check_bad_target(e, "target", -1);
+}
+
+int mellow_score(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples, const int32_t* input_ids, int B,
+                 const int32_t* cand_ids, const int32_t* cand_len, int K, int L, float* out_logprob, float* out_sum,
+                 int32_t* out_argmax) {
+    if (!e || !e->finalized) return fail("engine not finalized");
+    if (!audio1 || !audio2 || !input_ids || !cand_ids || !cand_len || !out_logprob || !out_sum) return fail("null argument");
+    if (B <= 0 || K <= 0 || L <= 0) return fail("B, K and L must be positive");
+    if (B > 1024) return fail("mellow_score takes at most 1024 examples per call (got %d)", B);
+    const int P = e->cfg.prefix_len, T = P + L - 1;
+    if ((int64_t)P + L > e->cfg.max_positions)
+        return fail("prefix + candidate length = %d + %d exceeds max_positions %d", P, L, e->cfg.max_positions);
+    const int64_t rows = (int64_t)B * K;
+    for (int64_t r = 0; r < rows; ++r)
+        if (cand_len[r] < 1 || cand_len[r] > L)
+            return fail("cand_len[%d][%d] = %d is outside [1, %d]", (int)(r / K), (int)(r % K), cand_len[r], L);
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    constexpr int kPassRows = 1024;                  // rows of one LM pass, as in mellow_generate
+    const int pass = rows < kPassRows ? (int)rows : kPassRows;
+    // per-row words: [target logits: pass x L | targets: pass x L | candidate lengths: rows]
+    CHK(ensure(e, e->sc_ws, (size_t)2 * pass * L + (size_t)rows));
+    int32_t* d_targets = reinterpret_cast<int32_t*>(e->sc_ws.p + (size_t)pass * L);
+    int32_t* d_len = reinterpret_cast<int32_t*>(e->sc_ws.p + (size_t)2 * pass * L);
+    CHK(ensure(e, e->sc_prefix, (size_t)B * P * 576));
+    clear_bad_id(e);
+    clear_bad_target(e);
+    HIPCHK(hipMemcpyAsync(d_len, cand_len, (size_t)rows * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    // front-end, encoder, projection and prefix: once per example
+    CHK(encode_pair_to_prefix(e, audio1, audio2, n_samples, input_ids, B, e->sc_prefix.p));
+    for (int64_t r0 = 0; r0 < rows; r0 += kPassRows) {
+        const int nr = rows - r0 < kPassRows ? (int)(rows - r0) : kPassRows;
+        CHK(ensure_lm(e, nr, T, T + 1));
+        { ProfScope ps(e, PF_MISC, 0, 2.0 * nr * T * 576 * 4);
+          launch_score_build_input(e->sc_prefix.p, e->embed, cand_ids, d_len, K, L, P, e->cfg.vocab_size, (int)r0, nr, e->lm_x.p,
+                                   d_targets, e->d_progress + 2, s); }
+        CHK(run_prefill(e, nr, T, nullptr, true));
+        e->cur_B = 0;
+        CHK(run_score_head(e, nr, T, P - 1, L, d_targets, out_logprob + r0 * L, out_argmax ? out_argmax + r0 * L : nullptr, nullptr,
+                           nullptr));
+    }
+    launch_score_sum(out_logprob, d_len, (int)rows, L, out_sum, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    CHK(check_bad_id(e));
+    return check_bad_target(e, "candidate", 0);
 }
 
 // sampling of one call (mellow_generate_sampled); on = false: the greedy arg-max of mellow_generate

@@ -275,4 +275,54 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[2
     }
 }
 
+// EPI_LSE (GemmArgs::lse_*): the LM head that never writes its logits.  The accumulators are exactly what EPI_LINEAR without
+// bias / activation / residual would have stored.  A lane owns one row of each 32-row tile and the lane pair (lane, lane ^ 32)
+// holds the row's 64 columns of the wave tile, so the group's (max, arg-max, sum of exponentials) is register work plus one
+// cross-half exchange; the lower half-wave stores the partial, the lane that holds the target column stores the target logit.
+// No atomics, one fixed order per row: bit-deterministic.
+template <int WN>
+__device__ __forceinline__ void gemm_epilogue_lse(const GemmArgs& g, f32x16 (&acc)[2][2], int pm, int pn, int wm, int wn, int lane,
+                                                  int BM) {
+    const int h = lane >> 5;
+    const int P = pn * WN + wn;             // 64-column group of this wave
+    const int col0 = P * 64;
+    if (col0 >= g.N) return;                // wave-uniform (N % 64 == 0)
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi) {
+        const int m = pm * BM + wm * 64 + mi * 32 + (lane & 31);
+        const bool live = m < g.M;          // (both lanes of a pair agree; the exchanges below run on every lane)
+        const int t = live ? g.lse_target[m] : -1;
+        float best = -INFINITY, tv = 0.f;
+        int bi = 0x7fffffff;
+        bool hit = false;
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int col = col0 + ni * 32 + 8 * (q >> 2) + 4 * h + (q & 3);
+                const float v = acc[ni][mi][q];
+                if (arg_better(v, col, best, bi)) { best = v; bi = col; }
+                if (col == t) { tv = v; hit = true; }
+            }
+        // r[0] = the lower half-wave's value, r[1] = the upper one's, on both lanes of the pair
+        const auto rv = __builtin_amdgcn_permlane32_swap(__float_as_uint(best), __float_as_uint(best), false, false);
+        const auto ri = __builtin_amdgcn_permlane32_swap((unsigned)bi, (unsigned)bi, false, false);
+        float M = __uint_as_float(rv[0]);
+        int arg = (int)ri[0];
+        if (arg_better(__uint_as_float(rv[1]), (int)ri[1], M, arg)) { M = __uint_as_float(rv[1]); arg = (int)ri[1]; }
+        const float Ms = M == -INFINITY ? 0.f : M;      // a group of -inf only: weights 0, not exp(-inf + inf)
+        float ssum = 0.f;
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) ssum += expf(acc[ni][mi][q] - Ms);
+        ssum = half_sum(ssum);              // lower half + upper half: the same order on both lanes
+        if (live && h == 0) {
+            g.lse_ms[(int64_t)P * g.lse_ld + m] = make_float2(M, ssum);
+            g.lse_arg[(int64_t)P * g.lse_ld + m] = arg;
+        }
+        if (live && hit) g.lse_tgt[m] = tv;
+    }
+}
+
 }  // namespace mellow

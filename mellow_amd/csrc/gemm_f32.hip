@@ -234,7 +234,8 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmDev p) {
         g_kdbg[62] = __builtin_amdgcn_s_getreg(0xf804);    // HW_REG_HW_ID bits 15:0
     }
 #endif
-    gemm_epilogue<WN, EPI>(g, acc, pm, pn, wm, wn, lane, BM, BN);
+    if constexpr (EPI == EPI_LSE) gemm_epilogue_lse<WN>(g, acc, pm, pn, wm, wn, lane, BM);
+    else gemm_epilogue<WN, EPI>(g, acc, pm, pn, wm, wn, lane, BM, BN);
 }
 
 template <int WM, int WN, int EPI, int BK>
@@ -264,6 +265,7 @@ void launch_gemm(const GemmArgs& a, hipStream_t s) {
         case EPI_LOGMEL: launch_epi<EPI_LOGMEL>(a, s); break;
         case EPI_SWIGLU: launch_epi<EPI_SWIGLU>(a, s); break;
         case EPI_QKV_ROPE: launch_epi<EPI_QKV_ROPE>(a, s); break;
+        case EPI_LSE: launch_cfg<2, 2, EPI_LSE, 32>(a, s); break;       // the scoring head: the tiling of the storing head
     }
 }
 

@@ -21,7 +21,7 @@ void launch_pack_weight_pairs(const float* w0, const float* w1, int N, int K, in
                               int KP, hipStream_t s);
 
 enum { ACT_NONE = 0, ACT_GELU = 1, ACT_SIGMOID = 2 };
-enum { EPI_LINEAR = 0, EPI_POWER = 1, EPI_LOGMEL = 2, EPI_SWIGLU = 3, EPI_QKV_ROPE = 4 };
+enum { EPI_LINEAR = 0, EPI_POWER = 1, EPI_LOGMEL = 2, EPI_SWIGLU = 3, EPI_QKV_ROPE = 4, EPI_LSE = 5 };
 enum { A_PLAIN = 0, A_FRAMES = 1 };
 
 struct GemmArgs {
@@ -91,6 +91,16 @@ struct GemmArgs {
     int c3_fmt = 0;
     uint8_t* C3s = nullptr;
     int c3_kt64 = 0;
+    // EPI_LSE (exact fp32 kernel only; the scoring head): nothing of C[M][N] is stored.  Every wave reduces its 64 x 64 tile per
+    // row to one log-softmax partial of the 64-column group P = column / 64 (N % 64 == 0): lse_ms[P * lse_ld + m] = (max logit of
+    // the group, sum of exp(logit - max) over it), lse_arg[P * lse_ld + m] = lowest column attaining the max (arg_better order:
+    // a NaN wins, lowest NaN column), and the group that holds column lse_target[m] writes that accumulator to lse_tgt[m]
+    // (a target outside [0, N) is written by nobody).  launch_lse_merge folds a row's N / 64 partials in ascending group order.
+    const int32_t* lse_target = nullptr;    // [M]
+    float2* lse_ms = nullptr;               // [N / 64][lse_ld]
+    int32_t* lse_arg = nullptr;             // [N / 64][lse_ld]
+    float* lse_tgt = nullptr;               // [M]
+    int64_t lse_ld = 0;                     // >= M
 };
 void launch_gemm(const GemmArgs& a, hipStream_t s);
 // ---- fp8 (e4m3) GEMM path: BASELINE config 5 (gemm_fp8.hip) -------------------------------------------------
@@ -345,6 +355,22 @@ void launch_downsample33(const float* proj33, int n, float* out, hipStream_t s);
 // o_scales != nullptr (fp8 mode): o_apb receives the AMX image (MXFP8, K = 576: 9 k64 steps) and o_scales its scale bytes
 void launch_prefill_attention(const float* q, const float* k_cache, const float* v_cache, float* o, void* o_apb, int B, int T,
                               int Tmax, bool x3, hipStream_t s, void* o_scales = nullptr, bool bf16_once = false, bool pages16 = false);
+// ---- scoring (score.hip) ------------------------------------------------------------------------------------------
+// One thread per row folds the row's `groups` EPI_LSE partials in ascending group order: M = max, arg = its lowest column,
+// lse = M + log(sum_g s_g exp(m_g - M)), logprob = target logit - lse (0 for target -1).  out_argmax / out_lse / out_max may be
+// null.  A target outside [-1, vocab) sets *bad_word (mapped host memory) to (1 << 63 | row << 32 | id) and scores 0.
+void launch_lse_merge(const float2* part_ms, const int32_t* part_arg, int64_t ld, int groups, int rows, const int32_t* targets,
+                      const float* tgt_logit, int vocab, float* out_logprob, int32_t* out_argmax, float* out_lse, float* out_max,
+                      unsigned long long* bad_word, hipStream_t s);
+// LM input of `nr` candidate rows (global rows row0 .. row0 + nr - 1 of [B][K]): x [nr][T][576] with T = P + L - 1,
+// x[r][t] = prefix[(row0 + r) / K][t] for t < P, else embed[cand_ids[row0 + r][t - P]] (the last candidate token predicts nothing
+// that is scored and is not fed); targets [nr][L] = cand_ids[row][j] for j < cand_len[row], else -1.  Ids are read clamped; one
+// outside [0, vocab) at j < cand_len sets *bad_word like launch_lse_merge.
+void launch_score_build_input(const float* prefix, const float* embed, const int32_t* cand_ids, const int32_t* cand_len, int K,
+                              int L, int P, int vocab, int row0, int nr, float* x, int32_t* targets, unsigned long long* bad_word,
+                              hipStream_t s);
+// out_sum[r] = sum of logprob[r][j] over j < cand_len[r], ascending j
+void launch_score_sum(const float* logprob, const int32_t* cand_len, int rows, int L, float* out_sum, hipStream_t s);
 // ---- misc ------------------------------------------------------------------------------------------------------
 void launch_argmax(const float* logits, int B, int V, int64_t ld, int32_t* tokens, hipStream_t s);
 

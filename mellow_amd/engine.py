@@ -39,6 +39,8 @@ class EngineError(RuntimeError):
 
 
 _lib = None
+# symbols added without a new ABI minor (include/mellow_hip.h): detected by lookup, so that a library built before them still loads
+_ADDED_UNDER_MINOR_4 = ("mellow_lm_score", "mellow_score")
 
 
 def load_library(path: Optional[str] = None):
@@ -77,6 +79,8 @@ def load_library(path: Optional[str] = None):
         "mellow_argmax": (ci, [vp, vp, ci, vp]),
         "mellow_embed_tokens": (ci, [vp, vp, ci, vp]),
         "mellow_lm_forward_logits": (ci, [vp, vp, ci, ci, ci, vp]),
+        "mellow_lm_score": (ci, [vp, vp, ci, ci, ci, vp, vp, vp, vp, vp]),
+        "mellow_score": (ci, [vp, vp, vp, i64, vp, ci, vp, P(C.c_int32), ci, ci, vp, vp, vp]),
         "mellow_resample": (ci, [vp, vp, ci, i64, ci, ci, vp, i64, P(i64)]),
         "mellow_debug_enable_taps": (ci, [vp, ci]),
         "mellow_debug_tap": (ci, [vp, C.c_char_p, vp, i64, P(i64)]),
@@ -103,6 +107,8 @@ def load_library(path: Optional[str] = None):
         "mellow_host_rope_tables": (ci, [cf, ci, ci, P(cf), P(cf)]),
     }
     for name, (res, args) in sig.items():
+        if name in _ADDED_UNDER_MINOR_4 and not hasattr(lib, name):
+            continue                     # an older minor-4 library: Engine.score / lm_score raise when called
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -118,6 +124,7 @@ EXPORTED_SYMBOLS = (
     "mellow_engine_destroy", "mellow_engine_fork", "mellow_engine_load_tensor", "mellow_engine_finalize",
     "mellow_engine_num_required", "mellow_engine_required_key", "mellow_generate", "mellow_generate_sampled", "mellow_sample_logits", "mellow_logmel",
     "mellow_encode", "mellow_prefix", "mellow_lm_prefill", "mellow_lm_decode_step", "mellow_argmax", "mellow_embed_tokens", "mellow_lm_forward_logits",
+    "mellow_lm_score", "mellow_score",
     "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
     "mellow_prof_num_families", "mellow_prof_family_name", "mellow_prof_get", "mellow_last_phase_ms", "mellow_last_steps_enqueued", "mellow_last_row_repacks", "mellow_stft_is_fft", "mellow_prefill_parts", "mellow_abi_minor",
     "mellow_resample", "mellow_engine_set_precision", "mellow_engine_set_option", "mellow_engine_describe", "mellow_debug_gemm_fp8", "mellow_debug_gemm_f32", "mellow_debug_dec_head", "mellow_set_graph", "mellow_host_window_map", "mellow_host_pack_weight", "mellow_host_rope_tables",
@@ -201,6 +208,10 @@ class Engine:
             if msg.startswith("index out of range in self"):      # the reference's embedding lookup raises IndexError with this text
                 raise IndexError(msg)
             raise EngineError(msg)
+
+    def _need(self, symbol: str):
+        if not hasattr(self.lib, symbol):
+            raise EngineError(f"this libmellow_hip.so predates {symbol}: rebuild it with `python mellow_amd/csrc/build.py`")
 
     def close(self):
         if getattr(self, "h", None):
@@ -404,6 +415,69 @@ class Engine:
         self._sync_inputs()
         self._chk(self.lib.mellow_lm_forward_logits(self.h, _ptr(p), B, T, int(from_pos), _ptr(out)))
         return out
+
+    def lm_score(self, embeds, targets, from_pos: int = 0):
+        """Teacher-forced scores of `lm(inputs_embeds=embeds).logits[:, from_pos:]` without materialising them (mellow_lm_score,
+        the fused log-softmax head): embeds (B, T, hidden), targets int (B, T - from_pos) with -1 = not scored ->
+        dict of device tensors {"logprob" f32, "argmax" i32, "lse" f32, "max" f32}, each (B, T - from_pos).
+        A target outside [-1, vocab) raises IndexError."""
+        p = self._f32(embeds)
+        B, T, H = p.shape
+        n = T - int(from_pos)
+        t = torch.as_tensor(targets)
+        if tuple(t.shape) != (B, n):
+            raise ValueError(f"targets must be ({B}, {n}), got {tuple(t.shape)}")
+        if t.numel() and (int(t.min()) < -1 or int(t.max()) >= self.lm.vocab_size):
+            raise IndexError("index out of range in self")
+        t = t.to(device=self.tdev, dtype=torch.int32).contiguous()
+        out = {"logprob": torch.empty((B, n), dtype=torch.float32, device=self.tdev),
+               "argmax": torch.empty((B, n), dtype=torch.int32, device=self.tdev),
+               "lse": torch.empty((B, n), dtype=torch.float32, device=self.tdev),
+               "max": torch.empty((B, n), dtype=torch.float32, device=self.tdev)}
+        self._need("mellow_lm_score")
+        self._sync_inputs()
+        self._chk(self.lib.mellow_lm_score(self.h, _ptr(p), B, T, int(from_pos), _ptr(t), _ptr(out["logprob"]), _ptr(out["argmax"]),
+                                           _ptr(out["lse"]), _ptr(out["max"])))
+        return out
+
+    def max_candidate_tokens(self) -> int:
+        """largest candidate length L `score` takes: prefix 389 + L may not exceed the engine's max_positions"""
+        return int(self.cfg.max_positions) - spec.PREFIX_LEN
+
+    def score(self, audio1, audio2, input_ids, cand_ids, cand_len):
+        """Teacher-forced log-probs of K candidate answers per example (mellow_score): audio1 / audio2 / input_ids as in
+        `generate`; cand_ids int (B, K, L), cand_len int (B, K) with 1 <= cand_len <= L (ids at j >= cand_len are padding).
+        -> (logprob f32 [B, K, L] (0 at j >= cand_len), sum f32 [B, K], argmax i32 [B, K, L]) as numpy arrays on the host.
+        ValueError for a cand_len outside [1, L] or an L beyond max_candidate_tokens(); IndexError for a scored id outside the
+        vocabulary."""
+        a1, a2, ids = self._f32(audio1), self._f32(audio2), self._prompt_ids(input_ids)
+        B, n = a1.shape
+        assert a2.shape == a1.shape and ids.shape == (B, spec.TEXT_LEN), (a1.shape, a2.shape, ids.shape)
+        c = torch.as_tensor(cand_ids)
+        if c.dim() != 3 or c.shape[0] != B or c.shape[1] < 1 or c.shape[2] < 1:
+            raise ValueError(f"cand_ids must be ({B}, K, L) with K, L >= 1, got {tuple(c.shape)}")
+        K, L = int(c.shape[1]), int(c.shape[2])
+        if L > self.max_candidate_tokens():
+            raise ValueError(f"candidates of {L} tokens exceed the engine's page budget: prefix {spec.PREFIX_LEN} + L <= "
+                             f"max_positions {int(self.cfg.max_positions)}, i.e. L <= {self.max_candidate_tokens()}")
+        ln = np.ascontiguousarray(torch.as_tensor(cand_len).cpu().numpy(), dtype=np.int32)
+        if ln.shape != (B, K):
+            raise ValueError(f"cand_len must be ({B}, {K}), got {ln.shape}")
+        if ln.min() < 1 or ln.max() > L:
+            raise ValueError(f"cand_len must be in [1, {L}] (got {int(ln.min())} .. {int(ln.max())})")
+        ch = c.cpu().numpy()
+        scored = ch[np.arange(L)[None, None, :] < ln[:, :, None]]
+        if scored.size and (int(scored.min()) < 0 or int(scored.max()) >= self.lm.vocab_size):
+            raise IndexError("index out of range in self")
+        c = c.clamp(0, self.lm.vocab_size - 1).to(device=self.tdev, dtype=torch.int32).contiguous()
+        lp = torch.empty((B, K, L), dtype=torch.float32, device=self.tdev)
+        sm = torch.empty((B, K), dtype=torch.float32, device=self.tdev)
+        am = torch.empty((B, K, L), dtype=torch.int32, device=self.tdev)
+        self._need("mellow_score")
+        self._sync_inputs()
+        self._chk(self.lib.mellow_score(self.h, _ptr(a1), _ptr(a2), n, _ptr(ids), B, _ptr(c), ln.ctypes.data_as(C.POINTER(C.c_int32)),
+                                        K, L, _ptr(lp), _ptr(sm), _ptr(am)))
+        return lp.cpu().numpy(), sm.cpu().numpy(), am.cpu().numpy()
 
     def forward(self, audio1, audio2, input_ids, answer_ids, from_pos: int = 0) -> torch.Tensor:
         """The training-time forward of the reference as inference arithmetic (`Mellow.forward`, mellow.py:89-98): logits of

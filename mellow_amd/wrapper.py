@@ -21,6 +21,9 @@ inside the captured decode step -- z = logits / temperature, the nucleus of the 
 softmax mass strictly before it in (z desc, index asc) order is <= top_p), then Gumbel-max with Philox4x32-10 noise keyed by
 (seed, row, step); include/mellow_hip.h mellow_generate_sampled gives the exact definition.  seed=None draws a 63-bit seed from
 `random` (kept as `last_seed`); under data parallelism the seed must be given and equal on every rank.
+Extension: `score(examples, candidates)` returns the teacher-forced log-probability of given answer strings and
+`choose(examples, candidates)` the index of the likeliest one (multiple-choice ranking, re-ranking of sampled answers); the LM
+head of that path reduces its logits to log-softmax statistics on the fly (include/mellow_hip.h mellow_score).
 Deviations: `tqdm` progress output is not produced; the B>1/steps==1 mis-shape and B==1/steps==1 crash of
 reference wrapper.py:251-253 are not reproduced (one string per example is always returned).
 """
@@ -312,3 +315,75 @@ class MellowWrapper:
         return self._generate_batch(audio1, audio2, ids, entry_length=max_len, top_p=top_p,
                                     temperature=temperature, stop_token=stop_token, n_total=n, do_sample=do_sample,
                                     seed=seed, row_offset=lo)
+
+    # ---- scoring ------------------------------------------------------------------------------------------------
+    def _candidate_ids(self, candidates, append_stop: bool, stop_token: str):
+        """candidate strings -> (ids int64 [B][K][L], lengths int32 [B][K], K of every example).  An example with fewer than the
+        largest K is padded by repeating its first candidate; ids beyond a candidate's length are 0 (never scored)."""
+        stop = int(self.tokenizer.encode(stop_token)[0]) if append_stop else None
+        rows, counts = [], []
+        for cands in candidates:
+            if isinstance(cands, str) or len(cands) == 0:
+                raise ValueError("candidates[i] must be a non-empty list of answer strings")
+            toks = []
+            for text in cands:
+                if not isinstance(text, str):
+                    raise TypeError(f"a candidate must be a string, got {type(text).__name__}")
+                ids = [int(t) for t in self.tokenizer.encode(text)]
+                if stop is not None:
+                    ids.append(stop)
+                if not ids:
+                    raise ValueError(f"candidate {text!r} has no tokens (append_stop=False and an empty encoding)")
+                toks.append(ids)
+            rows.append(toks)
+            counts.append(len(toks))
+        K = max(counts)
+        L = max(len(t) for toks in rows for t in toks)
+        limit = self.model.max_candidate_tokens()
+        if L > limit:
+            # not clamped: a truncated answer has another score
+            raise ValueError(f"a candidate has {L} tokens; the engine's KV pages hold prefix {spec.PREFIX_LEN} + at most {limit} "
+                             f"candidate tokens (max_positions {limit + spec.PREFIX_LEN})")
+        ids = np.zeros((len(rows), K, L), dtype=np.int64)
+        lens = np.zeros((len(rows), K), dtype=np.int32)
+        for b, toks in enumerate(rows):
+            for k in range(K):
+                t = toks[k] if k < len(toks) else toks[0]
+                ids[b, k, : len(t)] = t
+                lens[b, k] = len(t)
+        return ids, lens, counts
+
+    def score(self, examples, candidates, append_stop=True, stop_token="<|endoftext|>", audio_resample=True):
+        r"""Teacher-forced log-probabilities of given answers
+        examples: (list<list>) as in `generate`: [audio path 1, audio path 2, text prompt]
+        candidates: (list<list<str>>) candidates[i] = the answer strings to score for example i (any number per example)
+        append_stop: (bool) append the stop token's id to every candidate, so that its score includes ending there (what makes
+                     answers of different length comparable)
+        Returns per example a list, one entry per candidate: {"logprob": sum of the token log-probs, "tokens": how many tokens
+        were scored, "token_logprobs": [float per token]}.  The encoder and prefix run once per example, whatever the number of
+        candidates.  Not sharded: under data parallelism with more than one rank it raises NotImplementedError."""
+        if self._dp()[1] > 1:
+            raise NotImplementedError("score() is not sharded over data-parallel ranks: call it on one rank (or with data_parallel off)")
+        if len(examples) == 0:
+            raise RuntimeError("torch.cat(): expected a non-empty list of Tensors")
+        if len(candidates) != len(examples):
+            raise ValueError(f"{len(examples)} examples but {len(candidates)} candidate lists")
+        ids, lens, counts = self._candidate_ids(candidates, append_stop, stop_token)
+        audio1 = self.preprocess_audio([ex[0] for ex in examples], resample=audio_resample)
+        audio2 = self.preprocess_audio([ex[1] for ex in examples], resample=audio_resample)
+        prompt_ids = self.preprocess_text([ex[2] for ex in examples])["input_ids"]
+        logprob, sums, _ = self.model.score(audio1, audio2, prompt_ids, ids, lens)
+        return [[{"logprob": float(sums[b, k]), "tokens": int(lens[b, k]),
+                  "token_logprobs": [float(x) for x in logprob[b, k, : lens[b, k]]]} for k in range(counts[b])]
+                for b in range(len(examples))]
+
+    def choose(self, examples, candidates, normalize="sum", **score_kwargs):
+        """Index of the likeliest candidate of every example (lowest index on ties).  normalize="sum": by the answer's total
+        log-probability; "mean": by its log-probability per token."""
+        if normalize not in ("sum", "mean"):
+            raise ValueError(f"normalize must be 'sum' or 'mean', got {normalize!r}")
+        out = []
+        for cands in self.score(examples, candidates, **score_kwargs):
+            vals = [c["logprob"] / c["tokens"] if normalize == "mean" else c["logprob"] for c in cands]
+            out.append(max(range(len(vals)), key=lambda k: (vals[k], -k)))
+        return out
