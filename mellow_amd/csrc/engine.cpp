@@ -33,7 +33,7 @@ int ensure(mellow_engine* e, mellow_engine::Buf& b, size_t floats) {
 int dev_alloc(mellow_engine* e, float** out, size_t floats) {
     const size_t bytes = (floats * sizeof(float) + 4095) / 4096 * 4096;
     if (!e->arena) {
-        const size_t want = (size_t)(e->arena_mb < 0 ? 0 : e->arena_mb) << 20;        // option "arena_mb" (default 3400)
+        const size_t want = (size_t)(e->opt.arena_mb < 0 ? 0 : e->opt.arena_mb) << 20;        // option "arena_mb" (default 3400)
         if (want) {
             void* p = nullptr;
             if (hipMalloc(&p, want) == hipSuccess) {
@@ -251,17 +251,8 @@ void mellow_engine_destroy(mellow_engine_t* e) {
     hipSetDevice(e->device);
     if (e->stream) hipStreamSynchronize(e->stream);
     if (e->parent && --e->parent->n_forks == 0) e->parent->prefill_parts = e->parent->prefill_parts_saved;    // the last fork is gone
-    if (e->step_exec) hipGraphExecDestroy(e->step_exec);
-    if (e->step_exec8) hipGraphExecDestroy(e->step_exec8);
+    e->graphs.reset();                         // execs before the memory they address (its destructor would come too late for that order)
     for (void* p : e->allocs) hipFree(p);      // a fork's list holds only what it allocated itself (resample banks): the weights are its parent's
-    mellow_engine::Buf* bufs[] = {&e->wavcat, &e->wpad, &e->power, &e->logmel, &e->X0, &e->X1, &e->T, &e->QKV, &e->H, &e->ats,
-                                  &e->fpx, &e->fpxavg, &e->latv, &e->emb33, &e->e1, &e->gbuf, &e->sbuf, &e->proj33,
-                                  &e->lm_x, &e->lm_xn, &e->lm_q, &e->lm_o, &e->lm_h, &e->lm_xn3, &e->lm_o3, &e->lm_h3, &e->lm_ssq, &e->enc_a3, &e->enc_h3, &e->sk_ws, &e->kcache, &e->vcache, &e->kcache16, &e->vcache16, &e->dec,
-                                  &e->dlogits, &e->cand, &e->out_tok, &e->sc_prefix, &e->sc_part, &e->sc_ws};
-    for (auto* b : bufs)
-        if (b->p) hipFree(b->p);
-    for (auto& kv : e->taps)
-        if (kv.second.p) hipFree(kv.second.p);
     for (auto ev : e->ev_pool) hipEventDestroy(ev);
     for (int i = 0; i < 4; ++i)
         if (e->ev_phase[i]) hipEventDestroy(e->ev_phase[i]);
@@ -273,7 +264,7 @@ void mellow_engine_destroy(mellow_engine_t* e) {
         if (e->stream2[i]) hipStreamDestroy(e->stream2[i]);
     }
     if (e->stream) hipStreamDestroy(e->stream);
-    delete e;
+    delete e;                                  // the workspaces and taps (Buf) free themselves here: the stream was synchronised above
 }
 
 int mellow_engine_load_tensor(mellow_engine_t* e, const char* key, const void* data, const int64_t* shape, int ndim,
@@ -415,38 +406,38 @@ static const OptDesc* find_opt(const char* key) {
     return nullptr;
 }
 static long opt_val(const mellow_engine* e, const char* key) {
-    auto it = e->opts.find(key);
-    return strtol(it != e->opts.end() ? it->second.c_str() : find_opt(key)->dflt, nullptr, 0);
+    auto it = e->opt.given.find(key);
+    return strtol(it != e->opt.given.end() ? it->second.c_str() : find_opt(key)->dflt, nullptr, 0);
 }
 // option table + precision mode -> resolved fields (the only place they are written)
 int apply_options(mellow_engine* e) {
-    const int mode = e->mode;
+    const int mode = e->opt.mode;
     e->prefill_parts = (int)opt_val(e, "prefill_split");
-    e->prefill_fuse_norm = opt_val(e, "prefill_fuse_norm") != 0;
-    e->decode_fuse = opt_val(e, "decode_fuse") != 0;
-    e->dec_fuse_max_rb = (int)opt_val(e, "decode_fuse_max_rb");
-    e->sk_max = (int)opt_val(e, "splitk");
-    e->enc_apb_stages = (int)opt_val(e, "enc_apb");
+    e->opt.prefill_fuse_norm = opt_val(e, "prefill_fuse_norm") != 0;
+    e->opt.decode_fuse = opt_val(e, "decode_fuse") != 0;
+    e->opt.dec_fuse_max_rb = (int)opt_val(e, "decode_fuse_max_rb");
+    e->opt.sk_max = (int)opt_val(e, "splitk");
+    e->opt.enc_apb_stages = (int)opt_val(e, "enc_apb");
     e->use_graph = opt_val(e, "graph") != 0;
-    e->x3_stft = opt_val(e, "x3_stft") != 0;
-    e->stft_fft = opt_val(e, "stft_fft") != 0 && e->x3_stft;
-    e->x3_apb = opt_val(e, "x3_apb") != 0;
-    e->x3_attn = opt_val(e, "x3_attn") != 0;
-    e->x3w = opt_val(e, "x3w") != 0;
-    e->row_migration = opt_val(e, "row_migration") != 0;
-    e->arena_mb = (int)opt_val(e, "arena_mb");
-    e->fp8 = mode == MELLOW_PRECISION_FP8;
-    e->fp8_decode = e->fp8 && opt_val(e, "fp8_decode") != 0;
-    e->fp8_decode_act = e->fp8_decode && opt_val(e, "fp8_decode_act") != 0;
-    e->fp8_prefill = opt_val(e, "fp8_prefill") != 0;
-    e->fp8_attn_bf16 = opt_val(e, "fp8_attn_bf16") != 0;
-    e->kv16 = e->fp8_decode && opt_val(e, "fp8_kv16") != 0;      // fp8 mode: bf16 shadow pages for the decode step
+    e->opt.x3_stft = opt_val(e, "x3_stft") != 0;
+    e->opt.stft_fft = opt_val(e, "stft_fft") != 0 && e->opt.x3_stft;
+    e->opt.x3_apb = opt_val(e, "x3_apb") != 0;
+    e->opt.x3_attn = opt_val(e, "x3_attn") != 0;
+    e->opt.x3w = opt_val(e, "x3w") != 0;
+    e->opt.row_migration = opt_val(e, "row_migration") != 0;
+    e->opt.arena_mb = (int)opt_val(e, "arena_mb");
+    e->opt.fp8 = mode == MELLOW_PRECISION_FP8;
+    e->opt.fp8_decode = e->opt.fp8 && opt_val(e, "fp8_decode") != 0;
+    e->opt.fp8_decode_act = e->opt.fp8_decode && opt_val(e, "fp8_decode_act") != 0;
+    e->opt.fp8_prefill = opt_val(e, "fp8_prefill") != 0;
+    e->opt.fp8_attn_bf16 = opt_val(e, "fp8_attn_bf16") != 0;
+    e->opt.kv16 = e->opt.fp8_decode && opt_val(e, "fp8_kv16") != 0;      // fp8 mode: bf16 shadow pages for the decode step
     // f32x3: six partial products (a2*b3, a3*b2, a3*b3 dropped: < 2^-23 |a*b| in total); measured error against an fp64 product is
     // identical to the nine-term form and slightly below the fp32 MFMA kernel's (tools/f32x3_check.py)
-    e->f32x3_terms = mode == MELLOW_PRECISION_F32X3 ? 6 : 0;
+    e->opt.f32x3_terms = mode == MELLOW_PRECISION_F32X3 ? 6 : 0;
     // f32x3 mode: the decode step's GEMM launches split their operands in registers and run on the bf16 pipe as well (decode.hip)
-    e->dec_x3 = mode == MELLOW_PRECISION_F32X3 ? ((int)opt_val(e, "decode_x3") & DEC_X3_ALL) : 0;
-    e->dec_x3_min_rb = (int)opt_val(e, "decode_x3_min_rb") < 1 ? 1 : (int)opt_val(e, "decode_x3_min_rb");
+    e->opt.dec_x3 = mode == MELLOW_PRECISION_F32X3 ? ((int)opt_val(e, "decode_x3") & DEC_X3_ALL) : 0;
+    e->opt.dec_x3_min_rb = (int)opt_val(e, "decode_x3_min_rb") < 1 ? 1 : (int)opt_val(e, "decode_x3_min_rb");
     return 0;
 }
 
@@ -462,7 +453,7 @@ int mellow_engine_set_option(mellow_engine_t* e, const char* key, const char* va
     if (end == value || *end) return fail("option \"%s\": \"%s\" is not an integer", key, value);
     if (!strcmp(key, "prefill_split") && (v < 1 || v > 4)) return fail("option prefill_split must be 1..4");
     if (!strcmp(key, "arena_mb") && e->arena) return fail("option arena_mb must be set before the first tensor is loaded");
-    e->opts[key] = value;
+    e->opt.given[key] = value;
     return apply_options(e);
 }
 
@@ -472,11 +463,11 @@ int mellow_engine_set_option(mellow_engine_t* e, const char* key, const char* va
 int64_t mellow_engine_describe(mellow_engine_t* e, char* buf, int64_t capacity) {
     if (!e) return -1;
     std::string s = "{\"abi\": [" + std::to_string(MELLOW_ABI_VERSION) + ", " + std::to_string(MELLOW_ABI_MINOR) + "], \"precision\": \"";
-    s += e->mode == MELLOW_PRECISION_F32 ? "f32" : e->mode == MELLOW_PRECISION_FP8 ? "fp8" : "f32x3";
+    s += e->opt.mode == MELLOW_PRECISION_F32 ? "f32" : e->opt.mode == MELLOW_PRECISION_FP8 ? "fp8" : "f32x3";
     s += "\", \"reads_environment\": false, \"finalized\": ";
     s += e->finalized ? "true" : "false";
     s += ", \"stft_is_fft\": ";
-    s += e->fft_win ? "true" : "false";
+    s += e->w.fft_win ? "true" : "false";
     s += ", \"non_default\": [";
     bool first = true;
     for (const auto& o : kOptions)
@@ -497,12 +488,12 @@ int mellow_last_steps_enqueued(mellow_engine_t* e) { return e ? e->last_steps_en
 
 int mellow_last_row_repacks(mellow_engine_t* e) { return e ? e->last_compactions : -1; }
 
-int mellow_stft_is_fft(mellow_engine_t* e) { return e && e->fft_win ? 1 : 0; }
+int mellow_stft_is_fft(mellow_engine_t* e) { return e && e->w.fft_win ? 1 : 0; }
 
 int mellow_abi_minor(void) { return MELLOW_ABI_MINOR; }
 int mellow_prefill_parts(mellow_engine_t* e) {
     if (!e) return -1;
-    if (!e->f32x3_terms && !(e->fp8 && e->fp8_prefill)) return 1;             // only the f32x3 / fp8 prefills (producers hand over in operand format) split
+    if (!e->opt.f32x3_terms && !(e->opt.fp8 && e->opt.fp8_prefill)) return 1;             // only the f32x3 / fp8 prefills (producers hand over in operand format) split
     if (hipSetDevice(e->device) != hipSuccess) return -1;
     if (ensure_prefill_streams(e) != 0) return -1;
     return e->prefill_parts < 1 ? 1 : (e->prefill_parts > 4 ? 4 : e->prefill_parts);
@@ -554,7 +545,7 @@ int mellow_engine_set_precision(mellow_engine_t* e, int mode) {
     if (e->finalized) return fail("precision must be chosen before mellow_engine_finalize");
     if (mode != MELLOW_PRECISION_F32 && mode != MELLOW_PRECISION_FP8 && mode != MELLOW_PRECISION_F32X3)
         return fail("unknown precision mode %d", mode);
-    e->mode = mode;
+    e->opt.mode = mode;
     return apply_options(e);
 }
 
@@ -567,27 +558,11 @@ int mellow_engine_fork(mellow_engine_t* parent, mellow_engine_t** out) {
     HIPCHK(hipSetDevice(parent->device));
     HIPCHK(hipStreamSynchronize(parent->stream));
     mellow_engine* c = new mellow_engine();
-    c->cfg = parent->cfg; c->device = parent->device; c->finalized = true; c->owns_weights = false; c->use_graph = parent->use_graph;
-    c->opts = parent->opts; c->mode = parent->mode; c->x3_stft = parent->x3_stft; c->stft_fft = parent->stft_fft; c->x3_apb = parent->x3_apb; c->x3_attn = parent->x3_attn; c->x3w = parent->x3w;
-    c->row_migration = parent->row_migration; c->decode_fuse = parent->decode_fuse; c->arena_mb = parent->arena_mb;
-    c->prefill_fuse_norm = parent->prefill_fuse_norm; c->dec_fuse_max_rb = parent->dec_fuse_max_rb; c->enc_apb_stages = parent->enc_apb_stages; c->sk_max = parent->sk_max;
-    c->fp8 = parent->fp8; c->fp8_decode = parent->fp8_decode; c->fp8_decode_act = parent->fp8_decode_act; c->fp8_prefill = parent->fp8_prefill; c->fp8_attn_bf16 = parent->fp8_attn_bf16; c->kv16 = parent->kv16; c->f32x3_terms = parent->f32x3_terms; c->dec_x3 = parent->dec_x3; c->dec_x3_min_rb = parent->dec_x3_min_rb;
-    // weight pointers (device memory owned by the parent)
-    c->dft = parent->dft; c->mel = parent->mel; c->fft_win = parent->fft_win; c->fft_tw1 = parent->fft_tw1; c->fft_tw2 = parent->fft_tw2;
-    c->bn_alpha = parent->bn_alpha; c->bn_beta = parent->bn_beta;
-    c->pe_w = parent->pe_w; c->pe_b = parent->pe_b; c->pe_nw = parent->pe_nw; c->pe_nb = parent->pe_nb;
-    for (int i = 0; i < 4; ++i) c->blocks[i] = parent->blocks[i];
-    for (int i = 0; i < 3; ++i) c->merge[i] = parent->merge[i];
-    for (int i = 0; i < 4; ++i) for (int j = 0; j < 2; ++j) c->win_map[i][j] = parent->win_map[i][j];
-    c->fn_w = parent->fn_w; c->fn_b = parent->fn_b;
-    c->tscam = parent->tscam; c->c2l = parent->c2l; c->lin1 = parent->lin1; c->lin2 = parent->lin2;
-    c->tscam_b = parent->tscam_b; c->c2l_b = parent->c2l_b; c->pln_w = parent->pln_w; c->pln_b = parent->pln_b;
-    c->emb_row_map = parent->emb_row_map;
-    c->embed = parent->embed; c->lm_head = parent->lm_head; c->layers = parent->layers; c->final_norm = parent->final_norm;
-    c->rope_cos = parent->rope_cos; c->rope_sin = parent->rope_sin;
-    c->head8 = parent->head8; c->head_sc = parent->head_sc;
-    c->bf_w = parent->bf_w; c->fp8_w = parent->fp8_w;
-    c->resample_banks = parent->resample_banks;
+    c->cfg = parent->cfg; c->device = parent->device; c->finalized = true; c->owns_weights = false;
+    c->opt = parent->opt;                        // the configuration as resolved by the parent's apply_options ...
+    c->w = parent->w;                            // ... and every weight pointer (device memory owned by the parent)
+    c->use_graph = parent->use_graph;            // the parent's CURRENT setting (mellow_set_graph), not the option's
+    c->resample_banks = parent->resample_banks;  // (banks the fork builds later are its own: allocs)
     // every failure below releases what the child already owns (mellow_engine_destroy copes with a half-built context)
 #define FORK_HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { mellow_engine_destroy(c); return fail("HIP error %s at %s:%d", hipGetErrorString(e_), __FILE__, __LINE__); } } while (0)
     FORK_HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));

@@ -8,15 +8,15 @@ extern "C" {
 __attribute__((visibility("default"))) int mellow_dev_gemm_time(mellow_engine_t* e, int M, int N, int K, int iters, float* ms_out) {
     if (!e || M <= 0 || N <= 0 || K <= 0 || K % 32 || N % 4 || iters <= 0 || !ms_out) return fail("bad argument");
     HIPCHK(hipSetDevice(e->device));
-    float *A = nullptr, *W = nullptr, *Cc = nullptr;
+    mellow_engine::Buf A, W, Cc;
     const size_t NP = (size_t)rup(N, 128);
-    HIPCHK(hipMalloc(&A, (size_t)M * K * 4));
-    HIPCHK(hipMalloc(&W, NP * K * 4));
-    HIPCHK(hipMalloc(&Cc, (size_t)M * N * 4));
-    HIPCHK(hipMemsetAsync(A, 0x3c, (size_t)M * K * 4, e->stream));      // 0x3c3c3c3c = 0.0115 (finite, non-zero)
-    HIPCHK(hipMemsetAsync(W, 0x3c, NP * K * 4, e->stream));
+    CHK(ensure(e, A, (size_t)M * K));
+    CHK(ensure(e, W, NP * K));
+    CHK(ensure(e, Cc, (size_t)M * N));
+    HIPCHK(hipMemsetAsync(A.p, 0x3c, (size_t)M * K * 4, e->stream));      // 0x3c3c3c3c = 0.0115 (finite, non-zero)
+    HIPCHK(hipMemsetAsync(W.p, 0x3c, NP * K * 4, e->stream));
     GemmArgs g;
-    g.A = A; g.lda = K; g.M = M; g.K = K; g.Wp = W; g.Nw = N; g.N = N; g.C = Cc; g.ldc = N;
+    g.A = A.p; g.lda = K; g.M = M; g.K = K; g.Wp = W.p; g.Nw = N; g.N = N; g.C = Cc.p; g.ldc = N;
     launch_gemm(g, e->stream);
     hipEvent_t a, b;
     HIPCHK(hipEventCreate(&a));
@@ -29,7 +29,6 @@ __attribute__((visibility("default"))) int mellow_dev_gemm_time(mellow_engine_t*
     HIPCHK(hipEventElapsedTime(&ms, a, b));
     *ms_out = ms / iters;
     hipEventDestroy(a); hipEventDestroy(b);
-    hipFree(A); hipFree(W); hipFree(Cc);
     return 0;
 }
 
@@ -43,14 +42,15 @@ int mellow_debug_gemm_f32(mellow_engine_t* e, int mode, const float* A, int M, i
     HIPCHK(hipSetDevice(e->device));
     hipStream_t s = e->stream;
     const int NP = rup(N, 128);
-    float *dA = nullptr, *dW = nullptr, *dWp = nullptr, *dC = nullptr;
-    void *dA3 = nullptr, *dPB = nullptr;
-    HIPCHK(hipMalloc(&dA, (size_t)M * K * 4));
-    HIPCHK(hipMalloc(&dW, (size_t)N * K * 4));
-    HIPCHK(hipMalloc(&dWp, (size_t)NP * K * 4));
-    HIPCHK(hipMalloc(&dC, (size_t)M * N * 4));
-    HIPCHK(hipMalloc(&dA3, (size_t)rup(M, 128) * K * 6));
-    HIPCHK(hipMalloc(&dPB, (size_t)NP * K * 6));
+    mellow_engine::Buf bA, bW, bWp, bC, bA3, bPB;
+    CHK(ensure(e, bA, (size_t)M * K));
+    CHK(ensure(e, bW, (size_t)N * K));
+    CHK(ensure(e, bWp, (size_t)NP * K));
+    CHK(ensure(e, bC, (size_t)M * N));
+    CHK(ensure(e, bA3, (size_t)rup(M, 128) * K * 6 / 4));      // 6 bytes per element (the three bf16 pieces)
+    CHK(ensure(e, bPB, (size_t)NP * K * 6 / 4));
+    float *dA = bA.p, *dW = bW.p, *dWp = bWp.p, *dC = bC.p;
+    void *dA3 = bA3.p, *dPB = bPB.p;
     HIPCHK(hipMemcpy(dA, A, (size_t)M * K * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dW, W, (size_t)N * K * 4, hipMemcpyHostToDevice));
     launch_pack_weight(dW, N, K, K, dWp, NP, K, s);
@@ -86,7 +86,6 @@ int mellow_debug_gemm_f32(mellow_engine_t* e, int mode, const float* A, int M, i
         ms2[1] = m1 / iters;
         hipEventDestroy(a); hipEventDestroy(b);
     }
-    hipFree(dA); hipFree(dW); hipFree(dWp); hipFree(dC); hipFree(dA3); hipFree(dPB);
     return 0;
 }
 
@@ -98,16 +97,17 @@ int mellow_debug_gemm_fp8(mellow_engine_t* e, const float* A, int M, int K, cons
     HIPCHK(hipSetDevice(e->device));
     hipStream_t s = e->stream;
     const int NP = rup(N, 128), K64 = rup(K, 64), Mp = rup(M, 128);
-    float *dA = nullptr, *dW = nullptr, *dWp = nullptr, *dC = nullptr, *dsa = nullptr, *dsw = nullptr;
-    uint8_t *dA8 = nullptr, *dW8 = nullptr;
-    HIPCHK(hipMalloc(&dA, (size_t)M * K * 4));
-    HIPCHK(hipMalloc(&dW, (size_t)N * K * 4));
-    HIPCHK(hipMalloc(&dWp, (size_t)NP * K * 4));
-    HIPCHK(hipMalloc(&dC, (size_t)M * N * 4));
-    HIPCHK(hipMalloc(&dsa, (size_t)Mp * ((K64 / 64 + 3) / 4) * 8));       // 2 scale words per row and four k64 steps
-    HIPCHK(hipMalloc(&dsw, (size_t)NP * 4));
-    HIPCHK(hipMalloc(&dA8, (size_t)Mp * K64));
-    HIPCHK(hipMalloc(&dW8, (size_t)NP * K64));
+    mellow_engine::Buf bA, bW, bWp, bC, bsa, bsw, bA8, bW8;
+    CHK(ensure(e, bA, (size_t)M * K));
+    CHK(ensure(e, bW, (size_t)N * K));
+    CHK(ensure(e, bWp, (size_t)NP * K));
+    CHK(ensure(e, bC, (size_t)M * N));
+    CHK(ensure(e, bsa, (size_t)Mp * ((K64 / 64 + 3) / 4) * 2));       // 2 scale words per row and four k64 steps
+    CHK(ensure(e, bsw, (size_t)NP));
+    CHK(ensure(e, bA8, (size_t)Mp * K64 / 4));                        // one byte per element (Mp, NP and K64 are multiples of 64)
+    CHK(ensure(e, bW8, (size_t)NP * K64 / 4));
+    float *dA = bA.p, *dW = bW.p, *dWp = bWp.p, *dC = bC.p, *dsa = bsa.p, *dsw = bsw.p;
+    uint8_t *dA8 = reinterpret_cast<uint8_t*>(bA8.p), *dW8 = reinterpret_cast<uint8_t*>(bW8.p);
     HIPCHK(hipMemcpy(dA, A, (size_t)M * K * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dW, W, (size_t)N * K * 4, hipMemcpyHostToDevice));
     launch_pack_weight(dW, N, K, K, dWp, NP, K, s);
@@ -139,7 +139,6 @@ int mellow_debug_gemm_fp8(mellow_engine_t* e, const float* A, int M, int K, cons
         ms_out[1] = ms_g / iters;
         hipEventDestroy(a); hipEventDestroy(b);
     }
-    hipFree(dA); hipFree(dW); hipFree(dWp); hipFree(dC); hipFree(dsa); hipFree(dsw); hipFree(dA8); hipFree(dW8);
     return 0;
 }
 

@@ -4,10 +4,10 @@
 // ---- GEMM wrappers -------------------------------------------------------------------------------------------------------
 // split-K workspace of the f32x3 kernels (kernels.h: sk_*), handed to launches of the encoder chain only
 static void with_splitk(mellow_engine* e, GemmArgs& g) {
-    if (!e->sk_enable || e->sk_max < 2 || !e->sk_ws.p) return;
+    if (!e->sk_enable || e->opt.sk_max < 2 || !e->sk_ws.p) return;
     g.sk_ws = e->sk_ws.p;
     g.sk_tiles = 256;
-    g.sk_max = e->sk_max;
+    g.sk_max = e->opt.sk_max;
 }
 int run_gemm(mellow_engine* e, const GemmArgs& a) {
     // f32x3: every dense GEMM of encoder + prefill, the STFT (EPI_POWER, K = 1024, framed A operand) and the mel projection
@@ -15,11 +15,11 @@ int run_gemm(mellow_engine* e, const GemmArgs& a) {
     // of its maximum -- two fp32 summation orders of a 1024-term dot product, squared -- while against an fp64 STFT it is
     // closer than the oracle's own fp32 arithmetic (tests/test_gpu_parity.py::test_encoder_taps holds it to both).
     // Option "x3_stft" = 0 keeps the front-end on the exact fp32 kernel.
-    const bool x3_stft = e->x3_stft;
-    if (e->f32x3_terms && a.K % 16 == 0 &&
+    const bool x3_stft = e->opt.x3_stft;
+    if (e->opt.f32x3_terms && a.K % 16 == 0 &&
         ((a.a_mode == A_PLAIN && (a.epi == EPI_LINEAR || a.epi == EPI_SWIGLU || a.epi == EPI_QKV_ROPE)) || (x3_stft && a.K >= 192))) {
-        auto it = e->bf_w.find(a.Wp);
-        if (it != e->bf_w.end()) {
+        auto it = e->w.bf_w.find(a.Wp);
+        if (it != e->w.bf_w.end()) {
             // fused kernel: A stays fp32 (global and LDS) and is split into its three bf16 terms in registers
             GemmArgs g = a;
             g.W8 = reinterpret_cast<const uint8_t*>(it->second);
@@ -30,9 +30,9 @@ int run_gemm(mellow_engine* e, const GemmArgs& a) {
             return 0;
         }
     }
-    if (e->fp8 && e->fp8_prefill && a.a_mode == A_PLAIN && (a.epi == EPI_LINEAR || a.epi == EPI_SWIGLU || a.epi == EPI_QKV_ROPE)) {
-        auto it = e->fp8_w.find(a.Wp);
-        if (it != e->fp8_w.end()) {
+    if (e->opt.fp8 && e->opt.fp8_prefill && a.a_mode == A_PLAIN && (a.epi == EPI_LINEAR || a.epi == EPI_SWIGLU || a.epi == EPI_QKV_ROPE)) {
+        auto it = e->w.fp8_w.find(a.Wp);
+        if (it != e->w.fp8_w.end()) {
             // no producer handed this input over quantised: the standalone fp32 -> AMX pass, then the MX GEMM (same epilogue);
             // profiled as one launch of the family
             const int64_t lda8 = (a.K + 63) / 64 * 64, Mp = rup(a.M, 128);
@@ -61,8 +61,8 @@ int run_gemm_apb(mellow_engine* e, const GemmArgs& a, const void* a3, hipStream_
     GemmArgs g = a;
     g.A8 = reinterpret_cast<const uint8_t*>(a3);
     if (a3_scales) {
-        auto it = e->fp8_w.find(a.Wp);
-        if (it == e->fp8_w.end()) return fail("internal: no e4m3 copy of this weight");
+        auto it = e->w.fp8_w.find(a.Wp);
+        if (it == e->w.fp8_w.end()) return fail("internal: no e4m3 copy of this weight");
         g.a_sc = reinterpret_cast<const uint32_t*>(a3_scales); g.lda8 = rup(a.K, 64);
         g.W8 = it->second.w8; g.w_scale = it->second.scale;
         ProfScope ps(e, PF_GEMM, gemm_flops(a), 0.0);
@@ -70,11 +70,11 @@ int run_gemm_apb(mellow_engine* e, const GemmArgs& a, const void* a3, hipStream_
         launch_gemm_fp8(g, st ? st : e->stream);
         return 0;
     }
-    auto it = e->bf_w.find(a.Wp);
-    if (it == e->bf_w.end()) return fail("internal: no bf16-split copy of this weight");
+    auto it = e->w.bf_w.find(a.Wp);
+    if (it == e->w.bf_w.end()) return fail("internal: no bf16-split copy of this weight");
     g.W8 = reinterpret_cast<const uint8_t*>(it->second);
     if (!st || st == e->stream) with_splitk(e, g);
-    g.no_x3w = !e->x3w;
+    g.no_x3w = !e->opt.x3w;
     ProfScope ps(e, PF_GEMM, gemm_flops(a), 0.0);
     ps.r.M = a.M; ps.r.N = a.Nw; ps.r.K = a.K; ps.r.epi = a.epi + 300;
     launch_gemm_bf16x3_apb(g, st ? st : e->stream);
@@ -97,7 +97,7 @@ int run_encoder(mellow_engine* e, const float* wav, int n, int64_t n_samples, in
         mellow_engine* e;
         ~SkScope() { e->sk_enable = false; }
     } sk_scope{e};
-    if (e->f32x3_terms && e->sk_max >= 2) {
+    if (e->opt.f32x3_terms && e->opt.sk_max >= 2) {
         CHK(ensure(e, e->sk_ws, (size_t)512 * 16384));
         e->sk_enable = e->sk_ws.p != nullptr;
     }
@@ -111,22 +111,22 @@ int run_encoder(mellow_engine* e, const float* wav, int n, int64_t n_samples, in
         ProfScope ps(e, PF_MISC, 0, 2.0 * n * plen * 4);
         launch_reflect_pad(wav, n, n_samples, e->wpad.p, plen, kNfft / 2, s);
     }
-    if (e->fft_win) {   // A1 as a real FFT (f32x3 mode, weights verified to be the windowed DFT basis): 5 N log2 N flops per frame
+    if (e->w.fft_win) {   // A1 as a real FFT (f32x3 mode, weights verified to be the windowed DFT basis): 5 N log2 N flops per frame
         ProfScope ps(e, PF_GEMM, 5.0 * kNfft * 10.0 * M, (double)M * (kNfft + 544) * 4);
         ps.r.M = M; ps.r.N = 544; ps.r.K = kNfft; ps.r.epi = 400;
-        launch_stft_fft_power(e->wpad.p, frames, plen, kHop, M, e->fft_win, e->fft_tw1, e->fft_tw2, e->power.p, s);
+        launch_stft_fft_power(e->wpad.p, frames, plen, kHop, M, e->w.fft_win, e->w.fft_tw1, e->w.fft_tw2, e->power.p, s);
     } else {   // A1: STFT power as DFT GEMM on the checkpoint's conv weights (htsat.py:864)
         GemmArgs g;
         g.A = e->wpad.p; g.a_mode = A_FRAMES; g.fpc = frames; g.clip_stride = plen; g.hop = kHop;
-        g.M = M; g.K = kNfft; g.Wp = e->dft.p; g.Nw = e->dft.Nw; g.N = 544; g.C = e->power.p; g.ldc = 544; g.epi = EPI_POWER;
+        g.M = M; g.K = kNfft; g.Wp = e->w.dft.p; g.Nw = e->w.dft.Nw; g.N = 544; g.C = e->power.p; g.ldc = 544; g.epi = EPI_POWER;
         CHK(run_gemm(e, g));
     }
     CHK(tap(e, "power", e->power.p, (int64_t)M * 544));
     {   // A2+A3: mel projection, 10*log10, bn0 (htsat.py:865-870)
         GemmArgs g;
-        g.A = e->power.p; g.lda = 544; g.M = M; g.K = 544; g.Wp = e->mel.p; g.Nw = 64; g.N = 64;
+        g.A = e->power.p; g.lda = 544; g.M = M; g.K = 544; g.Wp = e->w.mel.p; g.Nw = 64; g.N = 64;
         g.C = want_logmel_only ? logmel_out : e->logmel.p; g.ldc = 64; g.epi = EPI_LOGMEL;
-        g.apply_bn = apply_bn; g.bn_alpha = e->bn_alpha; g.bn_beta = e->bn_beta;
+        g.apply_bn = apply_bn; g.bn_alpha = e->w.bn_alpha; g.bn_beta = e->w.bn_beta;
         CHK(run_gemm(e, g));
     }
     if (want_logmel_only) return 0;
@@ -149,7 +149,7 @@ int run_encoder(mellow_engine* e, const float* wav, int n, int64_t n_samples, in
     CHK(ensure(e, e->H, (size_t)M0 * 384));
     {
         ProfScope ps(e, PF_MISC, 0, (double)M0 * 96 * 4);
-        launch_fold_patch_embed(e->logmel.p, n, frames, n_crops, crop_hop, crop_len, e->pe_w, e->pe_b, e->pe_nw, e->pe_nb,
+        launch_fold_patch_embed(e->logmel.p, n, frames, n_crops, crop_hop, crop_len, e->w.pe_w, e->w.pe_b, e->w.pe_nw, e->w.pe_nb,
                                 e->X0.p, s);
     }
     CHK(tap(e, "patch", e->X0.p, M0 * 96));
@@ -159,9 +159,9 @@ int run_encoder(mellow_engine* e, const float* wav, int n, int64_t n_samples, in
         const int nW = R > kWin ? (R / kWin) * (R / kWin) : 1;
         const int M1 = nv * N;
         for (int b = 0; b < kDepths[st]; ++b) {
-            const SwinBlockW& w = e->blocks[st][b];
+            const SwinBlockW& w = e->w.blocks[st][b];
             const bool shifted = (b % 2 == 1) && R > kWin;
-            const int32_t* map = R > kWin ? e->win_map[st][shifted ? 1 : 0] : nullptr;
+            const int32_t* map = R > kWin ? e->w.win_map[st][shifted ? 1 : 0] : nullptr;
             // f32x3 mode, stages in enc_apb_stages: the LayerNorms and the GELU epilogue of fc1 write their output pre-split in APB
             // order and qkv / fc1 / fc2 run on the LDS-DMA kernel (gemm_x3q_kernel); H never exists as fp32
             // bit 8 + st: only the LayerNorms hand over pre-split (qkv and fc1 on the APB kernels, fc1 still writes fp32): stage 0,
@@ -170,10 +170,10 @@ int run_encoder(mellow_engine* e, const float* wav, int n, int64_t n_samples, in
             // epilogue of fc1 emit e4m3 + block scales in the consumer's LDS order, qkv / fc1 / fc2 run on gemm_mx8_kernel straight
             // from them (K = 96 zero-padded to two k64 steps); the window attention still writes fp32 (head_dim 24 does not tile 32-
             // column blocks) and the proj GEMM takes the standalone quantiser
-            const bool amx = e->fp8 && e->fp8_prefill && e->x3_apb && e->fp8_w.count(w.qkv.p) && e->fp8_w.count(w.fc1.p) && e->fp8_w.count(w.fc2.p);
-            const bool have_pb = e->f32x3_terms && e->bf_w.count(w.qkv.p) && e->bf_w.count(w.fc1.p) && e->bf_w.count(w.fc2.p);
-            const bool apb_h = amx || (have_pb && ((e->enc_apb_stages >> st) & 1));
-            const bool apb = apb_h || (have_pb && ((e->enc_apb_stages >> (8 + st)) & 1));
+            const bool amx = e->opt.fp8 && e->opt.fp8_prefill && e->opt.x3_apb && e->w.fp8_w.count(w.qkv.p) && e->w.fp8_w.count(w.fc1.p) && e->w.fp8_w.count(w.fc2.p);
+            const bool have_pb = e->opt.f32x3_terms && e->w.bf_w.count(w.qkv.p) && e->w.bf_w.count(w.fc1.p) && e->w.bf_w.count(w.fc2.p);
+            const bool apb_h = amx || (have_pb && ((e->opt.enc_apb_stages >> st) & 1));
+            const bool apb = apb_h || (have_pb && ((e->opt.enc_apb_stages >> (8 + st)) & 1));
             const size_t M1p = (size_t)rup(M1, 128);
             char *a3s = nullptr, *h3s = nullptr;          // fp8 mode: scale bytes behind the image data, in the same buffers
             if (apb) {
@@ -186,7 +186,7 @@ int run_encoder(mellow_engine* e, const float* wav, int n, int64_t n_samples, in
                 { ProfScope ps(e, PF_NORM, 0, 2.5 * M1 * C * 4); launch_layernorm_apb(x, e->enc_a3.p, M1, C, w.n1w, w.n1b, map, N, s, a3s); }
                 {
                     GemmArgs g = lin(nullptr, C, M1, w.qkv, e->QKV.p, 3 * C, w.qkv_b);
-                    g.c16 = (amx && e->fp8_attn_bf16) ? 1 : 0;      // fp8 mode: q / k / v of the block as bf16 rows (the window attention widens them)
+                    g.c16 = (amx && e->opt.fp8_attn_bf16) ? 1 : 0;      // fp8 mode: q / k / v of the block as bf16 rows (the window attention widens them)
                     CHK(run_gemm_apb(e, g, e->enc_a3.p, s, a3s));
                 }
             } else {
@@ -194,10 +194,10 @@ int run_encoder(mellow_engine* e, const float* wav, int n, int64_t n_samples, in
                 CHK(run_gemm(e, lin(t, C, M1, w.qkv, e->QKV.p, 3 * C, w.qkv_b)));
             }
             // bits 4..7 of enc_apb_stages: the window attention hands its output over pre-split too (proj on the x3q kernel)
-            const bool apb_proj = apb && !amx && ((e->enc_apb_stages >> (4 + st)) & 1) && e->bf_w.count(w.proj.p);
+            const bool apb_proj = apb && !amx && ((e->opt.enc_apb_stages >> (4 + st)) & 1) && e->w.bf_w.count(w.proj.p);
             {
                 ProfScope ps(e, PF_WINDOW_ATTN, 4.0 * 64 * 64 * 24 * (double)(M1 / 64) * nH, 4.0 * M1 * C * 4);
-                launch_window_attention(e->QKV.p, t, M1, C, nH, w.bias_exp, shifted ? w.mask : nullptr, nW, s, apb_proj ? e->enc_a3.p : nullptr, amx && e->fp8_attn_bf16);
+                launch_window_attention(e->QKV.p, t, M1, C, nH, w.bias_exp, shifted ? w.mask : nullptr, nW, s, apb_proj ? e->enc_a3.p : nullptr, amx && e->opt.fp8_attn_bf16);
             }
             {
                 GemmArgs g = lin(t, C, M1, w.proj, x, C, w.proj_b);
@@ -234,8 +234,8 @@ int run_encoder(mellow_engine* e, const float* wav, int n, int64_t n_samples, in
             }
         }
         if (st < 3) {
-            { ProfScope ps(e, PF_NORM, 0, 2.0 * M1 * C * 4); launch_merge_layernorm(x, t, nv, R, C, e->merge[st].nw, e->merge[st].nb, s); }
-            CHK(run_gemm(e, lin(t, 4 * C, M1 / 4, e->merge[st].red, x2, 2 * C, nullptr)));
+            { ProfScope ps(e, PF_NORM, 0, 2.0 * M1 * C * 4); launch_merge_layernorm(x, t, nv, R, C, e->w.merge[st].nw, e->w.merge[st].nb, s); }
+            CHK(run_gemm(e, lin(t, 4 * C, M1 / 4, e->w.merge[st].red, x2, 2 * C, nullptr)));
             float* tmp = x; x = x2; x2 = tmp;
         }
         if (e->taps_on) {
@@ -253,7 +253,7 @@ int run_encoder(mellow_engine* e, const float* wav, int n, int64_t n_samples, in
     CHK(ensure(e, e->gbuf, (size_t)n * 33 * 576));
     CHK(ensure(e, e->sbuf, (size_t)n * 33 * 576));
     CHK(ensure(e, e->proj33, (size_t)n * 33 * 576));
-    { ProfScope ps(e, PF_NORM, 0, 2.0 * nv * 64 * 768 * 4); launch_layernorm(x, t, nv * 64, kEncOut, e->fn_w, e->fn_b, nullptr, 64, s); }
+    { ProfScope ps(e, PF_NORM, 0, 2.0 * nv * 64 * 768 * 4); launch_layernorm(x, t, nv * 64, kEncOut, e->w.fn_w, e->w.fn_b, nullptr, 64, s); }
     float* latent_dst = e->emb33.p;
     int64_t latent_stride = 33 * 768;
     if (n_crops > 1) {
@@ -264,7 +264,7 @@ int run_encoder(mellow_engine* e, const float* wav, int n, int64_t n_samples, in
     }
     { ProfScope ps(e, PF_MISC, 0, 7.0 * nv * 64 * 768 * 4); launch_tail_latent_im2col(t, nv, latent_dst, latent_stride, e->ats.p, s); }
     {
-        GemmArgs g = lin(e->ats.p, 4608, nv * 32, e->tscam, e->fpx.p, 544, e->tscam_b);
+        GemmArgs g = lin(e->ats.p, 4608, nv * 32, e->w.tscam, e->fpx.p, 544, e->w.tscam_b);
         g.N = 544; g.act = ACT_SIGMOID;
         CHK(run_gemm(e, g));
     }
@@ -277,19 +277,19 @@ int run_encoder(mellow_engine* e, const float* wav, int n, int64_t n_samples, in
     }
     CHK(tap(e, "fpx", fpx, (int64_t)n * 32 * 544));
     {   // c2l on the 32 distinct framewise rows -> embedding rows 1..32 (htsat.py:952-954)
-        GemmArgs g = lin(fpx, 544, n * 32, e->c2l, e->emb33.p, 768, e->c2l_b);
-        g.crow_map = e->emb_row_map; g.rows_in = 32; g.rows_out = 33;
+        GemmArgs g = lin(fpx, 544, n * 32, e->w.c2l, e->emb33.p, 768, e->w.c2l_b);
+        g.crow_map = e->w.emb_row_map; g.rows_in = 32; g.rows_out = 33;
         CHK(run_gemm(e, g));
     }
     CHK(tap(e, "emb33", e->emb33.p, (int64_t)n * 33 * 768));
-    CHK(run_gemm(e, lin(e->emb33.p, 768, n * 33, e->lin1, e->e1.p, 576, nullptr)));
+    CHK(run_gemm(e, lin(e->emb33.p, 768, n * 33, e->w.lin1, e->e1.p, 576, nullptr)));
     { ProfScope ps(e, PF_MISC, 0, 0); launch_gelu(e->e1.p, e->gbuf.p, (int64_t)n * 33 * 576, s); }
     {
-        GemmArgs g = lin(e->gbuf.p, 576, n * 33, e->lin2, e->sbuf.p, 576, nullptr);
+        GemmArgs g = lin(e->gbuf.p, 576, n * 33, e->w.lin2, e->sbuf.p, 576, nullptr);
         g.resid = e->e1.p; g.ldr = 576;
         CHK(run_gemm(e, g));
     }
-    { ProfScope ps(e, PF_NORM, 0, 0); launch_layernorm(e->sbuf.p, e->proj33.p, n * 33, 576, e->pln_w, e->pln_b, nullptr, 33, s); }
+    { ProfScope ps(e, PF_NORM, 0, 0); launch_layernorm(e->sbuf.p, e->proj33.p, n * 33, 576, e->w.pln_w, e->w.pln_b, nullptr, 33, s); }
     CHK(tap(e, "proj33", e->proj33.p, (int64_t)n * 33 * 576));
     CHK(tap(e, "latent", e->emb33.p, 768));  // first clip's latent row (row 0 of emb33)
     HIPCHK(hipGetLastError());

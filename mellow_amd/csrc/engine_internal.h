@@ -5,6 +5,8 @@
 //   engine_encoder.cpp  GEMM dispatch, front-end + HTSAT encoder (A1-A13), the taps mellow_logmel / mellow_encode / mellow_resample
 //   engine_lm.cpp       KV pages, LM prefill (A15), the decode step, mellow_prefix / lm taps, mellow_generate (A16)
 //   engine_dev.cpp      developer entry points (GEMM timing / debug taps, kernel stamps)
+// The engine object (below): `Options` + `Weights` are what a fork shares, each copied by one assignment; everything else is one
+// context's own -- stream, events, workspaces (`Buf` frees itself), KV pages, loop words, the decode-graph cache (`StepGraphs`).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,6 +20,8 @@
 #include <unordered_map>
 #include <string>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/mellow_hip.h"
@@ -121,18 +125,98 @@ struct ProfRec {
     int M = 0, N = 0, K = 0, epi = 0;     // GEMM launches only (developer shape report)
 };
 
+// One execution context.  `opt` and `w` are what a fork shares with its parent (copied whole by mellow_engine_fork); the rest is its own.
+#define LOCAL __attribute__((visibility("hidden")))      // (the handle type is declared inside the public header's visibility pragma)
 struct mellow_engine {
+    // A grow-only device workspace (ensure(), engine.cpp).  It owns its memory and frees itself, so it moves and is never copied.
+    struct Buf {
+        float* p = nullptr;
+        size_t cap = 0;
+        Buf() = default; Buf(const Buf&) = delete; Buf& operator=(const Buf&) = delete;
+        Buf(Buf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+        Buf& operator=(Buf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+        LOCAL ~Buf() { if (p) (void)hipFree(p); }
+    };
+    // The configuration AS CONFIGURED: the caller's option table, the mode and what apply_options() (the only writer) resolves from
+    // them; read-only after finalize.  (use_graph and prefill_parts below are seeded there too but change per context: live state.)
+    struct LOCAL Options {
+        // explicit configuration (mellow_engine_set_option): key -> value as given by the caller.  The library reads NO environment
+        // variable; apply_options() turns this table + the mode into the fields below, mellow_engine_describe() reports them
+        std::map<std::string, std::string> given;
+        int mode = MELLOW_PRECISION_F32X3;
+        bool x3_stft = true, stft_fft = true, x3_apb = true, x3_attn = true, x3w = true, row_migration = true, decode_fuse = true;
+        int arena_mb = 3400;
+        bool kv16 = false;           // fp8 mode default; option "fp8_kv16" = 0 keeps the decode step on the fp32 pages
+        // fp8 GEMM mode (BASELINE config 5): every packed weight with KP % 64 == 0 also gets a P8 copy + per-row scales,
+        // looked up by the fp32 packed pointer when a GEMM is issued; activations are quantised per row right before the GEMM
+        bool fp8 = false;
+        bool fp8_decode = false;                     // fp8 mode: the decode kernels read e4m3 weights too (option "fp8_decode")
+        bool fp8_decode_act = false;                 // ... and quantise their activations: fp8 matrix pipe (option "fp8_decode_act")
+        bool fp8_attn_bf16 = true;                   // fp8 mode: prefill attention on operands rounded once to bf16 (option "fp8_attn_bf16" = 0: the exact 3-way split)
+        bool fp8_prefill = true;                     // fp8 mode: e4m3 GEMMs in encoder + prefill (option "fp8_prefill" = 0: a test isolating the decode weights)
+        int dec_x3_min_rb = 2;                       // the fewest 32-row blocks at which the layer GEMM launches take their f32x3 forms (option "decode_x3_min_rb")
+        int dec_x3 = 0;                              // f32x3 mode: DEC_X3_* mask of the decode GEMM launches on the bf16 pipe (option "decode_x3", developer A/B)
+        int f32x3_terms = 0;                         // 0 = off; 6 = fp32 GEMMs on the bf16 pipe by exact 3-way operand splitting (six partial products)
+        // f32x3 LM prefill without RMSNorm launches: the o_proj / down GEMMs write their output pre-split + its sum of squares,
+        // the q/k/v and gate/up GEMMs run on norm-folded weights and scale their accumulators by the row statistic (run_prefill).
+        // option "prefill_fuse_norm" = 0: the two-launch form (developer A/B).
+        bool prefill_fuse_norm = true;
+        int enc_apb_stages = 0x1CC;                  // f32x3 mode: Swin stages (bit st) whose LayerNorms / fc1 hand their output over pre-split (APB) to x3q GEMMs
+        int sk_max = 8;                              // f32x3 encoder: largest split count of the split-K launches (option "splitk"; < 2 = never split)
+        int dec_fuse_max_rb = 1;                     // decode: largest number of 32-row blocks that runs the fused down + q/k/v launch (fp32 weights)
+    };
+    struct Fp8W { uint8_t* w8; float* scale; };
+    // Every weight pointer and packed-weight record: memory of the engine that finalized them (allocs / arena), read-only afterwards; a fork copies the POINTERS
+    struct LOCAL Weights {
+        // encoder weights
+        Packed dft, mel;
+        // f32x3 mode: the STFT as a real FFT when the checkpoint's conv weights are window[n] * cos / sin(2 pi k n / 1024) (checked
+        // element by element at load time); fft_win == nullptr: the DFT GEMM on the checkpoint's weights
+        float *fft_win = nullptr, *fft_tw1 = nullptr, *fft_tw2 = nullptr;
+        float *bn_alpha = nullptr, *bn_beta = nullptr;
+        float *pe_w = nullptr, *pe_b = nullptr, *pe_nw = nullptr, *pe_nb = nullptr;
+        std::vector<SwinBlockW> blocks[4];
+        MergeW merge[3];
+        int32_t* win_map[4][2] = {{nullptr}};     // [stage][shifted]
+        float *fn_w = nullptr, *fn_b = nullptr;
+        Packed tscam, c2l, lin1, lin2;
+        float *tscam_b = nullptr, *c2l_b = nullptr, *pln_w = nullptr, *pln_b = nullptr;
+        int32_t* emb_row_map = nullptr;           // {1..32}
+        // LM
+        float* embed = nullptr;                   // row-major [V][H]
+        Packed lm_head;
+        std::vector<LMLayerW> layers;
+        float* final_norm = nullptr;
+        float *rope_cos = nullptr, *rope_sin = nullptr;
+        float *head8 = nullptr, *head_sc = nullptr;  // e4m3 lm_head for the decode step
+        DecW head_w() const { return head8 ? DecW{head8, head_sc} : DecW{lm_head.p, nullptr}; }
+        std::unordered_map<const float*, void*> bf_w;   // fp32 packed pointer -> PB copy
+        std::unordered_map<const float*, Fp8W> fp8_w;
+    };
+    // The captured decode step and what it was captured with: the graphs bake buffer addresses in (max_len / stop id travel in
+    // d_params, the sampling parameters in d_sparams).  generate_pass captures, ensure_lm invalidates.
+    struct LOCAL StepGraphs {
+        struct Key {
+            int B = -1, Tmax = -1, sample = -1;     // batch, page geometry, sampling mode (the sampler + logits store, or the arg-max)
+            const void *out_tok = nullptr, *blk_live = nullptr, *row_of_slot = nullptr;      // token record, DecArgs::blk_live / ::row_of_slot
+            bool operator==(const Key& k) const { return B == k.B && Tmax == k.Tmax && out_tok == k.out_tok && blk_live == k.blk_live && row_of_slot == k.row_of_slot && sample == k.sample; }
+        };
+        hipGraphExec_t one = nullptr, eight = nullptr;      // eight: the same step 8 times in a row (the step is position-independent)
+        Key key;
+        StepGraphs() = default; StepGraphs(const StepGraphs&) = delete; StepGraphs& operator=(const StepGraphs&) = delete;
+        void reset() {                              // the only place an exec is destroyed
+            for (hipGraphExec_t* x : {&one, &eight}) if (*x) { (void)hipGraphExecDestroy(*x); *x = nullptr; }
+        }
+        ~StepGraphs() { reset(); }
+    };
+
     mellow_config_t cfg;
     int device = 0;
     hipStream_t stream = nullptr;
-    // explicit configuration (mellow_engine_set_option, engine.cpp): key -> value as given by the caller.  The library reads NO
-    // environment variable; apply_options() turns this table (+ the precision mode) into the fields below, and
-    // mellow_engine_describe() reports the resolved values.
-    std::map<std::string, std::string> opts;
-    int mode = MELLOW_PRECISION_F32X3;
-    bool x3_stft = true, stft_fft = true, x3_apb = true, x3_attn = true, x3w = true, row_migration = true, decode_fuse = true;
-    int arena_mb = 3400;
-    int prefill_parts = 2;                      // parts of the split LM prefill (option "prefill_split")
+    Options opt;
+    Weights w;
+    bool use_graph = true;                      // live: option "graph", then mellow_set_graph
+    int prefill_parts = 2;                      // live: parts of the split LM prefill (option "prefill_split"; ensure_prefill_streams / forks lower it)
     bool streams_probed = false;                // a probe found fewer overlapping streams than asked for (ensure_prefill_streams): re-probed after 16 calls
     int probe_backoff = 0, prefill_parts_ok = 1, prefill_parts_want = 2;
     hipStream_t stream2[3] = {nullptr, nullptr, nullptr};      // further streams of the split LM prefill (run_prefill)
@@ -143,38 +227,13 @@ struct mellow_engine {
     std::vector<void*> allocs;                // everything hipMalloc'd for weights
     char* arena = nullptr;                    // one big allocation the weights are carved from
     size_t arena_size = 0, arena_used = 0;
+    bool decode_only_weight = false;          // set while packing weights only the decode kernels read: no bf16x3 / fp8 copy
 
-    // encoder weights
-    Packed dft, mel;
-    // f32x3 mode: the STFT as a real FFT when the checkpoint's conv weights are window[n] * cos / sin(2 pi k n / 1024) (checked
-    // element by element at load time); fft_win == nullptr: the DFT GEMM on the checkpoint's weights
-    float *fft_win = nullptr, *fft_tw1 = nullptr, *fft_tw2 = nullptr;
-    float *bn_alpha = nullptr, *bn_beta = nullptr;
-    float *pe_w = nullptr, *pe_b = nullptr, *pe_nw = nullptr, *pe_nb = nullptr;
-    std::vector<SwinBlockW> blocks[4];
-    MergeW merge[3];
-    int32_t* win_map[4][2] = {{nullptr}};     // [stage][shifted]
-    float *fn_w = nullptr, *fn_b = nullptr;
-    Packed tscam, c2l, lin1, lin2;
-    float *tscam_b = nullptr, *c2l_b = nullptr, *pln_w = nullptr, *pln_b = nullptr;
-    int32_t* emb_row_map = nullptr;           // {1..32}
-    // LM
-    float* embed = nullptr;                   // row-major [V][H]
-    Packed lm_head;
-    std::vector<LMLayerW> layers;
-    float* final_norm = nullptr;
-    float *rope_cos = nullptr, *rope_sin = nullptr;
-
-    // workspaces (grow-only)
-    struct Buf {
-        float* p = nullptr;
-        size_t cap = 0;
-    };
+    // workspaces (grow-only; released with the engine)
     Buf wavcat, wpad, power, logmel, X0, X1, T, QKV, H, ats, fpx, fpxavg, latv, emb33, e1, gbuf, sbuf, proj33;
     Buf lm_x, lm_xn, lm_q, lm_o, lm_h, kcache, vcache;
     Buf kcache16, vcache16;      // fp8 mode: bf16 shadow of the pages for the decode step (half the floats of kcache / vcache)
     bool kv16_direct = false;    // ... and the prefill writes them itself (q/k/v epilogue) and reads them (bf16-once attention): no fp32 pages, no conversion pass
-    bool kv16 = false;           // fp8 mode default; option "fp8_kv16" = 0 keeps the decode step on the fp32 pages
     Buf lm_xn3, lm_o3, lm_h3;                  // f32x3 mode: the GEMM inputs of LM prefill, pre-split by their producers (APB order)
     Buf lm_ssq;                                // ... and the per-row sum-of-squares partials of the residual stream (norm-free chaining)
     Buf dec;                                   // one arena for the decode-step buffers (DecArgs)
@@ -182,17 +241,19 @@ struct mellow_engine {
     // scoring (mellow_score / mellow_lm_score): the B prefixes of a call [B][prefix_len][hidden], the fused head's per-(64-column
     // group, row) partials (three words per entry), and the small per-row words (targets, target logits, candidate lengths)
     Buf sc_prefix, sc_part, sc_ws;
+    Buf sk_ws;                                 // split-K workspace of the f32x3 GEMMs (512 partial tiles of 128 x 128 fp32);
+    bool sk_enable = false;                    // ... only launches of the encoder chain (one stream) may use it: run_encoder switches it on
+    Buf enc_a3, enc_h3;                        // f32x3 / fp8 encoder: the two pre-split operands (LayerNorm output; GELU(fc1) output)
+    Buf a8, a8_scale;                          // quantised A operand of the GEMM in flight (bytes / floats, carved from float buffers)
     DecArgs da;
     int32_t *d_tokens = nullptr, *d_step = nullptr, *d_pos = nullptr, *d_seen = nullptr, *d_nseen = nullptr;
     int32_t *d_arrive = nullptr, *d_ticket = nullptr, *d_params = nullptr;   // loop bookkeeping words (LoopArgs)
     int32_t *d_blk_left = nullptr, *d_blk_live = nullptr;                    // per-row-block early exit (32 blocks max)
     int32_t *d_row_of_slot = nullptr, *d_ncompact = nullptr;                 // row migration (kernels.h, DecArgs::row_of_slot)
     int last_compactions = 0;
-    const void* graph_blk = nullptr;                                         // DecArgs::blk_live the graphs were captured with
-    const void* graph_rows = nullptr;                                        // DecArgs::row_of_slot likewise
     unsigned long long* h_progress = nullptr;  // mapped host word the arg-max kernel publishes (ticket << 32 | rows stopped) to
     unsigned long long* d_progress = nullptr;  // its device alias
-    std::map<std::pair<int, int>, float*> resample_banks;   // (orig, new) gcd-reduced -> device polyphase bank [klen][new]
+    std::map<std::pair<int, int>, float*> resample_banks;   // (orig, new) gcd-reduced -> device polyphase bank [klen][new]; a fork starts from its parent's
     int32_t h_params[2] = {0, 0};              // staging of d_params {max_len, stop id}
     uint32_t* d_sparams = nullptr;             // sampling parameter block (kernels.h SMP_*): graph replays serve any seed / top_p / T
     uint32_t h_sparams[SMP_WORDS] = {0};       // ... its staging
@@ -204,50 +265,17 @@ struct mellow_engine {
     int kv_B = 0, kv_Tmax = 0;                // current page geometry
     int cur_B = 0, cur_pos = 0;               // host mirror of the decode state
     int32_t h_pos_word = 0;                   // staging for the device position word
+    StepGraphs graphs;
 
     // taps
     bool taps_on = false;
     std::map<std::string, Buf> taps;
     std::map<std::string, int64_t> tap_numel;
 
-    // graph
-    bool use_graph = true;
-    // fp8 GEMM mode (BASELINE config 5): every packed weight with KP % 64 == 0 also gets a P8 copy + per-row scales,
-    // looked up by the fp32 packed pointer when a GEMM is issued; activations are quantised per row right before the GEMM
-    bool fp8 = false;
-    bool fp8_decode = false;                     // fp8 mode: the decode kernels read e4m3 weights too (option "fp8_decode")
-    bool fp8_decode_act = false;                 // ... and quantise their activations: fp8 matrix pipe (option "fp8_decode_act")
-    bool fp8_attn_bf16 = true;                   // fp8 mode: prefill attention on operands rounded once to bf16 (option "fp8_attn_bf16" = 0: the exact 3-way split)
-    bool fp8_prefill = true;                     // fp8 mode: e4m3 GEMMs in encoder + prefill (option "fp8_prefill" = 0: a test isolating the decode weights)
-    float *head8 = nullptr, *head_sc = nullptr;  // e4m3 lm_head for the decode step
-    DecW head_w() const { return head8 ? DecW{head8, head_sc} : DecW{lm_head.p, nullptr}; }
-    int dec_x3_min_rb = 2;                       // ... and the fewest 32-row blocks at which the layer GEMM launches take their f32x3 forms (option "decode_x3_min_rb")
-    int dec_x3 = 0;                              // f32x3 mode: DEC_X3_* mask of the decode GEMM launches on the bf16 pipe (option "decode_x3", developer A/B)
-    int f32x3_terms = 0;                         // 0 = off; 6 = fp32 GEMMs on the bf16 pipe by exact 3-way operand splitting (six partial products)
-    // f32x3 LM prefill without RMSNorm launches: the o_proj / down GEMMs write their output pre-split + its sum of squares,
-    // the q/k/v and gate/up GEMMs run on norm-folded weights and scale their accumulators by the row statistic (run_prefill).
-    // option "prefill_fuse_norm" = 0: the two-launch form (developer A/B).
-    bool prefill_fuse_norm = true;
-    int enc_apb_stages = 0x1CC;                   // f32x3 mode: Swin stages (bit st) whose LayerNorms / fc1 hand their output over pre-split (APB) to x3q GEMMs
-    Buf sk_ws;                                   // split-K workspace of the f32x3 GEMMs (512 partial tiles of 128 x 128 fp32);
-    bool sk_enable = false;                      // ... only launches of the encoder chain (one stream) may use it: run_encoder switches it on
-    int sk_max = 8;                              // ... largest split count (option "splitk"; < 2 = never split)
-    Buf enc_a3, enc_h3;                          // ... the two pre-split operands (LayerNorm output; GELU(fc1) output)
     uint64_t dbg_spans[960] = {};
     int dbg_seq0 = -1;                           // developer stamps (mellow_dev_kdebug): first launch index of a decode step, -1 = off
-    int dec_fuse_max_rb = 1;                     // decode: largest number of 32-row blocks that runs the fused down + q/k/v launch (fp32 weights)
     mellow_engine* parent = nullptr;             // a fork: the context whose weights it shares
     int n_forks = 0, prefill_parts_saved = 2;    // a parent: live forks; its own split setting, restored when the last fork goes
-    bool decode_only_weight = false;             // set while packing weights only the decode kernels read: no bf16x3 / fp8 copy
-    std::unordered_map<const float*, void*> bf_w;   // fp32 packed pointer -> PB copy
-    struct Fp8W { uint8_t* w8; float* scale; };
-    std::unordered_map<const float*, Fp8W> fp8_w;
-    Buf a8, a8_scale;     // quantised A operand of the GEMM in flight (bytes / floats, carved from float buffers)
-    hipGraphExec_t step_exec = nullptr;
-    hipGraphExec_t step_exec8 = nullptr;      // the same step captured 8 times in a row (the step is position-independent)
-    int step_exec_B = -1, step_exec_Tmax = -1;
-    const void* graph_out_tok = nullptr;      // the graphs bake buffer addresses in; max_len / stop id travel in d_params
-    int graph_sample = -1;                    // sampling mode the graphs were captured in (the sampler + logits store, or the arg-max)
 
     // profiling
     bool prof_on = false;
@@ -257,6 +285,10 @@ struct mellow_engine {
     hipEvent_t ev_phase[4] = {nullptr, nullptr, nullptr, nullptr};
     float phase_ms[3] = {0, 0, 0};
 };
+
+#undef LOCAL
+static_assert(!std::is_copy_constructible<mellow_engine::Buf>::value, "a Buf owns its device memory: it moves, it is never copied");
+static_assert(std::is_copy_assignable<mellow_engine::Weights>::value && std::is_copy_assignable<mellow_engine::Options>::value, "a fork copies these by assignment: no owning member (Buf, StepGraphs) belongs in them");
 
 // ---- helpers shared by the translation units (engine.cpp unless noted) ------------------------------------------------------
 int ensure(mellow_engine* e, mellow_engine::Buf& b, size_t floats);

@@ -2,7 +2,6 @@
 // mellow_generate (A16: reference wrapper.py:197-256).
 #include "engine_internal.h"
 
-
 int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end) {
     if (B > 1024) return fail("batch of %d exceeds the 1024 rows one pass takes (mellow_generate chunks larger batches itself; the decode state block is sized for 32 row blocks)", B);
     if (ctx_end <= 0 || ctx_end > Tmax) ctx_end = Tmax;      // last context length the call will reach (<= page capacity)
@@ -13,7 +12,7 @@ int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end) {
     CHK(ensure(e, e->lm_q, Mp * 576));
     CHK(ensure(e, e->lm_o, Mp * 576));
     CHK(ensure(e, e->lm_h, Mp * 1536));
-    if (e->f32x3_terms || (e->fp8 && e->fp8_prefill)) {      // 6 bytes per element (the fp8 mode's AMX images + scale bytes need 1.05), rows padded to whole 128-row panels
+    if (e->opt.f32x3_terms || (e->opt.fp8 && e->opt.fp8_prefill)) {      // 6 bytes per element (the fp8 mode's AMX images + scale bytes need 1.05), rows padded to whole 128-row panels
         const size_t Mq = (size_t)rup((int)Mp, 128) + 3 * 128;   // + three panels: every part of the split prefill starts on a panel boundary
         CHK(ensure(e, e->lm_xn3, Mq * 576 * 6 / 4));
         CHK(ensure(e, e->lm_o3, Mq * 576 * 6 / 4));
@@ -22,8 +21,8 @@ int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end) {
     }
     // fp8 mode at its defaults: K and V exist as bf16 pages ONLY -- written by the q/k/v epilogue (rounded once), read by the bf16-once
     // prefill attention and by the decode attention; the fp32 pages and the conversion pass of round 5 are not touched
-    e->kv16_direct = e->kv16 && e->fp8 && e->fp8_prefill && e->fp8_attn_bf16 && e->x3_apb && e->x3_attn && !e->layers.empty() &&
-                     e->fp8_w.count(e->layers[0].qkv.p) != 0;
+    e->kv16_direct = e->opt.kv16 && e->opt.fp8 && e->opt.fp8_prefill && e->opt.fp8_attn_bf16 && e->opt.x3_apb && e->opt.x3_attn && !e->w.layers.empty() &&
+                     e->w.fp8_w.count(e->w.layers[0].qkv.p) != 0;
     dec_prepare_lds_attributes();            // (remembered per device: a no-op after the first call)
     const int Bp = rb_of(B) * 32;
     if (e->kv_B != Bp || e->kv_Tmax != Tmax) {
@@ -31,7 +30,7 @@ int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end) {
         e->kv_Tmax = Tmax;
         CHK(ensure(e, e->kcache, kv_layer_floats(e) * e->cfg.num_layers));
         CHK(ensure(e, e->vcache, kv_layer_floats(e) * e->cfg.num_layers));
-        if (e->kv16) {
+        if (e->opt.kv16) {
             CHK(ensure(e, e->kcache16, kv_layer_floats(e) * e->cfg.num_layers / 2));
             CHK(ensure(e, e->vcache16, kv_layer_floats(e) * e->cfg.num_layers / 2));
         }
@@ -39,12 +38,11 @@ int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end) {
         // (weight 0 x value): never-written page slots must hold finite numbers
         HIPCHK(hipMemsetAsync(e->kcache.p, 0, kv_layer_floats(e) * e->cfg.num_layers * sizeof(float), e->stream));
         HIPCHK(hipMemsetAsync(e->vcache.p, 0, kv_layer_floats(e) * e->cfg.num_layers * sizeof(float), e->stream));
-        if (e->kv16) {
+        if (e->opt.kv16) {
             HIPCHK(hipMemsetAsync(e->kcache16.p, 0, kv_layer_floats(e) * e->cfg.num_layers * sizeof(float) / 2, e->stream));
             HIPCHK(hipMemsetAsync(e->vcache16.p, 0, kv_layer_floats(e) * e->cfg.num_layers * sizeof(float) / 2, e->stream));
         }
-        if (e->step_exec) { hipGraphExecDestroy(e->step_exec); e->step_exec = nullptr; }
-        if (e->step_exec8) { hipGraphExecDestroy(e->step_exec8); e->step_exec8 = nullptr; }
+        e->graphs.reset();      // the page geometry is baked into captured launches
     }
     {
         // carve the decode-step buffers out of one arena (all sizes are multiples of 64 floats = 256 B)
@@ -58,8 +56,8 @@ int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end) {
         const size_t o_att = take((size_t)DEC_TS * n_x), o_aml = take((size_t)DEC_TS * 9 * Bp * 2);
         const size_t o_ssq = take((size_t)Bp * 40), o_gu = take(RB * 192 * 256), o_xmidF16 = take(n_x);
         // f32x3 layer kernels: 6-byte pre-split images of x_mid (two fragment orders) and of h
-        const bool x3l = (e->dec_x3 & DEC_X3_GATEUP) && (e->dec_x3 & DEC_X3_QKV) && (int)RB >= e->dec_x3_min_rb && !e->fp8_decode &&
-                         e->layers.size() > 1 && e->layers[1].qkv2 != nullptr && e->layers[1].gu16n != nullptr;
+        const bool x3l = (e->opt.dec_x3 & DEC_X3_GATEUP) && (e->opt.dec_x3 & DEC_X3_QKV) && (int)RB >= e->opt.dec_x3_min_rb && !e->opt.fp8_decode &&
+                         e->w.layers.size() > 1 && e->w.layers[1].qkv2 != nullptr && e->w.layers[1].gu16n != nullptr;
         const size_t o_x3a = take(x3l ? n_x * 3 / 2 : 0), o_x3b = take(x3l ? n_x * 3 / 2 : 0), o_h3 = take(x3l ? RB * 192 * 256 * 3 / 2 : 0);
         const bool fresh = e->dec.cap < off;
         CHK(ensure(e, e->dec, off));
@@ -68,35 +66,31 @@ int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end) {
         if (fresh) {
             // padded batch rows are computed but never read back; start from finite values
             HIPCHK(hipMemsetAsync(e->dec.p, 0, off * sizeof(float), e->stream));
-            if (e->step_exec) { hipGraphExecDestroy(e->step_exec); e->step_exec = nullptr; }
-            if (e->step_exec8) { hipGraphExecDestroy(e->step_exec8); e->step_exec8 = nullptr; }
+            e->graphs.reset();      // ... and so are the addresses of the decode arena
         }
         float* p = e->dec.p;
         DecArgs& a = e->da;
         a.rows = Bp; a.RB = (int)RB; a.Tmax = Tmax; a.eps = e->cfg.rms_norm_eps; a.d_pos = e->d_pos; a.inc_pos = 0; a.first = 0;
-        a.a8 = e->fp8_decode_act ? 1 : 0;
-        a.kv16 = e->kv16 ? 1 : 0;
-        a.x3 = e->dec_x3;
+        a.a8 = e->opt.fp8_decode_act ? 1 : 0;
+        a.kv16 = e->opt.kv16 ? 1 : 0;
+        a.x3 = e->opt.dec_x3;
         a.blk_live = nullptr;                               // mellow_generate turns the per-block early exit on per call
         a.row_of_slot = nullptr;
         // (and the logits store off: the taps mellow_lm_prefill / mellow_lm_decode_step read dlogits, generation does not)
-        a.rope_cos = e->rope_cos; a.rope_sin = e->rope_sin;
+        a.rope_cos = e->w.rope_cos; a.rope_sin = e->w.rope_sin;
         a.xmidF = p + o_xmidF; a.xnewR = p + o_xnewR; a.xnF = p + o_xnF;
-        a.xn3 = (a.x3 & DEC_X3_HEAD) && !e->head8 && dec_head3r_fits(e->cfg.vocab_size) ? (void*)(p + o_xnF) : nullptr;
+        a.xn3 = (a.x3 & DEC_X3_HEAD) && !e->w.head8 && dec_head3r_fits(e->cfg.vocab_size) ? (void*)(p + o_xnF) : nullptr;
         a.xmid3_32 = x3l ? (void*)(p + o_x3a) : nullptr; a.xmid3_16 = x3l ? (void*)(p + o_x3b) : nullptr; a.h3 = x3l ? (void*)(p + o_h3) : nullptr;
         a.dslabF = p + o_dslabF; a.slabF_stride4 = (int64_t)(n_x / 4); a.ssq1 = p + o_ssq1; a.rope_cur = p + o_rope;
         {
             // key split of the decode attention: balanced at the END of the reserved context, rounded down to whole
             // passes of a workgroup when that costs at most 4 groups of imbalance
-            const int ng_end = (ctx_end - 1 + 3) / 4, chunk = dec_attn_chunk_groups(e->kv16);
-            a.ts = dec_key_splits((int)RB, e->kv16 || e->mode != MELLOW_PRECISION_F32X3);
+            const int ng_end = (ctx_end - 1 + 3) / 4, chunk = dec_attn_chunk_groups(e->opt.kv16);
+            a.ts = dec_key_splits((int)RB, e->opt.kv16 || e->opt.mode != MELLOW_PRECISION_F32X3);
             int gs = (ng_end + a.ts - 1) / a.ts;
             if (gs > chunk && gs % chunk <= 4) gs -= gs % chunk;
             gs = gs < 1 ? 1 : gs;
-            if (gs != a.gs) {     // the split is baked into captured launches
-                if (e->step_exec) { hipGraphExecDestroy(e->step_exec); e->step_exec = nullptr; }
-                if (e->step_exec8) { hipGraphExecDestroy(e->step_exec8); e->step_exec8 = nullptr; }
-            }
+            if (gs != a.gs) e->graphs.reset();     // the split is baked into captured launches
             a.gs = gs;
         }
         a.pq = p + o_pq; a.attF16 = p + o_att; a.att_ml = p + o_aml; a.ssq = p + o_ssq; a.guF = p + o_gu; a.xmidF16 = p + o_xmidF16;
@@ -120,7 +114,6 @@ int clear_page_tails(mellow_engine* e, int T, int t_end) {
     return 0;
 }
 
-
 LoopArgs loop_args(mellow_engine* e) {
     LoopArgs lp;
     lp.out_tokens = reinterpret_cast<int32_t*>(e->out_tok.p);
@@ -136,18 +129,18 @@ int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec)
     const int NT = e->cfg.vocab_size / 32, Bp = e->da.rows;
     auto dh = [&](int k) { DecArgs x = e->da; x.dbg_seq = e->dbg_seq0 >= 0 ? e->dbg_seq0 + 5 * e->cfg.num_layers + k : -1000; return x; };
     { ProfScope ps(e, PF_NORM, 0, (double)(pending_kcd + 2) * Bp * 576 * 4);
-      launch_dec_final_norm(dh(0), e->final_norm, pending_kcd, e->stream); }
+      launch_dec_final_norm(dh(0), e->w.final_norm, pending_kcd, e->stream); }
     { ProfScope ps(e, PF_SKINNY, 2.0 * Bp * 576.0 * e->cfg.vocab_size, 576.0 * e->cfg.vocab_size * 4);
-      const DecW h = e->head_w();
-      launch_dec_lm_head(dh(1), h.p, e->lm_head.KP / 8, e->cfg.vocab_size, e->stream, h.scale); }
+      const DecW h = e->w.head_w();
+      launch_dec_lm_head(dh(1), h.p, e->w.lm_head.KP / 8, e->cfg.vocab_size, e->stream, h.scale); }
     { ProfScope ps(e, PF_MISC, 0, 0);
       if (e->sample_on) {          // mellow_generate_sampled: the head stored the logits (da.logits); draw instead of the arg-max
           SampleArgs sa;
           sa.logits = e->da.logits; sa.ld = e->cfg.vocab_size; sa.prm = e->d_sparams;
-          launch_dec_sample(sa, dh(2), B, e->d_tokens, e->embed, (rec && rec->embed_next) ? 1 : 0, rec ? loop_args(e) : LoopArgs(),
+          launch_dec_sample(sa, dh(2), B, e->d_tokens, e->w.embed, (rec && rec->embed_next) ? 1 : 0, rec ? loop_args(e) : LoopArgs(),
                             e->stream);
       } else {
-          launch_dec_argmax(dh(2), B, NT, e->d_tokens, e->embed, (rec && rec->embed_next) ? 1 : 0, rec ? loop_args(e) : LoopArgs(),
+          launch_dec_argmax(dh(2), B, NT, e->d_tokens, e->w.embed, (rec && rec->embed_next) ? 1 : 0, rec ? loop_args(e) : LoopArgs(),
                             e->stream);
       }
       if (rec && e->da.row_of_slot) launch_dec_compact(e->da, B, loop_args(e), e->stream); }
@@ -161,8 +154,8 @@ int run_prefill(mellow_engine* e, int B, int T, const RecordArgs* rec, bool all_
     float *x = e->lm_x.p, *xn = e->lm_xn.p;
     // fp8 mode: the same producer -> consumer hand-over with AMX images (MXFP8, common.h) instead of APB ones: `amx`; the code below
     // says `apb` for "GEMM inputs leave their producers in operand format"
-    const bool amx = e->fp8 && e->fp8_prefill && e->x3_apb && e->fp8_w.count(e->layers[0].qkv.p) != 0;
-    const bool apb = (e->f32x3_terms && e->x3_apb) || amx;        // option "x3_apb" = 0: the register-staged x3p kernel / the standalone quantiser (developer A/B)
+    const bool amx = e->opt.fp8 && e->opt.fp8_prefill && e->opt.x3_apb && e->w.fp8_w.count(e->w.layers[0].qkv.p) != 0;
+    const bool apb = (e->opt.f32x3_terms && e->opt.x3_apb) || amx;        // option "x3_apb" = 0: the register-staged x3p kernel / the standalone quantiser (developer A/B)
     // Split prefill (f32x3 mode): the batch is cut into independent parts (2 by default) that run the same launches on their own
     // streams, so the tails and the fill / drain of one part's kernels are covered by another's (every buffer is indexed by row
     // or by example, so a part is an offset; its pre-split operands get their own panel-aligned region).  Measured before it was
@@ -200,7 +193,7 @@ int run_prefill(mellow_engine* e, int B, int T, const RecordArgs* rec, bool all_
         for (int h = 1; h < nh; ++h) HIPCHK(hipStreamWaitEvent(hs[h], e->ev_fork, 0));
     }
     for (int l = 0; l < NL; ++l) {
-        const LMLayerW& w = e->layers[l];
+        const LMLayerW& w = e->w.layers[l];
         bool last = false;
         for (int h = 0; h < nh; ++h) {
             hipStream_t st = hs[h];
@@ -230,7 +223,7 @@ int run_prefill(mellow_engine* e, int B, int T, const RecordArgs* rec, bool all_
             // sum-of-squares partials (ssq_mid after o_proj, ssq_in after down); the GEMM that follows runs on the norm-folded
             // weight and applies the row statistic to its accumulators -- 59 of the 60 normalisation launches of a prefill disappear
             // (the first layer's input is the prefix, which has no producing GEMM: it keeps its launch)
-            const bool fz = apb && e->prefill_fuse_norm && w.gateup_f.p != nullptr;
+            const bool fz = apb && e->opt.prefill_fuse_norm && w.gateup_f.p != nullptr;
             float* ssq_in = fz ? e->lm_ssq.p + prow[h] * 9 : nullptr;                       // [row][9], rows of this part
             float* ssq_mid = fz ? e->lm_ssq.p + e->lm_ssq.cap / 2 + prow[h] * 9 : nullptr;    // second half of the buffer
             auto with_rs = [&](GemmArgs& g, const float* ssq) { g.rs_ssq = ssq; g.rs_parts = 9; g.rs_dim = 576.f; g.rs_eps = e->cfg.rms_norm_eps; };
@@ -245,7 +238,7 @@ int run_prefill(mellow_engine* e, int B, int T, const RecordArgs* rec, bool all_
                 GemmArgs g;
                 g.A = xnh; g.lda = 576; g.M = Mh; g.K = 576; g.Wp = fz_in ? w.qkv_f.p : w.qkv.p; g.Nw = 960; g.N = 960; g.epi = EPI_QKV_ROPE;
                 if (fz_in) with_rs(g, ssq_in);
-                g.q_out = qh; g.k_cache = kc; g.v_cache = vc; g.rope_cos = e->rope_cos; g.rope_sin = e->rope_sin;
+                g.q_out = qh; g.k_cache = kc; g.v_cache = vc; g.rope_cos = e->w.rope_cos; g.rope_sin = e->w.rope_sin;
                 g.T = T; g.Tmax = Tmax; g.q_heads = 9; g.kv_heads = 3; g.kv16 = p16 ? 1 : 0;
                 if (apb) CHK(run_gemm_apb(e, g, xn3, st, xn3s)); else CHK(run_gemm(e, g));
             }
@@ -255,8 +248,8 @@ int run_prefill(mellow_engine* e, int B, int T, const RecordArgs* rec, bool all_
             {
                 // causal QK^T + PV: 4*64 flops per (query,key) pair per head
                 ProfScope ps(e, PF_PREFILL_ATTN, 4.0 * 64 * 9 * (double)Bh * ((double)T * (T + 1) / 2), 0);
-                const bool attn_f32 = !e->x3_attn;   // option "x3_attn" = 0: f32x3 mode on the fp32 kernel (A/B)
-                launch_prefill_attention(qh, kc, vc, oh, apb ? o3 : nullptr, Bh, T, Tmax, (e->f32x3_terms != 0 || amx) && !attn_f32, st, o3s, amx && e->fp8_attn_bf16, p16);
+                const bool attn_f32 = !e->opt.x3_attn;   // option "x3_attn" = 0: f32x3 mode on the fp32 kernel (A/B)
+                launch_prefill_attention(qh, kc, vc, oh, apb ? o3 : nullptr, Bh, T, Tmax, (e->opt.f32x3_terms != 0 || amx) && !attn_f32, st, o3s, amx && e->opt.fp8_attn_bf16, p16);
             }
             {
                 GemmArgs g = lin(oh, 576, Mh, w.o, xh, 576, nullptr);
@@ -284,7 +277,7 @@ int run_prefill(mellow_engine* e, int B, int T, const RecordArgs* rec, bool all_
         if (last) break;
     }
     CHK(join.run());
-    if (e->kv16 && !e->kv16_direct && !all_positions) {
+    if (e->opt.kv16 && !e->kv16_direct && !all_positions) {
         // fp8 mode: the decode step streams a bf16 shadow of the pages (whole pages: the cleared tails travel with them)
         ProfScope ps(e, PF_MISC, 0, 3.0 * kv_layer_floats(e) * NL * 4);
         launch_kv_to_bf16(e->kcache.p, e->kcache16.p, (int64_t)(kv_layer_floats(e) * NL), s);
@@ -327,11 +320,11 @@ int enqueue_decode_layer_range(mellow_engine* e, int B, int l_begin, int l_end, 
     constexpr int skip = 0;
 #endif
     for (int l = l_begin; l < l_end; ++l) {
-        const LMLayerW& w = e->layers[same_w ? 0 : l];
+        const LMLayerW& w = e->w.layers[same_w ? 0 : l];
         const DecW qkv = w.qkv_w(), o = w.o_w(), gu = w.gateup_w(), dn = w.down_w();      // fp32, or e4m3 + row scales (fp8 mode)
         // (KV16: the bf16 shadow pages; a layer's pages are half as many floats)
-        float* kc = e->kv16 ? e->kcache16.p + kv_layer_floats(e) / 2 * (same_kv ? 0 : l) : e->kcache.p + kv_layer_floats(e) * (same_kv ? 0 : l);
-        float* vc = e->kv16 ? e->vcache16.p + kv_layer_floats(e) / 2 * (same_kv ? 0 : l) : e->vcache.p + kv_layer_floats(e) * (same_kv ? 0 : l);
+        float* kc = e->opt.kv16 ? e->kcache16.p + kv_layer_floats(e) / 2 * (same_kv ? 0 : l) : e->kcache.p + kv_layer_floats(e) * (same_kv ? 0 : l);
+        float* vc = e->opt.kv16 ? e->vcache16.p + kv_layer_floats(e) / 2 * (same_kv ? 0 : l) : e->vcache.p + kv_layer_floats(e) * (same_kv ? 0 : l);
         const int kcd = l == l_begin ? 0 : DEC_KC_DOWN;   // the first layer of the range starts from a materialised x
         // fused_in: this layer's q/k/v slabs (and the down slabs of x_new) were written by the previous layer's dec_qkv2 launch
         // The fused launch pays at ONE row block (B <= 32: 46.8 ms per 63 steps against 49.9 with the five-launch layer) and loses
@@ -340,7 +333,7 @@ int enqueue_decode_layer_range(mellow_engine* e, int B, int l_begin, int l_end, 
         // replaces, and a larger batch is bound by bytes, not by launches); the e4m3 form was measured ahead at four row blocks
         // (round 3) and stays fused.  MELLOW_DECODE_FUSE_MAX_RB: developer override.
         const bool x3l = e->da.xmid3_32 != nullptr;       // f32x3 forms of gate/up and of the fused down + q/k/v launch (ensure_lm decides)
-        const bool fuse_rb = x3l || e->da.RB <= e->dec_fuse_max_rb;
+        const bool fuse_rb = x3l || e->da.RB <= e->opt.dec_fuse_max_rb;
         const bool fused_in = l > l_begin && ((w.qkv2 != nullptr && fuse_rb) || w.q2h8 != nullptr) && !same_w;
         DecArgs a = e->da;
         const int sq = e->dbg_seq0 >= 0 ? e->dbg_seq0 + 5 * (l - l_begin) : -1000;       // launch index inside the step (kdebug builds)
@@ -361,7 +354,7 @@ int enqueue_decode_layer_range(mellow_engine* e, int B, int l_begin, int l_end, 
         { ProfScope ps(e, PF_SKINNY, 2.0 * Bp * 576.0 * 3072.0, 576.0 * 3072.0 * 4);
           if (x3l && !w.gu8) launch_dec_gateup3(da(3), w.gu16n, s);      // (the f32x3 form reads fp32 weights only)
           else launch_dec_gateup(da(3), gu.p, s, gu.scale); }
-        const LMLayerW* nx = (l + 1 < l_end && !same_w) ? &e->layers[l + 1] : nullptr;
+        const LMLayerW* nx = (l + 1 < l_end && !same_w) ? &e->w.layers[l + 1] : nullptr;
         if (nx && ((nx->qkv2 && fuse_rb) || nx->q2h8)) {
             // the down projection of this layer and the q/k/v projection of the next one as one launch (decode.hip, dec_qkv2_kernel)
             if (!(skip & 16))
@@ -381,6 +374,20 @@ int enqueue_decode_layers(mellow_engine* e, int B, const RecordArgs* rec) {
     return 0;
 }
 
+// `n` consecutive decode steps captured from the stream into one exec.  Once the capture has begun it is ALWAYS ended and the
+// hipGraph_t ALWAYS destroyed, whatever failed in between; the first error is the one reported.
+static int capture_steps(mellow_engine* e, int B, const RecordArgs* rec, int n, hipGraphExec_t* exec) {
+    hipGraph_t gr = nullptr;
+    HIPCHK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
+    int rc = 0;
+    for (int k = 0; k < n && !rc; ++k) rc = enqueue_decode_layers(e, B, rec);
+    hipError_t err = hipStreamEndCapture(e->stream, &gr);
+    if (!rc && err != hipSuccess) rc = fail("hipStreamEndCapture failed: %s", hipGetErrorString(err));
+    if (!rc && (err = hipGraphInstantiate(exec, gr, nullptr, nullptr, 0)) != hipSuccess) { *exec = nullptr; rc = fail("instantiating the captured decode step failed: %s", hipGetErrorString(err)); }
+    if (gr) (void)hipGraphDestroy(gr);
+    return rc;
+}
+
 // audio1|audio2 are separate caller buffers: stage them into one [2B][n] batch so the encoder runs ONE pass
 // of 2B clips (the reference runs two passes of B, mellow.py:105-106)
 int encode_pair_to_prefix(mellow_engine* e, const float* a1, const float* a2, int64_t n_samples, const int32_t* ids,
@@ -391,7 +398,7 @@ int encode_pair_to_prefix(mellow_engine* e, const float* a1, const float* a2, in
     HIPCHK(hipMemcpyAsync(cat.p + (size_t)B * n_samples, a2, (size_t)B * n_samples * 4, hipMemcpyDeviceToDevice, e->stream));
     CHK(run_encoder(e, cat.p, 2 * B, n_samples, 0, 1, nullptr));
     { ProfScope ps(e, PF_MISC, 0, 0);
-      launch_prefix_assemble(e->proj33.p, e->embed, ids, B, e->cfg.text_len, e->cfg.sep_token_id, e->cfg.vocab_size, prefix_out,
+      launch_prefix_assemble(e->proj33.p, e->w.embed, ids, B, e->cfg.text_len, e->cfg.sep_token_id, e->cfg.vocab_size, prefix_out,
                              e->d_progress + 1, e->stream); }
     HIPCHK(hipGetLastError());
     return 0;
@@ -457,20 +464,20 @@ int run_score_head(mellow_engine* e, int B, int T, int from_pos, int n, const in
                    int32_t* out_argmax, float* out_lse, float* out_max) {
     hipStream_t s = e->stream;
     const int V = e->cfg.vocab_size, rows = B * n, groups = V / 64;
-    if (V % 64 != 0 || e->lm_head.Nw != V) return fail("the scoring head tiles the vocabulary in groups of 64 columns (vocab %d)", V);
+    if (V % 64 != 0 || e->w.lm_head.Nw != V) return fail("the scoring head tiles the vocabulary in groups of 64 columns (vocab %d)", V);
     const size_t ld = (size_t)rup(rows, 64);
     CHK(ensure(e, e->sc_part, (size_t)groups * ld * 3));         // (max, sum) pairs, then the arg-max words
     float2* part_ms = reinterpret_cast<float2*>(e->sc_part.p);
     int32_t* part_arg = reinterpret_cast<int32_t*>(e->sc_part.p + (size_t)groups * ld * 2);
     float* tgt_logit = e->sc_ws.p;                               // [rows] (the callers size sc_ws: target logits first)
-    GemmArgs g = lin(e->lm_xn.p, 576, rows, e->lm_head, nullptr, 0, nullptr);
+    GemmArgs g = lin(e->lm_xn.p, 576, rows, e->w.lm_head, nullptr, 0, nullptr);
     g.epi = EPI_LSE;
     g.lse_target = targets; g.lse_ms = part_ms; g.lse_arg = part_arg; g.lse_tgt = tgt_logit; g.lse_ld = (int64_t)ld;
     // bytes: the head weight once, the normed rows, and the partials written by the GEMM and read twice by the merge
     ProfScope ps(e, PF_LM_HEAD, gemm_flops(g), 576.0 * V * 4 + (double)rows * 576 * 4 + 3.0 * rows * groups * 12);
     // final norm on the scored rows only, as mellow_lm_forward_logits does
     launch_gather_span(e->lm_x.p, B, T, from_pos, n, e->lm_o.p, s);
-    launch_rmsnorm(e->lm_o.p, e->lm_xn.p, rows, 576, e->final_norm, e->cfg.rms_norm_eps, s);
+    launch_rmsnorm(e->lm_o.p, e->lm_xn.p, rows, 576, e->w.final_norm, e->cfg.rms_norm_eps, s);
     launch_gemm(g, s);
     launch_lse_merge(part_ms, part_arg, (int64_t)ld, groups, rows, targets, tgt_logit, V, out_logprob, out_argmax, out_lse, out_max,
                      e->d_progress + 2, s);
@@ -513,7 +520,7 @@ int mellow_lm_decode_step(mellow_engine_t* e, const int32_t* token_ids, float* l
     if (e->cur_pos + 1 > e->kv_Tmax) return fail("KV pages exhausted (reserve too small)");
     HIPCHK(hipSetDevice(e->device));
     const int B = e->cur_B;
-    launch_dec_load_rows(e->da, B, e->embed, 576, token_ids, 0, e->cfg.vocab_size, e->stream);
+    launch_dec_load_rows(e->da, B, e->w.embed, 576, token_ids, 0, e->cfg.vocab_size, e->stream);
     CHK(enqueue_decode_layers(e, B, nullptr));   // its first kernel advances the device position word
     e->cur_pos += 1;
     if (logits)
@@ -534,12 +541,12 @@ int mellow_debug_dec_head(mellow_engine_t* e, const float* x, int B, int act_fp8
     CHK(ensure_lm(e, B, 1, 2));
     DecArgs a = e->da;
     a.blk_live = nullptr; a.row_of_slot = nullptr;
-    a.a8 = (act_fp8 && e->head8) ? 1 : 0;
+    a.a8 = (act_fp8 && e->w.head8) ? 1 : 0;
     a.xnF = a.xmidF;                                  // dec_load_rows writes the F32-layout operand there
     a.xn3 = nullptr;                                  // (the f32x3 kernel splits these rows itself)
     launch_dec_load_rows(a, B, x, 576, nullptr, 1, 0, e->stream);
-    const DecW h = e->head_w();
-    launch_dec_lm_head(a, h.p, e->lm_head.KP / 8, e->cfg.vocab_size, e->stream, h.scale);
+    const DecW h = e->w.head_w();
+    launch_dec_lm_head(a, h.p, e->w.lm_head.KP / 8, e->cfg.vocab_size, e->stream, h.scale);
     HIPCHK(hipMemcpyAsync(logits, e->dlogits.p, (size_t)B * e->cfg.vocab_size * 4, hipMemcpyDeviceToDevice, e->stream));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -552,7 +559,7 @@ int mellow_embed_tokens(mellow_engine_t* e, const int32_t* token_ids, int n, flo
     if (!e || !e->finalized) return fail("engine not finalized");
     if (!token_ids || !out || n <= 0) return fail("bad argument");
     HIPCHK(hipSetDevice(e->device));
-    launch_gather_rows(e->embed, 576, token_ids, n, e->cfg.vocab_size, out, e->stream);
+    launch_gather_rows(e->w.embed, 576, token_ids, n, e->cfg.vocab_size, out, e->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(e->stream));
     return 0;
@@ -574,10 +581,10 @@ int mellow_lm_forward_logits(mellow_engine_t* e, const float* embeds, int B, int
     e->cur_B = 0;                                   // no decode state: a decode step needs a real prefill first
     const int n = T - from_pos;
     // final norm on the selected rows only: gather [B][n][576] out of [B][T][576] into lm_xn, then normalise in place
-    GemmArgs g = lin(e->lm_xn.p, 576, B * n, e->lm_head, logits, e->cfg.vocab_size, nullptr);
+    GemmArgs g = lin(e->lm_xn.p, 576, B * n, e->w.lm_head, logits, e->cfg.vocab_size, nullptr);
     { ProfScope ps(e, PF_LM_HEAD, gemm_flops(g), (576.0 + (double)B * n) * e->cfg.vocab_size * 4 + (double)B * n * 576 * 4);
       launch_gather_span(e->lm_x.p, B, T, from_pos, n, e->lm_o.p, s);
-      launch_rmsnorm(e->lm_o.p, e->lm_xn.p, B * n, 576, e->final_norm, e->cfg.rms_norm_eps, s);
+      launch_rmsnorm(e->lm_o.p, e->lm_xn.p, B * n, 576, e->w.final_norm, e->cfg.rms_norm_eps, s);
       launch_gemm(g, s); }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
@@ -633,7 +640,7 @@ int mellow_score(mellow_engine_t* e, const float* audio1, const float* audio2, i
         const int nr = rows - r0 < kPassRows ? (int)(rows - r0) : kPassRows;
         CHK(ensure_lm(e, nr, T, T + 1));
         { ProfScope ps(e, PF_MISC, 0, 2.0 * nr * T * 576 * 4);
-          launch_score_build_input(e->sc_prefix.p, e->embed, cand_ids, d_len, K, L, P, e->cfg.vocab_size, (int)r0, nr, e->lm_x.p,
+          launch_score_build_input(e->sc_prefix.p, e->w.embed, cand_ids, d_len, K, L, P, e->cfg.vocab_size, (int)r0, nr, e->lm_x.p,
                                    d_targets, e->d_progress + 2, s); }
         CHK(run_prefill(e, nr, T, nullptr, true));
         e->cur_B = 0;
@@ -807,7 +814,7 @@ static int generate_pass(mellow_engine_t* e, const float* audio1, const float* a
 #else
     constexpr bool dev_dead = false;
 #endif
-    const bool no_migrate = !e->row_migration;   // option "row_migration" = 0: block exit without repacking (developer A/B)
+    const bool no_migrate = !e->opt.row_migration;   // option "row_migration" = 0: block exit without repacking (developer A/B)
     e->da.row_of_slot = nullptr;
     if (dev_dead) {
         e->da.blk_live = e->d_blk_live;
@@ -840,30 +847,15 @@ static int generate_pass(mellow_engine_t* e, const float* audio1, const float* a
     // one decode step = 30 x (qkv | attention | o_proj | gate/up | down) + final norm + lm_head + arg-max/record/embed,
     // captured once per (B, page geometry, buffers) and replayed; max_len and the stop id are read from d_params
     const bool graph = e->use_graph && !e->prof_on && max_len > 1;
-    if (graph && (!e->step_exec || e->step_exec_B != B || e->step_exec_Tmax != e->kv_Tmax || e->graph_out_tok != e->out_tok.p ||
-                  e->graph_blk != e->da.blk_live || e->graph_rows != e->da.row_of_slot || e->graph_sample != (int)sc.on)) {
-        if (e->step_exec) { hipGraphExecDestroy(e->step_exec); e->step_exec = nullptr; }
-        if (e->step_exec8) { hipGraphExecDestroy(e->step_exec8); e->step_exec8 = nullptr; }
-        hipGraph_t gr = nullptr;
-        HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        int rc = enqueue_decode_layers(e, B, &rec);
-        hipError_t ce = hipStreamEndCapture(s, &gr);
-        if (rc) return rc;
-        if (ce != hipSuccess) return fail("hipStreamEndCapture failed: %s", hipGetErrorString(ce));
-        HIPCHK(hipGraphInstantiate(&e->step_exec, gr, nullptr, nullptr, 0));
-        HIPCHK(hipGraphDestroy(gr));
+    const mellow_engine::StepGraphs::Key want{B, e->kv_Tmax, (int)sc.on, e->out_tok.p, e->da.blk_live, e->da.row_of_slot};
+    if (graph && (!e->graphs.one || !(e->graphs.key == want))) {
+        e->graphs.reset();
         // eight consecutive steps as ONE graph: the step reads its position from the device word, so a replay of the
         // same kernel sequence IS the next step; one launch per 8 steps removes the host/CP hand-over between graphs
-        HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        int rc8 = 0;
-        for (int k = 0; k < 8 && !rc8; ++k) rc8 = enqueue_decode_layers(e, B, &rec);
-        hipError_t ce8 = hipStreamEndCapture(s, &gr);
-        if (rc8) return rc8;
-        if (ce8 != hipSuccess) return fail("hipStreamEndCapture failed: %s", hipGetErrorString(ce8));
-        HIPCHK(hipGraphInstantiate(&e->step_exec8, gr, nullptr, nullptr, 0));
-        HIPCHK(hipGraphDestroy(gr));
-        e->step_exec_B = B; e->step_exec_Tmax = e->kv_Tmax; e->graph_out_tok = e->out_tok.p; e->graph_blk = e->da.blk_live; e->graph_rows = e->da.row_of_slot;
-        e->graph_sample = (int)sc.on;
+        int rc = capture_steps(e, B, &rec, 1, &e->graphs.one);
+        if (!rc) rc = capture_steps(e, B, &rec, 8, &e->graphs.eight);
+        if (rc) { e->graphs.reset(); return rc; }      // never a cache that holds one exec of the two
+        e->graphs.key = want;
     }
     int steps_done = 1;   // token 0 came from the prefill
     double first_ms = -1.0;
@@ -874,8 +866,8 @@ static int generate_pass(mellow_engine_t* e, const float* audio1, const float* a
         // fixed-length mode: nothing to decide on the host, everything is enqueued at once
         for (int i = 1; i < max_len;) {
             const bool eight = graph && i + 8 <= max_len;
-            if (eight) HIPCHK(hipGraphLaunch(e->step_exec8, s));
-            else if (graph) HIPCHK(hipGraphLaunch(e->step_exec, s));
+            if (eight) HIPCHK(hipGraphLaunch(e->graphs.eight, s));
+            else if (graph) HIPCHK(hipGraphLaunch(e->graphs.one, s));
             else CHK(enqueue_decode_layers(e, B, &rec));
             i += eight ? 8 : 1;
             e->cur_pos += eight ? 8 : 1;
@@ -889,7 +881,7 @@ static int generate_pass(mellow_engine_t* e, const float* audio1, const float* a
         // host follows the rule one step behind the device without synchronising: step i+1 is enqueued while step i runs,
         // and at most ONE step is ever enqueued past the deciding one.
         for (int i = 1; i < max_len; ++i) {
-            if (graph) HIPCHK(hipGraphLaunch(e->step_exec, s));
+            if (graph) HIPCHK(hipGraphLaunch(e->graphs.one, s));
             else CHK(enqueue_decode_layers(e, B, &rec));
             e->cur_pos += 1;
             steps_done = i + 1;

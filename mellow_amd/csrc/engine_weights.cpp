@@ -34,61 +34,61 @@ static int make_packed(mellow_engine* e, const float* w0, const float* w1, int N
     p.KP = rup(K, 32);
     p.Nw = w1 ? 64 * ((N + 31) / 32) : N;
     p.NP = rup(p.Nw, 128);
-    float *d0 = nullptr, *d1 = nullptr;
-    HIPCHK(hipMalloc(&d0, (size_t)N * K * sizeof(float)));
-    HIPCHK(hipMemcpy(d0, w0, (size_t)N * K * sizeof(float), hipMemcpyHostToDevice));
-    if (w1) {
-        HIPCHK(hipMalloc(&d1, (size_t)N * K * sizeof(float)));
-        HIPCHK(hipMemcpy(d1, w1, (size_t)N * K * sizeof(float), hipMemcpyHostToDevice));
+    {
+        mellow_engine::Buf d0, d1;           // the row-major sources, until the pack kernel has run
+        CHK(ensure(e, d0, (size_t)N * K));
+        HIPCHK(hipMemcpy(d0.p, w0, (size_t)N * K * sizeof(float), hipMemcpyHostToDevice));
+        if (w1) {
+            CHK(ensure(e, d1, (size_t)N * K));
+            HIPCHK(hipMemcpy(d1.p, w1, (size_t)N * K * sizeof(float), hipMemcpyHostToDevice));
+        }
+        CHK(dev_alloc(e, &p.p, (size_t)p.NP * p.KP));
+        if (w1) launch_pack_weight_pairs(d0.p, d1.p, N, K, K, p.p, p.NP, p.KP, e->stream);
+        else launch_pack_weight(d0.p, N, K, K, p.p, p.NP, p.KP, e->stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(e->stream));
     }
-    CHK(dev_alloc(e, &p.p, (size_t)p.NP * p.KP));
-    if (w1) launch_pack_weight_pairs(d0, d1, N, K, K, p.p, p.NP, p.KP, e->stream);
-    else launch_pack_weight(d0, N, K, K, p.p, p.NP, p.KP, e->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipFree(d0));
-    if (d1) HIPCHK(hipFree(d1));
-    if (e->f32x3_terms && p.KP % 16 == 0 && !e->decode_only_weight) {
+    if (e->opt.f32x3_terms && p.KP % 16 == 0 && !e->decode_only_weight) {
         float* pb = nullptr;
         CHK(dev_alloc(e, &pb, ((size_t)p.NP * p.KP * 6 + 3) / 4));
         launch_pack_bf16x3(p.p, p.NP, p.KP, pb, e->stream);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(e->stream));
-        e->bf_w[p.p] = pb;
+        e->w.bf_w[p.p] = pb;
     }
-    if (e->fp8 && e->fp8_prefill && !e->decode_only_weight) {       // WMX image: K zero-padded to whole k64 steps (K = 96 -> 128)
+    if (e->opt.fp8 && e->opt.fp8_prefill && !e->decode_only_weight) {       // WMX image: K zero-padded to whole k64 steps (K = 96 -> 128)
         float *w8f = nullptr, *sc = nullptr;
         CHK(dev_alloc(e, &w8f, ((size_t)p.NP * rup(p.KP, 64) + 3) / 4));
         CHK(dev_alloc(e, &sc, (size_t)p.NP));
         launch_pack_fp8(p.p, p.NP, p.KP, reinterpret_cast<uint8_t*>(w8f), sc, e->stream);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(e->stream));
-        e->fp8_w[p.p] = {reinterpret_cast<uint8_t*>(w8f), sc};
+        e->w.fp8_w[p.p] = {reinterpret_cast<uint8_t*>(w8f), sc};
     }
     *out = p;
     return 0;
 }
 // e4m3 (WMX) copy of an already packed weight: the operand of gemm_mx8_kernel (fp8 mode)
 static int make_w8(mellow_engine* e, const Packed& p) {
-    if (!e->fp8 || !e->fp8_prefill || e->fp8_w.count(p.p)) return 0;
+    if (!e->opt.fp8 || !e->opt.fp8_prefill || e->w.fp8_w.count(p.p)) return 0;
     float *w8f = nullptr, *sc = nullptr;
     CHK(dev_alloc(e, &w8f, ((size_t)p.NP * rup(p.KP, 64) + 3) / 4));
     CHK(dev_alloc(e, &sc, (size_t)p.NP));
     launch_pack_fp8(p.p, p.NP, p.KP, reinterpret_cast<uint8_t*>(w8f), sc, e->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(e->stream));
-    e->fp8_w[p.p] = {reinterpret_cast<uint8_t*>(w8f), sc};
+    e->w.fp8_w[p.p] = {reinterpret_cast<uint8_t*>(w8f), sc};
     return 0;
 }
 // bf16-split (PB) copy of an already packed weight: the operand of the x3q GEMM (f32x3 mode)
 static int make_pb(mellow_engine* e, const Packed& p) {
-    if (!e->f32x3_terms || p.KP % 16 != 0 || e->bf_w.count(p.p)) return 0;
+    if (!e->opt.f32x3_terms || p.KP % 16 != 0 || e->w.bf_w.count(p.p)) return 0;
     float* pb = nullptr;
     CHK(dev_alloc(e, &pb, ((size_t)p.NP * p.KP * 6 + 3) / 4));
     launch_pack_bf16x3(p.p, p.NP, p.KP, pb, e->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(e->stream));
-    e->bf_w[p.p] = pb;
+    e->w.bf_w[p.p] = pb;
     return 0;
 }
 // e4m3 copy of a packed decode weight (tiles x slots float4 slots, `rows` packed rows per tile)
@@ -102,15 +102,14 @@ static int make_dec_fp8(mellow_engine* e, const float* Wp, int tiles, int slots,
 }
 static int make_packed16(mellow_engine* e, const float* w, int N, int K, float** out, bool natural = false) {
     if (N % 16 || K % (natural ? 32 : 16)) return fail("P16 packing needs N and K multiples of 16 (32 for the P16N order)");
-    float* d0 = nullptr;
-    HIPCHK(hipMalloc(&d0, (size_t)N * K * sizeof(float)));
-    HIPCHK(hipMemcpy(d0, w, (size_t)N * K * sizeof(float), hipMemcpyHostToDevice));
+    mellow_engine::Buf d0;
+    CHK(ensure(e, d0, (size_t)N * K));
+    HIPCHK(hipMemcpy(d0.p, w, (size_t)N * K * sizeof(float), hipMemcpyHostToDevice));
     CHK(dev_alloc(e, out, (size_t)N * K));
-    if (natural) launch_pack_weight16n(d0, N, K, *out, e->stream);
-    else launch_pack_weight16(d0, N, K, *out, e->stream);
+    if (natural) launch_pack_weight16n(d0.p, N, K, *out, e->stream);
+    else launch_pack_weight16(d0.p, N, K, *out, e->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipFree(d0));
     return 0;
 }
 static int pack_key(mellow_engine* e, const std::string& k, int N, int K, Packed* out) {
@@ -131,10 +130,10 @@ extern "C" int mellow_engine_finalize(mellow_engine_t* e) {
         const std::string kr = E + "spectrogram_extractor.stft.conv_real.weight", ki = E + "spectrogram_extractor.stft.conv_imag.weight";
         CHK(expect_shape(get(e, kr), kr, {kNfreq, 1, kNfft}));
         CHK(expect_shape(get(e, ki), ki, {kNfreq, 1, kNfft}));
-        CHK(make_packed(e, get(e, kr)->f(), get(e, ki)->f(), kNfreq, kNfft, &e->dft));
+        CHK(make_packed(e, get(e, kr)->f(), get(e, ki)->f(), kNfreq, kNfft, &e->w.dft));
         // MELLOW_STFT_FFT=0: the DFT GEMM on the split kernel; MELLOW_X3_STFT=0: the whole front-end on the exact fp32 kernel
-        const bool no_fft = !e->stft_fft;            // options "stft_fft" / "x3_stft"
-        if ((e->f32x3_terms || (e->fp8 && e->fp8_prefill)) && !no_fft && kNfft == 1024) {       // (fp8 mode: the front-end stays fp32 arithmetic; the FFT is that)
+        const bool no_fft = !e->opt.stft_fft;            // options "stft_fft" / "x3_stft"
+        if ((e->opt.f32x3_terms || (e->opt.fp8 && e->opt.fp8_prefill)) && !no_fft && kNfft == 1024) {       // (fp8 mode: the front-end stays fp32 arithmetic; the FFT is that)
             // the reference builds these weights as window[n] * cos / -sin(2 pi k n / N) (torchlibrosa STFT, frozen parameters);
             // a checkpoint that holds anything else keeps the GEMM.  Row k = 0 of the real part IS the window.
             const float *wr = get(e, kr)->f(), *wi = get(e, ki)->f();
@@ -158,9 +157,9 @@ extern "C" int mellow_engine_finalize(mellow_engine_t* e) {
                         const double a = -2.0 * M_PI * (double)(d * q) / 64.0;
                         t2[((size_t)d * 16 + q) * 2] = (float)cos(a); t2[((size_t)d * 16 + q) * 2 + 1] = (float)sin(a);
                     }
-                CHK(upload(e, &e->fft_win, wr, kNfft));
-                CHK(upload(e, &e->fft_tw1, t1.data(), t1.size()));
-                CHK(upload(e, &e->fft_tw2, t2.data(), t2.size()));
+                CHK(upload(e, &e->w.fft_win, wr, kNfft));
+                CHK(upload(e, &e->w.fft_tw1, t1.data(), t1.size()));
+                CHK(upload(e, &e->w.fft_tw2, t2.data(), t2.size()));
             }
         }
         const std::string km = E + "logmel_extractor.melW";
@@ -169,7 +168,7 @@ extern "C" int mellow_engine_finalize(mellow_engine_t* e) {
         const float* mw = get(e, km)->f();
         for (int k = 0; k < kNfreq; ++k)
             for (int n = 0; n < kMel; ++n) mt[(size_t)n * kNfreq + k] = mw[(size_t)k * kMel + n];
-        CHK(make_packed(e, mt.data(), nullptr, kMel, kNfreq, &e->mel));
+        CHK(make_packed(e, mt.data(), nullptr, kMel, kNfreq, &e->w.mel));
         const HostTensor *w = get(e, E + "bn0.weight"), *b = get(e, E + "bn0.bias"), *rm = get(e, E + "bn0.running_mean"),
                          *rv = get(e, E + "bn0.running_var");
         for (const char* nm : {"bn0.weight", "bn0.bias", "bn0.running_mean", "bn0.running_var"})
@@ -181,17 +180,17 @@ extern "C" int mellow_engine_finalize(mellow_engine_t* e) {
             al[i] = invstd * w->f()[i];
             be[i] = b->f()[i] - rm->f()[i] * al[i];
         }
-        CHK(upload(e, &e->bn_alpha, al.data(), kMel));
-        CHK(upload(e, &e->bn_beta, be.data(), kMel));
+        CHK(upload(e, &e->w.bn_alpha, al.data(), kMel));
+        CHK(upload(e, &e->w.bn_beta, be.data(), kMel));
     }
     // ---- patch embed ----
     {
         const std::string k = E + "patch_embed.proj.weight";
         CHK(expect_shape(get(e, k), k, {96, 1, 4, 4}));
-        CHK(upload(e, &e->pe_w, get(e, k)->f(), 96 * 16));
-        CHK(up_vec(e, E + "patch_embed.proj.bias", 96, &e->pe_b));
-        CHK(up_vec(e, E + "patch_embed.norm.weight", 96, &e->pe_nw));
-        CHK(up_vec(e, E + "patch_embed.norm.bias", 96, &e->pe_nb));
+        CHK(upload(e, &e->w.pe_w, get(e, k)->f(), 96 * 16));
+        CHK(up_vec(e, E + "patch_embed.proj.bias", 96, &e->w.pe_b));
+        CHK(up_vec(e, E + "patch_embed.norm.weight", 96, &e->w.pe_nw));
+        CHK(up_vec(e, E + "patch_embed.norm.bias", 96, &e->w.pe_nb));
     }
     // ---- Swin stages ----
     for (int s = 0; s < 4; ++s) {
@@ -202,7 +201,7 @@ extern "C" int mellow_engine_finalize(mellow_engine_t* e) {
             window_map_host(R, sh ? kWin / 2 : 0, m.data());
             float* d = nullptr;
             CHK(upload(e, &d, reinterpret_cast<const float*>(m.data()), m.size()));
-            e->win_map[s][sh] = reinterpret_cast<int32_t*>(d);
+            e->w.win_map[s][sh] = reinterpret_cast<int32_t*>(d);
         }
         for (int b = 0; b < kDepths[s]; ++b) {
             const std::string p = E + "layers." + std::to_string(s) + ".blocks." + std::to_string(b) + ".";
@@ -238,18 +237,18 @@ extern "C" int mellow_engine_finalize(mellow_engine_t* e) {
                 CHK(expect_shape(get(e, km), km, {nW, 64, 64}));
                 CHK(upload(e, &w.mask, get(e, km)->f(), (size_t)nW * 4096));
             }
-            e->blocks[s].push_back(w);
+            e->w.blocks[s].push_back(w);
         }
         if (s < 3) {
             const std::string p = E + "layers." + std::to_string(s) + ".downsample.";
-            CHK(up_vec(e, p + "norm.weight", 4 * C, &e->merge[s].nw));
-            CHK(up_vec(e, p + "norm.bias", 4 * C, &e->merge[s].nb));
-            CHK(pack_key(e, p + "reduction.weight", 2 * C, 4 * C, &e->merge[s].red));
+            CHK(up_vec(e, p + "norm.weight", 4 * C, &e->w.merge[s].nw));
+            CHK(up_vec(e, p + "norm.bias", 4 * C, &e->w.merge[s].nb));
+            CHK(pack_key(e, p + "reduction.weight", 2 * C, 4 * C, &e->w.merge[s].red));
         }
     }
     // ---- tail ----
-    CHK(up_vec(e, E + "norm.weight", kEncOut, &e->fn_w));
-    CHK(up_vec(e, E + "norm.bias", kEncOut, &e->fn_b));
+    CHK(up_vec(e, E + "norm.weight", kEncOut, &e->w.fn_w));
+    CHK(up_vec(e, E + "norm.bias", kEncOut, &e->w.fn_b));
     {
         const std::string k = E + "tscam_conv.weight";
         CHK(expect_shape(get(e, k), k, {kClasses, kEncOut, 2, 3}));
@@ -261,21 +260,21 @@ extern "C" int mellow_engine_finalize(mellow_engine_t* e) {
                 for (int cf = 0; cf < 2; ++cf)
                     for (int dt = 0; dt < 3; ++dt)
                         wt[(size_t)o * 4608 + (cf * 3 + dt) * 768 + ch] = src[(((size_t)o * kEncOut + ch) * 2 + cf) * 3 + dt];
-        CHK(make_packed(e, wt.data(), nullptr, kClasses, 4608, &e->tscam));
-        CHK(up_vec(e, E + "tscam_conv.bias", kClasses, &e->tscam_b, e->tscam.NP));
+        CHK(make_packed(e, wt.data(), nullptr, kClasses, 4608, &e->w.tscam));
+        CHK(up_vec(e, E + "tscam_conv.bias", kClasses, &e->w.tscam_b, e->w.tscam.NP));
     }
-    CHK(pack_key(e, std::string(C2L) + "weight", kEncOut, kClasses, &e->c2l));
-    CHK(up_vec(e, std::string(C2L) + "bias", kEncOut, &e->c2l_b, e->c2l.NP));
-    CHK(pack_key(e, std::string(PRJ) + "linear1.weight", kProj, kEncOut, &e->lin1));
-    CHK(pack_key(e, std::string(PRJ) + "linear2.weight", kProj, kProj, &e->lin2));
-    CHK(up_vec(e, std::string(PRJ) + "layer_norm.weight", kProj, &e->pln_w));
-    CHK(up_vec(e, std::string(PRJ) + "layer_norm.bias", kProj, &e->pln_b));
+    CHK(pack_key(e, std::string(C2L) + "weight", kEncOut, kClasses, &e->w.c2l));
+    CHK(up_vec(e, std::string(C2L) + "bias", kEncOut, &e->w.c2l_b, e->w.c2l.NP));
+    CHK(pack_key(e, std::string(PRJ) + "linear1.weight", kProj, kEncOut, &e->w.lin1));
+    CHK(pack_key(e, std::string(PRJ) + "linear2.weight", kProj, kProj, &e->w.lin2));
+    CHK(up_vec(e, std::string(PRJ) + "layer_norm.weight", kProj, &e->w.pln_w));
+    CHK(up_vec(e, std::string(PRJ) + "layer_norm.bias", kProj, &e->w.pln_b));
     {
         std::vector<int32_t> m(32);
         for (int i = 0; i < 32; ++i) m[i] = i + 1;
         float* d = nullptr;
         CHK(upload(e, &d, reinterpret_cast<const float*>(m.data()), 32));
-        e->emb_row_map = reinterpret_cast<int32_t*>(d);
+        e->w.emb_row_map = reinterpret_cast<int32_t*>(d);
     }
     // ---- LM ----
     const std::string L = LMK;
@@ -283,21 +282,21 @@ extern "C" int mellow_engine_finalize(mellow_engine_t* e) {
     {
         const std::string k = L + "model.embed_tokens.weight";
         CHK(expect_shape(get(e, k), k, {V, H}));
-        CHK(upload(e, &e->embed, get(e, k)->f(), (size_t)V * H));
+        CHK(upload(e, &e->w.embed, get(e, k)->f(), (size_t)V * H));
         e->decode_only_weight = true;                 // the lm_head runs in the decode kernels only (last position)
-        CHK(make_packed(e, get(e, k)->f(), nullptr, V, H, &e->lm_head));
+        CHK(make_packed(e, get(e, k)->f(), nullptr, V, H, &e->w.lm_head));
         e->decode_only_weight = false;
-        if (e->fp8_decode) CHK(make_dec_fp8(e, e->lm_head.p, e->lm_head.NP / 32, (e->lm_head.KP / 8) * 64, 32, &e->head8, &e->head_sc));
+        if (e->opt.fp8_decode) CHK(make_dec_fp8(e, e->w.lm_head.p, e->w.lm_head.NP / 32, (e->w.lm_head.KP / 8) * 64, 32, &e->w.head8, &e->w.head_sc));
     }
     // scratch for the load-time weight composition of dec_qkv2_kernel (fp32 decode weights only)
-    float *cmpF = nullptr, *cmpD = nullptr, *cmpQ = nullptr, *cmpCat = nullptr;
-    const bool no_fuse = !e->decode_fuse;   // option "decode_fuse" = 0: keep the 5-launch layer
+    mellow_engine::Buf cmpF, cmpD, cmpQ, cmpCat;      // (freed when finalize returns, on every path)
+    const bool no_fuse = !e->opt.decode_fuse;   // option "decode_fuse" = 0: keep the 5-launch layer
     const bool fuse = !no_fuse && H == 576 && I == 1536;
     if (fuse) {
-        HIPCHK(hipMalloc(&cmpF, (size_t)960 * 576 * 4));
-        HIPCHK(hipMalloc(&cmpD, (size_t)576 * 1536 * 4));
-        HIPCHK(hipMalloc(&cmpQ, (size_t)960 * 1536 * 4));
-        HIPCHK(hipMalloc(&cmpCat, (size_t)1024 * 2112 * 4));     // fp32: [W' | Q] row-major; fp8 mode: Q alone in P-layout (1024 x 1536)
+        CHK(ensure(e, cmpF, (size_t)960 * 576));
+        CHK(ensure(e, cmpD, (size_t)576 * 1536));
+        CHK(ensure(e, cmpQ, (size_t)960 * 1536));
+        CHK(ensure(e, cmpCat, (size_t)1024 * 2112));     // fp32: [W' | Q] row-major; fp8 mode: Q alone in P-layout (1024 x 1536)
     }
     for (int l = 0; l < e->cfg.num_layers; ++l) {
         const std::string p = L + "model.layers." + std::to_string(l) + ".";
@@ -328,25 +327,25 @@ extern "C" int mellow_engine_finalize(mellow_engine_t* e) {
             e->decode_only_weight = true;
             CHK(make_packed(e, f.data(), nullptr, 960, H, &w.qkv_f));
             e->decode_only_weight = false;
-            if (e->prefill_fuse_norm) { CHK(make_pb(e, w.qkv_f)); CHK(make_w8(e, w.qkv_f)); }        // f32x3 / fp8 prefill without norm launches (run_prefill)
+            if (e->opt.prefill_fuse_norm) { CHK(make_pb(e, w.qkv_f)); CHK(make_w8(e, w.qkv_f)); }        // f32x3 / fp8 prefill without norm launches (run_prefill)
             if (fuse && l > 0) {
                 // Q = W'_l . Wd_{l-1} in fp64, rounded once; then [W'_l | Q] re-tiled into P-layout
                 const std::string kd = L + "model.layers." + std::to_string(l - 1) + ".mlp.down_proj.weight";
                 CHK(expect_shape(get(e, kd), kd, {H, I}));
-                HIPCHK(hipMemcpyAsync(cmpF, f.data(), (size_t)960 * 576 * 4, hipMemcpyHostToDevice, e->stream));
-                HIPCHK(hipMemcpyAsync(cmpD, get(e, kd)->f(), (size_t)576 * 1536 * 4, hipMemcpyHostToDevice, e->stream));
-                launch_compose_f64(cmpF, cmpD, cmpQ, 960, 1536, 576, e->stream);
-                if (e->fp8_decode) {
+                HIPCHK(hipMemcpyAsync(cmpF.p, f.data(), (size_t)960 * 576 * 4, hipMemcpyHostToDevice, e->stream));
+                HIPCHK(hipMemcpyAsync(cmpD.p, get(e, kd)->f(), (size_t)576 * 1536 * 4, hipMemcpyHostToDevice, e->stream));
+                launch_compose_f64(cmpF.p, cmpD.p, cmpQ.p, 960, 1536, 576, e->stream);
+                if (e->opt.fp8_decode) {
                     // e4m3 decode weights: the composed part is quantised on its own (its rows have their own magnitude); the
                     // W' part and the down weight of the launch are the unfused layer's e4m3 copies (qkv8, dn8)
-                    launch_pack_weight(cmpQ, 960, 1536, 1536, cmpCat, 1024, 1536, e->stream);
+                    launch_pack_weight(cmpQ.p, 960, 1536, 1536, cmpCat.p, 1024, 1536, e->stream);
                     HIPCHK(hipGetLastError());
-                    CHK(make_dec_fp8(e, cmpCat, 32, (1536 / 8) * 64, 32, &w.q2h8, &w.q2h_sc));
+                    CHK(make_dec_fp8(e, cmpCat.p, 32, (1536 / 8) * 64, 32, &w.q2h8, &w.q2h_sc));
                 } else {
-                    HIPCHK(hipMemcpy2DAsync(cmpCat, (size_t)2112 * 4, cmpF, (size_t)576 * 4, (size_t)576 * 4, 960, hipMemcpyDeviceToDevice, e->stream));
-                    HIPCHK(hipMemcpy2DAsync(cmpCat + 576, (size_t)2112 * 4, cmpQ, (size_t)1536 * 4, (size_t)1536 * 4, 960, hipMemcpyDeviceToDevice, e->stream));
+                    HIPCHK(hipMemcpy2DAsync(cmpCat.p, (size_t)2112 * 4, cmpF.p, (size_t)576 * 4, (size_t)576 * 4, 960, hipMemcpyDeviceToDevice, e->stream));
+                    HIPCHK(hipMemcpy2DAsync(cmpCat.p + 576, (size_t)2112 * 4, cmpQ.p, (size_t)1536 * 4, (size_t)1536 * 4, 960, hipMemcpyDeviceToDevice, e->stream));
                     CHK(dev_alloc(e, &w.qkv2, (size_t)1024 * 2112));
-                    launch_pack_weight(cmpCat, 960, 2112, 2112, w.qkv2, 1024, 2112, e->stream);
+                    launch_pack_weight(cmpCat.p, 960, 2112, 2112, w.qkv2, 1024, 2112, e->stream);
                     HIPCHK(hipGetLastError());
                     HIPCHK(hipStreamSynchronize(e->stream));
                 }
@@ -357,7 +356,7 @@ extern "C" int mellow_engine_finalize(mellow_engine_t* e) {
                     gf[(size_t)n * H + kk] = g->f()[(size_t)n * H + kk] * l2->f()[kk];
                     uf[(size_t)n * H + kk] = u->f()[(size_t)n * H + kk] * l2->f()[kk];
                 }
-            if (e->prefill_fuse_norm && (e->f32x3_terms || (e->fp8 && e->fp8_prefill))) {   // the folded gate/up in the prefill's pair layout (+ its bf16 split / e4m3 copy)
+            if (e->opt.prefill_fuse_norm && (e->opt.f32x3_terms || (e->opt.fp8 && e->opt.fp8_prefill))) {   // the folded gate/up in the prefill's pair layout (+ its bf16 split / e4m3 copy)
                 e->decode_only_weight = true;
                 CHK(make_packed(e, gf.data(), uf.data(), I, H, &w.gateup_f));
                 e->decode_only_weight = false;
@@ -373,20 +372,19 @@ extern "C" int mellow_engine_finalize(mellow_engine_t* e) {
                     memcpy(il.data() + (size_t)(2 * t + 1) * 8 * H, uf.data() + (size_t)t * 8 * H, (size_t)8 * H * 4);
                 }
                 CHK(make_packed16(e, il.data(), 2 * I, H, &w.gu16));
-                if (e->f32x3_terms && fuse && !e->fp8_decode) CHK(make_packed16(e, il.data(), 2 * I, H, &w.gu16n, true));    // f32x3 layer kernels (row blocks >= dec_x3_min_rb)
+                if (e->opt.f32x3_terms && fuse && !e->opt.fp8_decode) CHK(make_packed16(e, il.data(), 2 * I, H, &w.gu16n, true));    // f32x3 layer kernels (row blocks >= dec_x3_min_rb)
             }
             CHK(make_packed16(e, get(e, p + "self_attn.o_proj.weight")->f(), H, 576, &w.o16));
         }
-        if (e->fp8_decode) {
+        if (e->opt.fp8_decode) {
             CHK(make_dec_fp8(e, w.qkv_f.p, w.qkv_f.NP / 32, (w.qkv_f.KP / 8) * 64, 32, &w.qkv8, &w.qkv_sc));
             CHK(make_dec_fp8(e, w.o16, H / 16, (576 / 16) * 64, 16, &w.o8, &w.o_sc));
             CHK(make_dec_fp8(e, w.gu16, 2 * I / 16, (H / 16) * 64, 16, &w.gu8, &w.gu_sc));
             CHK(make_dec_fp8(e, w.down.p, w.down.NP / 32, (w.down.KP / 8) * 64, 32, &w.dn8, &w.dn_sc));
         }
-        e->layers.push_back(w);
+        e->w.layers.push_back(w);
     }
-    if (cmpF) { HIPCHK(hipFree(cmpF)); HIPCHK(hipFree(cmpD)); HIPCHK(hipFree(cmpQ)); HIPCHK(hipFree(cmpCat)); }
-    CHK(up_vec(e, L + "model.norm.weight", H, &e->final_norm));
+    CHK(up_vec(e, L + "model.norm.weight", H, &e->w.final_norm));
     // ---- RoPE tables [max_pos][32]: supplied by the host wrapper (computed the HF way with torch) or built here ----
     {
         const int P = e->cfg.max_positions;
@@ -398,8 +396,8 @@ extern "C" int mellow_engine_finalize(mellow_engine_t* e) {
         } else {
             rope_tables_host(e->cfg.rope_theta, 64, P, c.data(), s.data());
         }
-        CHK(upload(e, &e->rope_cos, c.data(), c.size()));
-        CHK(upload(e, &e->rope_sin, s.data(), s.size()));
+        CHK(upload(e, &e->w.rope_cos, c.data(), c.size()));
+        CHK(upload(e, &e->w.rope_sin, s.data(), s.size()));
     }
     CHK(alloc_state_words(e));
     e->host.clear();
