@@ -50,7 +50,8 @@ extern "C" {
  *     (the pre-split debug kernel was removed; 16 / 17 are the engine's own f32x3 kernels).
  *  4: opt-in seeded nucleus sampling: mellow_generate_sampled and mellow_sample_logits.  mellow_generate is unchanged (greedy).
  *     The scoring symbols mellow_score and mellow_lm_score were added later under this same minor (no existing symbol or struct
- *     changed): a binding that must also load an older minor-4 library detects them by symbol lookup (dlsym), not by the number. */
+ *     changed): a binding that must also load an older minor-4 library detects them by symbol lookup (dlsym), not by the number.
+ *     mellow_generate_scored and mellow_debug_dec_head_lse (log-probs of the generated tokens) were added the same way. */
 #define MELLOW_ABI_MINOR 4
 
 typedef struct mellow_engine mellow_engine_t;
@@ -161,6 +162,35 @@ int  mellow_generate_sampled(mellow_engine_t* e, const float* audio1, const floa
                              const int32_t* input_ids, int B, int max_len, float top_p, float temperature, uint64_t seed,
                              int32_t row_offset, int stop_id, int ignore_stop, int32_t* out_tokens, int32_t* out_len,
                              int32_t* out_steps, float* first_token_ms);
+/* mellow_generate (do_sample == 0) or mellow_generate_sampled (do_sample != 0: the same validation and errors) that also records the
+ * log-probability of every token it records: out_logprob dev f32 [B][max_len], column t belongs to column t of out_tokens.  Tokens,
+ * lengths and steps are bit-identical to those calls.  The number is formed inside the decode step -- no second forward, and no
+ * logits store in a greedy call: the lm_head reduces every 32-column tile of a row to a partial of its log-sum-exp next to the
+ * arg-max candidate it already forms, and the kernel that picks the token merges the partials.
+ *
+ * Definition.  For the fp32 logits l[0..vocab) that chose token k at a step (the prefill's token included):
+ *     logprob = l_k - lse,   lse = M + log S,   M = max l,   S = sum over 32-column tiles t of s_t * exp(m_t - M),
+ *     m_t = max of tile t,   s_t = sum over the columns j of tile t of exp(l_j - m_t).
+ * It is the model's own log-softmax -- temperature 1, no nucleus -- also in a sampled call, whatever top_p / temperature drew the
+ * token: the number mellow_score returns for the same tokens (another kernel and summation order there: equal to rounding, not
+ * bit-equal).  A greedy call picks k = arg-max, so l_k = M and it records -log S; a sampled call reads l_k from the logits row the
+ * head stored for the sampler and records l_k - lse.  log S is taken in fp64 and rounded once; exp is fp32 expf.
+ * Summation orders (all fixed; no float atomics -- results are bit-identical run to run, graph or eager, and do not depend on the
+ * row's batch slot, on row migration or on the 1024-row passes):
+ *   - within a tile, streaming f32x3 head (the default mode): the two lanes of a pair hold columns 8 q + 4 h + j (h = lane half,
+ *     q = 0..3, j = 0..3); each adds its 16 terms in the order q, then j, ascending; s_t = (sum of h = 0) + (sum of h = 1).
+ *   - within a tile, fp32 / e4m3 head (MELLOW_PRECISION_F32, MELLOW_PRECISION_FP8, a vocabulary the streaming head does not tile):
+ *     eight threads hold columns 4 q .. 4 q + 3 (q = 0..7); each adds its four terms ascending; s_t = the eight sums, ascending q.
+ *   - over the tiles of a row: 256 threads, thread i adds the terms of tiles i, i + 256, ... ascending, starting from 0 (a tile
+ *     whose m_t is -inf contributes exactly 0); then a butterfly over each 64-lane wave (partner = lane xor 32, 16, 8, 4, 2, 1, each
+ *     lane adding its partner's value to its own); then the four waves: ((w0 + w1) + w2) + w3.
+ * A row whose M is not finite (a NaN or infinite logit) reports NaN.  Columns that are never computed hold exactly 0.0 wherever
+ * out_tokens holds -1 (per-block early exit; passes of a batch of more than 1024 rows that stopped before the longest pass).
+ * The vocabulary must be a multiple of 32 (and 49152 with do_sample). */
+int  mellow_generate_scored(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples,
+                            const int32_t* input_ids, int B, int max_len, int do_sample, float top_p, float temperature,
+                            uint64_t seed, int32_t row_offset, int stop_id, int ignore_stop, int32_t* out_tokens,
+                            float* out_logprob, int32_t* out_len, int32_t* out_steps, float* first_token_ms);
 /* The same draw on caller logits, no loop state (numeric tap): logits dev [B][vocab], row_ids dev i32 [B] (global row index
  * of each row; NULL = 0..B-1), step = t above -> tokens dev i32 [B]. */
 int  mellow_sample_logits(mellow_engine_t* e, const float* logits, int B, const int32_t* row_ids, int step, float top_p,
@@ -254,6 +284,11 @@ int  mellow_debug_gemm_fp8(mellow_engine_t* e, const float* A, int M, int K, con
  * own head weights (the e4m3 copy in MELLOW_PRECISION_FP8; act_fp8 != 0 then also quantises x inside the kernel: one scale per
  * batch row and 72-column slice, fp8 matrix pipe).  Invalidates the decode state of an earlier prefill. */
 int  mellow_debug_dec_head(mellow_engine_t* e, const float* x, int B, int act_fp8, float* logits);
+/* Its twin for mellow_generate_scored: the same kernel in the variant that also emits the per-tile log-sum-exp partials, and the
+ * merge above, on caller rows: logits dev [B][vocab] (may be NULL; bit-equal to mellow_debug_dec_head's), out_lse / out_max dev
+ * f32 [B] (lse = M + log S, M), out_argmax dev i32 [B] (the arg-max tap's rule).  Invalidates the decode state the same way. */
+int  mellow_debug_dec_head_lse(mellow_engine_t* e, const float* x, int B, int act_fp8, float* logits, float* out_lse,
+                               float* out_max, int32_t* out_argmax);
 
 /* (The library also exports three developer instrumentation entry points that are NOT part of this ABI and may change without
  *  a version bump: mellow_dev_gemm_time, mellow_dev_prof_dump, mellow_dev_kdebug -- timers and stamps used by tools/, none of

@@ -64,6 +64,53 @@ __device__ __forceinline__ bool arg_better(float v, int i, float bv, int bi) {
     return v > bv || (v == bv && i < bi);
 }
 
+// ---- log-sum-exp of one decode-step row from the lm_head's per-tile partials (include/mellow_hip.h, mellow_generate_scored) -------
+// Tile t of a row carries (m_t = its maximum logit in arg_better order, s_t = sum over its 32 columns of exp(logit - m_t)).  With the
+// row maximum M:  S = sum_t s_t exp(m_t - M)  in ONE fixed order, whatever kernel asks: the first 256 threads of the workgroup,
+// thread i adds tiles i, i + 256, ... in ascending order starting from 0; a butterfly over the wave (xor 32, 16, 8, 4, 2, 1: both
+// partners form the same sum); then the four waves in ascending order.  A tile whose maximum is -inf contributes exactly 0.
+// Every thread of the workgroup calls it (>= 256 threads, whole waves; `sh` = 4 floats of LDS, free again on return); M is
+// workgroup-uniform.  No atomics: the bits depend on (partials, M) only.
+__device__ __forceinline__ float dec_lse_sum(const float* __restrict__ cm, const float* __restrict__ cs, int n, float M, float* sh) {
+    const int tid = threadIdx.x;
+    float s = 0.f;
+    if (tid < 256)
+        for (int i = tid; i < n; i += 256) {
+            const float m = cm[i];
+            s += m > -INFINITY ? cs[i] * expf(m - M) : 0.f;
+        }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    if (tid < 256 && (tid & 63) == 0) sh[tid >> 6] = s;
+    __syncthreads();
+    const float S = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    __syncthreads();
+    return S;
+}
+// lse = M + log S, the logarithm taken in fp64 and rounded once; a row whose maximum is not finite (a NaN or +-inf logit) reports NaN
+__device__ __forceinline__ float dec_lse_log(float S) { return (float)log((double)S); }
+__device__ __forceinline__ float dec_lse_value(float M, float S) { return (M - M == 0.f) ? M + dec_lse_log(S) : __builtin_nanf(""); }
+// the row maximum from the tile maxima, for a kernel that has not formed it itself (the sampler): NaN if any tile holds one
+__device__ __forceinline__ float dec_lse_max(const float* __restrict__ cm, int n, float* sh) {
+    const int tid = threadIdx.x;
+    float m = -INFINITY;
+    bool nan = false;
+    if (tid < 256)
+        for (int i = tid; i < n; i += 256) {
+            const float v = cm[i];
+            nan |= v != v;
+            m = fmaxf(m, v);
+        }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    const bool any_nan = __syncthreads_or(nan ? 1 : 0) != 0;
+    if (tid < 256 && (tid & 63) == 0) sh[tid >> 6] = m;
+    __syncthreads();
+    const float M = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+    __syncthreads();
+    return any_nan ? __builtin_nanf("") : M;
+}
+
 // exact-erf GELU (nn.GELU() default, reference htsat.py:121 / mellow.py:50)
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }

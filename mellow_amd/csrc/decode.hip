@@ -1067,7 +1067,10 @@ enum { OUT_LOGITS = 1 };
 #define MELLOW_LM_WAVES 8     // 8 x 9 k-tiles: 53.45 vs 54.35 ms of decode per 63 steps with 4 x 18 (6 / 9 / 12 waves: 54.1 / 54.1 / 53.7)
 #endif
 constexpr int LM_WAVES = MELLOW_LM_WAVES;
-template <int OUT, bool BLK, int W8>
+// LSE (log-probs of the generated tokens, DecArgs::cand_sum): the tile maximum found for the arg-max candidate goes back to the 256
+// epilogue threads through the same LDS; thread (row mm, q = tid / 32) sums exp(v - max) over its four columns 4 q .. 4 q + 3 in
+// ascending order, and the thread that writes the row's candidate adds the eight partial sums in ascending q.
+template <int OUT, bool BLK, int W8, bool LSE = false>
 __global__ __launch_bounds__(LM_WAVES * 64) void dec_fullk_kernel(const float* __restrict__ Wp, const float* __restrict__ XF, int K8p,
                                                         int N, const DecArgs a, const float* __restrict__ wscale) {
     kspan(a.dbg_seq, 0);
@@ -1160,6 +1163,22 @@ __global__ __launch_bounds__(LM_WAVES * 64) void dec_fullk_kernel(const float* _
             const int64_t o = ((int64_t)rb * 32 + tid) * (N >> 5) + nt;          // N / 32 = gridDim.x (a dispatch-packet read in the tail otherwise)
             a.cand_val[o] = best;
             a.cand_idx[o] = idx;
+            if constexpr (LSE) red[512 + tid] = best;
+        }
+        if constexpr (LSE) {
+            __syncthreads();
+            const float tmax = red[512 + mm];
+            float ps = 0.f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) ps += expf(v[j] - tmax);
+            if (epi) red[768 + tid] = ps;
+            __syncthreads();
+            if (tid < 32) {
+                float ssum = red[768 + tid];
+#pragma unroll
+                for (int q = 1; q < 8; ++q) ssum += red[768 + tid + 32 * q];      // fixed order
+                a.cand_sum[((int64_t)rb * 32 + tid) * (N >> 5) + nt] = ssum;
+            }
         }
     }
     kspan(a.dbg_seq, 1);
@@ -1192,7 +1211,10 @@ constexpr int H3_NW = MELLOW_H3_NW, H3_CP = 3, H3_NC = 36 / H3_CP;
 //      phases), and inside a phase the waves run without any barrier -- each streams its own n-tile's weights D chunks ahead
 //      (D = 1: deeper register prefetch measured slower) and reads the fragments it needs from LDS.  (A first form refilled a small
 //      stage every chunk -- one barrier + one L2 round trip per chunk: tools/experiments/r05_dec_head3_kernel.hip.txt.)
-template <int G, int D, bool BLK>
+//      LSE (DecArgs::cand_sum): after the exchange below both lanes of a pair know the tile's maximum; each sums exp(acc - max)
+//      over its 16 accumulators in register order (columns 8 q + 4 h + j: q, then j, ascending), the halves are exchanged the same
+//      way and the h == 0 lane stores (its own sum) + (its partner's).
+template <int G, int D, bool BLK, bool LSE = false>
 __global__ __launch_bounds__(H3_NW * 64) void dec_head3r_kernel(const float* __restrict__ Wp, const i32x4* __restrict__ X3, int K8p, int N,
                                                                 int RB_p, const DecArgs a) {
     kspan(a.dbg_seq, 0);
@@ -1293,6 +1315,14 @@ __global__ __launch_bounds__(H3_NW * 64) void dec_head3r_kernel(const float* __r
                     const int64_t o = row * (N >> 5) + nt;
                     a.cand_val[o] = bv;
                     a.cand_idx[o] = bi;
+                }
+                if constexpr (LSE) {
+                    float ps = 0.f;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) ps += expf(acc[g][r] - bv);
+                    auto rs = __builtin_amdgcn_permlane32_swap(__float_as_uint(ps), __float_as_uint(ps), false, false);
+                    const float os = __uint_as_float(h ? rs[0] : rs[1]);
+                    if (h == 0) a.cand_sum[row * (N >> 5) + nt] = ps + os;
                 }
             }
         }
@@ -1962,6 +1992,9 @@ __global__ __launch_bounds__(192) void dec_final_norm_kernel(const float* __rest
 // arg-max over the lm_head's per-tile candidates, fused with the loop bookkeeping of reference wrapper.py:232-249:
 // record the token at column (*d_pos - T0 + 1), track stop ids, and gather its embedding row (embed_tokens,
 // wrapper.py:237) as the next step's residual stream (row-major + F32-layout).
+// LSE (LoopArgs::out_logprob): the chosen token is the row maximum M = `best`, so its log-prob is -log S with S merged from the
+// head's (cand_val, cand_sum) partials by dec_lse_sum (common.h): written where the token is.
+template <bool LSE>
 __global__ __launch_bounds__(256) void dec_argmax_kernel(const float* __restrict__ cand_val_p, const int32_t* __restrict__ cand_idx_p, int n,
                                                          const DecArgs a, int32_t* __restrict__ tokens,
                                                          const float* __restrict__ embed, int write_x, const LoopArgs lp) {
@@ -1969,6 +2002,7 @@ __global__ __launch_bounds__(256) void dec_argmax_kernel(const float* __restrict
     __shared__ float bv[4];
     __shared__ int bi[4];
     __shared__ int tok_s;
+    __shared__ float lse_sh[4];
     const int b = blockIdx.x, tid = threadIdx.x;
     // a slot whose whole block has stopped (or that is empty after a repack) computes nothing any more, but still takes part
     // in the step's arrival count
@@ -1991,6 +2025,17 @@ __global__ __launch_bounds__(256) void dec_argmax_kernel(const float* __restrict
         if ((tid & 63) == 0) { bv[tid >> 6] = best; bi[tid >> 6] = idx; }
     }
     __syncthreads();
+    float S = 0.f;
+    if constexpr (LSE) {
+        if (!dead) {            // (workgroup-uniform)
+            float M = bv[0];
+            int mi = bi[0];
+            for (int w = 1; w < 4; ++w)
+                if (arg_better(bv[w], bi[w], M, mi)) { M = bv[w]; mi = bi[w]; }
+            S = dec_lse_sum(cand_val_p + (int64_t)b * n, a.cand_sum + (int64_t)b * n, n, M, lse_sh);
+            S = (M - M == 0.f) ? S : __builtin_nanf("");
+        }
+    }
     if (tid == 0) {
         if (!dead) {
             for (int w = 1; w < 4; ++w)
@@ -2004,6 +2049,9 @@ __global__ __launch_bounds__(256) void dec_argmax_kernel(const float* __restrict
                 const int max_len = lp.params[0], stop_id = lp.params[1];
                 const int step = *a.d_pos - lp.T0 + 1;
                 if (step >= 0 && step < max_len) lp.out_tokens[(int64_t)row * max_len + step] = idx;
+                if constexpr (LSE) {
+                    if (step >= 0 && step < max_len) lp.out_logprob[(int64_t)row * max_len + step] = -dec_lse_log(S);
+                }
                 if (idx == stop_id && lp.seen_stop[row] == 0) {
                     lp.seen_stop[row] = 1;
                     atomicAdd(lp.n_seen, 1);
@@ -2034,6 +2082,19 @@ __global__ __launch_bounds__(256) void dec_argmax_kernel(const float* __restrict
         }
     }
     kspan(a.dbg_seq, 1);
+}
+
+// numeric tap of the same merge on caller rows (mellow_debug_dec_head_lse): the row maximum from the tile maxima, then dec_lse_sum
+__global__ __launch_bounds__(256) void dec_lse_tap_kernel(const float* __restrict__ cand_val_p, const float* __restrict__ cand_sum_p, int n,
+                                                          float* __restrict__ out_lse, float* __restrict__ out_max) {
+    __shared__ float sh[4];
+    const int b = blockIdx.x;
+    const float M = dec_lse_max(cand_val_p + (int64_t)b * n, n, sh);
+    const float S = dec_lse_sum(cand_val_p + (int64_t)b * n, cand_sum_p + (int64_t)b * n, n, M, sh);
+    if (threadIdx.x == 0) {
+        out_lse[b] = dec_lse_value(M, S);
+        out_max[b] = M;
+    }
 }
 
 // Row migration (reference stop rule, more than one 32-row block).  One workgroup, after the step's arg-max: the rows that
@@ -2224,11 +2285,11 @@ template <class F> static inline void with_qkv2x3(int rb, bool blk, F&& f) {
 template <class F> static inline void with_gateup3(int rb, bool blk, F&& f) {
     with_int<1, 2, 4>(rb, [&](auto rbm) { with_bool(blk, [&](auto b) { f(&dec_gateup3_kernel<b.value, rbm.value>, dec_gateup3_lds(rbm.value)); }); });
 }
-template <class F> static inline void with_head3r(int rb, bool blk, F&& f) {
-    with_int<1, 2, 4>(rb, [&](auto g) { with_bool(blk, [&](auto b) {
+template <class F> static inline void with_head3r(int rb, bool blk, bool lse, F&& f) {
+    with_int<1, 2, 4>(rb, [&](auto g) { with_bool(blk, [&](auto b) { with_bool(lse, [&](auto l) {
         constexpr int G = g.value, D = G == 1 ? MELLOW_H3R_D1 : G == 2 ? MELLOW_H3R_D2 : MELLOW_H3R_D4;      // weight chunks in flight
-        f(&dec_head3r_kernel<G, D, b.value>, dec_head3r_lds());
-    }); });
+        f(&dec_head3r_kernel<G, D, b.value, l.value>, dec_head3r_lds());
+    }); }); });
 }
 void launch_dec_qkv2x3(const DecArgs& a, const float* Wq2, const float* Wd, hipStream_t s) {
     const float* Wh = Wq2 + (size_t)72 * 64 * 4;
@@ -2310,17 +2371,17 @@ void launch_dec_lm_head(const DecArgs& a, const float* Wp, int K8p, int vocab, h
     if ((a.x3 & DEC_X3_HEAD) && !wscale && a.xn3 && (vocab / 32) % H3_NW == 0) {
         // f32x3 mode, activations pre-split by the final norm: the streaming form (weights read once for every row block)
         const i32x4* X3 = reinterpret_cast<const i32x4*>(a.xn3);
-        with_head3r(a.RB, a.blk_live != nullptr, [&](auto* kernel, size_t lds) {
+        with_head3r(a.RB, a.blk_live != nullptr, a.cand_sum != nullptr, [&](auto* kernel, size_t lds) {
             set_max_dynamic_lds(reinterpret_cast<const void*>(kernel), lds);
             hipLaunchKernelGGL(kernel, dim3(vocab / 32 / H3_NW), dim3(H3_NW * 64), lds, s, Wp, X3, K8p, vocab, a.RB, a);
         });
         return;
     }
     // (fp32 rows in xnF -- taps on caller rows, or a vocabulary the streaming form does not tile: the exact fp32 kernel below)
-    with_blk_w8(a, wscale, [&](auto blk, auto w8) {
-        hipLaunchKernelGGL((dec_fullk_kernel<OUT_LOGITS, blk.value, w8.value>), dim3(vocab / 32, 1, a.RB), dim3(LM_WAVES * 64), 0, s, Wp,
+    with_blk_w8(a, wscale, [&](auto blk, auto w8) { with_bool(a.cand_sum != nullptr, [&](auto lse) {
+        hipLaunchKernelGGL((dec_fullk_kernel<OUT_LOGITS, blk.value, w8.value, lse.value>), dim3(vocab / 32, 1, a.RB), dim3(LM_WAVES * 64), 0, s, Wp,
                            (const float*)a.xnF, K8p, vocab, a, wscale);
-    });
+    }); });
 }
 // The launchers raise a kernel's dynamic-LDS limit on first use; a decode step is launched inside a stream capture, so the engine
 // calls this once per device beforehand (ensure_lm): every instantiation the launchers can pick (set_max_dynamic_lds skips those
@@ -2329,7 +2390,7 @@ void dec_prepare_lds_attributes() {
     const auto raise = [](auto* kernel, size_t lds) { set_max_dynamic_lds(reinterpret_cast<const void*>(kernel), lds); };
     for (const int rb : {1, 2, 4})
         for (const bool blk : {false, true}) {
-            with_head3r(rb, blk, raise);
+            for (const bool lse : {false, true}) with_head3r(rb, blk, lse, raise);
             with_qkv2x3(rb, blk, raise);
             with_gateup3(rb, blk, raise);
         }
@@ -2372,8 +2433,14 @@ void launch_pack_dec_fp8(const float* Wp, int tiles, int slots_per_tile, int row
 }
 void launch_dec_argmax(const DecArgs& a, int B, int n_tiles, int32_t* tokens, const float* embed, int write_x,
                        const LoopArgs& loop, hipStream_t s) {
-    hipLaunchKernelGGL(dec_argmax_kernel, dim3(B), dim3(256), 0, s, (const float*)a.cand_val, (const int32_t*)a.cand_idx, n_tiles, a, tokens, embed,
-                       write_x, loop);
+    // the log-prob record needs the head's partial sums: both set (mellow_generate_scored) or neither
+    with_bool(loop.out_logprob != nullptr && a.cand_sum != nullptr, [&](auto lse) {
+        hipLaunchKernelGGL(dec_argmax_kernel<lse.value>, dim3(B), dim3(256), 0, s, (const float*)a.cand_val, (const int32_t*)a.cand_idx, n_tiles, a,
+                           tokens, embed, write_x, loop);
+    });
+}
+void launch_dec_lse_tap(const DecArgs& a, int B, int n_tiles, float* out_lse, float* out_max, hipStream_t s) {
+    hipLaunchKernelGGL(dec_lse_tap_kernel, dim3(B), dim3(256), 0, s, (const float*)a.cand_val, (const float*)a.cand_sum, n_tiles, out_lse, out_max);
 }
 void launch_dec_load_rows(const DecArgs& a, int B, const float* in, int64_t ld, const int32_t* row_ids, int T_last,
                           int n_src, hipStream_t s) {

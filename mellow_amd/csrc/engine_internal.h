@@ -199,7 +199,14 @@ struct mellow_engine {
         struct Key {
             int B = -1, Tmax = -1, sample = -1;     // batch, page geometry, sampling mode (the sampler + logits store, or the arg-max)
             const void *out_tok = nullptr, *blk_live = nullptr, *row_of_slot = nullptr;      // token record, DecArgs::blk_live / ::row_of_slot
-            bool operator==(const Key& k) const { return B == k.B && Tmax == k.Tmax && out_tok == k.out_tok && blk_live == k.blk_live && row_of_slot == k.row_of_slot && sample == k.sample; }
+            // log-probs of the generated tokens (mellow_generate_scored): other head / arg-max / sampler instantiations, and the
+            // addresses of the partial sums and of the record -- a call without never replays a graph captured with, nor the reverse
+            int logprob = 0;
+            const void *cand_sum = nullptr, *out_lp = nullptr;
+            bool operator==(const Key& k) const {
+                return B == k.B && Tmax == k.Tmax && out_tok == k.out_tok && blk_live == k.blk_live && row_of_slot == k.row_of_slot && sample == k.sample &&
+                       logprob == k.logprob && cand_sum == k.cand_sum && out_lp == k.out_lp;
+            }
         };
         hipGraphExec_t one = nullptr, eight = nullptr;      // eight: the same step 8 times in a row (the step is position-independent)
         Key key;
@@ -262,6 +269,10 @@ struct mellow_engine {
     std::vector<int32_t> h_ident;              // staging of d_row_of_slot
     int last_steps_enqueued = 0;               // decode steps (incl. the prefill's token) the last generate call enqueued
     Buf out_tok;                               // engine-owned token record [rows][max_len] (stable address: graph-safe)
+    // mellow_generate_scored, created on first use: the head's per-tile sums of exponentials [rows][vocab / 32] (DecArgs::cand_sum) and
+    // the log-prob record [rows][max_len] (LoopArgs::out_logprob); logprob_on: this call records (run_lm_head / loop_args)
+    Buf cand_sum, out_lp;
+    bool logprob_on = false;
     int kv_B = 0, kv_Tmax = 0;                // current page geometry
     int cur_B = 0, cur_pos = 0;               // host mirror of the decode state
     int32_t h_pos_word = 0;                   // staging for the device position word

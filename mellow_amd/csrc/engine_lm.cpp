@@ -95,6 +95,7 @@ int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end) {
         }
         a.pq = p + o_pq; a.attF16 = p + o_att; a.att_ml = p + o_aml; a.ssq = p + o_ssq; a.guF = p + o_gu; a.xmidF16 = p + o_xmidF16;
         a.logits = e->dlogits.p; a.cand_val = e->cand.p; a.cand_idx = reinterpret_cast<int32_t*>(e->cand.p + (size_t)Bp * (V / 32));
+        a.cand_sum = nullptr;                               // mellow_generate_scored / the lse tap turn the partial sums on per call
     }
     if (Bp > 1024) return fail("batch too large for the decode state block");
     return 0;
@@ -121,6 +122,7 @@ LoopArgs loop_args(mellow_engine* e) {
     lp.host_progress = e->d_progress; lp.T0 = e->cfg.prefix_len;
     if (e->da.blk_live) { lp.blk_left = e->d_blk_left; lp.blk_live = e->d_blk_live; lp.blk_snap = e->d_blk_live + 32; }
     if (e->da.row_of_slot) { lp.row_of_slot = e->d_row_of_slot; lp.n_compactions = e->d_ncompact; }
+    if (e->logprob_on && e->da.cand_sum) lp.out_logprob = e->out_lp.p;
     return lp;
 }
 
@@ -554,6 +556,37 @@ int mellow_debug_dec_head(mellow_engine_t* e, const float* x, int B, int act_fp8
     return 0;
 }
 
+// The twin of mellow_debug_dec_head with the head kernel in its LSE variant (DecArgs::cand_sum) and the merge of the partials that the
+// arg-max / the sampler of a scored generate call run (common.h: dec_lse_max, dec_lse_sum): per row lse = M + log S, M, and the arg-max.
+int mellow_debug_dec_head_lse(mellow_engine_t* e, const float* x, int B, int act_fp8, float* logits, float* out_lse, float* out_max,
+                              int32_t* out_argmax) {
+    if (!e || !e->finalized) return fail("engine not finalized");
+    if (!x || !out_lse || !out_max || !out_argmax || B <= 0 || B > 1024) return fail("bad argument");
+    if (e->cfg.hidden_size != 576) return fail("the decode kernels are built for hidden size 576");
+    HIPCHK(hipSetDevice(e->device));
+    CHK(ensure_lm(e, B, 1, 2));
+    const int NT = e->cfg.vocab_size / 32;
+    CHK(ensure(e, e->cand_sum, (size_t)e->da.rows * NT));
+    DecArgs a = e->da;
+    a.blk_live = nullptr; a.row_of_slot = nullptr;
+    a.a8 = (act_fp8 && e->w.head8) ? 1 : 0;
+    a.xnF = a.xmidF;                                  // dec_load_rows writes the F32-layout operand there
+    a.xn3 = nullptr;                                  // (fp32 rows: the exact fp32 / e4m3 kernel, as in mellow_debug_dec_head)
+    a.cand_sum = e->cand_sum.p;
+    if (!logits) a.logits = nullptr;
+    launch_dec_load_rows(a, B, x, 576, nullptr, 1, 0, e->stream);
+    const DecW h = e->w.head_w();
+    launch_dec_lm_head(a, h.p, e->w.lm_head.KP / 8, e->cfg.vocab_size, e->stream, h.scale);
+    launch_dec_argmax(a, B, NT, e->d_tokens, e->w.embed, 0, LoopArgs(), e->stream);
+    launch_dec_lse_tap(a, B, NT, out_lse, out_max, e->stream);
+    HIPCHK(hipMemcpyAsync(out_argmax, e->d_tokens, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, e->stream));
+    if (logits) HIPCHK(hipMemcpyAsync(logits, e->dlogits.p, (size_t)B * e->cfg.vocab_size * 4, hipMemcpyDeviceToDevice, e->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->cur_B = 0;                                     // the decode state of an earlier prefill is gone
+    return 0;
+}
+
 // lm.model.embed_tokens(ids) (reference decoder.py:47,64-66; wrapper.py:237): rows of the embedding table
 int mellow_embed_tokens(mellow_engine_t* e, const int32_t* token_ids, int n, float* out) {
     if (!e || !e->finalized) return fail("engine not finalized");
@@ -660,6 +693,7 @@ struct SampleCall {
     float top_p = 0.f, temperature = 1.f;
     uint64_t seed = 0;
     int32_t row_offset = 0;
+    float* out_logprob = nullptr;            // mellow_generate_scored: dev f32 [B][max_len], the log-prob of every recorded token
 };
 static int generate_pass(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples,
                          const int32_t* input_ids, int B, int max_len, int stop_id,
@@ -710,6 +744,26 @@ int mellow_generate_sampled(mellow_engine_t* e, const float* audio1, const float
                         first_token_ms, sc);
 }
 
+// mellow_generate (do_sample = 0) or mellow_generate_sampled (do_sample != 0) plus the log-prob record: the same launches with the
+// head, the arg-max and the sampler in their LSE instantiations (decode.hip, sample.hip); tokens, lengths and steps are bit-identical
+int mellow_generate_scored(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples, const int32_t* input_ids,
+                           int B, int max_len, int do_sample, float top_p, float temperature, uint64_t seed, int32_t row_offset,
+                           int stop_id, int ignore_stop, int32_t* out_tokens, float* out_logprob, int32_t* out_len, int32_t* out_steps,
+                           float* first_token_ms) {
+    if (!e || !e->finalized) return fail("engine not finalized");
+    if (!out_logprob) return fail("null argument");
+    if (e->cfg.vocab_size % 32 != 0) return fail("the log-prob partials tile the vocabulary in groups of 32 columns (vocab %d)", e->cfg.vocab_size);
+    SampleCall sc;
+    if (do_sample) {
+        CHK(check_sampling(e, top_p, temperature));
+        if (row_offset < 0) return fail("row_offset must be >= 0");
+        sc.on = true; sc.top_p = top_p; sc.temperature = temperature; sc.seed = seed; sc.row_offset = row_offset;
+    }
+    sc.out_logprob = out_logprob;
+    return generate_all(e, audio1, audio2, n_samples, input_ids, B, max_len, stop_id, ignore_stop, out_tokens, out_len, out_steps,
+                        first_token_ms, sc);
+}
+
 int mellow_sample_logits(mellow_engine_t* e, const float* logits, int B, const int32_t* row_ids, int step, float top_p,
                          float temperature, uint64_t seed, int32_t* tokens) {
     if (!e || !e->finalized) return fail("engine not finalized");
@@ -745,6 +799,7 @@ static int generate_all(mellow_engine_t* e, const float* audio1, const float* au
         float ftm = 0.f;
         SampleCall scp = sc;
         scp.row_offset = sc.row_offset + r0;           // a row's random stream follows its index in the whole call
+        if (sc.out_logprob) scp.out_logprob = sc.out_logprob + (size_t)r0 * max_len;
         CHK(generate_pass(e, audio1 + (size_t)r0 * n_samples, audio2 + (size_t)r0 * n_samples, n_samples, input_ids + (size_t)r0 * e->cfg.text_len,
                           nb, max_len, stop_id, ignore_stop, out_tokens + (size_t)r0 * max_len, out_len ? out_len + r0 : nullptr, &st, &ftm, scp));
         if (r0 == 0 && first_token_ms) *first_token_ms = ftm;      // the first answers of the call: entry -> first token of the first pass
@@ -765,6 +820,8 @@ static int generate_all(mellow_engine_t* e, const float* audio1, const float* au
         if (!on_device) (void)hipGetLastError();            // a plain host pointer is not an error here
         if (on_device) HIPCHK(hipMemset2D(dst, (size_t)max_len * sizeof(int32_t), 0xff, w, nb));
         else for (int r = 0; r < nb; ++r) memset(dst + (size_t)r * max_len, 0xff, w);
+        // ... and exactly 0.0 in the log-prob record (a device buffer) where the token record now says "never computed"
+        if (sc.out_logprob) HIPCHK(hipMemset2D(sc.out_logprob + (size_t)r0 * max_len + pass_steps[p], (size_t)max_len * sizeof(float), 0, w, nb));
     }
     e->last_steps_enqueued = enq_all;
     e->last_compactions = rep_all;
@@ -801,7 +858,15 @@ static int generate_pass(mellow_engine_t* e, const float* audio1, const float* a
     // row never reached are -1 in the token record.
     e->da.logits = nullptr;             // generation needs the arg-max candidates only: no 6 MB logits store per step
     e->sample_on = sc.on;               // ... unless it samples: the sampler reads the full logits rows
-    struct SampleOff { mellow_engine* e; ~SampleOff() { e->sample_on = false; } } sample_off{e};    // the taps never sample
+    struct SampleOff { mellow_engine* e; ~SampleOff() { e->sample_on = false; e->logprob_on = false; e->da.cand_sum = nullptr; } } sample_off{e};    // the taps never sample nor record
+    e->logprob_on = sc.out_logprob != nullptr;
+    if (e->logprob_on) {
+        // the head's partial sums and the record; columns that are never computed stay exactly 0.0
+        CHK(ensure(e, e->cand_sum, (size_t)Bp * (e->cfg.vocab_size / 32)));
+        CHK(ensure(e, e->out_lp, (size_t)Bp * max_len));
+        HIPCHK(hipMemsetAsync(e->out_lp.p, 0, (size_t)Bp * max_len * sizeof(float), s));
+        e->da.cand_sum = e->cand_sum.p;
+    }
     if (sc.on) {
         e->da.logits = e->dlogits.p;
         stage_sampling(e, sc.top_p, sc.temperature, sc.seed, sc.row_offset, 0);
@@ -847,7 +912,8 @@ static int generate_pass(mellow_engine_t* e, const float* audio1, const float* a
     // one decode step = 30 x (qkv | attention | o_proj | gate/up | down) + final norm + lm_head + arg-max/record/embed,
     // captured once per (B, page geometry, buffers) and replayed; max_len and the stop id are read from d_params
     const bool graph = e->use_graph && !e->prof_on && max_len > 1;
-    const mellow_engine::StepGraphs::Key want{B, e->kv_Tmax, (int)sc.on, e->out_tok.p, e->da.blk_live, e->da.row_of_slot};
+    const mellow_engine::StepGraphs::Key want{B, e->kv_Tmax, (int)sc.on, e->out_tok.p, e->da.blk_live, e->da.row_of_slot,
+                                              (int)e->logprob_on, e->da.cand_sum, e->logprob_on ? e->out_lp.p : nullptr};
     if (graph && (!e->graphs.one || !(e->graphs.key == want))) {
         e->graphs.reset();
         // eight consecutive steps as ONE graph: the step reads its position from the device word, so a replay of the
@@ -898,6 +964,7 @@ static int generate_pass(mellow_engine_t* e, const float* audio1, const float* a
     std::vector<int32_t> toks((size_t)B * max_len);
     HIPCHK(hipMemcpyAsync(out_tokens, e->out_tok.p, toks.size() * sizeof(int32_t), hipMemcpyDefault, s));
     HIPCHK(hipMemcpyAsync(toks.data(), e->out_tok.p, toks.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (e->logprob_on) HIPCHK(hipMemcpyAsync(sc.out_logprob, e->out_lp.p, toks.size() * sizeof(float), hipMemcpyDefault, s));
     HIPCHK(hipStreamSynchronize(s));
     CHK(check_bad_id(e));        // a prompt id outside the vocabulary (flagged by prefix_assemble_kernel): the reference raises IndexError
     for (int i = 0; i < 3; ++i) HIPCHK(hipEventElapsedTime(&e->phase_ms[i], e->ev_phase[i], e->ev_phase[i + 1]));

@@ -209,6 +209,11 @@ struct DecArgs {
     int dbg_seq = -1;              // -DMELLOW_KDEBUG builds: index of this launch in the step (span stamps of tools/kdebug.py), else unused
     float* logits = nullptr;       // [rows][vocab] (may be null)
     float* cand_val = nullptr; int32_t* cand_idx = nullptr;   // [rows][vocab/32]
+    // log-probs of the generated tokens (include/mellow_hip.h, mellow_generate_scored): when set, the lm_head also reduces every
+    // 32-column tile to s = sum exp(logit - cand_val) -> cand_sum[row * (vocab / 32) + tile], and the arg-max / the sampler merge
+    // the (cand_val, cand_sum) partials of a row into its log-sum-exp (common.h, dec_lse_sum).  Null = off: the kernels of the
+    // default step are the instantiations without it.
+    float* cand_sum = nullptr;                                // [rows][vocab/32]
 };
 // The five GEMM launchers take an optional `wscale`: when non-null, the weight pointer addresses the e4m3 copy of the same
 // layout (launch_pack_dec_fp8: one 4-byte word per float4 slot) and wscale holds one factor per packed weight row
@@ -256,11 +261,15 @@ struct LoopArgs {
     int32_t* n_compactions = nullptr;    // repacks done during the call (diagnostic)
     unsigned long long* host_progress = nullptr;   // mapped host memory
     int T0 = 0;                          // prefix length
+    float* out_logprob = nullptr;        // engine-owned [rows][params[0]] f32, written where out_tokens is (null = off; needs DecArgs::cand_sum)
 };
 // per-row arg-max over the lm_head candidates (torch.argmax order: NaN = maximum, lowest index on ties); with
 // write_x it gathers embed[token] as the next step's residual stream
 void launch_dec_argmax(const DecArgs& a, int B, int n_tiles, int32_t* tokens, const float* embed, int write_x,
                        const LoopArgs& loop, hipStream_t s);
+// numeric tap (mellow_debug_dec_head_lse): the same merge of a row's (cand_val, cand_sum) partials, no loop state:
+// out_lse[b] = M + log S, out_max[b] = M
+void launch_dec_lse_tap(const DecArgs& a, int B, int n_tiles, float* out_lse, float* out_max, hipStream_t s);
 // Seeded nucleus sampling (sample.hip; include/mellow_hip.h mellow_generate_sampled states the exact definition).  The
 // parameters live in a device block the host fills per call, so captured graphs serve any seed / top_p / temperature:
 // prm = {lo32(seed), hi32(seed), row offset, bits of top_p, bits of temperature, step (taps only)}.

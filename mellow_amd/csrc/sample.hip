@@ -251,9 +251,14 @@ __device__ __forceinline__ int sample_row(const float* __restrict__ lrow, const 
 
 // the decode step's sampler: replaces dec_argmax_kernel when sampling is on; after the draw the loop bookkeeping below is
 // dec_argmax_kernel's, line for line (decode.hip: dead-slot rule, token record, stop counts, arrival / publish, embedding gather)
+// LSE (LoopArgs::out_logprob): after the draw, the row's log-sum-exp is merged from the head's (cand_val, cand_sum) partials by the
+// function the arg-max kernel uses (common.h: dec_lse_max / dec_lse_sum -- the raw logits, temperature 1, no nucleus), the drawn
+// token's logit is read from the logits row the head stored, and logit - lse is recorded where the token is.
+template <bool LSE>
 __global__ __launch_bounds__(SMP_THREADS) void dec_sample_kernel(const SampleArgs sa, const DecArgs a, int32_t* __restrict__ tokens,
                                                                  const float* __restrict__ embed, int write_x, const LoopArgs lp) {
     __shared__ int tok_s;
+    __shared__ float lse_sh[4];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int row = lp.row_of_slot ? lp.row_of_slot[b] : b;         // the example in this slot
     const bool dead = (lp.blk_snap && lp.blk_snap[b >> 5] == 0) || row < 0;      // workgroup-uniform; written by an EARLIER launch
@@ -261,6 +266,14 @@ __global__ __launch_bounds__(SMP_THREADS) void dec_sample_kernel(const SampleArg
     if (!dead) {
         const int step = lp.out_tokens ? *a.d_pos - lp.T0 + 1 : (int)sa.prm[SMP_STEP];
         idx = sample_row(sa.logits + (int64_t)b * sa.ld, sa.prm, sa.prm[SMP_ROW_OFF] + (uint32_t)row, (uint32_t)step);
+    }
+    float lse = 0.f;
+    if constexpr (LSE) {
+        if (!dead) {            // (workgroup-uniform)
+            const int n = (int)(sa.ld >> 5);
+            const float M = dec_lse_max(a.cand_val + (int64_t)b * n, n, lse_sh);
+            lse = dec_lse_value(M, dec_lse_sum(a.cand_val + (int64_t)b * n, a.cand_sum + (int64_t)b * n, n, M, lse_sh));
+        }
     }
     if (tid == 0) {
         if (!dead) {
@@ -272,6 +285,9 @@ __global__ __launch_bounds__(SMP_THREADS) void dec_sample_kernel(const SampleArg
                 const int max_len = lp.params[0], stop_id = lp.params[1];
                 const int step = *a.d_pos - lp.T0 + 1;
                 if (step >= 0 && step < max_len) lp.out_tokens[(int64_t)row * max_len + step] = idx;
+                if constexpr (LSE) {
+                    if (step >= 0 && step < max_len) lp.out_logprob[(int64_t)row * max_len + step] = sa.logits[(int64_t)b * sa.ld + idx] - lse;
+                }
                 if (idx == stop_id && lp.seen_stop[row] == 0) {
                     lp.seen_stop[row] = 1;
                     atomicAdd(lp.n_seen, 1);
@@ -309,7 +325,10 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_logits_kernel(const Sample
 
 void launch_dec_sample(const SampleArgs& sa, const DecArgs& a, int B, int32_t* tokens, const float* embed, int write_x,
                        const LoopArgs& loop, hipStream_t s) {
-    hipLaunchKernelGGL(dec_sample_kernel, dim3(B), dim3(SMP_THREADS), 0, s, sa, a, tokens, embed, write_x, loop);
+    if (loop.out_logprob != nullptr && a.cand_sum != nullptr)
+        hipLaunchKernelGGL(dec_sample_kernel<true>, dim3(B), dim3(SMP_THREADS), 0, s, sa, a, tokens, embed, write_x, loop);
+    else
+        hipLaunchKernelGGL(dec_sample_kernel<false>, dim3(B), dim3(SMP_THREADS), 0, s, sa, a, tokens, embed, write_x, loop);
 }
 
 void launch_sample_logits(const SampleArgs& sa, int B, int32_t* tokens, hipStream_t s) {

@@ -40,7 +40,7 @@ class EngineError(RuntimeError):
 
 _lib = None
 # symbols added without a new ABI minor (include/mellow_hip.h): detected by lookup, so that a library built before them still loads
-_ADDED_UNDER_MINOR_4 = ("mellow_lm_score", "mellow_score")
+_ADDED_UNDER_MINOR_4 = ("mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse")
 
 
 def load_library(path: Optional[str] = None):
@@ -70,6 +70,8 @@ def load_library(path: Optional[str] = None):
         "mellow_generate": (ci, [vp, vp, vp, i64, vp, ci, ci, cf, cf, ci, ci, vp, P(C.c_int32), P(C.c_int32), P(cf)]),
         "mellow_generate_sampled": (ci, [vp, vp, vp, i64, vp, ci, ci, cf, cf, C.c_uint64, C.c_int32, ci, ci, vp, P(C.c_int32),
                                          P(C.c_int32), P(cf)]),
+        "mellow_generate_scored": (ci, [vp, vp, vp, i64, vp, ci, ci, ci, cf, cf, C.c_uint64, C.c_int32, ci, ci, vp, vp, P(C.c_int32),
+                                        P(C.c_int32), P(cf)]),
         "mellow_sample_logits": (ci, [vp, vp, ci, vp, ci, cf, cf, C.c_uint64, vp]),
         "mellow_logmel": (ci, [vp, vp, ci, i64, ci, vp]),
         "mellow_encode": (ci, [vp, vp, ci, i64, vp]),
@@ -87,6 +89,7 @@ def load_library(path: Optional[str] = None):
         "mellow_debug_gemm_fp8": (ci, [vp, vp, ci, ci, vp, ci, vp, ci, vp]),
         "mellow_debug_gemm_f32": (ci, [vp, ci, vp, ci, ci, vp, ci, vp, ci, vp]),
         "mellow_debug_dec_head": (ci, [vp, vp, ci, ci, vp]),
+        "mellow_debug_dec_head_lse": (ci, [vp, vp, ci, ci, vp, vp, vp, vp]),
         "mellow_prof_enable": (ci, [vp, ci]),
         "mellow_prof_reset": (ci, [vp]),
         "mellow_prof_num_families": (ci, []),
@@ -108,7 +111,7 @@ def load_library(path: Optional[str] = None):
     }
     for name, (res, args) in sig.items():
         if name in _ADDED_UNDER_MINOR_4 and not hasattr(lib, name):
-            continue                     # an older minor-4 library: Engine.score / lm_score raise when called
+            continue                     # an older minor-4 library: the Engine methods that need the symbol raise when called
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -124,7 +127,7 @@ EXPORTED_SYMBOLS = (
     "mellow_engine_destroy", "mellow_engine_fork", "mellow_engine_load_tensor", "mellow_engine_finalize",
     "mellow_engine_num_required", "mellow_engine_required_key", "mellow_generate", "mellow_generate_sampled", "mellow_sample_logits", "mellow_logmel",
     "mellow_encode", "mellow_prefix", "mellow_lm_prefill", "mellow_lm_decode_step", "mellow_argmax", "mellow_embed_tokens", "mellow_lm_forward_logits",
-    "mellow_lm_score", "mellow_score",
+    "mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse",
     "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
     "mellow_prof_num_families", "mellow_prof_family_name", "mellow_prof_get", "mellow_last_phase_ms", "mellow_last_steps_enqueued", "mellow_last_row_repacks", "mellow_stft_is_fft", "mellow_prefill_parts", "mellow_abi_minor",
     "mellow_resample", "mellow_engine_set_precision", "mellow_engine_set_option", "mellow_engine_describe", "mellow_debug_gemm_fp8", "mellow_debug_gemm_f32", "mellow_debug_dec_head", "mellow_set_graph", "mellow_host_window_map", "mellow_host_pack_weight", "mellow_host_rope_tables",
@@ -313,8 +316,11 @@ class Engine:
     # ---- hot path ----------------------------------------------------------------------------------
     def generate(self, audio1, audio2, input_ids, max_len: int, top_p: float = 0.8, temperature: float = 1.0,
                  stop_id: int = 0, ignore_stop: bool = False, do_sample: bool = False, seed: Optional[int] = None,
-                 row_offset: int = 0):
+                 row_offset: int = 0, return_logprobs: bool = False):
         """-> (tokens int32 [B, steps] on host, lengths [B], steps, first_token_ms)
+        return_logprobs=True appends a fifth value, logprobs float32 [B, steps]: the model's log-softmax (temperature 1, no
+        nucleus, also when sampling) at every recorded token, formed inside the decode step (mellow_generate_scored); exactly
+        0.0 where tokens is -1.  Tokens, lengths and steps are the same either way.
         first_token_ms is measured from the C entry (inputs on the device); `last_first_token_host_ms` adds the time this
         call spent bringing host arrays to the device (latency from audio in HOST memory).
         do_sample=False (default): greedy, the reference's result for every top_p / temperature.  do_sample=True: seeded
@@ -331,7 +337,15 @@ class Engine:
         lens = (C.c_int32 * B)()
         steps = C.c_int32(0)
         ftm = C.c_float(0.0)
-        if do_sample:
+        lp = None
+        if return_logprobs:
+            self._need("mellow_generate_scored")
+            lp = torch.empty((B, max_len), dtype=torch.float32, device=self.tdev)
+            self._chk(self.lib.mellow_generate_scored(self.h, _ptr(a1), _ptr(a2), n, _ptr(ids), B, int(max_len), 1 if do_sample else 0,
+                                                      float(top_p), float(temperature), _seed64(seed) if do_sample else 0,
+                                                      int(row_offset) if do_sample else 0, int(stop_id), 1 if ignore_stop else 0,
+                                                      _ptr(out), _ptr(lp), lens, C.byref(steps), C.byref(ftm)))
+        elif do_sample:
             self._chk(self.lib.mellow_generate_sampled(self.h, _ptr(a1), _ptr(a2), n, _ptr(ids), B, int(max_len), float(top_p),
                                                        float(temperature), _seed64(seed), int(row_offset), int(stop_id),
                                                        1 if ignore_stop else 0, _ptr(out), lens, C.byref(steps), C.byref(ftm)))
@@ -341,7 +355,8 @@ class Engine:
                                                lens, C.byref(steps), C.byref(ftm)))
         toks = out.cpu().numpy()[:, : steps.value]
         self.last_first_token_host_ms = t_up + float(ftm.value)
-        return toks, np.asarray(list(lens), dtype=np.int32), int(steps.value), float(ftm.value)
+        res = (toks, np.asarray(list(lens), dtype=np.int32), int(steps.value), float(ftm.value))
+        return res + (lp.cpu().numpy()[:, : steps.value],) if return_logprobs else res
 
     def stft_is_fft(self) -> bool:
         """the STFT runs as an FFT (f32x3 mode, windowed-DFT conv weights) instead of the DFT GEMM"""
@@ -568,6 +583,21 @@ class Engine:
         x = x.to(self.tdev).contiguous().float()
         out = torch.empty((x.shape[0], self.lm.vocab_size), dtype=torch.float32, device=self.tdev)
         self._chk(self.lib.mellow_debug_dec_head(self.h, _ptr(x), x.shape[0], 1 if act_fp8 else 0, _ptr(out)))
+        return out
+
+    def debug_dec_head_lse(self, x: torch.Tensor, act_fp8: bool = False) -> dict:
+        """The same kernel in the variant a generate(return_logprobs=True) step runs, plus the merge of its per-tile partials
+        (mellow_debug_dec_head_lse): x [B, hidden] -> {"logits" [B, vocab] f32, "lse" [B] f32, "max" [B] f32, "argmax" [B] i32}."""
+        self._need("mellow_debug_dec_head_lse")
+        x = x.to(self.tdev).contiguous().float()
+        B = x.shape[0]
+        out = {"logits": torch.empty((B, self.lm.vocab_size), dtype=torch.float32, device=self.tdev),
+               "lse": torch.empty((B,), dtype=torch.float32, device=self.tdev),
+               "max": torch.empty((B,), dtype=torch.float32, device=self.tdev),
+               "argmax": torch.empty((B,), dtype=torch.int32, device=self.tdev)}
+        self._sync_inputs()
+        self._chk(self.lib.mellow_debug_dec_head_lse(self.h, _ptr(x), B, 1 if act_fp8 else 0, _ptr(out["logits"]), _ptr(out["lse"]),
+                                                     _ptr(out["max"]), _ptr(out["argmax"])))
         return out
 
     def enable_taps(self, on: bool = True):

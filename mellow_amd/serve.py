@@ -61,7 +61,8 @@ class EnginePool:
     def generate_many(self, batches: Sequence, **kw):
         """batches: sequence of (audio1, audio2, input_ids); returns the per-batch results of Engine.generate, in order.
         With do_sample=True batch k samples as rows row_offset + (rows of the batches before it) of one concatenated list,
-        so the result does not depend on how many contexts run the batches or which one gets which."""
+        so the result does not depend on how many contexts run the batches or which one gets which.
+        Every keyword of Engine.generate passes through (return_logprobs=True: five values per batch)."""
         kws = [kw] * len(batches)
         if kw.get("do_sample"):
             off, kws = int(kw.get("row_offset", 0)), []

@@ -245,7 +245,7 @@ class MellowWrapper:
 
     def _generate_batch(self, audio1, audio2, input_ids, entry_length=300, top_p=0.8, temperature=1.0,
                         stop_token: str = "<|endoftext|>", n_total: Optional[int] = None, do_sample: bool = False,
-                        seed: Optional[int] = None, row_offset: int = 0):
+                        seed: Optional[int] = None, row_offset: int = 0, return_logprobs: bool = False):
         """Tokens for the rows given (this rank's shard under data parallelism), decoded for ALL `n_total` examples:
         the shards' token ids are all-gathered once (mellow_amd.dist, RCCL over xGMI under backend "nccl")."""
         stop_token_index = self.tokenizer.encode(stop_token)[0]
@@ -254,6 +254,12 @@ class MellowWrapper:
         n_local = int(audio1.shape[0])
         if n_local:
             samp = dict(do_sample=True, seed=seed, row_offset=row_offset) if do_sample else {}
+            if return_logprobs:       # (refused under data-parallel sharding by generate(): the gather below carries tokens only)
+                toks, lens, steps, ftm, logprobs = self.model.generate(audio1, audio2, input_ids, max_len=entry_length, top_p=top_p,
+                                                                       temperature=temperature, stop_id=stop_token_index,
+                                                                       return_logprobs=True, **samp)
+                self.last_first_token_ms = ftm
+                return self._scored_results(toks, logprobs, stop_token_index)
             toks, lens, steps, ftm = self.model.generate(audio1, audio2, input_ids, max_len=entry_length, top_p=top_p,
                                                          temperature=temperature, stop_id=stop_token_index, **samp)
             self.last_first_token_ms = ftm
@@ -268,8 +274,26 @@ class MellowWrapper:
         rows = [r[r >= 0] for r in toks]
         return [self.tokenizer.decode(x).split("<|endoftext|>")[0] for x in rows]
 
+    def _scored_results(self, toks, logprobs, stop_id: int):
+        """One dict per row of a generate(return_logprobs=True) call.  The counted tokens are those before the row's first stop id
+        plus the stop id itself if the row produced it -- score()'s append_stop=True convention, so `logprob` is the number
+        score() gives for `text`; it is their fp32 sum in ascending order."""
+        out = []
+        for r, lp in zip(np.asarray(toks), np.asarray(logprobs, dtype=np.float32)):
+            valid = r >= 0                       # -1 = never computed (wrapper docstring): a prefix of the row is valid
+            n_valid = int(valid.sum())
+            hit = np.nonzero(r[:n_valid] == stop_id)[0]
+            n = int(hit[0]) + 1 if hit.size else n_valid
+            total = np.float32(0.0)
+            for x in lp[:n]:
+                total = np.float32(total + x)
+            out.append({"text": self.tokenizer.decode(r[valid]).split("<|endoftext|>")[0],
+                        "token_ids": [int(t) for t in r[:n]], "token_logprobs": [float(x) for x in lp[:n]],
+                        "logprob": float(total), "tokens": n})
+        return out
+
     def generate(self, examples, max_len, top_p, temperature, stop_token="<|endoftext|>", audio_resample=True, *,
-                 do_sample: bool = False, seed: Optional[int] = None):
+                 do_sample: bool = False, seed: Optional[int] = None, return_logprobs: bool = False):
         r"""Produces text response for the given audio files and text prompts
         examples: (list<list>) each example is [audio path 1, audio path 2, text prompt]
         max_len: (int) maximum length for text generation
@@ -277,6 +301,10 @@ class MellowWrapper:
         do_sample, seed: opt-in seeded nucleus sampling (module docstring); seed=None draws one (kept as `last_seed`)
         stop_token: (str) token used to stop text generation
         audio_resample (bool) True for resampling audio. The model supports only 32 kHz
+        return_logprobs: (bool) instead of a string per example return a dict {"text", "token_ids", "token_logprobs", "logprob",
+                     "tokens"}: the model's log-probability (its own log-softmax: temperature 1, no nucleus, also when sampling)
+                     of every generated token up to and including the stop token, and their sum -- what `score` returns for the
+                     same answer, formed inside the decode step.  Not sharded: NotImplementedError with more than one rank.
 
         With `data_parallel=True` (or MELLOW_DATA_PARALLEL=1) under an initialised torch.distributed group (one process per
         GPU, every rank calling with the same examples) the examples are sharded contiguously over the ranks, each rank ingests
@@ -288,6 +316,8 @@ class MellowWrapper:
             audio_paths2.append(ap2)
             text_prompts.append(tp)
         rank, world = self._dp()
+        if return_logprobs and world > 1:
+            raise NotImplementedError("generate(return_logprobs=True) is not sharded over data-parallel ranks: call it on one rank (or with data_parallel off)")
         n = len(examples)
         if n == 0:          # the reference fails in torch.cat(audio_tensors) (wrapper.py:178) on an empty list
             raise RuntimeError("torch.cat(): expected a non-empty list of Tensors")
@@ -314,7 +344,7 @@ class MellowWrapper:
             ids = torch.zeros((0, spec.TEXT_LEN), dtype=torch.int64)
         return self._generate_batch(audio1, audio2, ids, entry_length=max_len, top_p=top_p,
                                     temperature=temperature, stop_token=stop_token, n_total=n, do_sample=do_sample,
-                                    seed=seed, row_offset=lo)
+                                    seed=seed, row_offset=lo, return_logprobs=return_logprobs)
 
     # ---- scoring ------------------------------------------------------------------------------------------------
     def _candidate_ids(self, candidates, append_stop: bool, stop_token: str):
