@@ -51,7 +51,8 @@ extern "C" {
  *  4: opt-in seeded nucleus sampling: mellow_generate_sampled and mellow_sample_logits.  mellow_generate is unchanged (greedy).
  *     The scoring symbols mellow_score and mellow_lm_score were added later under this same minor (no existing symbol or struct
  *     changed): a binding that must also load an older minor-4 library detects them by symbol lookup (dlsym), not by the number.
- *     mellow_generate_scored and mellow_debug_dec_head_lse (log-probs of the generated tokens) were added the same way. */
+ *     mellow_generate_scored and mellow_debug_dec_head_lse (log-probs of the generated tokens) were added the same way, and so
+ *     was mellow_generate_n (n sampled answers per example from one encode and one prefill). */
 #define MELLOW_ABI_MINOR 4
 
 typedef struct mellow_engine mellow_engine_t;
@@ -191,6 +192,33 @@ int  mellow_generate_scored(mellow_engine_t* e, const float* audio1, const float
                             const int32_t* input_ids, int B, int max_len, int do_sample, float top_p, float temperature,
                             uint64_t seed, int32_t row_offset, int stop_id, int ignore_stop, int32_t* out_tokens,
                             float* out_logprob, int32_t* out_len, int32_t* out_steps, float* first_token_ms);
+/* n sampled answers for each of B examples from ONE encode and ONE prefill per example: n = num_return_sequences >= 1, the call
+ * answers with N = B * n rows, row b * n + j is answer j of example b.  audio1 / audio2 / input_ids describe the B examples;
+ * out_tokens dev i32 [N][max_len], out_logprob dev f32 [N][max_len] (may be NULL: no log-prob record), out_len host i32 [N].
+ *
+ * Definition.  The result IS what mellow_generate_sampled (out_logprob NULL) or mellow_generate_scored (do_sample != 0) returns when
+ * it is given every example n times in a row -- B * n examples, example b at rows b * n .. b * n + n - 1 -- with the same seed and
+ * row_offset: tokens, lengths, steps, the -1 columns and the log-prob record.  So
+ *   - the global row index of the Philox stream of answer j of example b is row_offset + b * n + j (a caller that cuts its examples
+ *     into several calls advances row_offset by n per example);
+ *   - the stop rule, the per-block early exit and row migration act on the N rows exactly as they do there;
+ *   - in MELLOW_PRECISION_F32 the two results are bit-identical: that mode's prefill does not depend on the batch (minor 1), and both
+ *     forms run the last layer of the prefill, the head and every decode step on the same N rows;
+ *   - in the default MELLOW_PRECISION_F32X3 they agree as closely as two batch compositions do (minor 1: the prefill here runs on B
+ *     examples, there on B * n; last bits may differ, and a draw that such a bit decides may differ with them);
+ *   - n == 1 takes the path of those calls and returns their bytes.
+ * What the engine does with n > 1: front-end, encoder, projection and the LM prefill run on the B examples, with the prefill's K/V
+ * written to a prefix buffer of its own; one copy kernel hands every example's prefix K/V to the pages of its n rows; the last prefix
+ * position, the head, the first draw and the captured decode loop then run on N rows.  The kernels of the decode step and of the
+ * prefill are those of the calls above.
+ * Errors: do_sample == 0 (n greedy answers of one example are n copies of one answer: not offered); n < 1; B * n > 1024 (one pass
+ * of rows: the caller splits its examples); n > 1 on an MELLOW_PRECISION_FP8 engine (its bf16 K/V pages have no fan-out); and every
+ * error of mellow_generate_sampled.
+ * Added under minor 4 like the scoring symbols: a binding detects it by symbol lookup. */
+int  mellow_generate_n(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples, const int32_t* input_ids,
+                       int B, int n, int max_len, int do_sample, float top_p, float temperature, uint64_t seed, int32_t row_offset,
+                       int stop_id, int ignore_stop, int32_t* out_tokens, float* out_logprob, int32_t* out_len, int32_t* out_steps,
+                       float* first_token_ms);
 /* The same draw on caller logits, no loop state (numeric tap): logits dev [B][vocab], row_ids dev i32 [B] (global row index
  * of each row; NULL = 0..B-1), step = t above -> tokens dev i32 [B]. */
 int  mellow_sample_logits(mellow_engine_t* e, const float* logits, int B, const int32_t* row_ids, int step, float top_p,

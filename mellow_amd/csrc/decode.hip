@@ -2173,6 +2173,35 @@ void launch_kv_to_bf16(const float* src, void* dst, int64_t n, hipStream_t s) {
     const int blocks = (int)((n8 + 255) / 256 < 8192 ? (n8 + 255) / 256 : 8192);
     hipLaunchKernelGGL(kv_to_bf16_kernel, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const float4*>(src), reinterpret_cast<uint4*>(dst), n8);
 }
+// Prefix K/V of B examples -> the decode pages of their n answers each (mellow_generate_n): for every layer l, kv head h and
+// position t < T the 64 floats of K and of V of example b go to rows b * n .. b * n + n - 1.  src: [layer][B][3][Tp][64] (a
+// buffer of its own: never the pages), dst: [layer][Bp][3][Tmax][64].  Pure bandwidth: a thread owns one float4 of the source
+// (K and V), reads it ONCE and stores it n times -- HBM reads are 1 / n of the writes; for a fixed copy j consecutive threads
+// store consecutive 16-byte words of one page.  Positions >= T of a page are not touched.  64-bit indices throughout: one layer
+// of pages at 1024 rows is past 2^31 bytes.
+__global__ __launch_bounds__(256) void kv_fanout_kernel(const float4* __restrict__ ksrc, const float4* __restrict__ vsrc,
+                                                        float4* __restrict__ kdst, float4* __restrict__ vdst, int64_t total,
+                                                        int B, int n, int Bp, int T16, int64_t Tp16, int64_t Tmax16) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t pg = i / T16, q = i - pg * T16;          // source page (l * B + b) * 3 + h, float4 inside its first T positions
+        const int64_t lb = pg / 3, h = pg - lb * 3, l = lb / B, b = lb - l * B;
+        const float4 k = ksrc[pg * Tp16 + q], v = vsrc[pg * Tp16 + q];
+        int64_t d = ((l * Bp + b * n) * 3 + h) * Tmax16 + q;
+        for (int j = 0; j < n; ++j, d += 3 * Tmax16) {
+            kdst[d] = k;
+            vdst[d] = v;
+        }
+    }
+}
+void launch_kv_fanout(const float* k_prefix, const float* v_prefix, float* k_pages, float* v_pages, int layers, int B, int n, int Bp,
+                      int T, int Tp, int Tmax, hipStream_t s) {
+    if (layers <= 0 || B <= 0 || n <= 0 || T <= 0 || T > Tp || T > Tmax || (int64_t)B * n > Bp) return;      // (the engine never asks for these)
+    const int64_t total = (int64_t)layers * B * 3 * T * 16;
+    const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    hipLaunchKernelGGL(kv_fanout_kernel, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const float4*>(k_prefix),
+                       reinterpret_cast<const float4*>(v_prefix), reinterpret_cast<float4*>(k_pages), reinterpret_cast<float4*>(v_pages),
+                       total, B, n, Bp, T * 16, (int64_t)Tp * 16, (int64_t)Tmax * 16);
+}
 void launch_dec_compact(const DecArgs& a, int B, const LoopArgs& loop, hipStream_t s) {
     hipLaunchKernelGGL(dec_compact_kernel, dim3(1), dim3(1024), 0, s, a, B, loop);
 }

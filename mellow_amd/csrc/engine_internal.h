@@ -273,6 +273,11 @@ struct mellow_engine {
     // the log-prob record [rows][max_len] (LoopArgs::out_logprob); logprob_on: this call records (run_lm_head / loop_args)
     Buf cand_sum, out_lp;
     bool logprob_on = false;
+    // mellow_generate_n (n answers per example from one prefill), created on first use: the prefix K/V of the call's examples
+    // [layer][examples][3][Tp][64] -- the prefill writes them here, kv_fanout_kernel copies them to the pages of every answer row
+    // (source and destination never alias) -- and the source-row table of launch_dec_load_rows with its host staging
+    Buf kprefix, vprefix, nseq_rows;
+    std::vector<int32_t> h_nseq_rows;
     int kv_B = 0, kv_Tmax = 0;                // current page geometry
     int cur_B = 0, cur_pos = 0;               // host mirror of the decode state
     int32_t h_pos_word = 0;                   // staging for the device position word
@@ -347,11 +352,15 @@ static inline size_t kv_layer_floats(const mellow_engine* e) { return (size_t)e-
 struct RecordArgs {
     bool embed_next = false;
 };
-int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end = 0);
+// B rows of pages and decode arena; the prefill workspaces hold prefill_B examples (0 = B: every row is prefilled itself)
+int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end = 0, int prefill_B = 0);
+static inline int prefix_page_len(int T) { return rup(T, 64); }      // positions per page of kprefix / vprefix (rounded as the pages are)
 int clear_page_tails(mellow_engine* e, int T, int t_end);
 LoopArgs loop_args(mellow_engine* e);
 int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec);
-int run_prefill(mellow_engine* e, int B, int T, const RecordArgs* rec, bool all_positions = false);
+// n > 1 (mellow_generate_n; fp32 pages only): the layers run on the B examples and write K/V to kprefix / vprefix; the fan-out and
+// everything from the last prefix row on (last layer, head, first token) run on B * n rows
+int run_prefill(mellow_engine* e, int B, int T, const RecordArgs* rec, bool all_positions = false, int n = 1);
 int enqueue_decode_layer_range(mellow_engine* e, int B, int l_begin, int l_end, bool inc_pos);
 int enqueue_decode_layers(mellow_engine* e, int B, const RecordArgs* rec);
 int ensure_prefill_streams(mellow_engine* e);      // creates + probes the split prefill's side streams; may lower e->prefill_parts to 1

@@ -2,11 +2,11 @@
 // mellow_generate (A16: reference wrapper.py:197-256).
 #include "engine_internal.h"
 
-int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end) {
+int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end, int prefill_B) {
     if (B > 1024) return fail("batch of %d exceeds the 1024 rows one pass takes (mellow_generate chunks larger batches itself; the decode state block is sized for 32 row blocks)", B);
     if (ctx_end <= 0 || ctx_end > Tmax) ctx_end = Tmax;      // last context length the call will reach (<= page capacity)
     if (Tmax > e->cfg.max_positions) return fail("prefix + max_len = %d exceeds max_positions %d", Tmax, e->cfg.max_positions);
-    const size_t Mp = (size_t)B * T;
+    const size_t Mp = (size_t)(prefill_B > 0 ? prefill_B : B) * T;
     CHK(ensure(e, e->lm_x, Mp * 576));
     CHK(ensure(e, e->lm_xn, Mp * 576));
     CHK(ensure(e, e->lm_q, Mp * 576));
@@ -149,10 +149,17 @@ int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec)
     return 0;
 }
 
-int run_prefill(mellow_engine* e, int B, int T, const RecordArgs* rec, bool all_positions) {
+int run_prefill(mellow_engine* e, int B, int T, const RecordArgs* rec, bool all_positions, int n) {
     hipStream_t s = e->stream;
-    const int M = B * T, Tmax = e->kv_Tmax;
     const int NL = e->cfg.num_layers;
+    // fan: the K/V of the B examples go to the prefix buffer (page stride Tp), not to the pages -- a page of example b' would lie
+    // inside the rows another example's copies are written to, and one parallel copy kernel cannot order those writes
+    const bool fan = n > 1;
+    if (fan && (all_positions || e->opt.kv16 || !e->kprefix.p || !e->vprefix.p || !e->nseq_rows.p || B * n > e->kv_B))
+        return fail("internal: the fan-out prefill needs fp32 pages for %d rows and its prefix buffer", B * n);
+    const int Tmax = fan ? prefix_page_len(T) : e->kv_Tmax;                      // page stride the prefill kernels are given
+    const size_t lay = fan ? (size_t)B * 3 * Tmax * 64 : kv_layer_floats(e);    // floats of one layer of what they write
+    float *kbase = fan ? e->kprefix.p : e->kcache.p, *vbase = fan ? e->vprefix.p : e->vcache.p;
     float *x = e->lm_x.p, *xn = e->lm_xn.p;
     // fp8 mode: the same producer -> consumer hand-over with AMX images (MXFP8, common.h) instead of APB ones: `amx`; the code below
     // says `apb` for "GEMM inputs leave their producers in operand format"
@@ -208,9 +215,9 @@ int run_prefill(mellow_engine* e, int B, int T, const RecordArgs* rec, bool all_
             float* hh = e->lm_h.p + r0 * 1536;
             const bool p16 = amx && e->kv16_direct;          // bf16 pages: the same element offsets, two bytes each
             float* kc = p16 ? e->kcache16.p + (kv_layer_floats(e) * l + (size_t)hb0[h] * 3 * Tmax * 64) / 2
-                            : e->kcache.p + kv_layer_floats(e) * l + (size_t)hb0[h] * 3 * Tmax * 64;
+                            : kbase + lay * l + (size_t)hb0[h] * 3 * Tmax * 64;
             float* vc = p16 ? e->vcache16.p + (kv_layer_floats(e) * l + (size_t)hb0[h] * 3 * Tmax * 64) / 2
-                            : e->vcache.p + kv_layer_floats(e) * l + (size_t)hb0[h] * 3 * Tmax * 64;
+                            : vbase + lay * l + (size_t)hb0[h] * 3 * Tmax * 64;
             // pre-split operand regions of this half (6 bytes per element, whole 128-row panels)
             char* xn3 = apb ? reinterpret_cast<char*>(e->lm_xn3.p) + prow[h] * 576 * 6 : nullptr;
             char* o3 = apb ? reinterpret_cast<char*>(e->lm_o3.p) + prow[h] * 576 * 6 : nullptr;
@@ -292,13 +299,20 @@ int run_prefill(mellow_engine* e, int B, int T, const RecordArgs* rec, bool all_
     // x now holds the input of the last layer.  Position word = index of the LAST prefix token: the decode kernels
     // treat it as "the new token" (keys 0..T-2 from the pages, key T-1 recomputed and re-appended), and the first
     // kernel of every later decode step advances it; the arg-max records its token at column (*d_pos - prefix_len + 1) = 0.
-    { ProfScope ps(e, PF_MISC, 0, 0); launch_dec_load_rows(e->da, B, x, 576, nullptr, T, 0, s); }
-    e->cur_B = B;
+    // n answers per example: every row's pages get its example's prefix K/V, and row r starts from its example's last prefix row
+    const int N = B * n;
+    if (fan) {
+        ProfScope ps(e, PF_MISC, 0, (1.0 + n) * 2.0 * NL * B * 3 * T * 64 * 4);
+        launch_kv_fanout(e->kprefix.p, e->vprefix.p, e->kcache.p, e->vcache.p, NL, B, n, e->kv_B, T, Tmax, e->kv_Tmax, s);
+    }
+    { ProfScope ps(e, PF_MISC, 0, 0);
+      launch_dec_load_rows(e->da, N, x, 576, fan ? reinterpret_cast<const int32_t*>(e->nseq_rows.p) : nullptr, T, fan ? B * T : 0, s); }
+    e->cur_B = N;
     e->cur_pos = T;
     e->h_pos_word = T - 1;
     HIPCHK(hipMemcpyAsync(e->d_pos, &e->h_pos_word, sizeof(int32_t), hipMemcpyHostToDevice, s));
-    CHK(enqueue_decode_layer_range(e, B, NL - 1, NL, false));
-    CHK(run_lm_head(e, B, DEC_KC_DOWN, rec));
+    CHK(enqueue_decode_layer_range(e, N, NL - 1, NL, false));
+    CHK(run_lm_head(e, N, DEC_KC_DOWN, rec));
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -695,10 +709,11 @@ struct SampleCall {
     int32_t row_offset = 0;
     float* out_logprob = nullptr;            // mellow_generate_scored: dev f32 [B][max_len], the log-prob of every recorded token
 };
+// one pass: `examples` examples, n answer rows each (n = 1: every row is an example of its own, encoded and prefilled itself)
 static int generate_pass(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples,
-                         const int32_t* input_ids, int B, int max_len, int stop_id,
+                         const int32_t* input_ids, int examples, int max_len, int stop_id,
                          int ignore_stop, int32_t* out_tokens, int32_t* out_len, int32_t* out_steps, float* first_token_ms,
-                         const SampleCall& sc);
+                         const SampleCall& sc, int n = 1);
 static int generate_all(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples,
                         const int32_t* input_ids, int B, int max_len, int stop_id,
                         int ignore_stop, int32_t* out_tokens, int32_t* out_len, int32_t* out_steps, float* first_token_ms,
@@ -762,6 +777,38 @@ int mellow_generate_scored(mellow_engine_t* e, const float* audio1, const float*
     sc.out_logprob = out_logprob;
     return generate_all(e, audio1, audio2, n_samples, input_ids, B, max_len, stop_id, ignore_stop, out_tokens, out_len, out_steps,
                         first_token_ms, sc);
+}
+
+// n sampled answers per example from ONE encode and ONE prefill per example (include/mellow_hip.h states the semantics).  The step
+// graph is shared with a plain call of the same B * n rows on purpose: the key holds the row count, the page geometry and every
+// address a captured launch reads, and from the first decode step on the two calls run the same launches on the same buffers --
+// everything that differs (prefix buffer, fan-out, row table) happens before the loop and is never captured.
+int mellow_generate_n(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples, const int32_t* input_ids,
+                      int B, int n, int max_len, int do_sample, float top_p, float temperature, uint64_t seed, int32_t row_offset,
+                      int stop_id, int ignore_stop, int32_t* out_tokens, float* out_logprob, int32_t* out_len, int32_t* out_steps,
+                      float* first_token_ms) {
+    if (!e || !e->finalized) return fail("engine not finalized");
+    if (n < 1) return fail("n must be >= 1 (got %d)", n);
+    if (!do_sample) return fail("mellow_generate_n needs do_sample != 0: %d greedy answers of one example are %d copies of one answer", n, n);
+    if (!audio1 || !audio2 || !input_ids || !out_tokens) return fail("null argument");
+    if (B <= 0 || max_len <= 0) return fail("B and max_len must be positive");
+    if ((int64_t)B * n > 1024)
+        return fail("mellow_generate_n takes at most 1024 answer rows per call: B * n = %d * %d = %lld (split the examples over several calls, "
+                    "advancing row_offset by n per example)", B, n, (long long)B * n);
+    if (out_logprob && e->cfg.vocab_size % 32 != 0) return fail("the log-prob partials tile the vocabulary in groups of 32 columns (vocab %d)", e->cfg.vocab_size);
+    if (n > 1 && (e->opt.fp8 || e->opt.kv16))
+        return fail("mellow_generate_n with n > 1 is not available in MELLOW_PRECISION_FP8: the bf16 K/V pages of that mode have no fan-out "
+                    "(n = 1 works; or pass every example n times to mellow_generate_sampled)");
+    CHK(check_sampling(e, top_p, temperature));
+    if (row_offset < 0) return fail("row_offset must be >= 0");
+    SampleCall sc;
+    sc.on = true; sc.top_p = top_p; sc.temperature = temperature; sc.seed = seed; sc.row_offset = row_offset;
+    sc.out_logprob = out_logprob;
+    if (n == 1)       // today's path, today's bytes
+        return generate_all(e, audio1, audio2, n_samples, input_ids, B, max_len, stop_id, ignore_stop, out_tokens, out_len, out_steps,
+                            first_token_ms, sc);
+    return generate_pass(e, audio1, audio2, n_samples, input_ids, B, max_len, stop_id, ignore_stop, out_tokens, out_len, out_steps,
+                         first_token_ms, sc, n);
 }
 
 int mellow_sample_logits(mellow_engine_t* e, const float* logits, int B, const int32_t* row_ids, int step, float top_p,
@@ -831,18 +878,35 @@ static int generate_all(mellow_engine_t* e, const float* audio1, const float* au
 }
 
 static int generate_pass(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples,
-                         const int32_t* input_ids, int B, int max_len, int stop_id,
+                         const int32_t* input_ids, int examples, int max_len, int stop_id,
                          int ignore_stop, int32_t* out_tokens, int32_t* out_len, int32_t* out_steps, float* first_token_ms,
-                         const SampleCall& sc) {
+                         const SampleCall& sc, int n) {
     const auto t_entry = std::chrono::steady_clock::now();
+    const int B = examples * n;       // rows of the pass: pages, decode arena, loop state, records and the step graph are sized by it
     HIPCHK(hipSetDevice(e->device));
     hipStream_t s = e->stream;
     const int T = e->cfg.prefix_len;
     // KV page geometry in buckets of 64 positions, so that nearby max_len values share pages, key split and graphs
     int Tmax = rup(T + max_len, 64);
     if (Tmax > e->cfg.max_positions) Tmax = T + max_len;
-    CHK(ensure_lm(e, B, T, Tmax, T + max_len));
+    CHK(ensure_lm(e, B, T, Tmax, T + max_len, examples));
     const int Bp = e->da.rows;
+    if (n > 1) {
+        // the prefix K/V of the examples (run_prefill writes, kv_fanout_kernel reads).  Zeroed when (re)allocated: positions
+        // [T, Tp) of a page are never written and never read (the prefill attention clamps its key loads to T - 1); a page starts
+        // at a multiple of Tp * 64 floats whatever the number of examples, so a larger call finds its tails where they were
+        const size_t fl = (size_t)e->cfg.num_layers * examples * 3 * prefix_page_len(T) * 64;
+        for (mellow_engine::Buf* b : {&e->kprefix, &e->vprefix})
+            if (b->cap < fl) {
+                CHK(ensure(e, *b, fl));
+                HIPCHK(hipMemsetAsync(b->p, 0, fl * sizeof(float), s));
+            }
+        // source row of every answer row for launch_dec_load_rows: the last prefix position of its example
+        CHK(ensure(e, e->nseq_rows, 1024));
+        e->h_nseq_rows.assign(1024, 0);      // (a member: alive until the copy has run)
+        for (int r = 0; r < B; ++r) e->h_nseq_rows[r] = (r / n) * T + T - 1;
+        HIPCHK(hipMemcpyAsync(e->nseq_rows.p, e->h_nseq_rows.data(), 1024 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    }
     CHK(ensure(e, e->out_tok, (size_t)Bp * max_len));
     HIPCHK(hipEventRecord(e->ev_phase[0], s));
     // loop state (the prefill's arg-max already records token 0 and publishes ticket 1)
@@ -902,11 +966,11 @@ static int generate_pass(mellow_engine_t* e, const float* audio1, const float* a
         HIPCHK(hipMemsetAsync(e->out_tok.p, 0xff, (size_t)Bp * max_len * sizeof(int32_t), s));
     }
     CHK(clear_page_tails(e, T, e->kv_Tmax));     // everything a key-group load can touch (whole chunks are loaded, then masked)
-    CHK(encode_pair_to_prefix(e, audio1, audio2, n_samples, input_ids, B, e->lm_x.p));
+    CHK(encode_pair_to_prefix(e, audio1, audio2, n_samples, input_ids, examples, e->lm_x.p));
     HIPCHK(hipEventRecord(e->ev_phase[1], s));
     RecordArgs rec;
     rec.embed_next = true;
-    CHK(run_prefill(e, B, T, &rec));
+    CHK(run_prefill(e, examples, T, &rec, false, n));
     HIPCHK(hipEventRecord(e->ev_phase[2], s));
 
     // one decode step = 30 x (qkv | attention | o_proj | gate/up | down) + final norm + lm_head + arg-max/record/embed,

@@ -223,6 +223,11 @@ void launch_pack_dec_fp8(const float* Wp, int tiles, int slots_per_tile, int row
 void launch_dec_attn(const DecArgs& a, float* k_cache, float* v_cache, bool fused, hipStream_t s);
 // n fp32 values (n % 8 == 0) -> bf16, round to nearest even (the K/V shadow pages of the fp8 mode)
 void launch_kv_to_bf16(const float* src, void* dst, int64_t n, hipStream_t s);
+// mellow_generate_n: the prefix K/V of B examples, positions [0, T) of [layers][B][3][Tp][64], copied to the decode pages
+// [layers][Bp][3][Tmax][64] of rows b * n .. b * n + n - 1 (B * n <= Bp; source and destination are different buffers);
+// positions >= T of the pages are left as they are
+void launch_kv_fanout(const float* k_prefix, const float* v_prefix, float* k_pages, float* v_pages, int layers, int B, int n, int Bp,
+                      int T, int Tp, int Tmax, hipStream_t s);
 // down projection of a layer + q/k/v projection of the next one: Wq2 = P-layout [30][Q2_K8] of [W'_{l+1} | W'_{l+1} Wd_l],
 // Wd = this layer's down weight in P-layout (K8p = 192)
 void launch_dec_qkv2(const DecArgs& a, const float* Wq2, const float* Wd, hipStream_t s);

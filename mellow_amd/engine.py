@@ -40,7 +40,7 @@ class EngineError(RuntimeError):
 
 _lib = None
 # symbols added without a new ABI minor (include/mellow_hip.h): detected by lookup, so that a library built before them still loads
-_ADDED_UNDER_MINOR_4 = ("mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse")
+_ADDED_UNDER_MINOR_4 = ("mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse", "mellow_generate_n")
 
 
 def load_library(path: Optional[str] = None):
@@ -72,6 +72,8 @@ def load_library(path: Optional[str] = None):
                                          P(C.c_int32), P(cf)]),
         "mellow_generate_scored": (ci, [vp, vp, vp, i64, vp, ci, ci, ci, cf, cf, C.c_uint64, C.c_int32, ci, ci, vp, vp, P(C.c_int32),
                                         P(C.c_int32), P(cf)]),
+        "mellow_generate_n": (ci, [vp, vp, vp, i64, vp, ci, ci, ci, ci, cf, cf, C.c_uint64, C.c_int32, ci, ci, vp, vp, P(C.c_int32),
+                                   P(C.c_int32), P(cf)]),
         "mellow_sample_logits": (ci, [vp, vp, ci, vp, ci, cf, cf, C.c_uint64, vp]),
         "mellow_logmel": (ci, [vp, vp, ci, i64, ci, vp]),
         "mellow_encode": (ci, [vp, vp, ci, i64, vp]),
@@ -127,7 +129,7 @@ EXPORTED_SYMBOLS = (
     "mellow_engine_destroy", "mellow_engine_fork", "mellow_engine_load_tensor", "mellow_engine_finalize",
     "mellow_engine_num_required", "mellow_engine_required_key", "mellow_generate", "mellow_generate_sampled", "mellow_sample_logits", "mellow_logmel",
     "mellow_encode", "mellow_prefix", "mellow_lm_prefill", "mellow_lm_decode_step", "mellow_argmax", "mellow_embed_tokens", "mellow_lm_forward_logits",
-    "mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse",
+    "mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse", "mellow_generate_n",
     "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
     "mellow_prof_num_families", "mellow_prof_family_name", "mellow_prof_get", "mellow_last_phase_ms", "mellow_last_steps_enqueued", "mellow_last_row_repacks", "mellow_stft_is_fft", "mellow_prefill_parts", "mellow_abi_minor",
     "mellow_resample", "mellow_engine_set_precision", "mellow_engine_set_option", "mellow_engine_describe", "mellow_debug_gemm_fp8", "mellow_debug_gemm_f32", "mellow_debug_dec_head", "mellow_set_graph", "mellow_host_window_map", "mellow_host_pack_weight", "mellow_host_rope_tables",
@@ -148,6 +150,22 @@ def _seed64(seed) -> int:
     if seed is None:
         raise ValueError("do_sample needs an integer seed")
     return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+NSEQ_PASS_ROWS = 1024      # answer rows one mellow_generate_n call takes (B * n)
+
+
+def plan_nseq_passes(B: int, n: int, row_offset: int = 0):
+    """The consecutive mellow_generate_n calls that answer B examples with n rows each: [(lo, hi, row_offset)] -- examples
+    [lo, hi) of at most 1024 // n per call, with the random-stream offset of the call's first row (the caller's row_offset plus
+    n per example before it), so that the rows are those of one call on every example given n times in a row."""
+    B, n, row_offset = int(B), int(n), int(row_offset)
+    if n < 1:
+        raise ValueError(f"num_return_sequences must be >= 1 (got {n})")
+    if n > NSEQ_PASS_ROWS:
+        raise ValueError(f"num_return_sequences = {n} exceeds the {NSEQ_PASS_ROWS} answer rows one pass of the engine takes")
+    per = NSEQ_PASS_ROWS // n
+    return [(lo, min(B, lo + per), row_offset + lo * n) for lo in range(0, B, per)]
 
 
 def _ptr(t: torch.Tensor) -> C.c_void_p:
@@ -316,8 +334,12 @@ class Engine:
     # ---- hot path ----------------------------------------------------------------------------------
     def generate(self, audio1, audio2, input_ids, max_len: int, top_p: float = 0.8, temperature: float = 1.0,
                  stop_id: int = 0, ignore_stop: bool = False, do_sample: bool = False, seed: Optional[int] = None,
-                 row_offset: int = 0, return_logprobs: bool = False):
+                 row_offset: int = 0, return_logprobs: bool = False, num_return_sequences: int = 1):
         """-> (tokens int32 [B, steps] on host, lengths [B], steps, first_token_ms)
+        num_return_sequences = n > 1 (needs do_sample=True): n sampled answers per example from one encode and one prefill per
+        example (mellow_generate_n).  Every array has B * n rows, row b * n + j = answer j of example b, and holds what this call
+        returns for every example given n times in a row with the same seed and row_offset (bit-equal in "f32").  More than
+        1024 rows run as consecutive calls of 1024 // n examples; n > 1024 is a ValueError.
         return_logprobs=True appends a fifth value, logprobs float32 [B, steps]: the model's log-softmax (temperature 1, no
         nucleus, also when sampling) at every recorded token, formed inside the decode step (mellow_generate_scored); exactly
         0.0 where tokens is -1.  Tokens, lengths and steps are the same either way.
@@ -328,6 +350,14 @@ class Engine:
         row_offset + b, so a shard or batch given its first row's offset reproduces the rows of one big call."""
         import time
         t_in = time.perf_counter()
+        nseq = int(num_return_sequences)
+        if nseq != 1:
+            if nseq < 1:
+                raise ValueError(f"num_return_sequences must be >= 1 (got {nseq})")
+            if not do_sample:
+                raise ValueError("num_return_sequences > 1 needs do_sample=True: greedy answers of one example are all the same")
+            return self._generate_nseq(audio1, audio2, input_ids, int(max_len), nseq, float(top_p), float(temperature), int(stop_id),
+                                       bool(ignore_stop), _seed64(seed), int(row_offset), bool(return_logprobs), t_in)
         a1, a2, ids = self._f32(audio1), self._f32(audio2), self._prompt_ids(input_ids)
         B, n = a1.shape
         assert a2.shape == a1.shape and ids.shape == (B, spec.TEXT_LEN), (a1.shape, a2.shape, ids.shape)
@@ -357,6 +387,45 @@ class Engine:
         self.last_first_token_host_ms = t_up + float(ftm.value)
         res = (toks, np.asarray(list(lens), dtype=np.int32), int(steps.value), float(ftm.value))
         return res + (lp.cpu().numpy()[:, : steps.value],) if return_logprobs else res
+
+    def _generate_nseq(self, audio1, audio2, input_ids, max_len, nseq, top_p, temperature, stop_id, ignore_stop, seed, row_offset,
+                       return_logprobs, t_in):
+        """generate(num_return_sequences=nseq > 1): one mellow_generate_n call per pass of plan_nseq_passes; a pass that stopped
+        before the longest one is padded like the passes of a batch of more than 1024 rows (-1 tokens, 0.0 log-probs)."""
+        import time
+        self._need("mellow_generate_n")
+        a1, a2, ids = self._f32(audio1), self._f32(audio2), self._prompt_ids(input_ids)
+        B, ns = a1.shape
+        assert a2.shape == a1.shape and ids.shape == (B, spec.TEXT_LEN), (a1.shape, a2.shape, ids.shape)
+        passes = plan_nseq_passes(B, nseq, row_offset)
+        N = B * nseq
+        out = torch.empty((N, max_len), dtype=torch.int32, device=self.tdev)
+        lp = torch.empty((N, max_len), dtype=torch.float32, device=self.tdev) if return_logprobs else None
+        self._sync_inputs()
+        t_up = (time.perf_counter() - t_in) * 1e3
+        lens = np.zeros((N,), dtype=np.int32)
+        pass_steps, ftm0 = [], 0.0
+        for k, (lo, hi, off) in enumerate(passes):
+            r0, nr = lo * nseq, (hi - lo) * nseq
+            ln = (C.c_int32 * nr)()
+            steps, ftm = C.c_int32(0), C.c_float(0.0)
+            self._chk(self.lib.mellow_generate_n(self.h, _ptr(a1[lo:hi]), _ptr(a2[lo:hi]), ns, _ptr(ids[lo:hi]), hi - lo, nseq, max_len, 1,
+                                                 top_p, temperature, seed, off, stop_id, 1 if ignore_stop else 0, _ptr(out[r0:r0 + nr]),
+                                                 None if lp is None else _ptr(lp[r0:r0 + nr]), ln, C.byref(steps), C.byref(ftm)))
+            lens[r0:r0 + nr] = np.asarray(list(ln), dtype=np.int32)
+            pass_steps.append(int(steps.value))
+            if k == 0:
+                ftm0 = float(ftm.value)
+        steps_all = max(pass_steps)
+        toks = out.cpu().numpy()[:, :steps_all].copy()
+        lps = lp.cpu().numpy()[:, :steps_all].copy() if return_logprobs else None
+        for (lo, hi, _), st in zip(passes, pass_steps):      # columns a pass never reached: never computed
+            toks[lo * nseq:hi * nseq, st:] = -1
+            if lps is not None:
+                lps[lo * nseq:hi * nseq, st:] = 0.0
+        self.last_first_token_host_ms = t_up + ftm0
+        res = (toks, lens, steps_all, ftm0)
+        return res + (lps,) if return_logprobs else res
 
     def stft_is_fft(self) -> bool:
         """the STFT runs as an FFT (f32x3 mode, windowed-DFT conv weights) instead of the DFT GEMM"""

@@ -61,13 +61,14 @@ class EnginePool:
     def generate_many(self, batches: Sequence, **kw):
         """batches: sequence of (audio1, audio2, input_ids); returns the per-batch results of Engine.generate, in order.
         With do_sample=True batch k samples as rows row_offset + (rows of the batches before it) of one concatenated list,
-        so the result does not depend on how many contexts run the batches or which one gets which.
+        so the result does not depend on how many contexts run the batches or which one gets which (num_return_sequences=n: every
+        example counts n rows).
         Every keyword of Engine.generate passes through (return_logprobs=True: five values per batch)."""
         kws = [kw] * len(batches)
         if kw.get("do_sample"):
             off, kws = int(kw.get("row_offset", 0)), []
             for b in batches:
                 kws.append(dict(kw, row_offset=off))
-                off += int(len(b[0]))
+                off += int(len(b[0])) * int(kw.get("num_return_sequences", 1))      # n answer rows per example
         futs = [self._pool.submit(self._run, i % len(self.engines), b, kws[i]) for i, b in enumerate(batches)]
         return [f.result() for f in futs]

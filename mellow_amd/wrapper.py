@@ -21,6 +21,11 @@ inside the captured decode step -- z = logits / temperature, the nucleus of the 
 softmax mass strictly before it in (z desc, index asc) order is <= top_p), then Gumbel-max with Philox4x32-10 noise keyed by
 (seed, row, step); include/mellow_hip.h mellow_generate_sampled gives the exact definition.  seed=None draws a 63-bit seed from
 `random` (kept as `last_seed`); under data parallelism the seed must be given and equal on every rank.
+Extension (keyword-only): `generate(..., do_sample=True, num_return_sequences=n)` returns n sampled answers per example -- a list
+of n strings (with return_logprobs=True: of n dicts, so `max(out[i], key=lambda a: a["logprob"])` re-ranks) -- for self-consistency
+voting or re-ranking.  Log-mel, encoder, projection and the LM prefill run ONCE per example; the prefix K/V is copied to the n answer
+rows, which then decode like n rows of a batch (include/mellow_hip.h mellow_generate_n).  Answer j of example i draws from the random
+stream of global row i * n + j: the answers are those of the same call on a list that holds every example n times in a row.
 Extension: `score(examples, candidates)` returns the teacher-forced log-probability of given answer strings and
 `choose(examples, candidates)` the index of the likeliest one (multiple-choice ranking, re-ranking of sampled answers); the LM
 head of that path reduces its logits to log-softmax statistics on the fly (include/mellow_hip.h mellow_score).
@@ -245,21 +250,25 @@ class MellowWrapper:
 
     def _generate_batch(self, audio1, audio2, input_ids, entry_length=300, top_p=0.8, temperature=1.0,
                         stop_token: str = "<|endoftext|>", n_total: Optional[int] = None, do_sample: bool = False,
-                        seed: Optional[int] = None, row_offset: int = 0, return_logprobs: bool = False):
+                        seed: Optional[int] = None, row_offset: int = 0, return_logprobs: bool = False, nseq: int = 1):
         """Tokens for the rows given (this rank's shard under data parallelism), decoded for ALL `n_total` examples:
-        the shards' token ids are all-gathered once (mellow_amd.dist, RCCL over xGMI under backend "nccl")."""
+        the shards' token ids are all-gathered once (mellow_amd.dist, RCCL over xGMI under backend "nccl").
+        nseq > 1: nseq answer rows per example (row_offset counts rows); the result is nested, one list of nseq per example."""
         stop_token_index = self.tokenizer.encode(stop_token)[0]
         entry_length = self._clamp_max_len(int(entry_length))
         rank, world = self._dp()
         n_local = int(audio1.shape[0])
         if n_local:
             samp = dict(do_sample=True, seed=seed, row_offset=row_offset) if do_sample else {}
+            if nseq > 1:
+                samp["num_return_sequences"] = nseq
             if return_logprobs:       # (refused under data-parallel sharding by generate(): the gather below carries tokens only)
                 toks, lens, steps, ftm, logprobs = self.model.generate(audio1, audio2, input_ids, max_len=entry_length, top_p=top_p,
                                                                        temperature=temperature, stop_id=stop_token_index,
                                                                        return_logprobs=True, **samp)
                 self.last_first_token_ms = ftm
-                return self._scored_results(toks, logprobs, stop_token_index)
+                res = self._scored_results(toks, logprobs, stop_token_index)
+                return res if nseq == 1 else [res[i:i + nseq] for i in range(0, len(res), nseq)]
             toks, lens, steps, ftm = self.model.generate(audio1, audio2, input_ids, max_len=entry_length, top_p=top_p,
                                                          temperature=temperature, stop_id=stop_token_index, **samp)
             self.last_first_token_ms = ftm
@@ -269,10 +278,15 @@ class MellowWrapper:
             import torch.distributed as dist
             from . import dist as mdist
             dev = self.model.tdev if dist.get_backend() == "nccl" else torch.device("cpu")
-            toks, lens = mdist.gather_tokens(toks, lens, int(n_total), entry_length, device=dev)
+            if nseq > 1:      # shards are whole examples: every rank's block holds nseq rows per example of a full shard
+                toks, lens = mdist.gather_tokens(toks, lens, int(n_total) * nseq, entry_length, device=dev,
+                                                 per_rank=nseq * ((int(n_total) + world - 1) // world))
+            else:
+                toks, lens = mdist.gather_tokens(toks, lens, int(n_total), entry_length, device=dev)
         # -1 = never computed: padding of shards that stopped earlier, or steps after a whole 32-row block had stopped
         rows = [r[r >= 0] for r in toks]
-        return [self.tokenizer.decode(x).split("<|endoftext|>")[0] for x in rows]
+        texts = [self.tokenizer.decode(x).split("<|endoftext|>")[0] for x in rows]
+        return texts if nseq == 1 else [texts[i:i + nseq] for i in range(0, len(texts), nseq)]
 
     def _scored_results(self, toks, logprobs, stop_id: int):
         """One dict per row of a generate(return_logprobs=True) call.  The counted tokens are those before the row's first stop id
@@ -293,7 +307,8 @@ class MellowWrapper:
         return out
 
     def generate(self, examples, max_len, top_p, temperature, stop_token="<|endoftext|>", audio_resample=True, *,
-                 do_sample: bool = False, seed: Optional[int] = None, return_logprobs: bool = False):
+                 do_sample: bool = False, seed: Optional[int] = None, return_logprobs: bool = False,
+                 num_return_sequences: int = 1):
         r"""Produces text response for the given audio files and text prompts
         examples: (list<list>) each example is [audio path 1, audio path 2, text prompt]
         max_len: (int) maximum length for text generation
@@ -305,6 +320,9 @@ class MellowWrapper:
                      "tokens"}: the model's log-probability (its own log-softmax: temperature 1, no nucleus, also when sampling)
                      of every generated token up to and including the stop token, and their sum -- what `score` returns for the
                      same answer, formed inside the decode step.  Not sharded: NotImplementedError with more than one rank.
+        num_return_sequences: (int) n > 1 (needs do_sample=True, else ValueError): n sampled answers per example from one encoder
+                     pass and one prefill per example; the result holds, per example, a list of n strings (or of n dicts with
+                     return_logprobs=True).  1 (default): one answer per example, exactly as without the keyword.
 
         With `data_parallel=True` (or MELLOW_DATA_PARALLEL=1) under an initialised torch.distributed group (one process per
         GPU, every rank calling with the same examples) the examples are sharded contiguously over the ranks, each rank ingests
@@ -315,6 +333,13 @@ class MellowWrapper:
             audio_paths1.append(ap1)
             audio_paths2.append(ap2)
             text_prompts.append(tp)
+        nseq = int(num_return_sequences)
+        if nseq < 1:
+            raise ValueError(f"num_return_sequences must be >= 1 (got {nseq})")
+        if nseq > 1 and not do_sample:
+            raise ValueError("num_return_sequences > 1 needs do_sample=True: greedy answers of one example are all the same")
+        if nseq > 1024:
+            raise ValueError(f"num_return_sequences = {nseq} exceeds the 1024 answer rows one pass of the engine takes")
         rank, world = self._dp()
         if return_logprobs and world > 1:
             raise NotImplementedError("generate(return_logprobs=True) is not sharded over data-parallel ranks: call it on one rank (or with data_parallel off)")
@@ -330,6 +355,8 @@ class MellowWrapper:
             seed = int(seed)
             self.last_seed = seed
             extra = repr(("sample", seed, float(top_p), float(temperature))).encode()
+            if nseq > 1:
+                extra += repr(("nseq", nseq)).encode()
         lo, hi = 0, n
         if world > 1:
             from .dist import shard_range
@@ -344,7 +371,7 @@ class MellowWrapper:
             ids = torch.zeros((0, spec.TEXT_LEN), dtype=torch.int64)
         return self._generate_batch(audio1, audio2, ids, entry_length=max_len, top_p=top_p,
                                     temperature=temperature, stop_token=stop_token, n_total=n, do_sample=do_sample,
-                                    seed=seed, row_offset=lo, return_logprobs=return_logprobs)
+                                    seed=seed, row_offset=lo * nseq, return_logprobs=return_logprobs, nseq=nseq)
 
     # ---- scoring ------------------------------------------------------------------------------------------------
     def _candidate_ids(self, candidates, append_stop: bool, stop_token: str):
