@@ -1,0 +1,391 @@
+// The generation loop on top of the LM (A16: reference wrapper.py:197-256): one request record and its checks, the split into passes
+// of <= 1024 rows, the pass body (loop state, step graphs, ticket waiting, length bookkeeping) and the mellow_generate* entry points.
+#include "engine_internal.h"
+
+// Every argument of a generation call, named once.  The four entry points fill one and call generate().
+struct GenRequest {
+    const float *audio1, *audio2;                // inputs: dev f32 [examples][n_samples] each
+    int64_t n_samples;
+    const int32_t* input_ids;                    // dev [examples][text_len]
+    int examples, n, max_len, stop_id, ignore_stop;      // n answer rows per example (n = 1: every row is an example of its own)
+    bool on;                                     // sampling: false = the greedy arg-max, and the four fields below are not read
+    float top_p, temperature;
+    uint64_t seed;
+    int32_t row_offset;
+    int32_t* out_tokens;                         // outputs: [rows][max_len], host or device
+    float* out_logprob;                          // dev f32 [rows][max_len], the log-prob of every recorded token; null: not recorded
+    int32_t *out_len, *out_steps;
+    float* first_token_ms;
+    int rows() const { return examples * n; }
+    // rows [r0, r0 + nb) of an n = 1 request as a request of their own; a row's random stream follows its index in the whole call
+    GenRequest pass(int r0, int nb, int text_len, int32_t* steps, float* ftm) const {
+        GenRequest p = *this;
+        p.audio1 += (size_t)r0 * n_samples; p.audio2 += (size_t)r0 * n_samples; p.input_ids += (size_t)r0 * text_len;
+        p.examples = nb; p.row_offset += r0;
+        p.out_tokens += (size_t)r0 * max_len;
+        if (out_logprob) p.out_logprob += (size_t)r0 * max_len;
+        if (out_len) p.out_len += r0;
+        p.out_steps = steps; p.first_token_ms = ftm;
+        return p;
+    }
+};
+enum { DOOR_SCORED = 1, DOOR_N = 2 };            // what a rule of one entry point needs to know: mellow_generate_scored, mellow_generate_n
+constexpr int kPassRows = 1024;                  // rows of one pass: 32 row blocks of loop state
+
+static int check_sampling(mellow_engine_t* e, float top_p, float temperature) {
+    if (e->cfg.vocab_size != SAMPLE_MAX_V) return fail("the sampler is built for a vocabulary of %d (engine: %d)", SAMPLE_MAX_V, e->cfg.vocab_size);
+    if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail("temperature must be finite and > 0 (got %g); greedy is mellow_generate", (double)temperature);
+    if (top_p != top_p) return fail("top_p is NaN");
+    return 0;
+}
+
+static void stage_sampling(mellow_engine_t* e, float top_p, float temperature, uint64_t seed, int32_t row_offset, int step) {
+    uint32_t* w = e->h_sparams;
+    w[SMP_SEED_LO] = (uint32_t)seed; w[SMP_SEED_HI] = (uint32_t)(seed >> 32); w[SMP_ROW_OFF] = (uint32_t)row_offset;
+    memcpy(&w[SMP_TOP_P], &top_p, 4); memcpy(&w[SMP_TEMP], &temperature, 4); w[SMP_STEP] = (uint32_t)step;
+}
+
+// Every argument rule of the four entry points, each once.
+static int check_request(mellow_engine_t* e, const GenRequest& r, int door) {
+    if (!e || !e->finalized) return fail("engine not finalized");
+    if (r.n < 1) return fail("n must be >= 1 (got %d)", r.n);
+    if ((door & DOOR_N) && !r.on) return fail("mellow_generate_n needs do_sample != 0: %d greedy answers of one example are %d copies of one answer", r.n, r.n);
+    if (!r.audio1 || !r.audio2 || !r.input_ids || !r.out_tokens || ((door & DOOR_SCORED) && !r.out_logprob)) return fail("null argument");
+    if (r.examples <= 0 || r.max_len <= 0) return fail("B and max_len must be positive");
+    if ((door & DOOR_N) && (int64_t)r.examples * r.n > kPassRows)
+        return fail("mellow_generate_n takes at most 1024 answer rows per call: B * n = %d * %d = %lld (split the examples over several calls, "
+                    "advancing row_offset by n per example)", r.examples, r.n, (long long)r.examples * r.n);
+    if (r.out_logprob && e->cfg.vocab_size % 32 != 0) return fail("the log-prob partials tile the vocabulary in groups of 32 columns (vocab %d)", e->cfg.vocab_size);
+    if (r.n > 1 && (e->opt.fp8 || e->opt.kv16))
+        return fail("mellow_generate_n with n > 1 is not available in MELLOW_PRECISION_FP8: the bf16 K/V pages of that mode have no fan-out "
+                    "(n = 1 works; or pass every example n times to mellow_generate_sampled)");
+    if (r.on) {
+        CHK(check_sampling(e, r.top_p, r.temperature));
+        if (r.row_offset < 0) return fail("row_offset must be >= 0");
+    }
+    return 0;
+}
+
+// `n` consecutive decode steps captured from the stream into one exec.  Once the capture has begun it is ALWAYS ended and the
+// hipGraph_t ALWAYS destroyed, whatever failed in between; the first error is the one reported.
+static int capture_steps(mellow_engine* e, int B, const RecordArgs* rec, int n, hipGraphExec_t* exec) {
+    hipGraph_t gr = nullptr;
+    HIPCHK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
+    int rc = 0;
+    for (int k = 0; k < n && !rc; ++k) rc = enqueue_decode_layers(e, B, rec);
+    hipError_t err = hipStreamEndCapture(e->stream, &gr);
+    if (!rc && err != hipSuccess) rc = fail("hipStreamEndCapture failed: %s", hipGetErrorString(err));
+    if (!rc && (err = hipGraphInstantiate(exec, gr, nullptr, nullptr, 0)) != hipSuccess) { *exec = nullptr; rc = fail("instantiating the captured decode step failed: %s", hipGetErrorString(err)); }
+    if (gr) (void)hipGraphDestroy(gr);
+    return rc;
+}
+
+// Wait (without touching the stream) until the arg-max kernel has published ticket >= want; *nseen = rows stopped so far.
+static int wait_ticket(mellow_engine* e, unsigned want, unsigned* nseen) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned spins = 1;; ++spins) {
+        const unsigned long long v = __atomic_load_n(e->h_progress, __ATOMIC_ACQUIRE);
+        if ((unsigned)(v >> 32) >= want) {
+            if (nseen) *nseen = (unsigned)(v & 0xffffffffu);
+            return 0;
+        }
+        if ((spins & 0x3ff) == 0) {
+            const hipError_t q = hipStreamQuery(e->stream);
+            if (q == hipSuccess) {      // nothing left in flight: the ticket must be there now
+                const unsigned long long v2 = __atomic_load_n(e->h_progress, __ATOMIC_ACQUIRE);
+                if ((unsigned)(v2 >> 32) >= want) continue;
+                return fail("decode progress word stalled at ticket %u (wanted %u) with an idle stream", (unsigned)(v2 >> 32), want);
+            }
+            if (q != hipErrorNotReady) return fail("stream error while waiting for a decode step: %s", hipGetErrorString(q));
+            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(60))
+                return fail("timed out waiting for decode ticket %u", want);
+        }
+        // spin politely: a pause per poll, and after ~50 us of spinning yield the core between polls (EnginePool runs one
+        // such loop per context thread)
+#if defined(__x86_64__) || defined(__i386__)
+        __builtin_ia32_pause();
+#elif defined(__aarch64__)
+        __asm__ __volatile__("yield");
+#endif
+        if (spins > 4096) std::this_thread::yield();
+    }
+}
+
+// one pass: r.examples examples, r.n answer rows each (n = 1: every row is encoded and prefilled itself)
+static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
+    const auto t_entry = std::chrono::steady_clock::now();
+    const int examples = r.examples, n = r.n, max_len = r.max_len, stop_id = r.stop_id;
+    const int B = r.rows();           // rows of the pass: pages, decode arena, loop state, records and the step graph are sized by it
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    const int T = e->cfg.prefix_len;
+    // KV page geometry in buckets of 64 positions, so that nearby max_len values share pages, key split and graphs
+    int Tmax = rup(T + max_len, 64);
+    if (Tmax > e->cfg.max_positions) Tmax = T + max_len;
+    CHK(ensure_lm(e, B, T, Tmax, T + max_len, examples));
+    const int Bp = e->da.rows;
+    if (n > 1) {
+        // the prefix K/V of the examples (run_prefill writes, kv_fanout_kernel reads).  Zeroed when (re)allocated: positions
+        // [T, Tp) of a page are never written and never read (the prefill attention clamps its key loads to T - 1); a page starts
+        // at a multiple of Tp * 64 floats whatever the number of examples, so a larger call finds its tails where they were
+        const size_t fl = (size_t)e->cfg.num_layers * examples * 3 * prefix_page_len(T) * 64;
+        for (mellow_engine::Buf* b : {&e->kprefix, &e->vprefix})
+            if (b->cap < fl) {
+                CHK(ensure(e, *b, fl));
+                HIPCHK(hipMemsetAsync(b->p, 0, fl * sizeof(float), s));
+            }
+        // source row of every answer row for launch_dec_load_rows: the last prefix position of its example
+        CHK(ensure(e, e->nseq_rows, 1024));
+        e->h_nseq_rows.assign(1024, 0);      // (a member: alive until the copy has run)
+        for (int row = 0; row < B; ++row) e->h_nseq_rows[row] = (row / n) * T + T - 1;
+        HIPCHK(hipMemcpyAsync(e->nseq_rows.p, e->h_nseq_rows.data(), 1024 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    }
+    CHK(ensure(e, e->out_tok, (size_t)Bp * max_len));
+    HIPCHK(hipEventRecord(e->ev_phase[0], s));
+    // loop state (the prefill's arg-max already records token 0 and publishes ticket 1)
+    __atomic_store_n(e->h_progress, 0ull, __ATOMIC_RELEASE);
+    clear_bad_id(e);
+    HIPCHK(hipMemsetAsync(e->d_nseen, 0, 3 * sizeof(int32_t), s));       // n_seen, arrive, ticket
+    HIPCHK(hipMemsetAsync(e->d_seen, 0, 1024 * sizeof(int32_t), s));
+    e->h_params[0] = max_len;
+    e->h_params[1] = stop_id;
+    HIPCHK(hipMemcpyAsync(e->d_params, e->h_params, 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+#ifdef MELLOW_DEVPROBE
+    static const bool dev_dead = getenv("MELLOW_DEV_DEAD_BLOCKS") != nullptr;    // developer probe: launch-chain floor of a step
+#else
+    constexpr bool dev_dead = false;
+#endif
+    // Per-row-block early exit (reference stop rule, more than one 32-row block): once every row of a block has produced the
+    // stop id, the block's workgroups return at once in every later kernel (its rows' texts are already cut there).  Columns a
+    // row never reached are -1 in the token record.
+    StepMode m;
+    m.logits = m.sample = r.on;         // the sampler reads the full logits rows
+    m.logprob = r.out_logprob != nullptr;
+    m.early_exit = dev_dead || (!r.ignore_stop && e->da.RB > 1);
+    m.migrate = m.early_exit && !dev_dead && e->opt.row_migration;   // option "row_migration" = 0: block exit without repacking (developer A/B)
+    if (m.logprob) {
+        // the head's partial sums and the record; columns that are never computed stay exactly 0.0
+        CHK(ensure(e, e->cand_sum, (size_t)Bp * (e->cfg.vocab_size / 32)));
+        CHK(ensure(e, e->out_lp, (size_t)Bp * max_len));
+        HIPCHK(hipMemsetAsync(e->out_lp.p, 0, (size_t)Bp * max_len * sizeof(float), s));
+    }
+    // the pass runs in its mode; the taps' defaults are back on every way out (the taps never sample, record nor exit early)
+    struct ModeScope { mellow_engine* e; ~ModeScope() { apply_step_mode(e, StepMode()); } } mode_scope{e};
+    apply_step_mode(e, m);
+    if (r.on) {
+        stage_sampling(e, r.top_p, r.temperature, r.seed, r.row_offset, 0);
+        HIPCHK(hipMemcpyAsync(e->d_sparams, e->h_sparams, sizeof(e->h_sparams), hipMemcpyHostToDevice, s));
+    }
+    if (dev_dead) {
+        HIPCHK(hipMemsetAsync(e->d_blk_left, 0, 96 * sizeof(int32_t), s));
+    } else if (m.early_exit) {
+        if (m.migrate) {
+            std::vector<int32_t> ident(1024);
+            for (int i = 0; i < 1024; ++i) ident[i] = i < B ? i : -1;
+            e->h_ident = ident;       // kept alive until the copy has run
+            HIPCHK(hipMemcpyAsync(e->d_row_of_slot, e->h_ident.data(), 1024 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemsetAsync(e->d_ncompact, 0, sizeof(int32_t), s));
+        }
+        for (int rb = 0; rb < 32; ++rb) {
+            const int left = B - 32 * rb;
+            e->h_blk[rb] = left <= 0 ? 0 : (left > 32 ? 32 : left);
+            e->h_blk[32 + rb] = left > 0 ? 1 : 0;
+        }
+        HIPCHK(hipMemcpyAsync(e->d_blk_left, e->h_blk, 64 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemsetAsync(e->out_tok.p, 0xff, (size_t)Bp * max_len * sizeof(int32_t), s));
+    }
+    CHK(clear_page_tails(e, T, e->kv_Tmax));     // everything a key-group load can touch (whole chunks are loaded, then masked)
+    CHK(encode_pair_to_prefix(e, r.audio1, r.audio2, r.n_samples, r.input_ids, examples, e->lm_x.p));
+    HIPCHK(hipEventRecord(e->ev_phase[1], s));
+    RecordArgs rec;
+    rec.embed_next = true;
+    CHK(run_prefill(e, examples, T, &rec, false, n));
+    HIPCHK(hipEventRecord(e->ev_phase[2], s));
+
+    // one decode step = 30 x (qkv | attention | o_proj | gate/up | down) + final norm + lm_head + arg-max/record/embed,
+    // captured once per (B, page geometry, buffers) and replayed; max_len and the stop id are read from d_params
+    const bool graph = e->use_graph && !e->prof_on && max_len > 1;
+    const mellow_engine::StepGraphs::Key want = mellow_engine::StepGraphs::Key::of(e, B);
+    if (graph && (!e->graphs.one || !(e->graphs.key == want))) {
+        e->graphs.reset();
+        // eight consecutive steps as ONE graph: the step reads its position from the device word, so a replay of the
+        // same kernel sequence IS the next step; one launch per 8 steps removes the host/CP hand-over between graphs
+        int rc = capture_steps(e, B, &rec, 1, &e->graphs.one);
+        if (!rc) rc = capture_steps(e, B, &rec, 8, &e->graphs.eight);
+        if (rc) { e->graphs.reset(); return rc; }      // never a cache that holds one exec of the two
+        e->graphs.key = want;
+    }
+    int steps_done = 1;   // token 0 came from the prefill
+    double first_ms = -1.0;
+    auto note_first = [&]() {
+        if (first_ms < 0) first_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count();
+    };
+    if (r.ignore_stop) {
+        // fixed-length mode: nothing to decide on the host, everything is enqueued at once
+        for (int i = 1; i < max_len;) {
+            const bool eight = graph && i + 8 <= max_len;
+            if (eight) HIPCHK(hipGraphLaunch(e->graphs.eight, s));
+            else if (graph) HIPCHK(hipGraphLaunch(e->graphs.one, s));
+            else CHK(enqueue_decode_layers(e, B, &rec));
+            i += eight ? 8 : 1;
+            e->cur_pos += eight ? 8 : 1;
+            steps_done = i;
+        }
+        CHK(wait_ticket(e, 1, nullptr));
+        note_first();
+    } else {
+        // reference stop rule (wrapper.py:247-249): the loop ends after the first step at which every row has produced the
+        // stop id at least once.  The arg-max kernel publishes (step ticket, rows stopped) to a host-visible word, so the
+        // host follows the rule one step behind the device without synchronising: step i+1 is enqueued while step i runs,
+        // and at most ONE step is ever enqueued past the deciding one.
+        for (int i = 1; i < max_len; ++i) {
+            if (graph) HIPCHK(hipGraphLaunch(e->graphs.one, s));
+            else CHK(enqueue_decode_layers(e, B, &rec));
+            e->cur_pos += 1;
+            steps_done = i + 1;
+            unsigned nseen = 0;
+            CHK(wait_ticket(e, (unsigned)i, &nseen));      // ticket i = the arg-max of step index i-1 is complete
+            note_first();
+            if ((int)nseen >= B) break;
+        }
+        if (first_ms < 0) { CHK(wait_ticket(e, 1, nullptr)); note_first(); }
+    }
+    HIPCHK(hipEventRecord(e->ev_phase[3], s));
+    HIPCHK(hipGetLastError());
+    // host-side length bookkeeping (reference wrapper.py:247-254) on the engine-owned record
+    std::vector<int32_t> toks((size_t)B * max_len);
+    HIPCHK(hipMemcpyAsync(r.out_tokens, e->out_tok.p, toks.size() * sizeof(int32_t), hipMemcpyDefault, s));
+    HIPCHK(hipMemcpyAsync(toks.data(), e->out_tok.p, toks.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (r.out_logprob) HIPCHK(hipMemcpyAsync(r.out_logprob, e->out_lp.p, toks.size() * sizeof(float), hipMemcpyDefault, s));
+    HIPCHK(hipStreamSynchronize(s));
+    CHK(check_bad_id(e));        // a prompt id outside the vocabulary (flagged by prefix_assemble_kernel): the reference raises IndexError
+    for (int i = 0; i < 3; ++i) HIPCHK(hipEventElapsedTime(&e->phase_ms[i], e->ev_phase[i], e->ev_phase[i + 1]));
+    if (r.first_token_ms) *r.first_token_ms = (float)first_ms;
+    int ref_steps = steps_done;
+    if (!r.ignore_stop) {
+        // the reference stops after the first step at which every row has produced stop_id at least once
+        std::vector<char> seen(B, 0);
+        int nseen = 0;
+        for (int st = 0; st < steps_done; ++st) {
+            for (int b = 0; b < B; ++b)
+                if (!seen[b] && toks[(size_t)b * max_len + st] == stop_id) { seen[b] = 1; ++nseen; }
+            if (nseen == B) { ref_steps = st + 1; break; }
+        }
+    }
+    e->last_steps_enqueued = steps_done;
+    e->cur_B = 0;      // the decode state of a generate call (no logits store, early-exit words) is not a base for the step taps:
+                       // mellow_lm_decode_step needs a mellow_lm_prefill of its own
+    e->last_compactions = 0;
+    if (m.migrate) HIPCHK(hipMemcpy(&e->last_compactions, e->d_ncompact, sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (r.out_steps) *r.out_steps = ref_steps;
+    if (r.out_len)
+        for (int b = 0; b < B; ++b) {
+            int len = ref_steps;
+            for (int st = 0; st < ref_steps; ++st)
+                if (toks[(size_t)b * max_len + st] == stop_id) { len = st; break; }
+            r.out_len[b] = len;
+        }
+    return 0;
+}
+
+// The reference's loop (wrapper.py:216-249) takes any number of examples.  One pass of the engine takes up to 1024 rows (32 row
+// blocks of loop state), so a larger batch runs as consecutive passes of <= 1024 rows on the same pages: examples are
+// independent, the token record of every pass lands at its rows of `out_tokens`, a pass that stopped before the longest one is
+// padded with -1 (never computed), and the reference's stop rule -- the loop ends at the first step at which EVERY row has
+// produced the stop id -- is the maximum over the passes (a row's own length never depends on other rows).
+static int generate(mellow_engine_t* e, const GenRequest& r, int door = 0) {
+    CHK(check_request(e, r, door));
+    if (r.rows() <= kPassRows) return generate_pass(e, r);      // (always so for n > 1: check_request)
+    const int B = r.examples, max_len = r.max_len;
+    int steps_all = 0, enq_all = 0, rep_all = 0;
+    float ph[3] = {0.f, 0.f, 0.f};
+    std::vector<int> pass_steps;
+    for (int r0 = 0; r0 < B; r0 += kPassRows) {
+        int st = 0;
+        float ftm = 0.f;
+        CHK(generate_pass(e, r.pass(r0, B - r0 < kPassRows ? B - r0 : kPassRows, e->cfg.text_len, &st, &ftm)));
+        if (r0 == 0 && r.first_token_ms) *r.first_token_ms = ftm;      // the first answers of the call: entry -> first token of the first pass
+        pass_steps.push_back(st);
+        steps_all = st > steps_all ? st : steps_all;
+        enq_all = e->last_steps_enqueued > enq_all ? e->last_steps_enqueued : enq_all;
+        rep_all += e->last_compactions;
+        for (int i = 0; i < 3; ++i) ph[i] += e->phase_ms[i];
+    }
+    // columns a pass never reached (it stopped before the longest pass): -1, like the rows of a block that stopped early
+    for (size_t p = 0; p < pass_steps.size(); ++p) {
+        const int r0 = (int)p * kPassRows, nb = B - r0 < kPassRows ? B - r0 : kPassRows;
+        if (pass_steps[p] >= steps_all) continue;
+        int32_t* dst = r.out_tokens + (size_t)r0 * max_len + pass_steps[p];
+        const size_t w = (size_t)(steps_all - pass_steps[p]) * sizeof(int32_t);
+        hipPointerAttribute_t at;
+        const bool on_device = hipPointerGetAttributes(&at, r.out_tokens) == hipSuccess && at.type == hipMemoryTypeDevice;
+        if (!on_device) (void)hipGetLastError();            // a plain host pointer is not an error here
+        if (on_device) HIPCHK(hipMemset2D(dst, (size_t)max_len * sizeof(int32_t), 0xff, w, nb));
+        else for (int row = 0; row < nb; ++row) memset(dst + (size_t)row * max_len, 0xff, w);
+        // ... and exactly 0.0 in the log-prob record (a device buffer) where the token record now says "never computed"
+        if (r.out_logprob) HIPCHK(hipMemset2D(r.out_logprob + (size_t)r0 * max_len + pass_steps[p], (size_t)max_len * sizeof(float), 0, w, nb));
+    }
+    e->last_steps_enqueued = enq_all;
+    e->last_compactions = rep_all;
+    for (int i = 0; i < 3; ++i) e->phase_ms[i] = ph[i];
+    if (r.out_steps) *r.out_steps = steps_all;
+    return 0;
+}
+
+extern "C" {
+
+int mellow_generate(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples,
+                    const int32_t* input_ids, int B, int max_len, float top_p, float temperature, int stop_id,
+                    int ignore_stop, int32_t* out_tokens, int32_t* out_len, int32_t* out_steps, float* first_token_ms) {
+    // greedy: the reference's top-p/temperature path never changes the arg-max (wrapper.py:219-232)
+    return generate(e, {audio1, audio2, n_samples, input_ids, B, 1, max_len, stop_id, ignore_stop, false, top_p, temperature, 0, 0,
+                        out_tokens, nullptr, out_len, out_steps, first_token_ms});
+}
+
+int mellow_generate_sampled(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples,
+                            const int32_t* input_ids, int B, int max_len, float top_p, float temperature, uint64_t seed,
+                            int32_t row_offset, int stop_id, int ignore_stop, int32_t* out_tokens, int32_t* out_len,
+                            int32_t* out_steps, float* first_token_ms) {
+    return generate(e, {audio1, audio2, n_samples, input_ids, B, 1, max_len, stop_id, ignore_stop, true, top_p, temperature, seed, row_offset,
+                        out_tokens, nullptr, out_len, out_steps, first_token_ms});
+}
+
+// mellow_generate (do_sample = 0) or mellow_generate_sampled (do_sample != 0) plus the log-prob record: the same launches with the
+// head, the arg-max and the sampler in their LSE instantiations (decode.hip, sample.hip); tokens, lengths and steps are bit-identical
+int mellow_generate_scored(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples, const int32_t* input_ids,
+                           int B, int max_len, int do_sample, float top_p, float temperature, uint64_t seed, int32_t row_offset,
+                           int stop_id, int ignore_stop, int32_t* out_tokens, float* out_logprob, int32_t* out_len, int32_t* out_steps,
+                           float* first_token_ms) {
+    return generate(e, {audio1, audio2, n_samples, input_ids, B, 1, max_len, stop_id, ignore_stop, do_sample != 0, top_p, temperature, seed, row_offset,
+                        out_tokens, out_logprob, out_len, out_steps, first_token_ms}, DOOR_SCORED);
+}
+
+// n sampled answers per example from ONE encode and ONE prefill per example (include/mellow_hip.h states the semantics).  The step
+// graph is shared with a plain call of the same B * n rows on purpose: the key holds the row count, the page geometry and every
+// address a captured launch reads, and from the first decode step on the two calls run the same launches on the same buffers --
+// everything that differs (prefix buffer, fan-out, row table) happens before the loop and is never captured.
+int mellow_generate_n(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples, const int32_t* input_ids,
+                      int B, int n, int max_len, int do_sample, float top_p, float temperature, uint64_t seed, int32_t row_offset,
+                      int stop_id, int ignore_stop, int32_t* out_tokens, float* out_logprob, int32_t* out_len, int32_t* out_steps,
+                      float* first_token_ms) {
+    return generate(e, {audio1, audio2, n_samples, input_ids, B, n, max_len, stop_id, ignore_stop, do_sample != 0, top_p, temperature, seed, row_offset,
+                        out_tokens, out_logprob, out_len, out_steps, first_token_ms}, DOOR_N);
+}
+
+int mellow_sample_logits(mellow_engine_t* e, const float* logits, int B, const int32_t* row_ids, int step, float top_p,
+                         float temperature, uint64_t seed, int32_t* tokens) {
+    if (!e || !e->finalized) return fail("engine not finalized");
+    if (!logits || !tokens || B <= 0) return fail("bad argument");
+    CHK(check_sampling(e, top_p, temperature));
+    HIPCHK(hipSetDevice(e->device));
+    stage_sampling(e, top_p, temperature, seed, 0, step);
+    HIPCHK(hipMemcpyAsync(e->d_sparams, e->h_sparams, sizeof(e->h_sparams), hipMemcpyHostToDevice, e->stream));
+    SampleArgs sa;
+    sa.logits = logits; sa.ld = e->cfg.vocab_size; sa.prm = e->d_sparams; sa.row_ids = row_ids;
+    launch_sample_logits(sa, B, tokens, e->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+}  // extern "C"

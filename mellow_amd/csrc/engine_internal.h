@@ -3,13 +3,15 @@
 //   engine.cpp          errors, allocation helpers, create / destroy / fork / load_tensor, precision, profiler read-out
 //   engine_weights.cpp  mellow_engine_finalize: every reference checkpoint key -> device layouts (P / PB / P16 / e4m3, composed decode weights)
 //   engine_encoder.cpp  GEMM dispatch, front-end + HTSAT encoder (A1-A13), the taps mellow_logmel / mellow_encode / mellow_resample
-//   engine_lm.cpp       KV pages, LM prefill (A15), the decode step, mellow_prefix / lm taps, mellow_generate (A16)
+//   engine_lm.cpp       KV pages, LM prefill (A15), the decode step and its per-call mode, mellow_prefix / lm taps, scoring
+//   engine_generate.cpp the generation loop on top of it (A16): request + checks, passes, step graphs, the mellow_generate* entry points
 //   engine_dev.cpp      developer entry points (GEMM timing / debug taps, kernel stamps)
 // The engine object (below): `Options` + `Weights` are what a fork shares, each copied by one assignment; everything else is one
 // context's own -- stream, events, workspaces (`Buf` frees itself), KV pages, loop words, the decode-graph cache (`StepGraphs`).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -125,6 +127,16 @@ struct ProfRec {
     int M = 0, N = 0, K = 0, epi = 0;     // GEMM launches only (developer shape report)
 };
 
+// What one call decides about the decode step.  The default is what the taps run: logits stored, arg-max, no record, every block live.
+// apply_step_mode (engine_lm.cpp) is the only writer of the engine's copy and of the DecArgs fields that follow from it.
+struct StepMode {
+    bool logits = true;          // the head stores its logits rows (the taps read them, and so does the sampler)
+    bool sample = false;         // dec_sample_kernel draws the token instead of the arg-max
+    bool logprob = false;        // head / arg-max / sampler in their LSE forms, log-probs recorded next to the tokens
+    bool early_exit = false;     // per-row-block early exit (DecArgs::blk_live)
+    bool migrate = false;        // ... with row migration (DecArgs::row_of_slot)
+};
+
 // One execution context.  `opt` and `w` are what a fork shares with its parent (copied whole by mellow_engine_fork); the rest is its own.
 #define LOCAL __attribute__((visibility("hidden")))      // (the handle type is declared inside the public header's visibility pragma)
 struct mellow_engine {
@@ -194,19 +206,12 @@ struct mellow_engine {
         std::unordered_map<const float*, Fp8W> fp8_w;
     };
     // The captured decode step and what it was captured with: the graphs bake buffer addresses in (max_len / stop id travel in
-    // d_params, the sampling parameters in d_sparams).  generate_pass captures, ensure_lm invalidates.
+    // d_params, the sampling parameters in d_sparams).  generate_pass (engine_generate.cpp) captures, ensure_lm invalidates.
     struct LOCAL StepGraphs {
         struct Key {
-            int B = -1, Tmax = -1, sample = -1;     // batch, page geometry, sampling mode (the sampler + logits store, or the arg-max)
-            const void *out_tok = nullptr, *blk_live = nullptr, *row_of_slot = nullptr;      // token record, DecArgs::blk_live / ::row_of_slot
-            // log-probs of the generated tokens (mellow_generate_scored): other head / arg-max / sampler instantiations, and the
-            // addresses of the partial sums and of the record -- a call without never replays a graph captured with, nor the reverse
-            int logprob = 0;
-            const void *cand_sum = nullptr, *out_lp = nullptr;
-            bool operator==(const Key& k) const {
-                return B == k.B && Tmax == k.Tmax && out_tok == k.out_tok && blk_live == k.blk_live && row_of_slot == k.row_of_slot && sample == k.sample &&
-                       logprob == k.logprob && cand_sum == k.cand_sum && out_lp == k.out_lp;
-            }
+            std::array<uintptr_t, 9> v{};       // all zero: no capture (a pass has at least one row)
+            static Key of(const mellow_engine* e, int B);      // from the engine as configured for the pass (below the engine)
+            bool operator==(const Key& k) const { return v == k.v; }
         };
         hipGraphExec_t one = nullptr, eight = nullptr;      // eight: the same step 8 times in a row (the step is position-independent)
         Key key;
@@ -264,15 +269,14 @@ struct mellow_engine {
     int32_t h_params[2] = {0, 0};              // staging of d_params {max_len, stop id}
     uint32_t* d_sparams = nullptr;             // sampling parameter block (kernels.h SMP_*): graph replays serve any seed / top_p / T
     uint32_t h_sparams[SMP_WORDS] = {0};       // ... its staging
-    bool sample_on = false;                    // run_lm_head draws with dec_sample_kernel instead of the arg-max (mellow_generate_sampled)
+    StepMode mode;                             // what apply_step_mode last set (run_lm_head, loop_args and StepGraphs::Key::of read it)
     int32_t h_blk[64] = {0};                   // staging of d_blk_left[32] | d_blk_live[32]
     std::vector<int32_t> h_ident;              // staging of d_row_of_slot
     int last_steps_enqueued = 0;               // decode steps (incl. the prefill's token) the last generate call enqueued
     Buf out_tok;                               // engine-owned token record [rows][max_len] (stable address: graph-safe)
     // mellow_generate_scored, created on first use: the head's per-tile sums of exponentials [rows][vocab / 32] (DecArgs::cand_sum) and
-    // the log-prob record [rows][max_len] (LoopArgs::out_logprob); logprob_on: this call records (run_lm_head / loop_args)
+    // the log-prob record [rows][max_len] (LoopArgs::out_logprob)
     Buf cand_sum, out_lp;
-    bool logprob_on = false;
     // mellow_generate_n (n answers per example from one prefill), created on first use: the prefix K/V of the call's examples
     // [layer][examples][3][Tp][64] -- the prefill writes them here, kv_fanout_kernel copies them to the pages of every answer row
     // (source and destination never alias) -- and the source-row table of launch_dec_load_rows with its host staging
@@ -303,6 +307,19 @@ struct mellow_engine {
 };
 
 #undef LOCAL
+// Everything a captured step bakes in that differs between calls, and which launch bakes it in.  A new StepMode field that changes
+// a captured launch or one of its arguments belongs here.
+inline mellow_engine::StepGraphs::Key mellow_engine::StepGraphs::Key::of(const mellow_engine* e, int B) {
+    return Key{{(uintptr_t)B,                      // rows: every launch's grid and its live-row count
+                (uintptr_t)e->kv_Tmax,             // page stride: dec_attn, and with it the arena and page addresses (ensure_lm)
+                (uintptr_t)e->mode.sample,         // dec_sample_kernel or the arg-max; the head with or without its logits store
+                (uintptr_t)e->out_tok.p,           // token record: LoopArgs of the arg-max / sampler (and of dec_compact)
+                (uintptr_t)e->da.blk_live,         // early exit: the DecArgs of every launch
+                (uintptr_t)e->da.row_of_slot,      // row table: the DecArgs of every launch, and whether dec_compact is in the step
+                (uintptr_t)e->mode.logprob,        // LSE forms of the head and of the arg-max / sampler
+                (uintptr_t)e->da.cand_sum,         // partial sums: DecArgs of the head and of the arg-max / sampler
+                (uintptr_t)(e->mode.logprob ? e->out_lp.p : nullptr)}};      // log-prob record: LoopArgs of the arg-max / sampler
+}
 static_assert(!std::is_copy_constructible<mellow_engine::Buf>::value, "a Buf owns its device memory: it moves, it is never copied");
 static_assert(std::is_copy_assignable<mellow_engine::Weights>::value && std::is_copy_assignable<mellow_engine::Options>::value, "a fork copies these by assignment: no owning member (Buf, StepGraphs) belongs in them");
 
@@ -357,6 +374,8 @@ int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end = 0, int pre
 static inline int prefix_page_len(int T) { return rup(T, 64); }      // positions per page of kprefix / vprefix (rounded as the pages are)
 int clear_page_tails(mellow_engine* e, int T, int t_end);
 LoopArgs loop_args(mellow_engine* e);
+// sets e->mode and the DecArgs fields logits, cand_sum, blk_live, blk_snap, row_of_slot from it (cand_sum must be allocated for logprob)
+void apply_step_mode(mellow_engine* e, const StepMode& m);
 int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec);
 // n > 1 (mellow_generate_n; fp32 pages only): the layers run on the B examples and write K/V to kprefix / vprefix; the fan-out and
 // everything from the last prefix row on (last layer, head, first token) run on B * n rows

@@ -1,5 +1,5 @@
-// The decoder LM: KV pages and decode workspaces, prefill (A15), the KV-cached decode step, prefix assembly (A14), the lm taps and
-// mellow_generate (A16: reference wrapper.py:197-256).
+// The decoder LM: KV pages and decode workspaces, prefill (A15), the KV-cached decode step and its per-call mode, prefix assembly
+// (A14), the lm taps and scoring.  The generation loop on top of it is engine_generate.cpp.
 #include "engine_internal.h"
 
 int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end, int prefill_B) {
@@ -74,9 +74,6 @@ int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end, int prefill
         a.a8 = e->opt.fp8_decode_act ? 1 : 0;
         a.kv16 = e->opt.kv16 ? 1 : 0;
         a.x3 = e->opt.dec_x3;
-        a.blk_live = nullptr;                               // mellow_generate turns the per-block early exit on per call
-        a.row_of_slot = nullptr;
-        // (and the logits store off: the taps mellow_lm_prefill / mellow_lm_decode_step read dlogits, generation does not)
         a.rope_cos = e->w.rope_cos; a.rope_sin = e->w.rope_sin;
         a.xmidF = p + o_xmidF; a.xnewR = p + o_xnewR; a.xnF = p + o_xnF;
         a.xn3 = (a.x3 & DEC_X3_HEAD) && !e->w.head8 && dec_head3r_fits(e->cfg.vocab_size) ? (void*)(p + o_xnF) : nullptr;
@@ -94,11 +91,20 @@ int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end, int prefill
             a.gs = gs;
         }
         a.pq = p + o_pq; a.attF16 = p + o_att; a.att_ml = p + o_aml; a.ssq = p + o_ssq; a.guF = p + o_gu; a.xmidF16 = p + o_xmidF16;
-        a.logits = e->dlogits.p; a.cand_val = e->cand.p; a.cand_idx = reinterpret_cast<int32_t*>(e->cand.p + (size_t)Bp * (V / 32));
-        a.cand_sum = nullptr;                               // mellow_generate_scored / the lse tap turn the partial sums on per call
+        a.cand_val = e->cand.p; a.cand_idx = reinterpret_cast<int32_t*>(e->cand.p + (size_t)Bp * (V / 32));
+        apply_step_mode(e, StepMode());                     // the taps' step; a generation pass applies its own afterwards
     }
-    if (Bp > 1024) return fail("batch too large for the decode state block");
     return 0;
+}
+
+void apply_step_mode(mellow_engine* e, const StepMode& m) {
+    e->mode = m;
+    DecArgs& a = e->da;
+    a.logits = m.logits ? e->dlogits.p : nullptr;      // (off: generation's arg-max needs the candidates only, no 6 MB store per step)
+    a.cand_sum = m.logprob ? e->cand_sum.p : nullptr;
+    a.blk_live = m.early_exit ? e->d_blk_live : nullptr;
+    a.blk_snap = e->d_blk_live + 32;
+    a.row_of_slot = m.migrate ? e->d_row_of_slot : nullptr;
 }
 
 // The decode attention loads whole key groups before it knows the position and masks them by WEIGHT (exp(-inf) = 0): a
@@ -122,7 +128,7 @@ LoopArgs loop_args(mellow_engine* e) {
     lp.host_progress = e->d_progress; lp.T0 = e->cfg.prefix_len;
     if (e->da.blk_live) { lp.blk_left = e->d_blk_left; lp.blk_live = e->d_blk_live; lp.blk_snap = e->d_blk_live + 32; }
     if (e->da.row_of_slot) { lp.row_of_slot = e->d_row_of_slot; lp.n_compactions = e->d_ncompact; }
-    if (e->logprob_on && e->da.cand_sum) lp.out_logprob = e->out_lp.p;
+    if (e->mode.logprob) lp.out_logprob = e->out_lp.p;
     return lp;
 }
 
@@ -136,7 +142,7 @@ int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec)
       const DecW h = e->w.head_w();
       launch_dec_lm_head(dh(1), h.p, e->w.lm_head.KP / 8, e->cfg.vocab_size, e->stream, h.scale); }
     { ProfScope ps(e, PF_MISC, 0, 0);
-      if (e->sample_on) {          // mellow_generate_sampled: the head stored the logits (da.logits); draw instead of the arg-max
+      if (e->mode.sample) {        // mellow_generate_sampled: the head stored the logits (da.logits); draw instead of the arg-max
           SampleArgs sa;
           sa.logits = e->da.logits; sa.ld = e->cfg.vocab_size; sa.prm = e->d_sparams;
           launch_dec_sample(sa, dh(2), B, e->d_tokens, e->w.embed, (rec && rec->embed_next) ? 1 : 0, rec ? loop_args(e) : LoopArgs(),
@@ -390,20 +396,6 @@ int enqueue_decode_layers(mellow_engine* e, int B, const RecordArgs* rec) {
     return 0;
 }
 
-// `n` consecutive decode steps captured from the stream into one exec.  Once the capture has begun it is ALWAYS ended and the
-// hipGraph_t ALWAYS destroyed, whatever failed in between; the first error is the one reported.
-static int capture_steps(mellow_engine* e, int B, const RecordArgs* rec, int n, hipGraphExec_t* exec) {
-    hipGraph_t gr = nullptr;
-    HIPCHK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-    int rc = 0;
-    for (int k = 0; k < n && !rc; ++k) rc = enqueue_decode_layers(e, B, rec);
-    hipError_t err = hipStreamEndCapture(e->stream, &gr);
-    if (!rc && err != hipSuccess) rc = fail("hipStreamEndCapture failed: %s", hipGetErrorString(err));
-    if (!rc && (err = hipGraphInstantiate(exec, gr, nullptr, nullptr, 0)) != hipSuccess) { *exec = nullptr; rc = fail("instantiating the captured decode step failed: %s", hipGetErrorString(err)); }
-    if (gr) (void)hipGraphDestroy(gr);
-    return rc;
-}
-
 // audio1|audio2 are separate caller buffers: stage them into one [2B][n] batch so the encoder runs ONE pass
 // of 2B clips (the reference runs two passes of B, mellow.py:105-106)
 int encode_pair_to_prefix(mellow_engine* e, const float* a1, const float* a2, int64_t n_samples, const int32_t* ids,
@@ -429,37 +421,6 @@ int check_bad_id(mellow_engine* e) {
     if (!w) return 0;
     return fail("index out of range in self: prompt id %d of example %u is outside the vocabulary [0, %d)", (int)(unsigned)(w & 0xffffffffu),
                 (unsigned)((w >> 32) & 0x7fffffffu), e->cfg.vocab_size);
-}
-
-// Wait (without touching the stream) until the arg-max kernel has published ticket >= want; *nseen = rows stopped so far.
-static int wait_ticket(mellow_engine* e, unsigned want, unsigned* nseen) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 1;; ++spins) {
-        const unsigned long long v = __atomic_load_n(e->h_progress, __ATOMIC_ACQUIRE);
-        if ((unsigned)(v >> 32) >= want) {
-            if (nseen) *nseen = (unsigned)(v & 0xffffffffu);
-            return 0;
-        }
-        if ((spins & 0x3ff) == 0) {
-            const hipError_t q = hipStreamQuery(e->stream);
-            if (q == hipSuccess) {      // nothing left in flight: the ticket must be there now
-                const unsigned long long v2 = __atomic_load_n(e->h_progress, __ATOMIC_ACQUIRE);
-                if ((unsigned)(v2 >> 32) >= want) continue;
-                return fail("decode progress word stalled at ticket %u (wanted %u) with an idle stream", (unsigned)(v2 >> 32), want);
-            }
-            if (q != hipErrorNotReady) return fail("stream error while waiting for a decode step: %s", hipGetErrorString(q));
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(60))
-                return fail("timed out waiting for decode ticket %u", want);
-        }
-        // spin politely: a pause per poll, and after ~50 us of spinning yield the core between polls (EnginePool runs one
-        // such loop per context thread)
-#if defined(__x86_64__) || defined(__i386__)
-        __builtin_ia32_pause();
-#elif defined(__aarch64__)
-        __asm__ __volatile__("yield");
-#endif
-        if (spins > 4096) std::this_thread::yield();
-    }
 }
 
 // ---- scoring: teacher-forced log-probs through an LM head that never writes its logits ------------------------------------------
@@ -699,365 +660,6 @@ int mellow_score(mellow_engine_t* e, const float* audio1, const float* audio2, i
     HIPCHK(hipStreamSynchronize(s));
     CHK(check_bad_id(e));
     return check_bad_target(e, "candidate", 0);
-}
-
-// sampling of one call (mellow_generate_sampled); on = false: the greedy arg-max of mellow_generate
-struct SampleCall {
-    bool on = false;
-    float top_p = 0.f, temperature = 1.f;
-    uint64_t seed = 0;
-    int32_t row_offset = 0;
-    float* out_logprob = nullptr;            // mellow_generate_scored: dev f32 [B][max_len], the log-prob of every recorded token
-};
-// one pass: `examples` examples, n answer rows each (n = 1: every row is an example of its own, encoded and prefilled itself)
-static int generate_pass(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples,
-                         const int32_t* input_ids, int examples, int max_len, int stop_id,
-                         int ignore_stop, int32_t* out_tokens, int32_t* out_len, int32_t* out_steps, float* first_token_ms,
-                         const SampleCall& sc, int n = 1);
-static int generate_all(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples,
-                        const int32_t* input_ids, int B, int max_len, int stop_id,
-                        int ignore_stop, int32_t* out_tokens, int32_t* out_len, int32_t* out_steps, float* first_token_ms,
-                        const SampleCall& sc);
-
-// The reference's loop (wrapper.py:216-249) takes any number of examples.  One pass of the engine takes up to 1024 rows (32 row
-// blocks of loop state), so a larger batch runs as consecutive passes of <= 1024 rows on the same pages: examples are
-// independent, the token record of every pass lands at its rows of `out_tokens`, a pass that stopped before the longest one is
-// padded with -1 (never computed), and the reference's stop rule -- the loop ends at the first step at which EVERY row has
-// produced the stop id -- is the maximum over the passes (a row's own length never depends on other rows).
-int mellow_generate(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples,
-                    const int32_t* input_ids, int B, int max_len, float top_p, float temperature, int stop_id,
-                    int ignore_stop, int32_t* out_tokens, int32_t* out_len, int32_t* out_steps, float* first_token_ms) {
-    (void)top_p;
-    (void)temperature;  // the reference's top-p/temperature path never changes the arg-max (wrapper.py:219-232)
-    return generate_all(e, audio1, audio2, n_samples, input_ids, B, max_len, stop_id, ignore_stop, out_tokens, out_len, out_steps,
-                        first_token_ms, SampleCall());
-}
-
-static int check_sampling(mellow_engine_t* e, float top_p, float temperature) {
-    if (e->cfg.vocab_size != SAMPLE_MAX_V) return fail("the sampler is built for a vocabulary of %d (engine: %d)", SAMPLE_MAX_V, e->cfg.vocab_size);
-    if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail("temperature must be finite and > 0 (got %g); greedy is mellow_generate", (double)temperature);
-    if (top_p != top_p) return fail("top_p is NaN");
-    return 0;
-}
-
-static void stage_sampling(mellow_engine_t* e, float top_p, float temperature, uint64_t seed, int32_t row_offset, int step) {
-    uint32_t* w = e->h_sparams;
-    w[SMP_SEED_LO] = (uint32_t)seed; w[SMP_SEED_HI] = (uint32_t)(seed >> 32); w[SMP_ROW_OFF] = (uint32_t)row_offset;
-    memcpy(&w[SMP_TOP_P], &top_p, 4); memcpy(&w[SMP_TEMP], &temperature, 4); w[SMP_STEP] = (uint32_t)step;
-}
-
-int mellow_generate_sampled(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples,
-                            const int32_t* input_ids, int B, int max_len, float top_p, float temperature, uint64_t seed,
-                            int32_t row_offset, int stop_id, int ignore_stop, int32_t* out_tokens, int32_t* out_len,
-                            int32_t* out_steps, float* first_token_ms) {
-    if (!e || !e->finalized) return fail("engine not finalized");
-    CHK(check_sampling(e, top_p, temperature));
-    if (row_offset < 0) return fail("row_offset must be >= 0");
-    SampleCall sc;
-    sc.on = true; sc.top_p = top_p; sc.temperature = temperature; sc.seed = seed; sc.row_offset = row_offset;
-    return generate_all(e, audio1, audio2, n_samples, input_ids, B, max_len, stop_id, ignore_stop, out_tokens, out_len, out_steps,
-                        first_token_ms, sc);
-}
-
-// mellow_generate (do_sample = 0) or mellow_generate_sampled (do_sample != 0) plus the log-prob record: the same launches with the
-// head, the arg-max and the sampler in their LSE instantiations (decode.hip, sample.hip); tokens, lengths and steps are bit-identical
-int mellow_generate_scored(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples, const int32_t* input_ids,
-                           int B, int max_len, int do_sample, float top_p, float temperature, uint64_t seed, int32_t row_offset,
-                           int stop_id, int ignore_stop, int32_t* out_tokens, float* out_logprob, int32_t* out_len, int32_t* out_steps,
-                           float* first_token_ms) {
-    if (!e || !e->finalized) return fail("engine not finalized");
-    if (!out_logprob) return fail("null argument");
-    if (e->cfg.vocab_size % 32 != 0) return fail("the log-prob partials tile the vocabulary in groups of 32 columns (vocab %d)", e->cfg.vocab_size);
-    SampleCall sc;
-    if (do_sample) {
-        CHK(check_sampling(e, top_p, temperature));
-        if (row_offset < 0) return fail("row_offset must be >= 0");
-        sc.on = true; sc.top_p = top_p; sc.temperature = temperature; sc.seed = seed; sc.row_offset = row_offset;
-    }
-    sc.out_logprob = out_logprob;
-    return generate_all(e, audio1, audio2, n_samples, input_ids, B, max_len, stop_id, ignore_stop, out_tokens, out_len, out_steps,
-                        first_token_ms, sc);
-}
-
-// n sampled answers per example from ONE encode and ONE prefill per example (include/mellow_hip.h states the semantics).  The step
-// graph is shared with a plain call of the same B * n rows on purpose: the key holds the row count, the page geometry and every
-// address a captured launch reads, and from the first decode step on the two calls run the same launches on the same buffers --
-// everything that differs (prefix buffer, fan-out, row table) happens before the loop and is never captured.
-int mellow_generate_n(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples, const int32_t* input_ids,
-                      int B, int n, int max_len, int do_sample, float top_p, float temperature, uint64_t seed, int32_t row_offset,
-                      int stop_id, int ignore_stop, int32_t* out_tokens, float* out_logprob, int32_t* out_len, int32_t* out_steps,
-                      float* first_token_ms) {
-    if (!e || !e->finalized) return fail("engine not finalized");
-    if (n < 1) return fail("n must be >= 1 (got %d)", n);
-    if (!do_sample) return fail("mellow_generate_n needs do_sample != 0: %d greedy answers of one example are %d copies of one answer", n, n);
-    if (!audio1 || !audio2 || !input_ids || !out_tokens) return fail("null argument");
-    if (B <= 0 || max_len <= 0) return fail("B and max_len must be positive");
-    if ((int64_t)B * n > 1024)
-        return fail("mellow_generate_n takes at most 1024 answer rows per call: B * n = %d * %d = %lld (split the examples over several calls, "
-                    "advancing row_offset by n per example)", B, n, (long long)B * n);
-    if (out_logprob && e->cfg.vocab_size % 32 != 0) return fail("the log-prob partials tile the vocabulary in groups of 32 columns (vocab %d)", e->cfg.vocab_size);
-    if (n > 1 && (e->opt.fp8 || e->opt.kv16))
-        return fail("mellow_generate_n with n > 1 is not available in MELLOW_PRECISION_FP8: the bf16 K/V pages of that mode have no fan-out "
-                    "(n = 1 works; or pass every example n times to mellow_generate_sampled)");
-    CHK(check_sampling(e, top_p, temperature));
-    if (row_offset < 0) return fail("row_offset must be >= 0");
-    SampleCall sc;
-    sc.on = true; sc.top_p = top_p; sc.temperature = temperature; sc.seed = seed; sc.row_offset = row_offset;
-    sc.out_logprob = out_logprob;
-    if (n == 1)       // today's path, today's bytes
-        return generate_all(e, audio1, audio2, n_samples, input_ids, B, max_len, stop_id, ignore_stop, out_tokens, out_len, out_steps,
-                            first_token_ms, sc);
-    return generate_pass(e, audio1, audio2, n_samples, input_ids, B, max_len, stop_id, ignore_stop, out_tokens, out_len, out_steps,
-                         first_token_ms, sc, n);
-}
-
-int mellow_sample_logits(mellow_engine_t* e, const float* logits, int B, const int32_t* row_ids, int step, float top_p,
-                         float temperature, uint64_t seed, int32_t* tokens) {
-    if (!e || !e->finalized) return fail("engine not finalized");
-    if (!logits || !tokens || B <= 0) return fail("bad argument");
-    CHK(check_sampling(e, top_p, temperature));
-    HIPCHK(hipSetDevice(e->device));
-    stage_sampling(e, top_p, temperature, seed, 0, step);
-    HIPCHK(hipMemcpyAsync(e->d_sparams, e->h_sparams, sizeof(e->h_sparams), hipMemcpyHostToDevice, e->stream));
-    SampleArgs sa;
-    sa.logits = logits; sa.ld = e->cfg.vocab_size; sa.prm = e->d_sparams; sa.row_ids = row_ids;
-    launch_sample_logits(sa, B, tokens, e->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 0;
-}
-
-static int generate_all(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples,
-                        const int32_t* input_ids, int B, int max_len, int stop_id,
-                        int ignore_stop, int32_t* out_tokens, int32_t* out_len, int32_t* out_steps, float* first_token_ms,
-                        const SampleCall& sc) {
-    if (!e || !e->finalized) return fail("engine not finalized");
-    if (!audio1 || !audio2 || !input_ids || !out_tokens) return fail("null argument");
-    if (B <= 0 || max_len <= 0) return fail("B and max_len must be positive");
-    constexpr int kPassRows = 1024;
-    if (B <= kPassRows)
-        return generate_pass(e, audio1, audio2, n_samples, input_ids, B, max_len, stop_id, ignore_stop, out_tokens, out_len, out_steps, first_token_ms, sc);
-    int steps_all = 0, enq_all = 0, rep_all = 0;
-    float ph[3] = {0.f, 0.f, 0.f};
-    std::vector<int> pass_steps;
-    for (int r0 = 0; r0 < B; r0 += kPassRows) {
-        const int nb = B - r0 < kPassRows ? B - r0 : kPassRows;
-        int st = 0;
-        float ftm = 0.f;
-        SampleCall scp = sc;
-        scp.row_offset = sc.row_offset + r0;           // a row's random stream follows its index in the whole call
-        if (sc.out_logprob) scp.out_logprob = sc.out_logprob + (size_t)r0 * max_len;
-        CHK(generate_pass(e, audio1 + (size_t)r0 * n_samples, audio2 + (size_t)r0 * n_samples, n_samples, input_ids + (size_t)r0 * e->cfg.text_len,
-                          nb, max_len, stop_id, ignore_stop, out_tokens + (size_t)r0 * max_len, out_len ? out_len + r0 : nullptr, &st, &ftm, scp));
-        if (r0 == 0 && first_token_ms) *first_token_ms = ftm;      // the first answers of the call: entry -> first token of the first pass
-        pass_steps.push_back(st);
-        steps_all = st > steps_all ? st : steps_all;
-        enq_all = e->last_steps_enqueued > enq_all ? e->last_steps_enqueued : enq_all;
-        rep_all += e->last_compactions;
-        for (int i = 0; i < 3; ++i) ph[i] += e->phase_ms[i];
-    }
-    // columns a pass never reached (it stopped before the longest pass): -1, like the rows of a block that stopped early
-    for (size_t p = 0; p < pass_steps.size(); ++p) {
-        const int r0 = (int)p * kPassRows, nb = B - r0 < kPassRows ? B - r0 : kPassRows;
-        if (pass_steps[p] >= steps_all) continue;
-        int32_t* dst = out_tokens + (size_t)r0 * max_len + pass_steps[p];
-        const size_t w = (size_t)(steps_all - pass_steps[p]) * sizeof(int32_t);
-        hipPointerAttribute_t at;
-        const bool on_device = hipPointerGetAttributes(&at, out_tokens) == hipSuccess && at.type == hipMemoryTypeDevice;
-        if (!on_device) (void)hipGetLastError();            // a plain host pointer is not an error here
-        if (on_device) HIPCHK(hipMemset2D(dst, (size_t)max_len * sizeof(int32_t), 0xff, w, nb));
-        else for (int r = 0; r < nb; ++r) memset(dst + (size_t)r * max_len, 0xff, w);
-        // ... and exactly 0.0 in the log-prob record (a device buffer) where the token record now says "never computed"
-        if (sc.out_logprob) HIPCHK(hipMemset2D(sc.out_logprob + (size_t)r0 * max_len + pass_steps[p], (size_t)max_len * sizeof(float), 0, w, nb));
-    }
-    e->last_steps_enqueued = enq_all;
-    e->last_compactions = rep_all;
-    for (int i = 0; i < 3; ++i) e->phase_ms[i] = ph[i];
-    if (out_steps) *out_steps = steps_all;
-    return 0;
-}
-
-static int generate_pass(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples,
-                         const int32_t* input_ids, int examples, int max_len, int stop_id,
-                         int ignore_stop, int32_t* out_tokens, int32_t* out_len, int32_t* out_steps, float* first_token_ms,
-                         const SampleCall& sc, int n) {
-    const auto t_entry = std::chrono::steady_clock::now();
-    const int B = examples * n;       // rows of the pass: pages, decode arena, loop state, records and the step graph are sized by it
-    HIPCHK(hipSetDevice(e->device));
-    hipStream_t s = e->stream;
-    const int T = e->cfg.prefix_len;
-    // KV page geometry in buckets of 64 positions, so that nearby max_len values share pages, key split and graphs
-    int Tmax = rup(T + max_len, 64);
-    if (Tmax > e->cfg.max_positions) Tmax = T + max_len;
-    CHK(ensure_lm(e, B, T, Tmax, T + max_len, examples));
-    const int Bp = e->da.rows;
-    if (n > 1) {
-        // the prefix K/V of the examples (run_prefill writes, kv_fanout_kernel reads).  Zeroed when (re)allocated: positions
-        // [T, Tp) of a page are never written and never read (the prefill attention clamps its key loads to T - 1); a page starts
-        // at a multiple of Tp * 64 floats whatever the number of examples, so a larger call finds its tails where they were
-        const size_t fl = (size_t)e->cfg.num_layers * examples * 3 * prefix_page_len(T) * 64;
-        for (mellow_engine::Buf* b : {&e->kprefix, &e->vprefix})
-            if (b->cap < fl) {
-                CHK(ensure(e, *b, fl));
-                HIPCHK(hipMemsetAsync(b->p, 0, fl * sizeof(float), s));
-            }
-        // source row of every answer row for launch_dec_load_rows: the last prefix position of its example
-        CHK(ensure(e, e->nseq_rows, 1024));
-        e->h_nseq_rows.assign(1024, 0);      // (a member: alive until the copy has run)
-        for (int r = 0; r < B; ++r) e->h_nseq_rows[r] = (r / n) * T + T - 1;
-        HIPCHK(hipMemcpyAsync(e->nseq_rows.p, e->h_nseq_rows.data(), 1024 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    }
-    CHK(ensure(e, e->out_tok, (size_t)Bp * max_len));
-    HIPCHK(hipEventRecord(e->ev_phase[0], s));
-    // loop state (the prefill's arg-max already records token 0 and publishes ticket 1)
-    __atomic_store_n(e->h_progress, 0ull, __ATOMIC_RELEASE);
-    clear_bad_id(e);
-    HIPCHK(hipMemsetAsync(e->d_nseen, 0, 3 * sizeof(int32_t), s));       // n_seen, arrive, ticket
-    HIPCHK(hipMemsetAsync(e->d_seen, 0, 1024 * sizeof(int32_t), s));
-    e->h_params[0] = max_len;
-    e->h_params[1] = stop_id;
-    HIPCHK(hipMemcpyAsync(e->d_params, e->h_params, 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    // Per-row-block early exit (reference stop rule, more than one 32-row block): once every row of a block has produced the
-    // stop id, the block's workgroups return at once in every later kernel (its rows' texts are already cut there).  Columns a
-    // row never reached are -1 in the token record.
-    e->da.logits = nullptr;             // generation needs the arg-max candidates only: no 6 MB logits store per step
-    e->sample_on = sc.on;               // ... unless it samples: the sampler reads the full logits rows
-    struct SampleOff { mellow_engine* e; ~SampleOff() { e->sample_on = false; e->logprob_on = false; e->da.cand_sum = nullptr; } } sample_off{e};    // the taps never sample nor record
-    e->logprob_on = sc.out_logprob != nullptr;
-    if (e->logprob_on) {
-        // the head's partial sums and the record; columns that are never computed stay exactly 0.0
-        CHK(ensure(e, e->cand_sum, (size_t)Bp * (e->cfg.vocab_size / 32)));
-        CHK(ensure(e, e->out_lp, (size_t)Bp * max_len));
-        HIPCHK(hipMemsetAsync(e->out_lp.p, 0, (size_t)Bp * max_len * sizeof(float), s));
-        e->da.cand_sum = e->cand_sum.p;
-    }
-    if (sc.on) {
-        e->da.logits = e->dlogits.p;
-        stage_sampling(e, sc.top_p, sc.temperature, sc.seed, sc.row_offset, 0);
-        HIPCHK(hipMemcpyAsync(e->d_sparams, e->h_sparams, sizeof(e->h_sparams), hipMemcpyHostToDevice, s));
-    }
-    e->da.blk_live = (!ignore_stop && e->da.RB > 1) ? e->d_blk_live : nullptr;
-    e->da.blk_snap = e->d_blk_live + 32;
-#ifdef MELLOW_DEVPROBE
-    static const bool dev_dead = getenv("MELLOW_DEV_DEAD_BLOCKS") != nullptr;    // developer probe: launch-chain floor of a step
-#else
-    constexpr bool dev_dead = false;
-#endif
-    const bool no_migrate = !e->opt.row_migration;   // option "row_migration" = 0: block exit without repacking (developer A/B)
-    e->da.row_of_slot = nullptr;
-    if (dev_dead) {
-        e->da.blk_live = e->d_blk_live;
-        HIPCHK(hipMemsetAsync(e->d_blk_left, 0, 96 * sizeof(int32_t), s));
-    } else if (e->da.blk_live) {
-        if (!no_migrate && B <= 1024) {
-            std::vector<int32_t> ident(1024);
-            for (int i = 0; i < 1024; ++i) ident[i] = i < B ? i : -1;
-            e->h_ident = ident;       // kept alive until the copy has run
-            HIPCHK(hipMemcpyAsync(e->d_row_of_slot, e->h_ident.data(), 1024 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemsetAsync(e->d_ncompact, 0, sizeof(int32_t), s));
-            e->da.row_of_slot = e->d_row_of_slot;
-        }
-        for (int rb = 0; rb < 32; ++rb) {
-            const int left = B - 32 * rb;
-            e->h_blk[rb] = left <= 0 ? 0 : (left > 32 ? 32 : left);
-            e->h_blk[32 + rb] = left > 0 ? 1 : 0;
-        }
-        HIPCHK(hipMemcpyAsync(e->d_blk_left, e->h_blk, 64 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemsetAsync(e->out_tok.p, 0xff, (size_t)Bp * max_len * sizeof(int32_t), s));
-    }
-    CHK(clear_page_tails(e, T, e->kv_Tmax));     // everything a key-group load can touch (whole chunks are loaded, then masked)
-    CHK(encode_pair_to_prefix(e, audio1, audio2, n_samples, input_ids, examples, e->lm_x.p));
-    HIPCHK(hipEventRecord(e->ev_phase[1], s));
-    RecordArgs rec;
-    rec.embed_next = true;
-    CHK(run_prefill(e, examples, T, &rec, false, n));
-    HIPCHK(hipEventRecord(e->ev_phase[2], s));
-
-    // one decode step = 30 x (qkv | attention | o_proj | gate/up | down) + final norm + lm_head + arg-max/record/embed,
-    // captured once per (B, page geometry, buffers) and replayed; max_len and the stop id are read from d_params
-    const bool graph = e->use_graph && !e->prof_on && max_len > 1;
-    const mellow_engine::StepGraphs::Key want{B, e->kv_Tmax, (int)sc.on, e->out_tok.p, e->da.blk_live, e->da.row_of_slot,
-                                              (int)e->logprob_on, e->da.cand_sum, e->logprob_on ? e->out_lp.p : nullptr};
-    if (graph && (!e->graphs.one || !(e->graphs.key == want))) {
-        e->graphs.reset();
-        // eight consecutive steps as ONE graph: the step reads its position from the device word, so a replay of the
-        // same kernel sequence IS the next step; one launch per 8 steps removes the host/CP hand-over between graphs
-        int rc = capture_steps(e, B, &rec, 1, &e->graphs.one);
-        if (!rc) rc = capture_steps(e, B, &rec, 8, &e->graphs.eight);
-        if (rc) { e->graphs.reset(); return rc; }      // never a cache that holds one exec of the two
-        e->graphs.key = want;
-    }
-    int steps_done = 1;   // token 0 came from the prefill
-    double first_ms = -1.0;
-    auto note_first = [&]() {
-        if (first_ms < 0) first_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count();
-    };
-    if (ignore_stop) {
-        // fixed-length mode: nothing to decide on the host, everything is enqueued at once
-        for (int i = 1; i < max_len;) {
-            const bool eight = graph && i + 8 <= max_len;
-            if (eight) HIPCHK(hipGraphLaunch(e->graphs.eight, s));
-            else if (graph) HIPCHK(hipGraphLaunch(e->graphs.one, s));
-            else CHK(enqueue_decode_layers(e, B, &rec));
-            i += eight ? 8 : 1;
-            e->cur_pos += eight ? 8 : 1;
-            steps_done = i;
-        }
-        CHK(wait_ticket(e, 1, nullptr));
-        note_first();
-    } else {
-        // reference stop rule (wrapper.py:247-249): the loop ends after the first step at which every row has produced the
-        // stop id at least once.  The arg-max kernel publishes (step ticket, rows stopped) to a host-visible word, so the
-        // host follows the rule one step behind the device without synchronising: step i+1 is enqueued while step i runs,
-        // and at most ONE step is ever enqueued past the deciding one.
-        for (int i = 1; i < max_len; ++i) {
-            if (graph) HIPCHK(hipGraphLaunch(e->graphs.one, s));
-            else CHK(enqueue_decode_layers(e, B, &rec));
-            e->cur_pos += 1;
-            steps_done = i + 1;
-            unsigned nseen = 0;
-            CHK(wait_ticket(e, (unsigned)i, &nseen));      // ticket i = the arg-max of step index i-1 is complete
-            note_first();
-            if ((int)nseen >= B) break;
-        }
-        if (first_ms < 0) { CHK(wait_ticket(e, 1, nullptr)); note_first(); }
-    }
-    HIPCHK(hipEventRecord(e->ev_phase[3], s));
-    HIPCHK(hipGetLastError());
-    // host-side length bookkeeping (reference wrapper.py:247-254) on the engine-owned record
-    std::vector<int32_t> toks((size_t)B * max_len);
-    HIPCHK(hipMemcpyAsync(out_tokens, e->out_tok.p, toks.size() * sizeof(int32_t), hipMemcpyDefault, s));
-    HIPCHK(hipMemcpyAsync(toks.data(), e->out_tok.p, toks.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (e->logprob_on) HIPCHK(hipMemcpyAsync(sc.out_logprob, e->out_lp.p, toks.size() * sizeof(float), hipMemcpyDefault, s));
-    HIPCHK(hipStreamSynchronize(s));
-    CHK(check_bad_id(e));        // a prompt id outside the vocabulary (flagged by prefix_assemble_kernel): the reference raises IndexError
-    for (int i = 0; i < 3; ++i) HIPCHK(hipEventElapsedTime(&e->phase_ms[i], e->ev_phase[i], e->ev_phase[i + 1]));
-    if (first_token_ms) *first_token_ms = (float)first_ms;
-    int ref_steps = steps_done;
-    if (!ignore_stop) {
-        // the reference stops after the first step at which every row has produced stop_id at least once
-        std::vector<char> seen(B, 0);
-        int nseen = 0;
-        for (int st = 0; st < steps_done; ++st) {
-            for (int b = 0; b < B; ++b)
-                if (!seen[b] && toks[(size_t)b * max_len + st] == stop_id) { seen[b] = 1; ++nseen; }
-            if (nseen == B) { ref_steps = st + 1; break; }
-        }
-    }
-    e->last_steps_enqueued = steps_done;
-    e->cur_B = 0;      // the decode state of a generate call (no logits store, early-exit words) is not a base for the step taps:
-                       // mellow_lm_decode_step needs a mellow_lm_prefill of its own
-    e->last_compactions = 0;
-    if (e->da.row_of_slot) HIPCHK(hipMemcpy(&e->last_compactions, e->d_ncompact, sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (out_steps) *out_steps = ref_steps;
-    if (out_len)
-        for (int b = 0; b < B; ++b) {
-            int n = ref_steps;
-            for (int st = 0; st < ref_steps; ++st)
-                if (toks[(size_t)b * max_len + st] == stop_id) { n = st; break; }
-            out_len[b] = n;
-        }
-    return 0;
 }
 
 }  // extern "C"

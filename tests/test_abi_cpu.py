@@ -52,6 +52,15 @@ def test_engine_create_fails_loudly_without_gpu(lib):
         E.Engine()
 
 
+@pytest.mark.parametrize("name", ["mellow_generate", "mellow_generate_sampled", "mellow_generate_scored", "mellow_generate_n"])
+def test_every_generate_entry_point_refuses_a_null_engine(lib, name):
+    """the four doors share one argument check (engine_generate.cpp): host code only, no device is touched"""
+    fn = getattr(lib, name)
+    args = [None if t is ctypes.c_void_p or hasattr(t, "contents") else t(1) for t in fn.argtypes]
+    assert fn(*args) != 0
+    assert "engine not finalized" in lib.mellow_last_error().decode()
+
+
 @pytest.mark.parametrize("R,shift", [(64, 0), (64, 4), (32, 4), (16, 0), (16, 4), (8, 0)])
 def test_window_map_is_roll_plus_partition(lib, R, shift):
     """row m of the window-ordered batch must be token map[m] (reference htsat.py:427-436)."""
