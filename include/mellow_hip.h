@@ -52,7 +52,8 @@ extern "C" {
  *     The scoring symbols mellow_score and mellow_lm_score were added later under this same minor (no existing symbol or struct
  *     changed): a binding that must also load an older minor-4 library detects them by symbol lookup (dlsym), not by the number.
  *     mellow_generate_scored and mellow_debug_dec_head_lse (log-probs of the generated tokens) were added the same way, and so
- *     was mellow_generate_n (n sampled answers per example from one encode and one prefill). */
+ *     was mellow_generate_n (n sampled answers per example from one encode and one prefill), and then mellow_generate_q (several
+ *     questions per example from one encode and one prefill of the clips' positions). */
 #define MELLOW_ABI_MINOR 4
 
 typedef struct mellow_engine mellow_engine_t;
@@ -217,6 +218,35 @@ int  mellow_generate_scored(mellow_engine_t* e, const float* audio1, const float
  * Added under minor 4 like the scoring symbols: a binding detects it by symbol lookup. */
 int  mellow_generate_n(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples, const int32_t* input_ids,
                        int B, int n, int max_len, int do_sample, float top_p, float temperature, uint64_t seed, int32_t row_offset,
+                       int stop_id, int ignore_stop, int32_t* out_tokens, float* out_logprob, int32_t* out_len, int32_t* out_steps,
+                       float* first_token_ms);
+/* Q questions about every example -- N = B * Q answers, row b * Q + j answers question j of example b -- from ONE pass of front-end,
+ * encoder and projection per example and ONE LM prefill of the positions that depend on the clips only.  audio1 / audio2 describe
+ * the B examples; input_ids dev i32 [B][Q][text_len]; out_tokens dev i32 [N][max_len], out_logprob dev f32 [N][max_len] (may be
+ * NULL: no log-prob record), out_len host i32 [N].
+ *
+ * Definition.  The result IS what the plain call returns for N examples, example b * Q + j being (audio1[b], audio2[b],
+ * input_ids[b][j]), with the same seed and row_offset: tokens, lengths, steps, the -1 columns and the log-prob record.  The plain
+ * call is mellow_generate_scored when out_logprob != NULL, else mellow_generate_sampled when do_sample != 0, else mellow_generate.  So
+ *   - the global row index of the Philox stream of answer j of example b is row_offset + b * Q + j (a caller that cuts its examples
+ *     into several calls advances row_offset by Q per example);
+ *   - the stop rule, the per-block early exit and row migration act on the N rows exactly as they do there;
+ *   - a prompt id outside the vocabulary, in any question, fails as it does there;
+ *   - in MELLOW_PRECISION_F32 the two results are bit-identical: that mode's GEMMs do not depend on the batch (minor 1), the cut
+ *     between the two prefills is a multiple of the attention's query tile, so every query meets the key tiles it meets there in the
+ *     same order, and both forms run the last layer of the prefill, the head and every decode step on the same N rows;
+ *   - in the default MELLOW_PRECISION_F32X3 they agree as closely as two batch compositions do (minor 1);
+ *   - Q == 1 takes the path of those calls and returns their bytes.
+ * What the engine does with Q > 1: of the prefix_len = 389 positions [audio1 129 | sep | audio2 129 | sep | prompt text_len] the
+ * first 260 are the same for every question, and in a causal decoder so are their K/V at every layer.  The LM runs over positions
+ * [0, 256) -- the largest multiple of 32 below 260 -- of the B examples into a prefix buffer; one copy kernel hands that K/V to the
+ * pages of each example's Q rows; the LM then runs over positions [256, 389) of the N rows, attending to the row's pages; the last
+ * prefix position, the head, the first token and the captured decode loop run on N rows as in the plain call.
+ * Errors: Q < 1; B * Q > 1024 (one pass of rows: the caller splits its examples); Q > 1 on an MELLOW_PRECISION_FP8 engine (its bf16
+ * K/V pages have no fan-out); and every error of the plain call.
+ * Added under minor 4 like the scoring symbols: a binding detects it by symbol lookup. */
+int  mellow_generate_q(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples, const int32_t* input_ids,
+                       int B, int Q, int max_len, int do_sample, float top_p, float temperature, uint64_t seed, int32_t row_offset,
                        int stop_id, int ignore_stop, int32_t* out_tokens, float* out_logprob, int32_t* out_len, int32_t* out_steps,
                        float* first_token_ms);
 /* The same draw on caller logits, no loop state (numeric tap): logits dev [B][vocab], row_ids dev i32 [B] (global row index

@@ -773,6 +773,46 @@ void launch_prefix_assemble(const float* proj33, const float* embed, const int32
     hipLaunchKernelGGL(prefix_assemble_kernel, dim3(260 + text_len, B), dim3(192), 0, s, proj33, embed, ids, B,
                        text_len, sep_id, vocab, prefix, bad_id_word);
 }
+// The same prefix rows for Q questions per example (mellow_generate_q), cut at position P <= 260: block x < P writes row x of the
+// head [B][P] (a function of the clips only), block x >= P writes one row of the tail [B * Q][260 - P + text_len]: global position
+// P + i of (example b, question j), i.e. the last 260 - P audio / separator rows again and then the question's embedded ids
+// (ids [B][Q][text_len]).  A bad id is flagged with row b * Q + j: the example index of the plain call on the B * Q expanded examples.
+__global__ __launch_bounds__(192) void prefix_assemble_q_kernel(const float* __restrict__ proj33, const float* __restrict__ embed,
+                                                                const int32_t* __restrict__ ids, int B, int Q, int text_len, int P,
+                                                                int sep_id, int vocab, float* __restrict__ head,
+                                                                float* __restrict__ tail, unsigned long long* __restrict__ bad_id_word) {
+    const int b = blockIdx.y, Tt = 260 - P + text_len;
+    int pos = blockIdx.x, row = b * Q;
+    float* dst;
+    if (pos < P) dst = head + ((int64_t)b * P + pos) * 576;
+    else {
+        const int i = (pos - P) % Tt;
+        row += (pos - P) / Tt;
+        pos = P + i;
+        dst = tail + ((int64_t)row * Tt + i) * 576;
+    }
+    const int32_t* qid = ids + (int64_t)row * text_len;      // the ids of this row's question
+    if (pos >= 260 && threadIdx.x == 0 && bad_id_word) {
+        const int id = qid[pos - 260];
+        if (id < 0 || id >= vocab)
+            __hip_atomic_store(bad_id_word, (1ull << 63) | ((unsigned long long)(unsigned)row << 32) | (unsigned)id, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    for (int c = threadIdx.x; c < 576; c += 192) {
+        float v;
+        if (pos < 129) v = audio_row_value(proj33 + (int64_t)b * 33 * 576, pos, c);
+        else if (pos == 129 || pos == 259) v = embed[(int64_t)sep_id * 576 + c];
+        else if (pos < 259) v = audio_row_value(proj33 + (int64_t)(B + b) * 33 * 576, pos - 130, c);
+        else v = embed[(int64_t)min(max(qid[pos - 260], 0), vocab - 1) * 576 + c];
+        dst[c] = v;
+    }
+}
+void launch_prefix_assemble_q(const float* proj33, const float* embed, const int32_t* ids, int B, int Q, int text_len, int P,
+                              int sep_id, int vocab, float* head, float* tail, unsigned long long* bad_id_word, hipStream_t s) {
+    if (B <= 0 || Q <= 0 || P < 0 || P > 260 || text_len <= 0) return;      // (the engine never asks for these)
+    hipLaunchKernelGGL(prefix_assemble_q_kernel, dim3(P + Q * (260 - P + text_len), B), dim3(192), 0, s, proj33, embed, ids, B, Q,
+                       text_len, P, sep_id, vocab, head, tail, bad_id_word);
+}
 __global__ __launch_bounds__(192) void downsample33_kernel(const float* __restrict__ proj33, float* __restrict__ out) {
     const int r = blockIdx.x, clip = blockIdx.y;
     for (int c = threadIdx.x; c < 576; c += 192)

@@ -17,7 +17,7 @@ int run_gemm(mellow_engine* e, const GemmArgs& a) {
     // Option "x3_stft" = 0 keeps the front-end on the exact fp32 kernel.
     const bool x3_stft = e->opt.x3_stft;
     if (e->opt.f32x3_terms && a.K % 16 == 0 &&
-        ((a.a_mode == A_PLAIN && (a.epi == EPI_LINEAR || a.epi == EPI_SWIGLU || a.epi == EPI_QKV_ROPE)) || (x3_stft && a.K >= 192))) {
+        ((a.a_mode == A_PLAIN && (a.epi == EPI_LINEAR || a.epi == EPI_SWIGLU || a.epi == EPI_QKV_ROPE || a.epi == EPI_QKV_ROPE_AT)) || (x3_stft && a.K >= 192))) {
         auto it = e->w.bf_w.find(a.Wp);
         if (it != e->w.bf_w.end()) {
             // fused kernel: A stays fp32 (global and LDS) and is split into its three bf16 terms in registers

@@ -6,8 +6,10 @@
 struct GenRequest {
     const float *audio1, *audio2;                // inputs: dev f32 [examples][n_samples] each
     int64_t n_samples;
-    const int32_t* input_ids;                    // dev [examples][text_len]
-    int examples, n, max_len, stop_id, ignore_stop;      // n answer rows per example (n = 1: every row is an example of its own)
+    const int32_t* input_ids;                    // dev [examples][q][text_len]
+    // n answer rows per example (n = 1: every row is an example of its own); q questions per example, a row each (mellow_generate_q);
+    // never both above 1
+    int examples, n, q, max_len, stop_id, ignore_stop;
     bool on;                                     // sampling: false = the greedy arg-max, and the four fields below are not read
     float top_p, temperature;
     uint64_t seed;
@@ -16,8 +18,8 @@ struct GenRequest {
     float* out_logprob;                          // dev f32 [rows][max_len], the log-prob of every recorded token; null: not recorded
     int32_t *out_len, *out_steps;
     float* first_token_ms;
-    int rows() const { return examples * n; }
-    // rows [r0, r0 + nb) of an n = 1 request as a request of their own; a row's random stream follows its index in the whole call
+    int rows() const { return examples * n * q; }
+    // rows [r0, r0 + nb) of an n = 1, q = 1 request as a request of their own; a row's random stream follows its index in the whole call
     GenRequest pass(int r0, int nb, int text_len, int32_t* steps, float* ftm) const {
         GenRequest p = *this;
         p.audio1 += (size_t)r0 * n_samples; p.audio2 += (size_t)r0 * n_samples; p.input_ids += (size_t)r0 * text_len;
@@ -29,7 +31,7 @@ struct GenRequest {
         return p;
     }
 };
-enum { DOOR_SCORED = 1, DOOR_N = 2 };            // what a rule of one entry point needs to know: mellow_generate_scored, mellow_generate_n
+enum { DOOR_SCORED = 1, DOOR_N = 2, DOOR_Q = 4 };     // what a rule of one entry point needs to know: mellow_generate_scored, mellow_generate_n, mellow_generate_q
 constexpr int kPassRows = 1024;                  // rows of one pass: 32 row blocks of loop state
 
 static int check_sampling(mellow_engine_t* e, float top_p, float temperature) {
@@ -45,20 +47,28 @@ static void stage_sampling(mellow_engine_t* e, float top_p, float temperature, u
     memcpy(&w[SMP_TOP_P], &top_p, 4); memcpy(&w[SMP_TEMP], &temperature, 4); w[SMP_STEP] = (uint32_t)step;
 }
 
-// Every argument rule of the four entry points, each once.
+// Every argument rule of the five entry points, each once.
 static int check_request(mellow_engine_t* e, const GenRequest& r, int door) {
     if (!e || !e->finalized) return fail("engine not finalized");
     if (r.n < 1) return fail("n must be >= 1 (got %d)", r.n);
+    if (r.q < 1) return fail("Q must be >= 1 (got %d)", r.q);
+    if (r.n > 1 && r.q > 1) return fail("internal: n and Q are never both above 1");
     if ((door & DOOR_N) && !r.on) return fail("mellow_generate_n needs do_sample != 0: %d greedy answers of one example are %d copies of one answer", r.n, r.n);
     if (!r.audio1 || !r.audio2 || !r.input_ids || !r.out_tokens || ((door & DOOR_SCORED) && !r.out_logprob)) return fail("null argument");
     if (r.examples <= 0 || r.max_len <= 0) return fail("B and max_len must be positive");
     if ((door & DOOR_N) && (int64_t)r.examples * r.n > kPassRows)
         return fail("mellow_generate_n takes at most 1024 answer rows per call: B * n = %d * %d = %lld (split the examples over several calls, "
                     "advancing row_offset by n per example)", r.examples, r.n, (long long)r.examples * r.n);
+    if ((door & DOOR_Q) && (int64_t)r.examples * r.q > kPassRows)
+        return fail("mellow_generate_q takes at most 1024 answer rows per call: B * Q = %d * %d = %lld (split the examples over several calls, "
+                    "advancing row_offset by Q per example)", r.examples, r.q, (long long)r.examples * r.q);
     if (r.out_logprob && e->cfg.vocab_size % 32 != 0) return fail("the log-prob partials tile the vocabulary in groups of 32 columns (vocab %d)", e->cfg.vocab_size);
     if (r.n > 1 && (e->opt.fp8 || e->opt.kv16))
         return fail("mellow_generate_n with n > 1 is not available in MELLOW_PRECISION_FP8: the bf16 K/V pages of that mode have no fan-out "
                     "(n = 1 works; or pass every example n times to mellow_generate_sampled)");
+    if (r.q > 1 && (e->opt.fp8 || e->opt.kv16))
+        return fail("mellow_generate_q with Q > 1 is not available in MELLOW_PRECISION_FP8: the bf16 K/V pages of that mode have no fan-out "
+                    "(Q = 1 works; or pass every example once per question to mellow_generate)");
     if (r.on) {
         CHK(check_sampling(e, r.top_p, r.temperature));
         if (r.row_offset < 0) return fail("row_offset must be >= 0");
@@ -111,10 +121,10 @@ static int wait_ticket(mellow_engine* e, unsigned want, unsigned* nseen) {
     }
 }
 
-// one pass: r.examples examples, r.n answer rows each (n = 1: every row is encoded and prefilled itself)
+// one pass: r.examples examples, r.n answer rows or r.q questions each (both 1: every row is encoded and prefilled itself)
 static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
     const auto t_entry = std::chrono::steady_clock::now();
-    const int examples = r.examples, n = r.n, max_len = r.max_len, stop_id = r.stop_id;
+    const int examples = r.examples, n = r.n, Q = r.q, max_len = r.max_len, stop_id = r.stop_id;
     const int B = r.rows();           // rows of the pass: pages, decode arena, loop state, records and the step graph are sized by it
     HIPCHK(hipSetDevice(e->device));
     hipStream_t s = e->stream;
@@ -122,9 +132,14 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
     // KV page geometry in buckets of 64 positions, so that nearby max_len values share pages, key split and graphs
     int Tmax = rup(T + max_len, 64);
     if (Tmax > e->cfg.max_positions) Tmax = T + max_len;
-    CHK(ensure_lm(e, B, T, Tmax, T + max_len, examples));
+    // Q > 1: positions [0, P) of a prefix -- the clips and separators up to the largest multiple of the attention's 32-query tile --
+    // are prefilled once per example, positions [P, T) once per row (run_prefill_q)
+    const int P = (T - e->cfg.text_len) / 32 * 32, Tt = T - P;
+    const size_t tail_rows = (size_t)B * Tt, head_rows = (size_t)examples * P;
+    CHK(ensure_lm(e, B, T, Tmax, T + max_len, examples, Q > 1 ? (head_rows > tail_rows ? head_rows : tail_rows) : 0));
+    if (Q > 1) CHK(ensure(e, e->lm_xq, tail_rows * 576));
     const int Bp = e->da.rows;
-    if (n > 1) {
+    if (n > 1 || Q > 1) {
         // the prefix K/V of the examples (run_prefill writes, kv_fanout_kernel reads).  Zeroed when (re)allocated: positions
         // [T, Tp) of a page are never written and never read (the prefill attention clamps its key loads to T - 1); a page starts
         // at a multiple of Tp * 64 floats whatever the number of examples, so a larger call finds its tails where they were
@@ -134,10 +149,11 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
                 CHK(ensure(e, *b, fl));
                 HIPCHK(hipMemsetAsync(b->p, 0, fl * sizeof(float), s));
             }
-        // source row of every answer row for launch_dec_load_rows: the last prefix position of its example
+        // source row of every answer row for launch_dec_load_rows: the last prefix position of its example, or (Q > 1) the last
+        // row of its own tail
         CHK(ensure(e, e->nseq_rows, 1024));
         e->h_nseq_rows.assign(1024, 0);      // (a member: alive until the copy has run)
-        for (int row = 0; row < B; ++row) e->h_nseq_rows[row] = (row / n) * T + T - 1;
+        for (int row = 0; row < B; ++row) e->h_nseq_rows[row] = Q > 1 ? row * Tt + Tt - 1 : (row / n) * T + T - 1;
         HIPCHK(hipMemcpyAsync(e->nseq_rows.p, e->h_nseq_rows.data(), 1024 * sizeof(int32_t), hipMemcpyHostToDevice, s));
     }
     CHK(ensure(e, e->out_tok, (size_t)Bp * max_len));
@@ -195,11 +211,13 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
         HIPCHK(hipMemsetAsync(e->out_tok.p, 0xff, (size_t)Bp * max_len * sizeof(int32_t), s));
     }
     CHK(clear_page_tails(e, T, e->kv_Tmax));     // everything a key-group load can touch (whole chunks are loaded, then masked)
-    CHK(encode_pair_to_prefix(e, r.audio1, r.audio2, r.n_samples, r.input_ids, examples, e->lm_x.p));
+    if (Q > 1) CHK(encode_pair_to_head_tail(e, r.audio1, r.audio2, r.n_samples, r.input_ids, examples, Q, P, e->lm_x.p, e->lm_xq.p));
+    else CHK(encode_pair_to_prefix(e, r.audio1, r.audio2, r.n_samples, r.input_ids, examples, e->lm_x.p));
     HIPCHK(hipEventRecord(e->ev_phase[1], s));
     RecordArgs rec;
     rec.embed_next = true;
-    CHK(run_prefill(e, examples, T, &rec, false, n));
+    if (Q > 1) CHK(run_prefill_q(e, examples, Q, T, P, &rec));
+    else CHK(run_prefill(e, examples, T, &rec, false, n));
     HIPCHK(hipEventRecord(e->ev_phase[2], s));
 
     // one decode step = 30 x (qkv | attention | o_proj | gate/up | down) + final norm + lm_head + arg-max/record/embed,
@@ -295,7 +313,7 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
 // produced the stop id -- is the maximum over the passes (a row's own length never depends on other rows).
 static int generate(mellow_engine_t* e, const GenRequest& r, int door = 0) {
     CHK(check_request(e, r, door));
-    if (r.rows() <= kPassRows) return generate_pass(e, r);      // (always so for n > 1: check_request)
+    if (r.rows() <= kPassRows) return generate_pass(e, r);      // (always so for n > 1 and, through mellow_generate_q, for Q > 1: check_request)
     const int B = r.examples, max_len = r.max_len;
     int steps_all = 0, enq_all = 0, rep_all = 0;
     float ph[3] = {0.f, 0.f, 0.f};
@@ -338,7 +356,7 @@ int mellow_generate(mellow_engine_t* e, const float* audio1, const float* audio2
                     const int32_t* input_ids, int B, int max_len, float top_p, float temperature, int stop_id,
                     int ignore_stop, int32_t* out_tokens, int32_t* out_len, int32_t* out_steps, float* first_token_ms) {
     // greedy: the reference's top-p/temperature path never changes the arg-max (wrapper.py:219-232)
-    return generate(e, {audio1, audio2, n_samples, input_ids, B, 1, max_len, stop_id, ignore_stop, false, top_p, temperature, 0, 0,
+    return generate(e, {audio1, audio2, n_samples, input_ids, B, 1, 1, max_len, stop_id, ignore_stop, false, top_p, temperature, 0, 0,
                         out_tokens, nullptr, out_len, out_steps, first_token_ms});
 }
 
@@ -346,7 +364,7 @@ int mellow_generate_sampled(mellow_engine_t* e, const float* audio1, const float
                             const int32_t* input_ids, int B, int max_len, float top_p, float temperature, uint64_t seed,
                             int32_t row_offset, int stop_id, int ignore_stop, int32_t* out_tokens, int32_t* out_len,
                             int32_t* out_steps, float* first_token_ms) {
-    return generate(e, {audio1, audio2, n_samples, input_ids, B, 1, max_len, stop_id, ignore_stop, true, top_p, temperature, seed, row_offset,
+    return generate(e, {audio1, audio2, n_samples, input_ids, B, 1, 1, max_len, stop_id, ignore_stop, true, top_p, temperature, seed, row_offset,
                         out_tokens, nullptr, out_len, out_steps, first_token_ms});
 }
 
@@ -356,7 +374,7 @@ int mellow_generate_scored(mellow_engine_t* e, const float* audio1, const float*
                            int B, int max_len, int do_sample, float top_p, float temperature, uint64_t seed, int32_t row_offset,
                            int stop_id, int ignore_stop, int32_t* out_tokens, float* out_logprob, int32_t* out_len, int32_t* out_steps,
                            float* first_token_ms) {
-    return generate(e, {audio1, audio2, n_samples, input_ids, B, 1, max_len, stop_id, ignore_stop, do_sample != 0, top_p, temperature, seed, row_offset,
+    return generate(e, {audio1, audio2, n_samples, input_ids, B, 1, 1, max_len, stop_id, ignore_stop, do_sample != 0, top_p, temperature, seed, row_offset,
                         out_tokens, out_logprob, out_len, out_steps, first_token_ms}, DOOR_SCORED);
 }
 
@@ -368,8 +386,19 @@ int mellow_generate_n(mellow_engine_t* e, const float* audio1, const float* audi
                       int B, int n, int max_len, int do_sample, float top_p, float temperature, uint64_t seed, int32_t row_offset,
                       int stop_id, int ignore_stop, int32_t* out_tokens, float* out_logprob, int32_t* out_len, int32_t* out_steps,
                       float* first_token_ms) {
-    return generate(e, {audio1, audio2, n_samples, input_ids, B, n, max_len, stop_id, ignore_stop, do_sample != 0, top_p, temperature, seed, row_offset,
+    return generate(e, {audio1, audio2, n_samples, input_ids, B, n, 1, max_len, stop_id, ignore_stop, do_sample != 0, top_p, temperature, seed, row_offset,
                         out_tokens, out_logprob, out_len, out_steps, first_token_ms}, DOOR_N);
+}
+
+// Q questions per example from ONE encode and ONE prefill of the clips' positions per example (include/mellow_hip.h states the
+// semantics; run_prefill_q the pass).  Like mellow_generate_n it shares the step graph of a plain call of the same B * Q rows.
+// Q = 1 is that plain call: the request below is then the one mellow_generate / _sampled / _scored build.
+int mellow_generate_q(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples, const int32_t* input_ids,
+                      int B, int Q, int max_len, int do_sample, float top_p, float temperature, uint64_t seed, int32_t row_offset,
+                      int stop_id, int ignore_stop, int32_t* out_tokens, float* out_logprob, int32_t* out_len, int32_t* out_steps,
+                      float* first_token_ms) {
+    return generate(e, {audio1, audio2, n_samples, input_ids, B, 1, Q, max_len, stop_id, ignore_stop, do_sample != 0, top_p, temperature, seed, row_offset,
+                        out_tokens, out_logprob, out_len, out_steps, first_token_ms}, DOOR_Q);
 }
 
 int mellow_sample_logits(mellow_engine_t* e, const float* logits, int B, const int32_t* row_ids, int step, float top_p,

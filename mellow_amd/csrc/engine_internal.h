@@ -281,6 +281,7 @@ struct mellow_engine {
     // [layer][examples][3][Tp][64] -- the prefill writes them here, kv_fanout_kernel copies them to the pages of every answer row
     // (source and destination never alias) -- and the source-row table of launch_dec_load_rows with its host staging
     Buf kprefix, vprefix, nseq_rows;
+    Buf lm_xq;                                // mellow_generate_q: the LM input of the tail prefill, [rows][prefix_len - P][hidden] (run_prefill_q)
     std::vector<int32_t> h_nseq_rows;
     int kv_B = 0, kv_Tmax = 0;                // current page geometry
     int cur_B = 0, cur_pos = 0;               // host mirror of the decode state
@@ -370,7 +371,8 @@ struct RecordArgs {
     bool embed_next = false;
 };
 // B rows of pages and decode arena; the prefill workspaces hold prefill_B examples (0 = B: every row is prefilled itself)
-int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end = 0, int prefill_B = 0);
+// (prefill_rows > 0: their row count itself, for a prefill that is not prefill_B x T rows)
+int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end = 0, int prefill_B = 0, size_t prefill_rows = 0);
 static inline int prefix_page_len(int T) { return rup(T, 64); }      // positions per page of kprefix / vprefix (rounded as the pages are)
 int clear_page_tails(mellow_engine* e, int T, int t_end);
 LoopArgs loop_args(mellow_engine* e);
@@ -380,10 +382,25 @@ int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec)
 // n > 1 (mellow_generate_n; fp32 pages only): the layers run on the B examples and write K/V to kprefix / vprefix; the fan-out and
 // everything from the last prefix row on (last layer, head, first token) run on B * n rows
 int run_prefill(mellow_engine* e, int B, int T, const RecordArgs* rec, bool all_positions = false, int n = 1);
+// One run of the LM layers: positions [pos0, pos0 + rows) of every sequence.  run_prefill is one span over the whole prefix;
+// run_prefill_q is two, with the fan-out between them.
+struct PrefillSpan {
+    int rows;            // positions per sequence the run computes; q, attention output and MLP buffers hold this many rows each
+    int pos0;            // their first position: 0, or a multiple of 32 with the K/V of [0, pos0) already in the pages
+    float* x;            // [sequences][rows][hidden]: the layer-0 input, updated in place to the input of the last layer that ran whole
+    bool to_prefix;      // K/V go to kprefix / vprefix (one page per example, stride prefix_page_len) instead of the decode pages
+    bool all_layers;     // the last layer runs whole too (x = the final hidden states); else it stops after its q/k/v GEMM
+};
+// mellow_generate_q, Q > 1 (fp32 pages only): head [0, P) on the B examples (input lm_x), fan-out, tail [P, T) on the B * Q rows
+// (input lm_xq), then everything from the last prefix row on as run_prefill does it for B * Q rows
+int run_prefill_q(mellow_engine* e, int B, int Q, int T, int P, const RecordArgs* rec);
 int enqueue_decode_layer_range(mellow_engine* e, int B, int l_begin, int l_end, bool inc_pos);
 int enqueue_decode_layers(mellow_engine* e, int B, const RecordArgs* rec);
 int ensure_prefill_streams(mellow_engine* e);      // creates + probes the split prefill's side streams; may lower e->prefill_parts to 1
 int encode_pair_to_prefix(mellow_engine* e, const float* a1, const float* a2, int64_t n_samples, const int32_t* ids, int B, float* prefix_out);
+// ids [B][Q][text_len]: head_out [B][P][hidden] and tail_out [B * Q][prefix_len - P][hidden] (kernels.h, launch_prefix_assemble_q)
+int encode_pair_to_head_tail(mellow_engine* e, const float* a1, const float* a2, int64_t n_samples, const int32_t* ids, int B, int Q,
+                             int P, float* head_out, float* tail_out);
 // final norm + fused log-softmax head (EPI_LSE + merge) on rows from_pos .. from_pos + n - 1 of the hidden states in lm_x [B][T]
 int run_score_head(mellow_engine* e, int B, int T, int from_pos, int n, const int32_t* targets, float* out_logprob,
                    int32_t* out_argmax, float* out_lse, float* out_max);

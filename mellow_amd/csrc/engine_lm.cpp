@@ -2,11 +2,11 @@
 // (A14), the lm taps and scoring.  The generation loop on top of it is engine_generate.cpp.
 #include "engine_internal.h"
 
-int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end, int prefill_B) {
+int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end, int prefill_B, size_t prefill_rows) {
     if (B > 1024) return fail("batch of %d exceeds the 1024 rows one pass takes (mellow_generate chunks larger batches itself; the decode state block is sized for 32 row blocks)", B);
     if (ctx_end <= 0 || ctx_end > Tmax) ctx_end = Tmax;      // last context length the call will reach (<= page capacity)
     if (Tmax > e->cfg.max_positions) return fail("prefix + max_len = %d exceeds max_positions %d", Tmax, e->cfg.max_positions);
-    const size_t Mp = (size_t)(prefill_B > 0 ? prefill_B : B) * T;
+    const size_t Mp = prefill_rows > 0 ? prefill_rows : (size_t)(prefill_B > 0 ? prefill_B : B) * T;
     CHK(ensure(e, e->lm_x, Mp * 576));
     CHK(ensure(e, e->lm_xn, Mp * 576));
     CHK(ensure(e, e->lm_q, Mp * 576));
@@ -155,18 +155,22 @@ int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec)
     return 0;
 }
 
-int run_prefill(mellow_engine* e, int B, int T, const RecordArgs* rec, bool all_positions, int n) {
+// The LM layers over positions [pos0, pos0 + rows) of B sequences (engine_internal.h, PrefillSpan): what run_prefill and
+// run_prefill_q are made of.  Nothing of the decode state is touched; every side stream is joined back into e->stream on return.
+static int run_prefill_span(mellow_engine* e, int B, const PrefillSpan& sp) {
     hipStream_t s = e->stream;
     const int NL = e->cfg.num_layers;
-    // fan: the K/V of the B examples go to the prefix buffer (page stride Tp), not to the pages -- a page of example b' would lie
-    // inside the rows another example's copies are written to, and one parallel copy kernel cannot order those writes
-    const bool fan = n > 1;
-    if (fan && (all_positions || e->opt.kv16 || !e->kprefix.p || !e->vprefix.p || !e->nseq_rows.p || B * n > e->kv_B))
-        return fail("internal: the fan-out prefill needs fp32 pages for %d rows and its prefix buffer", B * n);
-    const int Tmax = fan ? prefix_page_len(T) : e->kv_Tmax;                      // page stride the prefill kernels are given
+    const int T = sp.rows, pos0 = sp.pos0, T_end = pos0 + T;                 // rows per sequence of every activation; keys [0, T_end)
+    const bool all_positions = sp.all_layers;
+    // to_prefix: the K/V of the B sequences go to the prefix buffer (page stride Tp), not to the pages -- a page of example b' would
+    // lie inside the rows another example's copies are written to, and one parallel copy kernel cannot order those writes
+    const bool fan = sp.to_prefix;
+    if (pos0 > 0 && (pos0 % 32 != 0 || fan || all_positions || e->opt.fp8 || e->opt.kv16 || B > e->kv_B))
+        return fail("internal: a prefill from position %d needs fp32 pages that hold the positions before it", pos0);
+    const int Tmax = fan ? prefix_page_len(e->cfg.prefix_len) : e->kv_Tmax;      // page stride the prefill kernels are given
     const size_t lay = fan ? (size_t)B * 3 * Tmax * 64 : kv_layer_floats(e);    // floats of one layer of what they write
     float *kbase = fan ? e->kprefix.p : e->kcache.p, *vbase = fan ? e->vprefix.p : e->vcache.p;
-    float *x = e->lm_x.p, *xn = e->lm_xn.p;
+    float *x = sp.x, *xn = e->lm_xn.p;
     // fp8 mode: the same producer -> consumer hand-over with AMX images (MXFP8, common.h) instead of APB ones: `amx`; the code below
     // says `apb` for "GEMM inputs leave their producers in operand format"
     const bool amx = e->opt.fp8 && e->opt.fp8_prefill && e->opt.x3_apb && e->w.fp8_w.count(e->w.layers[0].qkv.p) != 0;
@@ -251,7 +255,8 @@ int run_prefill(mellow_engine* e, int B, int T, const RecordArgs* rec, bool all_
             else { ProfScope ps(e, PF_NORM, 0, 2.0 * Mh * 576 * 4); launch_rmsnorm(xh, xnh, Mh, 576, w.in_ln, e->cfg.rms_norm_eps, st); }
             {
                 GemmArgs g;
-                g.A = xnh; g.lda = 576; g.M = Mh; g.K = 576; g.Wp = fz_in ? w.qkv_f.p : w.qkv.p; g.Nw = 960; g.N = 960; g.epi = EPI_QKV_ROPE;
+                g.A = xnh; g.lda = 576; g.M = Mh; g.K = 576; g.Wp = fz_in ? w.qkv_f.p : w.qkv.p; g.Nw = 960; g.N = 960;
+                g.epi = pos0 > 0 ? EPI_QKV_ROPE_AT : EPI_QKV_ROPE; g.pos0 = pos0;
                 if (fz_in) with_rs(g, ssq_in);
                 g.q_out = qh; g.k_cache = kc; g.v_cache = vc; g.rope_cos = e->w.rope_cos; g.rope_sin = e->w.rope_sin;
                 g.T = T; g.Tmax = Tmax; g.q_heads = 9; g.kv_heads = 3; g.kv16 = p16 ? 1 : 0;
@@ -262,9 +267,10 @@ int run_prefill(mellow_engine* e, int B, int T, const RecordArgs* rec, bool all_
             if (l == NL - 1 && !all_positions) { last = true; continue; }
             {
                 // causal QK^T + PV: 4*64 flops per (query,key) pair per head
-                ProfScope ps(e, PF_PREFILL_ATTN, 4.0 * 64 * 9 * (double)Bh * ((double)T * (T + 1) / 2), 0);
+                ProfScope ps(e, PF_PREFILL_ATTN, 4.0 * 64 * 9 * (double)Bh * ((double)T_end * (T_end + 1) / 2 - (double)pos0 * (pos0 + 1) / 2), 0);
                 const bool attn_f32 = !e->opt.x3_attn;   // option "x3_attn" = 0: f32x3 mode on the fp32 kernel (A/B)
-                launch_prefill_attention(qh, kc, vc, oh, apb ? o3 : nullptr, Bh, T, Tmax, (e->opt.f32x3_terms != 0 || amx) && !attn_f32, st, o3s, amx && e->opt.fp8_attn_bf16, p16);
+                if (pos0 > 0) launch_prefill_attention_past(qh, kc, vc, oh, apb ? o3 : nullptr, Bh, T_end, Tmax, pos0, e->opt.f32x3_terms != 0 && !attn_f32, st);
+                else launch_prefill_attention(qh, kc, vc, oh, apb ? o3 : nullptr, Bh, T, Tmax, (e->opt.f32x3_terms != 0 || amx) && !attn_f32, st, o3s, amx && e->opt.fp8_attn_bf16, p16);
             }
             {
                 GemmArgs g = lin(oh, 576, Mh, w.o, xh, 576, nullptr);
@@ -292,27 +298,19 @@ int run_prefill(mellow_engine* e, int B, int T, const RecordArgs* rec, bool all_
         if (last) break;
     }
     CHK(join.run());
-    if (e->opt.kv16 && !e->kv16_direct && !all_positions) {
-        // fp8 mode: the decode step streams a bf16 shadow of the pages (whole pages: the cleared tails travel with them)
-        ProfScope ps(e, PF_MISC, 0, 3.0 * kv_layer_floats(e) * NL * 4);
-        launch_kv_to_bf16(e->kcache.p, e->kcache16.p, (int64_t)(kv_layer_floats(e) * NL), s);
-        launch_kv_to_bf16(e->vcache.p, e->vcache16.p, (int64_t)(kv_layer_floats(e) * NL), s);
-    }
-    if (all_positions) {        // x = the hidden states after all layers, every position (mellow_lm_forward_logits)
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    // x now holds the input of the last layer.  Position word = index of the LAST prefix token: the decode kernels
-    // treat it as "the new token" (keys 0..T-2 from the pages, key T-1 recomputed and re-appended), and the first
-    // kernel of every later decode step advances it; the arg-max records its token at column (*d_pos - prefix_len + 1) = 0.
-    // n answers per example: every row's pages get its example's prefix K/V, and row r starts from its example's last prefix row
-    const int N = B * n;
-    if (fan) {
-        ProfScope ps(e, PF_MISC, 0, (1.0 + n) * 2.0 * NL * B * 3 * T * 64 * 4);
-        launch_kv_fanout(e->kprefix.p, e->vprefix.p, e->kcache.p, e->vcache.p, NL, B, n, e->kv_B, T, Tmax, e->kv_Tmax, s);
-    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// `x` [rows per sequence = T_last ...] holds the input of the last layer.  Position word = index of the LAST prefix token: the decode
+// kernels treat it as "the new token" (keys 0..T-2 from the pages, key T-1 recomputed and re-appended), and the first kernel of
+// every later decode step advances it; the arg-max records its token at column (*d_pos - prefix_len + 1) = 0.
+// row_ids (null: row r starts from row r * T + T - 1 of x): the source row of every decode row among the n_src rows of x.
+static int finish_prefill(mellow_engine* e, int N, int T, const float* x, const int32_t* row_ids, int n_src, const RecordArgs* rec) {
+    hipStream_t s = e->stream;
+    const int NL = e->cfg.num_layers;
     { ProfScope ps(e, PF_MISC, 0, 0);
-      launch_dec_load_rows(e->da, N, x, 576, fan ? reinterpret_cast<const int32_t*>(e->nseq_rows.p) : nullptr, T, fan ? B * T : 0, s); }
+      launch_dec_load_rows(e->da, N, x, 576, row_ids, T, row_ids ? n_src : 0, s); }
     e->cur_B = N;
     e->cur_pos = T;
     e->h_pos_word = T - 1;
@@ -321,6 +319,45 @@ int run_prefill(mellow_engine* e, int B, int T, const RecordArgs* rec, bool all_
     CHK(run_lm_head(e, N, DEC_KC_DOWN, rec));
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+int run_prefill(mellow_engine* e, int B, int T, const RecordArgs* rec, bool all_positions, int n) {
+    hipStream_t s = e->stream;
+    const int NL = e->cfg.num_layers;
+    const bool fan = n > 1;
+    if (fan && (all_positions || T != e->cfg.prefix_len || e->opt.kv16 || !e->kprefix.p || !e->vprefix.p || !e->nseq_rows.p || B * n > e->kv_B))
+        return fail("internal: the fan-out prefill needs fp32 pages for %d rows and its prefix buffer", B * n);
+    CHK(run_prefill_span(e, B, PrefillSpan{T, 0, e->lm_x.p, fan, all_positions}));
+    if (e->opt.kv16 && !e->kv16_direct && !all_positions) {
+        // fp8 mode: the decode step streams a bf16 shadow of the pages (whole pages: the cleared tails travel with them)
+        ProfScope ps(e, PF_MISC, 0, 3.0 * kv_layer_floats(e) * NL * 4);
+        launch_kv_to_bf16(e->kcache.p, e->kcache16.p, (int64_t)(kv_layer_floats(e) * NL), s);
+        launch_kv_to_bf16(e->vcache.p, e->vcache16.p, (int64_t)(kv_layer_floats(e) * NL), s);
+    }
+    if (all_positions) return 0;        // x = the hidden states after all layers, every position (mellow_lm_forward_logits)
+    // n answers per example: every row's pages get its example's prefix K/V, and row r starts from its example's last prefix row
+    if (fan) {
+        ProfScope ps(e, PF_MISC, 0, (1.0 + n) * 2.0 * NL * B * 3 * T * 64 * 4);
+        launch_kv_fanout(e->kprefix.p, e->vprefix.p, e->kcache.p, e->vcache.p, NL, B, n, e->kv_B, T, prefix_page_len(T), e->kv_Tmax, s);
+    }
+    return finish_prefill(e, B * n, T, e->lm_x.p, fan ? reinterpret_cast<const int32_t*>(e->nseq_rows.p) : nullptr, B * T, rec);
+}
+
+// Q questions per example (mellow_generate_q): positions [0, P) of a prefix depend on the clips only, so the layers run over them
+// once per EXAMPLE (head: lm_x [B][P], K/V to the prefix buffer), the fan-out copies that K/V to the pages of the example's Q rows,
+// and the layers run over [P, T) once per ROW (tail: lm_xq [B * Q][T - P], attention over the row's pages).  From the last prefix
+// position on the pass is a plain one of B * Q rows.  P is a multiple of the attention's query tile, so every query of the tail sees
+// the key tiles -- composition and order -- of the whole-sequence launch.
+int run_prefill_q(mellow_engine* e, int B, int Q, int T, int P, const RecordArgs* rec) {
+    const int NL = e->cfg.num_layers, N = B * Q, Tt = T - P;
+    if (Q < 2 || P <= 0 || P >= T || P % 32 != 0 || T != e->cfg.prefix_len || e->opt.fp8 || e->opt.kv16 || !e->kprefix.p || !e->vprefix.p ||
+        !e->nseq_rows.p || !e->lm_xq.p || N > e->kv_B)
+        return fail("internal: the question prefill needs fp32 pages for %d rows, its prefix buffer and its tail input", N);
+    CHK(run_prefill_span(e, B, PrefillSpan{P, 0, e->lm_x.p, true, false}));
+    { ProfScope ps(e, PF_MISC, 0, (1.0 + Q) * 2.0 * NL * B * 3 * P * 64 * 4);
+      launch_kv_fanout(e->kprefix.p, e->vprefix.p, e->kcache.p, e->vcache.p, NL, B, Q, e->kv_B, P, prefix_page_len(T), e->kv_Tmax, e->stream); }
+    CHK(run_prefill_span(e, N, PrefillSpan{Tt, P, e->lm_xq.p, false, false}));
+    return finish_prefill(e, N, T, e->lm_xq.p, reinterpret_cast<const int32_t*>(e->nseq_rows.p), N * Tt, rec);
 }
 
 // the 30 decode layers + head at position *d_pos (enqueue only; capture-safe).  5 launches per layer (decode.hip):
@@ -398,16 +435,28 @@ int enqueue_decode_layers(mellow_engine* e, int B, const RecordArgs* rec) {
 
 // audio1|audio2 are separate caller buffers: stage them into one [2B][n] batch so the encoder runs ONE pass
 // of 2B clips (the reference runs two passes of B, mellow.py:105-106)
-int encode_pair_to_prefix(mellow_engine* e, const float* a1, const float* a2, int64_t n_samples, const int32_t* ids,
-                                 int B, float* prefix_out) {
+static int encode_pair(mellow_engine* e, const float* a1, const float* a2, int64_t n_samples, int B) {
     mellow_engine::Buf& cat = e->wavcat;
     CHK(ensure(e, cat, (size_t)2 * B * n_samples));
     HIPCHK(hipMemcpyAsync(cat.p, a1, (size_t)B * n_samples * 4, hipMemcpyDeviceToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(cat.p + (size_t)B * n_samples, a2, (size_t)B * n_samples * 4, hipMemcpyDeviceToDevice, e->stream));
-    CHK(run_encoder(e, cat.p, 2 * B, n_samples, 0, 1, nullptr));
+    return run_encoder(e, cat.p, 2 * B, n_samples, 0, 1, nullptr);
+}
+int encode_pair_to_prefix(mellow_engine* e, const float* a1, const float* a2, int64_t n_samples, const int32_t* ids,
+                                 int B, float* prefix_out) {
+    CHK(encode_pair(e, a1, a2, n_samples, B));
     { ProfScope ps(e, PF_MISC, 0, 0);
       launch_prefix_assemble(e->proj33.p, e->w.embed, ids, B, e->cfg.text_len, e->cfg.sep_token_id, e->cfg.vocab_size, prefix_out,
                              e->d_progress + 1, e->stream); }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int encode_pair_to_head_tail(mellow_engine* e, const float* a1, const float* a2, int64_t n_samples, const int32_t* ids, int B, int Q,
+                             int P, float* head_out, float* tail_out) {
+    CHK(encode_pair(e, a1, a2, n_samples, B));
+    { ProfScope ps(e, PF_MISC, 0, 0);
+      launch_prefix_assemble_q(e->proj33.p, e->w.embed, ids, B, Q, e->cfg.text_len, P, e->cfg.sep_token_id, e->cfg.vocab_size, head_out,
+                               tail_out, e->d_progress + 1, e->stream); }
     HIPCHK(hipGetLastError());
     return 0;
 }

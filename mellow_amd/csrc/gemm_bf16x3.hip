@@ -799,6 +799,7 @@ void launch_gemm_bf16x3_apb(const GemmArgs& a, hipStream_t s) {
         case EPI_LINEAR: launchq<EPI_LINEAR>(a, s); break;
         case EPI_SWIGLU: launchq<EPI_SWIGLU>(a, s); break;
         case EPI_QKV_ROPE: launchq<EPI_QKV_ROPE>(a, s); break;
+        case EPI_QKV_ROPE_AT: launchq<EPI_QKV_ROPE_AT>(a, s); break;
         default: break;
     }
 }
@@ -827,6 +828,7 @@ void launch_gemm_bf16x3_fused(const GemmArgs& a, hipStream_t s) {
         case EPI_LINEAR: launchbf<EPI_LINEAR>(a, s); break;
         case EPI_SWIGLU: launchbf<EPI_SWIGLU>(a, s); break;
         case EPI_QKV_ROPE: launchbf<EPI_QKV_ROPE>(a, s); break;
+        case EPI_QKV_ROPE_AT: launchbf<EPI_QKV_ROPE_AT>(a, s); break;
         case EPI_POWER: launchbf<EPI_POWER>(a, s); break;       // A_FRAMES only through the pipelined kernel (K = 1024)
         case EPI_LOGMEL: launchbf<EPI_LOGMEL>(a, s); break;
         default: break;

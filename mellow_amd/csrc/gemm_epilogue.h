@@ -18,6 +18,12 @@ __device__ __forceinline__ void store4_bf16(__bf16* dst, const float (&v)[4]) {
 
 // C16: EPI_LINEAR stores C as bf16 (GemmArgs::c16).  AMX: a C3 output is an AMX image (GemmArgs::c3_fmt == 1: the fp8 kernel), else an APB
 // one (the f32x3 kernels).  Compile-time forms: each GEMM family carries only its own hand-over code and registers.
+// EPI_QKV_ROPE_AT is EPI_QKV_ROPE with the row's position counted from GemmArgs::pos0 (qkv_pos below); nothing else differs.
+template <int EPI>
+__device__ __forceinline__ int qkv_pos(const GemmArgs& g, int m) {
+    if constexpr (EPI == EPI_QKV_ROPE_AT) return g.pos0 + m % g.T;
+    else return m % g.T;
+}
 template <int WN, int EPI, bool C16 = false, bool AMX = false>
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[2][2], int pm, int pn, int wm, int wn,
                                               int lane, int BM, int BN, const float* rs_rows = nullptr) {
@@ -60,13 +66,13 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[2
                     }
             }
         }
-    } else if constexpr (EPI == EPI_QKV_ROPE) {
+    } else if constexpr (EPI == EPI_QKV_ROPE || EPI == EPI_QKV_ROPE_AT) {
         const int P = pn * WN + wn;
         if (P < g.q_heads + g.kv_heads) {
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi) {
                 const int m = pm * BM + wm * 64 + mi * 32 + (lane & 31);
-                const int t = (m < g.M ? m : g.M - 1) % g.T;
+                const int t = qkv_pos<EPI>(g, m < g.M ? m : g.M - 1);
 #pragma unroll
                 for (int gq = 0; gq < 4; ++gq) {
                     pre_a[mi][0][gq] = *reinterpret_cast<const float4*>(g.rope_cos + (int64_t)t * 32 + 8 * gq + 4 * h);
@@ -232,9 +238,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[2
                         }
                         *reinterpret_cast<float4*>(g.C + (int64_t)m * g.ldc + col) = make_float4(v[0], v[1], v[2], v[3]);
                     }
-                } else if constexpr (EPI == EPI_QKV_ROPE) {
+                } else if constexpr (EPI == EPI_QKV_ROPE || EPI == EPI_QKV_ROPE_AT) {
                     // P = head slot: [0,q_heads) query heads, then kv_heads key heads, then kv_heads value heads
-                    const int b = m / g.T, t = m % g.T;
+                    const int b = m / g.T, t = qkv_pos<EPI>(g, m);
                     if (P < g.q_heads + g.kv_heads) {
                         const float4 c4 = pre_a[mi][0][gq], s4 = pre_a[mi][1][gq];        // (t, i0 = 8 gq + 4 h: fetched up front)
                         const float c[4] = {c4.x, c4.y, c4.z, c4.w};

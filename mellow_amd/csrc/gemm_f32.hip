@@ -265,6 +265,7 @@ void launch_gemm(const GemmArgs& a, hipStream_t s) {
         case EPI_LOGMEL: launch_epi<EPI_LOGMEL>(a, s); break;
         case EPI_SWIGLU: launch_epi<EPI_SWIGLU>(a, s); break;
         case EPI_QKV_ROPE: launch_epi<EPI_QKV_ROPE>(a, s); break;
+        case EPI_QKV_ROPE_AT: launch_epi<EPI_QKV_ROPE_AT>(a, s); break;
         case EPI_LSE: launch_cfg<2, 2, EPI_LSE, 32>(a, s); break;       // the scoring head: the tiling of the storing head
     }
 }

@@ -21,7 +21,7 @@ void launch_pack_weight_pairs(const float* w0, const float* w1, int N, int K, in
                               int KP, hipStream_t s);
 
 enum { ACT_NONE = 0, ACT_GELU = 1, ACT_SIGMOID = 2 };
-enum { EPI_LINEAR = 0, EPI_POWER = 1, EPI_LOGMEL = 2, EPI_SWIGLU = 3, EPI_QKV_ROPE = 4, EPI_LSE = 5 };
+enum { EPI_LINEAR = 0, EPI_POWER = 1, EPI_LOGMEL = 2, EPI_SWIGLU = 3, EPI_QKV_ROPE = 4, EPI_LSE = 5, EPI_QKV_ROPE_AT = 6 };
 enum { A_PLAIN = 0, A_FRAMES = 1 };
 
 struct GemmArgs {
@@ -51,7 +51,8 @@ struct GemmArgs {
     const float* bn_alpha = nullptr;
     const float* bn_beta = nullptr;
     int apply_bn = 0;
-    // EPI_QKV_ROPE (rows m = b*T + t)
+    // EPI_QKV_ROPE (rows m = b*T + t).  EPI_QKV_ROPE_AT (a prefill that starts at position pos0 of its sequences: rows m = b*T + i
+    // are positions t = pos0 + i): RoPE row and K/V page slot t, q_out by row m
     float* q_out = nullptr;     // [M][q_heads*64]
     float* k_cache = nullptr;   // [B][kv_heads][Tmax][64] of this layer
     float* v_cache = nullptr;
@@ -71,6 +72,7 @@ struct GemmArgs {
     float* sk_ws = nullptr;
     int sk_tiles = 0, sk_max = 0;
     bool no_x3w = false;        // engine option "x3w" = 0: K = 96 launches stay on the LDS-DMA tile kernel (developer A/B, bit-identical)
+    int pos0 = 0;               // EPI_QKV_ROPE_AT only (it fills the alignment gap after no_x3w: no other field moves)
     float* ssq_out = nullptr;
     int ssq_parts = 0;
     // consumer side: every accumulator of row m is multiplied by 1 / sqrt(sum_p rs_ssq[m * rs_parts + p] / rs_dim + rs_eps)
@@ -352,6 +354,11 @@ void launch_gelu(const float* in, float* out, int64_t n, hipStream_t s);
 // prefix [B][389][576] from proj33 [2B][33][576] (clips 0..B-1 = audio1, B..2B-1 = audio2)
 void launch_prefix_assemble(const float* proj33, const float* embed, const int32_t* ids, int B, int text_len,
                             int sep_id, int vocab, float* prefix, unsigned long long* bad_id_word, hipStream_t s);
+// Q questions per example (mellow_generate_q), ids [B][Q][text_len]: the prefix rows of launch_prefix_assemble cut at position P
+// (P <= 260): head [B][P][576] = rows 0 .. P - 1 of example b (the clips only), tail [B * Q][260 - P + text_len][576] = rows P .. of
+// (example b, question j) at row b * Q + j.  A bad id is flagged with its row b * Q + j, as the plain call on B * Q examples would.
+void launch_prefix_assemble_q(const float* proj33, const float* embed, const int32_t* ids, int B, int Q, int text_len, int P,
+                              int sep_id, int vocab, float* head, float* tail, unsigned long long* bad_id_word, hipStream_t s);
 // out[i] = table[ids[i]] (rows of `width` floats, width % 4 == 0; ids clamped to [0, n_rows))
 void launch_gather_rows(const float* table, int width, const int32_t* ids, int n, int n_rows, float* out, hipStream_t s);
 // out [B][n][576] = in [B][T][576] rows from_pos .. from_pos + n - 1
@@ -369,6 +376,11 @@ void launch_downsample33(const float* proj33, int n, float* out, hipStream_t s);
 // o_scales != nullptr (fp8 mode): o_apb receives the AMX image (MXFP8, K = 576: 9 k64 steps) and o_scales its scale bytes
 void launch_prefill_attention(const float* q, const float* k_cache, const float* v_cache, float* o, void* o_apb, int B, int T,
                               int Tmax, bool x3, hipStream_t s, void* o_scales = nullptr, bool bf16_once = false, bool pages16 = false);
+// The same attention for the queries at positions [q0, T) only (q0 a multiple of 32, 0 < q0 < T): q, o and o_apb hold T - q0 rows per
+// example (row b * (T - q0) + t - q0); keys [0, t] come from the pages, where an earlier launch left positions [0, q0).  A query
+// visits the key tiles it visits in the whole-sequence launch, in the same order.  fp32 pages; x3 = the exact 3-way split kernel.
+void launch_prefill_attention_past(const float* q, const float* k_cache, const float* v_cache, float* o, void* o_apb, int B, int T,
+                                   int Tmax, int q0, bool x3, hipStream_t s);
 // ---- scoring (score.hip) ------------------------------------------------------------------------------------------
 // One thread per row folds the row's `groups` EPI_LSE partials in ascending group order: M = max, arg = its lowest column,
 // lse = M + log(sum_g s_g exp(m_g - M)), logprob = target logit - lse (0 for target -1).  out_argmax / out_lse / out_max may be

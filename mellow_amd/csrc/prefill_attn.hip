@@ -20,161 +20,29 @@ constexpr int PA_KT_STRIDE = 33;   // transposed K tile row stride (floats): con
 // softmax weights on the hardware exp2 (x <= 0; ~1e-6 relative, inside fp32 summation-order noise); exp(-inf) = 0
 __device__ __forceinline__ float pa_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
 
+// The kernel body is prefill_attn_f32.inc, included once per kernel: the whole-sequence launch, and the launch for the queries at
+// positions [qpos0, T) only (launch_prefill_attention_past; qpos0 a multiple of 32).  There grid x counts the query tiles from qpos0
+// on, q / o / o_apb hold T - qpos0 rows per example, and everything else -- the key tiles a query walks and their order, the causal
+// mask, the T - 1 clamp -- is in global positions.
 __global__ __launch_bounds__(256) void prefill_attention_kernel(const float* __restrict__ q,
                                                                 const float* __restrict__ k_cache,
                                                                 const float* __restrict__ v_cache,
                                                                 float* __restrict__ o, i32x4* __restrict__ o_apb, uint8_t* __restrict__ o_sc, int T, int Tmax) {
-    // wave specialisation: waves 0..2 = the three query heads of kv head g (MFMA + softmax), wave 3 = loader: it owns
-    // the global -> LDS staging (K transposed, V row-major) of the NEXT key tile into the other LDS stage while the
-    // compute waves work, so they carry no staging registers (148 VGPRs -> three workgroups per CU) and never wait
-    // for a load.  (Pairing a long and a short query tile per workgroup was measured too: slower, the hardware's
-    // dynamic dispatch of 1248 unequal workgroups balances better than 672 equal ones.)
-    __shared__ __attribute__((aligned(16))) float Kt[2][64 * PA_KT_STRIDE];   // [stage][d][key]
-    __shared__ __attribute__((aligned(16))) float Vs[2][32 * 64];             // [stage][key][d]
-    // heavy tiles first: a query tile qt walks qt+1 key tiles (causal), so the long workgroups must not start last
-    const int qt = (int)gridDim.x - 1 - (int)blockIdx.x, g = blockIdx.y, b = blockIdx.z;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* kpage = k_cache + ((int64_t)b * 3 + g) * Tmax * 64;
-    const float* vpage = v_cache + ((int64_t)b * 3 + g) * Tmax * 64;
-
-    if (wave == 3) {
-        // ---------------- loader wave: 512 float4 per operand per tile = 8 + 8 per lane ----------------
-        f32x4 pk[8], pv[8];
-        auto fetch = [&](int kt) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int i = lane + 64 * j, key = i >> 4, quad = i & 15;
-                int t = kt * 32 + key;
-                t = t < T ? t : T - 1;
-                pk[j] = *reinterpret_cast<const f32x4*>(kpage + (int64_t)t * 64 + quad * 4);
-                pv[j] = *reinterpret_cast<const f32x4*>(vpage + (int64_t)t * 64 + quad * 4);
-            }
-        };
-        auto stage = [&](int st) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int i = lane + 64 * j, key = i >> 4, quad = i & 15;
-                Kt[st][(quad * 4 + 0) * PA_KT_STRIDE + key] = pk[j].x;
-                Kt[st][(quad * 4 + 1) * PA_KT_STRIDE + key] = pk[j].y;
-                Kt[st][(quad * 4 + 2) * PA_KT_STRIDE + key] = pk[j].z;
-                Kt[st][(quad * 4 + 3) * PA_KT_STRIDE + key] = pk[j].w;
-                *reinterpret_cast<f32x4*>(&Vs[st][key * 64 + quad * 4]) = pv[j];
-            }
-        };
-        fetch(0);
-        stage(0);
-        fetch(qt >= 1 ? 1 : 0);
-        __syncthreads();                                   // tile 0 visible
-        for (int kt = 0; kt <= qt; ++kt) {
-            stage((kt + 1) & 1);                           // tile kt+1 (or a harmless re-read past the end) -> other stage
-            fetch(kt + 2 <= qt ? kt + 2 : qt);
-            __syncthreads();                               // compute waves are done with stage kt & 1; stage (kt+1) & 1 is visible
-        }
-        return;
-    }
-
-    // ---------------- compute waves ----------------
-    const int hq = 3 * g + wave;
-    const int h = lane >> 5, ql = lane & 31;
-    const int q0 = qt * 32;
-    const int qi = q0 + ql;                              // this lane's query position
-    const int qc = qi < T ? qi : T - 1;
-    // Q as MFMA B operand: step s holds Q[query][2s + h], pre-scaled by 1/8 (exact)
-    float qreg[32];
-    {
-        const float* qrow = q + ((int64_t)b * T + qc) * 576 + hq * 64 + h;
-#pragma unroll
-        for (int s = 0; s < 32; ++s) qreg[s] = qrow[2 * s] * 0.125f;
-    }
-    f32x16 O0, O1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { O0[r] = 0.f; O1[r] = 0.f; }
-    float m_run = -INFINITY, l_run = 0.f;
-    __syncthreads();                                       // tile 0 staged by the loader
-
-    for (int kt = 0; kt <= qt; ++kt) {
-        const int k0 = kt * 32;
-        const float* Kc = Kt[kt & 1];
-        const float* Vc = Vs[kt & 1];
-        // S^T[key][query] = sum_d K[key][d] Q[query][d]
-        f32x16 S;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) S[r] = 0.f;
-#pragma unroll
-        for (int s = 0; s < 32; ++s) {
-            const float a = Kc[(2 * s + h) * PA_KT_STRIDE + ql];
-            S = __builtin_amdgcn_mfma_f32_32x32x2f32(a, qreg[s], S, 0, 0, 0);
-        }
-        // lane: query ql, keys k0 + (r&3) + 8(r>>2) + 4h
-        float tmax = -INFINITY;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            if (key > qi) S[r] = -INFINITY;          // causal mask (only bites on the diagonal tile)
-            tmax = fmaxf(tmax, S[r]);
-        }
-        tmax = half_max(tmax);                       // the other 16 keys of this query live in lane ^ 32
-        const float m_new = fmaxf(m_run, tmax);      // finite: key k0 <= q0 <= qi is never masked
-        const float alpha = pa_exp(m_run - m_new);   // exp(-inf) = 0 on the first tile
-        float rsum = 0.f;
-        float p[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            p[r] = pa_exp(S[r] - m_new);
-            rsum += p[r];
-        }
-        rsum = half_sum(rsum);
-        l_run = l_run * alpha + rsum;
-        m_run = m_new;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { O0[r] *= alpha; O1[r] *= alpha; }
-        // O^T[d][query] += sum_key V[key][d] P^T[key][query]
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int key = (r & 3) + 8 * (r >> 2) + 4 * h;
-            const float a0 = Vc[key * 64 + ql];
-            const float a1 = Vc[key * 64 + 32 + ql];
-            O0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, p[r], O0, 0, 0, 0);
-            O1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, p[r], O1, 0, 0, 0);
-        }
-        __syncthreads();                                   // done with stage kt & 1; the next tile is visible
-    }
-    if (qi < T) {
-        const float inv = 1.0f / l_run;
-        if (o_sc) {       // fp8 mode: the o_proj is gemm_mx8_kernel -- the row as MXFP8 in AMX order (K = 576: blocks 2 hq, 2 hq + 1)
-            const int64_t m = (int64_t)b * T + qi;
-            float v[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = O0[r] * inv;
-            amx_store_block(o_apb, o_sc, m, hq * 2, 9, 3, v, h);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = O1[r] * inv;
-            amx_store_block(o_apb, o_sc, m, hq * 2 + 1, 9, 3, v, h);
-        } else
-        if (o_apb) {      // the o_proj is an x3q GEMM: write the row pre-split in APB order (K = 576: 72 column octets)
-            const int64_t m = (int64_t)b * T + qi;
-#pragma unroll
-            for (int gp = 0; gp < 2; ++gp) {
-                float X[4], Y[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { X[j] = O0[8 * gp + j] * inv; Y[j] = O0[8 * gp + 4 + j] * inv; }
-                apb_store_quads(o_apb, m, hq * 8 + 2 * gp, 36, X, Y, h);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { X[j] = O1[8 * gp + j] * inv; Y[j] = O1[8 * gp + 4 + j] * inv; }
-                apb_store_quads(o_apb, m, hq * 8 + 4 + 2 * gp, 36, X, Y, h);
-            }
-        } else {
-            float* orow = o + ((int64_t)b * T + qi) * 576 + hq * 64;
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const int d = 8 * gq + 4 * h;
-                *reinterpret_cast<float4*>(orow + d) =
-                    make_float4(O0[4 * gq] * inv, O0[4 * gq + 1] * inv, O0[4 * gq + 2] * inv, O0[4 * gq + 3] * inv);
-                *reinterpret_cast<float4*>(orow + 32 + d) =
-                    make_float4(O1[4 * gq] * inv, O1[4 * gq + 1] * inv, O1[4 * gq + 2] * inv, O1[4 * gq + 3] * inv);
-            }
-        }
-    }
+#define PA_TILE0
+#define PA_ROW(t) ((int64_t)b * T + t)
+#include "prefill_attn_f32.inc"
+#undef PA_TILE0
+#undef PA_ROW
+}
+// the same kernel for the queries at positions [qpos0, T) (launch_prefill_attention_past)
+__global__ __launch_bounds__(256) void prefill_attention_past_kernel(const float* __restrict__ q, const float* __restrict__ k_cache,
+                                                                     const float* __restrict__ v_cache, float* __restrict__ o,
+                                                                     i32x4* __restrict__ o_apb, uint8_t* __restrict__ o_sc, int T, int Tmax, int qpos0) {
+#define PA_TILE0 + (qpos0 >> 5)
+#define PA_ROW(t) ((int64_t)b * (T - qpos0) + ((t) - qpos0))
+#include "prefill_attn_f32.inc"
+#undef PA_TILE0
+#undef PA_ROW
 }
 
 // ----------------------------------------------------------------------------------------------------------------------------
@@ -225,13 +93,26 @@ __device__ __forceinline__ void pax_split(const float (&v)[8], i32x4 (&p)[NP]) {
 }
 // P16 (NP = 1 only; fp8 mode with bf16 K/V pages written by the q/k/v epilogue): the loader wave copies -- a 16-byte load of a key's
 // 8 dims IS a K slot, and the V slots are eight 8-byte loads transposed with v_perm_b32; no conversion, half the page bytes.
-template <int NP, bool P16>
+// Past... is empty (the whole-sequence launch: signature and code are those of the kernel without the pack) or one int qpos0: the
+// launch for the queries at positions [qpos0, T) only, as prefill_attention_past_kernel above.
+__device__ __forceinline__ int pa_first() { return 0; }
+__device__ __forceinline__ int pa_first(int v) { return v; }
+template <bool PAST> __device__ __forceinline__ int pa_tile(int local_tile, int qpos0) {
+    if constexpr (PAST) return local_tile + (qpos0 >> 5); else return local_tile;
+}
+// row of q / o / o_apb that holds position t of example b
+template <bool PAST> __device__ __forceinline__ int64_t pa_row(int b, int T, int t, int qpos0) {
+    if constexpr (PAST) return (int64_t)b * (T - qpos0) + (t - qpos0); else return (int64_t)b * T + t;
+}
+template <int NP, bool P16, typename... Past>
 __global__ __launch_bounds__(PAX_THREADS, MELLOW_PAX_MINW) void prefill_attention_x3_kernel(const float* __restrict__ q, const float* __restrict__ k_cache,
                                                                    const float* __restrict__ v_cache, float* __restrict__ o,
-                                                                   i32x4* __restrict__ o_apb, uint8_t* __restrict__ o_sc, int T, int Tmax) {
+                                                                   i32x4* __restrict__ o_apb, uint8_t* __restrict__ o_sc, int T, int Tmax, Past... past) {
+    constexpr bool PAST = sizeof...(Past) != 0;
+    static_assert(!(PAST && P16), "the launch with a past reads fp32 pages");
     __shared__ i32x4 Kp[2][4 * NP * 64];
     __shared__ i32x4 Vp[2][2 * 2 * NP * 64];
-    const int qt = (int)gridDim.x - 1 - (int)blockIdx.x, g = blockIdx.y, b = blockIdx.z;
+    const int qt = pa_tile<PAST>((int)gridDim.x - 1 - (int)blockIdx.x, pa_first(past...)), g = blockIdx.y, b = blockIdx.z;      // (global query tile)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* kpage = k_cache + ((int64_t)b * 3 + g) * Tmax * 64;
     const float* vpage = v_cache + ((int64_t)b * 3 + g) * Tmax * 64;
@@ -362,7 +243,7 @@ __global__ __launch_bounds__(PAX_THREADS, MELLOW_PAX_MINW) void prefill_attentio
             pax_split<NP>(v, qp[s]);
         }
     } else {
-        const float* qrow = q + ((int64_t)b * T + qc) * 576 + hq * 64 + 8 * h;
+        const float* qrow = q + pa_row<PAST>(b, T, qc, pa_first(past...)) * 576 + hq * 64 + 8 * h;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             const float4 a = *reinterpret_cast<const float4*>(qrow + 16 * s), c = *reinterpret_cast<const float4*>(qrow + 16 * s + 4);
@@ -464,7 +345,7 @@ __global__ __launch_bounds__(PAX_THREADS, MELLOW_PAX_MINW) void prefill_attentio
     if (qi < T) {
         const float inv = 1.0f / l_run;
         if (o_sc) {       // fp8 mode: the o_proj is gemm_mx8_kernel -- the row as MXFP8 in AMX order (K = 576: blocks 2 hq, 2 hq + 1)
-            const int64_t m = (int64_t)b * T + qi;
+            const int64_t m = pa_row<PAST>(b, T, qi, pa_first(past...));
             float v[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) v[r] = O0[r] * inv;
@@ -474,7 +355,7 @@ __global__ __launch_bounds__(PAX_THREADS, MELLOW_PAX_MINW) void prefill_attentio
             amx_store_block(o_apb, o_sc, m, hq * 2 + 1, 9, 3, v, h);
         } else
         if (o_apb) {
-            const int64_t m = (int64_t)b * T + qi;
+            const int64_t m = pa_row<PAST>(b, T, qi, pa_first(past...));
 #pragma unroll
             for (int gp = 0; gp < 2; ++gp) {
                 float X[4], Y[4];
@@ -486,7 +367,7 @@ __global__ __launch_bounds__(PAX_THREADS, MELLOW_PAX_MINW) void prefill_attentio
                 apb_store_quads(o_apb, m, hq * 8 + 4 + 2 * gp, 36, X, Y, h);
             }
         } else {
-            float* orow = o + ((int64_t)b * T + qi) * 576 + hq * 64;
+            float* orow = o + pa_row<PAST>(b, T, qi, pa_first(past...)) * 576 + hq * 64;
 #pragma unroll
             for (int gq = 0; gq < 4; ++gq) {
                 const int d = 8 * gq + 4 * h;
@@ -508,6 +389,15 @@ void launch_prefill_attention(const float* q, const float* k_cache, const float*
     else if (x3 && bf16_once) hipLaunchKernelGGL((prefill_attention_x3_kernel<1, false>), dim3(qtiles, 3, B), dim3(PAX_THREADS), 0, s, q, k_cache, v_cache, o, reinterpret_cast<i32x4*>(o_apb), sc, T, Tmax);
     else if (x3) hipLaunchKernelGGL((prefill_attention_x3_kernel<3, false>), dim3(qtiles, 3, B), dim3(PAX_THREADS), 0, s, q, k_cache, v_cache, o, reinterpret_cast<i32x4*>(o_apb), sc, T, Tmax);
     else hipLaunchKernelGGL(prefill_attention_kernel, dim3(qtiles, 3, B), dim3(256), 0, s, q, k_cache, v_cache, o, reinterpret_cast<i32x4*>(o_apb), sc, T, Tmax);
+}
+
+void launch_prefill_attention_past(const float* q, const float* k_cache, const float* v_cache, float* o, void* o_apb, int B, int T,
+                                   int Tmax, int q0, bool x3, hipStream_t s) {
+    if (q0 <= 0 || q0 >= T || q0 % 32 != 0) return;      // (the engine never asks for these)
+    const int qtiles = (T - q0 + 31) / 32;
+    uint8_t* no_sc = nullptr;      // (the MXFP8 hand-over is the fp8 mode's)
+    if (x3) hipLaunchKernelGGL((prefill_attention_x3_kernel<3, false, int>), dim3(qtiles, 3, B), dim3(PAX_THREADS), 0, s, q, k_cache, v_cache, o, reinterpret_cast<i32x4*>(o_apb), no_sc, T, Tmax, q0);
+    else hipLaunchKernelGGL(prefill_attention_past_kernel, dim3(qtiles, 3, B), dim3(256), 0, s, q, k_cache, v_cache, o, reinterpret_cast<i32x4*>(o_apb), no_sc, T, Tmax, q0);
 }
 
 }  // namespace mellow

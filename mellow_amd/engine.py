@@ -40,7 +40,8 @@ class EngineError(RuntimeError):
 
 _lib = None
 # symbols added without a new ABI minor (include/mellow_hip.h): detected by lookup, so that a library built before them still loads
-_ADDED_UNDER_MINOR_4 = ("mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse", "mellow_generate_n")
+_ADDED_UNDER_MINOR_4 = ("mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse", "mellow_generate_n",
+                        "mellow_generate_q")
 
 
 def load_library(path: Optional[str] = None):
@@ -73,6 +74,8 @@ def load_library(path: Optional[str] = None):
         "mellow_generate_scored": (ci, [vp, vp, vp, i64, vp, ci, ci, ci, cf, cf, C.c_uint64, C.c_int32, ci, ci, vp, vp, P(C.c_int32),
                                         P(C.c_int32), P(cf)]),
         "mellow_generate_n": (ci, [vp, vp, vp, i64, vp, ci, ci, ci, ci, cf, cf, C.c_uint64, C.c_int32, ci, ci, vp, vp, P(C.c_int32),
+                                   P(C.c_int32), P(cf)]),
+        "mellow_generate_q": (ci, [vp, vp, vp, i64, vp, ci, ci, ci, ci, cf, cf, C.c_uint64, C.c_int32, ci, ci, vp, vp, P(C.c_int32),
                                    P(C.c_int32), P(cf)]),
         "mellow_sample_logits": (ci, [vp, vp, ci, vp, ci, cf, cf, C.c_uint64, vp]),
         "mellow_logmel": (ci, [vp, vp, ci, i64, ci, vp]),
@@ -129,7 +132,7 @@ EXPORTED_SYMBOLS = (
     "mellow_engine_destroy", "mellow_engine_fork", "mellow_engine_load_tensor", "mellow_engine_finalize",
     "mellow_engine_num_required", "mellow_engine_required_key", "mellow_generate", "mellow_generate_sampled", "mellow_sample_logits", "mellow_logmel",
     "mellow_encode", "mellow_prefix", "mellow_lm_prefill", "mellow_lm_decode_step", "mellow_argmax", "mellow_embed_tokens", "mellow_lm_forward_logits",
-    "mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse", "mellow_generate_n",
+    "mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse", "mellow_generate_n", "mellow_generate_q",
     "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
     "mellow_prof_num_families", "mellow_prof_family_name", "mellow_prof_get", "mellow_last_phase_ms", "mellow_last_steps_enqueued", "mellow_last_row_repacks", "mellow_stft_is_fft", "mellow_prefill_parts", "mellow_abi_minor",
     "mellow_resample", "mellow_engine_set_precision", "mellow_engine_set_option", "mellow_engine_describe", "mellow_debug_gemm_fp8", "mellow_debug_gemm_f32", "mellow_debug_dec_head", "mellow_set_graph", "mellow_host_window_map", "mellow_host_pack_weight", "mellow_host_rope_tables",
@@ -347,10 +350,21 @@ class Engine:
         call spent bringing host arrays to the device (latency from audio in HOST memory).
         do_sample=False (default): greedy, the reference's result for every top_p / temperature.  do_sample=True: seeded
         nucleus sampling (include/mellow_hip.h mellow_generate_sampled); row b draws from the stream of global row
-        row_offset + b, so a shard or batch given its first row's offset reproduces the rows of one big call."""
+        row_offset + b, so a shard or batch given its first row's offset reproduces the rows of one big call.
+        input_ids of shape [B][Q][text_len] (3-D): Q questions about every example from one encode and one prefill of the clips'
+        positions per example (mellow_generate_q).  Every array has B * Q rows, row b * Q + j = question j of example b, and holds
+        what this call returns for the B * Q expanded examples (audio rows repeated Q times, ids flattened) with the same seed and
+        row_offset (bit-equal in "f32").  At most 1024 rows per call; not together with num_return_sequences > 1."""
         import time
         t_in = time.perf_counter()
         nseq = int(num_return_sequences)
+        if (input_ids.ndim if hasattr(input_ids, "ndim") else np.ndim(input_ids)) == 3:
+            if nseq != 1:
+                raise ValueError("num_return_sequences > 1 and several questions per example do not combine: ask each question in a "
+                                 "call of its own with num_return_sequences, or repeat the question in the list")
+            return self._generate_multiq(audio1, audio2, input_ids, int(max_len), float(top_p), float(temperature), int(stop_id),
+                                         bool(ignore_stop), bool(do_sample), _seed64(seed) if do_sample else 0,
+                                         int(row_offset) if do_sample else 0, bool(return_logprobs), t_in)
         if nseq != 1:
             if nseq < 1:
                 raise ValueError(f"num_return_sequences must be >= 1 (got {nseq})")
@@ -426,6 +440,38 @@ class Engine:
         self.last_first_token_host_ms = t_up + ftm0
         res = (toks, lens, steps_all, ftm0)
         return res + (lps,) if return_logprobs else res
+
+    def _generate_multiq(self, audio1, audio2, input_ids, max_len, top_p, temperature, stop_id, ignore_stop, do_sample, seed, row_offset,
+                         return_logprobs, t_in):
+        """generate() with input_ids [B][Q][text_len]: one mellow_generate_q call on B * Q <= 1024 rows."""
+        import time
+        self._need("mellow_generate_q")
+        a1, a2, ids = self._f32(audio1), self._f32(audio2), self._prompt_ids(input_ids)
+        B, ns = a1.shape
+        assert a2.shape == a1.shape and ids.dim() == 3 and ids.shape[0] == B and ids.shape[2] == spec.TEXT_LEN, (a1.shape, a2.shape, ids.shape)
+        Q = int(ids.shape[1])
+        if Q < 1:
+            raise ValueError("every example needs at least one question (input_ids [B][0][text_len])")
+        N = B * Q
+        if N > NSEQ_PASS_ROWS:
+            raise ValueError(f"{B} examples x {Q} questions = {N} answer rows exceed the {NSEQ_PASS_ROWS} one call takes: split the "
+                             "examples over several calls, advancing row_offset by Q per example")
+        if Q > 1 and self.precision == "fp8":
+            raise ValueError('several questions per example are not available with precision="fp8": the bf16 K/V pages of that mode '
+                             "have no fan-out (pass the pair once per question instead)")
+        out = torch.empty((N, max_len), dtype=torch.int32, device=self.tdev)
+        lp = torch.empty((N, max_len), dtype=torch.float32, device=self.tdev) if return_logprobs else None
+        self._sync_inputs()
+        t_up = (time.perf_counter() - t_in) * 1e3
+        lens = (C.c_int32 * N)()
+        steps, ftm = C.c_int32(0), C.c_float(0.0)
+        self._chk(self.lib.mellow_generate_q(self.h, _ptr(a1), _ptr(a2), ns, _ptr(ids), B, Q, max_len, 1 if do_sample else 0, top_p,
+                                             temperature, seed, row_offset, stop_id, 1 if ignore_stop else 0, _ptr(out),
+                                             None if lp is None else _ptr(lp), lens, C.byref(steps), C.byref(ftm)))
+        toks = out.cpu().numpy()[:, : steps.value]
+        self.last_first_token_host_ms = t_up + float(ftm.value)
+        res = (toks, np.asarray(list(lens), dtype=np.int32), int(steps.value), float(ftm.value))
+        return res + (lp.cpu().numpy()[:, : steps.value],) if return_logprobs else res
 
     def stft_is_fft(self) -> bool:
         """the STFT runs as an FFT (f32x3 mode, windowed-DFT conv weights) instead of the DFT GEMM"""

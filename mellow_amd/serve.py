@@ -15,6 +15,7 @@ import threading
 from concurrent.futures import ThreadPoolExecutor
 from typing import Dict, List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from .engine import Engine
@@ -62,13 +63,15 @@ class EnginePool:
         """batches: sequence of (audio1, audio2, input_ids); returns the per-batch results of Engine.generate, in order.
         With do_sample=True batch k samples as rows row_offset + (rows of the batches before it) of one concatenated list,
         so the result does not depend on how many contexts run the batches or which one gets which (num_return_sequences=n: every
-        example counts n rows).
+        example counts n rows; input_ids [B][Q][text_len]: every example counts Q rows).
         Every keyword of Engine.generate passes through (return_logprobs=True: five values per batch)."""
         kws = [kw] * len(batches)
         if kw.get("do_sample"):
             off, kws = int(kw.get("row_offset", 0)), []
             for b in batches:
                 kws.append(dict(kw, row_offset=off))
-                off += int(len(b[0])) * int(kw.get("num_return_sequences", 1))      # n answer rows per example
+                ids = b[2]
+                q = int(ids.shape[1]) if (ids.ndim if hasattr(ids, "ndim") else np.ndim(ids)) == 3 else 1
+                off += int(len(b[0])) * int(kw.get("num_return_sequences", 1)) * q      # n answer rows, or Q questions, per example
         futs = [self._pool.submit(self._run, i % len(self.engines), b, kws[i]) for i, b in enumerate(batches)]
         return [f.result() for f in futs]

@@ -26,6 +26,13 @@ of n strings (with return_logprobs=True: of n dicts, so `max(out[i], key=lambda 
 voting or re-ranking.  Log-mel, encoder, projection and the LM prefill run ONCE per example; the prefix K/V is copied to the n answer
 rows, which then decode like n rows of a batch (include/mellow_hip.h mellow_generate_n).  Answer j of example i draws from the random
 stream of global row i * n + j: the answers are those of the same call on a list that holds every example n times in a row.
+Extension: the third element of an example may be a list (or tuple) of prompts, several questions about the one pair of clips:
+`generate([[a, b, ["what differs?", "caption both"]]], ...)` returns, per example, the list of answers in question order (greedy,
+do_sample and return_logprobs all apply).  Log-mel, encoder and projection run ONCE per example, and so does the LM prefill of the
+256 prefix positions that depend on the clips only; their K/V is copied to the example's answer rows, and only the remaining 133
+positions are prefilled per question (include/mellow_hip.h mellow_generate_q).  Question counts may differ between examples.  Answer j
+of example i draws from the random stream of global row i * Q + j (Q = the largest count): the answers are those of the same call on a
+list that holds the pair once per question.  Not combined with num_return_sequences > 1, data parallelism or precision="fp8".
 Extension: `score(examples, candidates)` returns the teacher-forced log-probability of given answer strings and
 `choose(examples, candidates)` the index of the likeliest one (multiple-choice ranking, re-ranking of sampled answers); the LM
 head of that path reduces its logits to log-softmax statistics on the fly (include/mellow_hip.h mellow_score).
@@ -250,10 +257,13 @@ class MellowWrapper:
 
     def _generate_batch(self, audio1, audio2, input_ids, entry_length=300, top_p=0.8, temperature=1.0,
                         stop_token: str = "<|endoftext|>", n_total: Optional[int] = None, do_sample: bool = False,
-                        seed: Optional[int] = None, row_offset: int = 0, return_logprobs: bool = False, nseq: int = 1):
+                        seed: Optional[int] = None, row_offset: int = 0, return_logprobs: bool = False, nseq: int = 1,
+                        counts: Optional[Sequence[int]] = None):
         """Tokens for the rows given (this rank's shard under data parallelism), decoded for ALL `n_total` examples:
         the shards' token ids are all-gathered once (mellow_amd.dist, RCCL over xGMI under backend "nccl").
-        nseq > 1: nseq answer rows per example (row_offset counts rows); the result is nested, one list of nseq per example."""
+        nseq > 1: nseq answer rows per example (row_offset counts rows); the result is nested, one list of nseq per example.
+        counts (question lists; one rank only): input_ids is [B][Q][text_len], example i asked counts[i] <= Q questions and the
+        rest of its Q rows is padding; the result is nested, one list of counts[i] answers per example."""
         stop_token_index = self.tokenizer.encode(stop_token)[0]
         entry_length = self._clamp_max_len(int(entry_length))
         rank, world = self._dp()
@@ -268,6 +278,8 @@ class MellowWrapper:
                                                                        return_logprobs=True, **samp)
                 self.last_first_token_ms = ftm
                 res = self._scored_results(toks, logprobs, stop_token_index)
+                if counts is not None:
+                    return self._per_question(res, counts, int(input_ids.shape[1]))
                 return res if nseq == 1 else [res[i:i + nseq] for i in range(0, len(res), nseq)]
             toks, lens, steps, ftm = self.model.generate(audio1, audio2, input_ids, max_len=entry_length, top_p=top_p,
                                                          temperature=temperature, stop_id=stop_token_index, **samp)
@@ -286,7 +298,14 @@ class MellowWrapper:
         # -1 = never computed: padding of shards that stopped earlier, or steps after a whole 32-row block had stopped
         rows = [r[r >= 0] for r in toks]
         texts = [self.tokenizer.decode(x).split("<|endoftext|>")[0] for x in rows]
+        if counts is not None:
+            return self._per_question(texts, counts, int(input_ids.shape[1]))
         return texts if nseq == 1 else [texts[i:i + nseq] for i in range(0, len(texts), nseq)]
+
+    @staticmethod
+    def _per_question(rows, counts, Q: int):
+        """rows of the padded [B][Q] layout -> per example the answers to its own counts[i] questions (the padding is dropped)"""
+        return [rows[i * Q:i * Q + int(c)] for i, c in enumerate(counts)]
 
     def _scored_results(self, toks, logprobs, stop_id: int):
         """One dict per row of a generate(return_logprobs=True) call.  The counted tokens are those before the row's first stop id
@@ -310,7 +329,9 @@ class MellowWrapper:
                  do_sample: bool = False, seed: Optional[int] = None, return_logprobs: bool = False,
                  num_return_sequences: int = 1):
         r"""Produces text response for the given audio files and text prompts
-        examples: (list<list>) each example is [audio path 1, audio path 2, text prompt]
+        examples: (list<list>) each example is [audio path 1, audio path 2, text prompt]; the text prompt may be a list or tuple of
+                     prompts, several questions about the one pair of clips (module docstring).  If any example has a list, the
+                     result holds, per example, a list of answers in question order (one answer for an example with a plain string).
         max_len: (int) maximum length for text generation
         top_p, temperature: accepted for API parity; decoding is greedy (see module docstring) unless do_sample
         do_sample, seed: opt-in seeded nucleus sampling (module docstring); seed=None draws one (kept as `last_seed`)
@@ -341,6 +362,9 @@ class MellowWrapper:
         if nseq > 1024:
             raise ValueError(f"num_return_sequences = {nseq} exceeds the 1024 answer rows one pass of the engine takes")
         rank, world = self._dp()
+        if any(isinstance(tp, (list, tuple)) for tp in text_prompts):
+            return self._generate_questions(audio_paths1, audio_paths2, text_prompts, max_len, top_p, temperature, stop_token,
+                                            audio_resample, do_sample, seed, return_logprobs, nseq)
         if return_logprobs and world > 1:
             raise NotImplementedError("generate(return_logprobs=True) is not sharded over data-parallel ranks: call it on one rank (or with data_parallel off)")
         n = len(examples)
@@ -372,6 +396,40 @@ class MellowWrapper:
         return self._generate_batch(audio1, audio2, ids, entry_length=max_len, top_p=top_p,
                                     temperature=temperature, stop_token=stop_token, n_total=n, do_sample=do_sample,
                                     seed=seed, row_offset=lo * nseq, return_logprobs=return_logprobs, nseq=nseq)
+
+    def _generate_questions(self, audio_paths1, audio_paths2, text_prompts, max_len, top_p, temperature, stop_token, audio_resample,
+                            do_sample, seed, return_logprobs, nseq):
+        """generate() with a list of prompts in at least one example.  Every example gets Q = the largest question count of the
+        call; one with fewer is padded by repeating its first question (as _candidate_ids pads candidates) and the padded answers
+        are dropped.  Answer j of example i is global row i * Q + j of that layout: the row its random stream is keyed by."""
+        questions = [list(tp) if isinstance(tp, (list, tuple)) else [tp] for tp in text_prompts]
+        if any(len(q) == 0 for q in questions):
+            raise ValueError("an example has an empty list of questions")
+        if nseq > 1:
+            raise ValueError("num_return_sequences > 1 and question lists do not combine: ask the question in a call of its own with "
+                             "num_return_sequences, or repeat it in the list")
+        rank, world = self._dp()
+        if world > 1:
+            raise NotImplementedError("question lists are not sharded over data-parallel ranks: call generate on one rank (or with "
+                                      "data_parallel off), or pass the pair once per question")
+        counts = [len(q) for q in questions]
+        B, Q = len(questions), max(counts)
+        if Q > 1 and getattr(self.model, "precision", None) == "fp8":
+            raise ValueError('question lists are not available with precision="fp8": the bf16 K/V pages of that mode have no fan-out '
+                             "(pass the pair once per question instead)")
+        if B * Q > 1024:
+            raise ValueError(f"{B} examples x {Q} questions = {B * Q} answer rows exceed the 1024 one call takes: split the examples "
+                             "over several calls")
+        if do_sample:
+            seed = random.getrandbits(63) if seed is None else int(seed)
+            self.last_seed = seed
+        flat = [q[j] if j < len(q) else q[0] for q in questions for j in range(Q)]
+        audio1 = self.preprocess_audio(audio_paths1, resample=audio_resample)
+        audio2 = self.preprocess_audio(audio_paths2, resample=audio_resample)
+        ids = self.preprocess_text(flat)["input_ids"].reshape(B, Q, spec.TEXT_LEN)
+        return self._generate_batch(audio1, audio2, ids, entry_length=max_len, top_p=top_p, temperature=temperature,
+                                    stop_token=stop_token, n_total=B, do_sample=do_sample, seed=seed, row_offset=0,
+                                    return_logprobs=return_logprobs, counts=counts)
 
     # ---- scoring ------------------------------------------------------------------------------------------------
     def _candidate_ids(self, candidates, append_stop: bool, stop_token: str):
