@@ -53,7 +53,8 @@ extern "C" {
  *     changed): a binding that must also load an older minor-4 library detects them by symbol lookup (dlsym), not by the number.
  *     mellow_generate_scored and mellow_debug_dec_head_lse (log-probs of the generated tokens) were added the same way, and so
  *     was mellow_generate_n (n sampled answers per example from one encode and one prefill), and then mellow_generate_q (several
- *     questions per example from one encode and one prefill of the clips' positions). */
+ *     questions per example from one encode and one prefill of the clips' positions), and then mellow_generate_beam with its tap
+ *     mellow_beam_select (beam search inside the decode step). */
 #define MELLOW_ABI_MINOR 4
 
 typedef struct mellow_engine mellow_engine_t;
@@ -249,6 +250,50 @@ int  mellow_generate_q(mellow_engine_t* e, const float* audio1, const float* aud
                        int B, int Q, int max_len, int do_sample, float top_p, float temperature, uint64_t seed, int32_t row_offset,
                        int stop_id, int ignore_stop, int32_t* out_tokens, float* out_logprob, int32_t* out_len, int32_t* out_steps,
                        float* first_token_ms);
+/* Beam search: B examples, k beams each, N = B * k rows, row b * k + j = beam j of example b; 1 <= k <= 8 and N <= 1024.  ONE
+ * encoder pass and ONE LM prefill per example, as in mellow_generate_n (prefix buffer, fan-out copy with n = k, row table); the
+ * selection and the K/V hand-over below run inside the captured decode step.  audio1 / audio2 / input_ids describe the B examples.
+ *
+ * Definition.
+ *   State per row: cum (fp32, the sum of the log-probs of the row's tokens) and fin (0 / 1, set when the row's last token was the
+ *   stop id).  Initially cum = 0 for j = 0 and -inf for j > 0, fin = 0: the first selection expands one beam into k distinct tokens.
+ *   A step: step s = 0 is the prefill's logits, steps s >= 1 are the decode steps.  An unfinished row r with fp32 logits l offers,
+ *   for every token i, the candidate (parent = r, token = i) with value c = cum[r] + (l_i - lse(l)); lse = M + log S, M = max l,
+ *   S = sum exp(l_i - M) added in one fixed order (no float atomics), everything in fp32 except the one logarithm (fp64, rounded
+ *   once).  A finished row offers exactly one candidate, (r, stop_id) with c = cum[r] and log-prob increment 0: it stays finished.
+ *   Selection: the new beams 0 .. k - 1 of an example are its k best candidates in the order c descending, then parent ascending,
+ *   then token ascending.  A NaN candidate ranks as the arg-max kernel ranks a NaN: it is the maximum, and several NaNs rank by
+ *   (parent, token) ascending.  A NaN logit makes lse, and with it EVERY candidate of its row, NaN; a row whose maximum is +-inf
+ *   likewise.  Values that are equal AS fp32 numbers tie (two tokens of a row whose logits differ by less than the rounding of c
+ *   tie on c and rank by token).
+ *   Record: per (step, row) the step writes parent (0 .. k - 1, the beam index inside the example), token and lp (the increment)
+ *   into tables [max_len][N]; a fourth table holds cum after the step.  The caller backtracks the tables; no token record is
+ *   permuted on the device.
+ *   K/V ownership: after the selection of step s >= 1, row r's pages hold its parent's K/V at positions [T, T + s - 1] (T =
+ *   prefix_len) for every layer and kv head; position T + s - 1 was appended by this step's attention launch.  Rows whose parent is
+ *   another row gather that span from the parent's pages into a staging buffer [layer][N][3][max_len][64] per tensor and scatter it
+ *   into their own (a parent can itself be overwritten in the same step: never in place); rows that keep their page move nothing.
+ *   Positions below T are identical across an example's rows after the fan-out and never move.
+ *   End: the loop ends after the first step at which every row of every example is finished, or at max_len; ignore_stop != 0 (or a
+ *   stop_id no token has, e.g. -1) means nothing ever finishes.  The count of finished rows can fall as well as rise (a finished
+ *   beam can be displaced), so the kernel that finishes a step publishes the CURRENT count with the step ticket; the host follows
+ *   it one step behind without synchronising, and at most one step is enqueued past the deciding one.
+ * Outputs (host or device memory): out_parent / out_token i32 [max_len][N] and out_lp f32 [max_len][N], rows 0 .. *out_steps - 1
+ * written; out_cum f32 [N] = cum after step *out_steps - 1 (the hypotheses' log-probs; during the search the beams compete on this
+ * raw sum -- length penalties and the final ranking are the caller's, from the tables).  *out_steps = steps counted by the rule
+ * above.  k = 1 is the greedy call with frozen finished rows.
+ * Errors: k < 1 or k > 8; B * k > 1024 (the caller splits its examples); k > 1 with B * k * max_len > 65536 (the staging bound:
+ * 30 layers x 65536 x 3 x 64 fp32 = 1.5 GB per tensor); k > 1 on an MELLOW_PRECISION_FP8 engine (its bf16 K/V pages have no
+ * fan-out); a vocabulary other than 49152 (the row tiling of the sampler); and every error of mellow_generate.
+ * Added under minor 4 like the scoring symbols: a binding detects it by symbol lookup. */
+int  mellow_generate_beam(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples, const int32_t* input_ids,
+                          int B, int k, int max_len, int stop_id, int ignore_stop, int32_t* out_parent, int32_t* out_token,
+                          float* out_lp, float* out_cum, int32_t* out_steps, float* first_token_ms);
+/* The same selection on caller data, no loop state (numeric tap): logits dev f32 [B * k][vocab], cum dev f32 [B * k], fin dev i32
+ * [B * k] -> out_parent / out_token dev i32 [B * k], out_cum / out_lp dev f32 [B * k] (row b * k + j = the new beam j of example b).
+ * Added under minor 4 with mellow_generate_beam. */
+int  mellow_beam_select(mellow_engine_t* e, const float* logits, const float* cum, const int32_t* fin, int B, int k, int stop_id,
+                        int32_t* out_parent, int32_t* out_token, float* out_cum, float* out_lp);
 /* The same draw on caller logits, no loop state (numeric tap): logits dev [B][vocab], row_ids dev i32 [B] (global row index
  * of each row; NULL = 0..B-1), step = t above -> tokens dev i32 [B]. */
 int  mellow_sample_logits(mellow_engine_t* e, const float* logits, int B, const int32_t* row_ids, int step, float top_p,

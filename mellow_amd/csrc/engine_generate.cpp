@@ -18,6 +18,11 @@ struct GenRequest {
     float* out_logprob;                          // dev f32 [rows][max_len], the log-prob of every recorded token; null: not recorded
     int32_t *out_len, *out_steps;
     float* first_token_ms;
+    // beam search (mellow_generate_beam): beam = k >= 1 beams per example, carried in n as the rows per example are; out_tokens /
+    // out_logprob are then the token / increment tables [max_len][rows], out_parent the parent table and out_cum [rows]
+    int beam = 0;
+    int32_t* out_parent = nullptr;
+    float* out_cum = nullptr;
     int rows() const { return examples * n * q; }
     // rows [r0, r0 + nb) of an n = 1, q = 1 request as a request of their own; a row's random stream follows its index in the whole call
     GenRequest pass(int r0, int nb, int text_len, int32_t* steps, float* ftm) const {
@@ -31,7 +36,8 @@ struct GenRequest {
         return p;
     }
 };
-enum { DOOR_SCORED = 1, DOOR_N = 2, DOOR_Q = 4 };     // what a rule of one entry point needs to know: mellow_generate_scored, mellow_generate_n, mellow_generate_q
+enum { DOOR_SCORED = 1, DOOR_N = 2, DOOR_Q = 4, DOOR_BEAM = 8 };     // what a rule of one entry point needs to know: mellow_generate_scored, mellow_generate_n, mellow_generate_q, mellow_generate_beam
+constexpr int64_t kBeamStageRows = 65536;        // B * k * max_len a beam call may stage: 30 layers x 65536 x 3 x 64 fp32 = 1.5 GB per tensor
 constexpr int kPassRows = 1024;                  // rows of one pass: 32 row blocks of loop state
 
 static int check_sampling(mellow_engine_t* e, float top_p, float temperature) {
@@ -47,12 +53,17 @@ static void stage_sampling(mellow_engine_t* e, float top_p, float temperature, u
     memcpy(&w[SMP_TOP_P], &top_p, 4); memcpy(&w[SMP_TEMP], &temperature, 4); w[SMP_STEP] = (uint32_t)step;
 }
 
-// Every argument rule of the five entry points, each once.
+// Every argument rule of the six entry points, each once.
 static int check_request(mellow_engine_t* e, const GenRequest& r, int door) {
     if (!e || !e->finalized) return fail("engine not finalized");
     if (r.n < 1) return fail("n must be >= 1 (got %d)", r.n);
     if (r.q < 1) return fail("Q must be >= 1 (got %d)", r.q);
     if (r.n > 1 && r.q > 1) return fail("internal: n and Q are never both above 1");
+    if (door & DOOR_BEAM) {
+        if (r.beam < 1 || r.beam > BEAM_MAX_K) return fail("mellow_generate_beam takes 1 to %d beams per example (got k = %d)", BEAM_MAX_K, r.beam);
+        if (r.beam != r.n || r.q != 1 || r.on) return fail("internal: a beam request carries k in n and neither samples nor asks several questions");
+        if (!r.out_parent || !r.out_cum) return fail("null argument");
+    }
     if ((door & DOOR_N) && !r.on) return fail("mellow_generate_n needs do_sample != 0: %d greedy answers of one example are %d copies of one answer", r.n, r.n);
     if (!r.audio1 || !r.audio2 || !r.input_ids || !r.out_tokens || ((door & DOOR_SCORED) && !r.out_logprob)) return fail("null argument");
     if (r.examples <= 0 || r.max_len <= 0) return fail("B and max_len must be positive");
@@ -62,7 +73,20 @@ static int check_request(mellow_engine_t* e, const GenRequest& r, int door) {
     if ((door & DOOR_Q) && (int64_t)r.examples * r.q > kPassRows)
         return fail("mellow_generate_q takes at most 1024 answer rows per call: B * Q = %d * %d = %lld (split the examples over several calls, "
                     "advancing row_offset by Q per example)", r.examples, r.q, (long long)r.examples * r.q);
-    if (r.out_logprob && e->cfg.vocab_size % 32 != 0) return fail("the log-prob partials tile the vocabulary in groups of 32 columns (vocab %d)", e->cfg.vocab_size);
+    if (door & DOOR_BEAM) {
+        if ((int64_t)r.examples * r.beam > kPassRows)
+            return fail("mellow_generate_beam takes at most 1024 beam rows per call: B * k = %d * %d = %lld (split the examples over several calls)",
+                        r.examples, r.beam, (long long)r.examples * r.beam);
+        if (r.beam > 1 && (int64_t)r.examples * r.beam * r.max_len > kBeamStageRows)
+            return fail("mellow_generate_beam stages at most %lld rows x positions of K/V per call (1.5 GB per tensor): B * k * max_len = %d * %d * %d "
+                        "= %lld (split the examples over several calls, or lower max_len)", (long long)kBeamStageRows, r.examples, r.beam, r.max_len,
+                        (long long)r.examples * r.beam * r.max_len);
+        if (e->cfg.vocab_size != SAMPLE_MAX_V) return fail("the beam select is built for a vocabulary of %d (engine: %d)", SAMPLE_MAX_V, e->cfg.vocab_size);
+        if (r.beam > 1 && (e->opt.fp8 || e->opt.kv16))
+            return fail("mellow_generate_beam with k > 1 is not available in MELLOW_PRECISION_FP8: the bf16 K/V pages of that mode have no fan-out "
+                        "(k = 1 works; or sample and re-rank with mellow_generate_scored)");
+    }
+    if (r.out_logprob && !(door & DOOR_BEAM) && e->cfg.vocab_size % 32 != 0) return fail("the log-prob partials tile the vocabulary in groups of 32 columns (vocab %d)", e->cfg.vocab_size);
     if (r.n > 1 && (e->opt.fp8 || e->opt.kv16))
         return fail("mellow_generate_n with n > 1 is not available in MELLOW_PRECISION_FP8: the bf16 K/V pages of that mode have no fan-out "
                     "(n = 1 works; or pass every example n times to mellow_generate_sampled)");
@@ -121,6 +145,43 @@ static int wait_ticket(mellow_engine* e, unsigned want, unsigned* nseen) {
     }
 }
 
+// The steps a beam call counts: the loop ends after the first step at which every row is finished.  A row is finished after step
+// st exactly when its token there is the stop id (a finished row keeps offering it, an unfinished one that takes it finishes).
+static int beam_steps(const std::vector<int32_t>& tok, int N, int steps_done, int stop_id, bool ignore_stop) {
+    if (ignore_stop) return steps_done;
+    for (int st = 0; st < steps_done; ++st) {
+        int nfin = 0;
+        for (int row = 0; row < N; ++row) nfin += tok[(size_t)st * N + row] == stop_id;
+        if (nfin == N) return st + 1;
+    }
+    return steps_done;
+}
+
+// the end of a beam pass: the three tables and cum (after the last counted step) go to the caller; the host backtracks them
+static int finish_beam_pass(mellow_engine_t* e, const GenRequest& r, int N, int steps_done, double first_ms) {
+    hipStream_t s = e->stream;
+    const BeamArgs g = beam_args(e, N, r.beam);
+    const size_t tab = (size_t)r.max_len * N;
+    std::vector<int32_t> tok(tab);
+    HIPCHK(hipMemcpyAsync(tok.data(), g.out_token, tab * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    CHK(check_bad_id(e));
+    for (int i = 0; i < 3; ++i) HIPCHK(hipEventElapsedTime(&e->phase_ms[i], e->ev_phase[i], e->ev_phase[i + 1]));
+    const int steps = beam_steps(tok, N, steps_done, r.stop_id, r.ignore_stop != 0);
+    const size_t used = (size_t)steps * N;
+    HIPCHK(hipMemcpyAsync(r.out_parent, g.out_parent, used * sizeof(int32_t), hipMemcpyDefault, s));
+    HIPCHK(hipMemcpyAsync(r.out_tokens, g.out_token, used * sizeof(int32_t), hipMemcpyDefault, s));
+    HIPCHK(hipMemcpyAsync(r.out_logprob, g.out_lp, used * sizeof(float), hipMemcpyDefault, s));
+    HIPCHK(hipMemcpyAsync(r.out_cum, g.out_cum + (size_t)(steps - 1) * N, (size_t)N * sizeof(float), hipMemcpyDefault, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (r.first_token_ms) *r.first_token_ms = (float)first_ms;
+    e->last_steps_enqueued = steps_done;
+    e->cur_B = 0;
+    e->last_compactions = 0;
+    if (r.out_steps) *r.out_steps = steps;
+    return 0;
+}
+
 // one pass: r.examples examples, r.n answer rows or r.q questions each (both 1: every row is encoded and prefilled itself)
 static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
     const auto t_entry = std::chrono::steady_clock::now();
@@ -157,6 +218,20 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
         HIPCHK(hipMemcpyAsync(e->nseq_rows.p, e->h_nseq_rows.data(), 1024 * sizeof(int32_t), hipMemcpyHostToDevice, s));
     }
     CHK(ensure(e, e->out_tok, (size_t)Bp * max_len));
+    if (r.beam) {
+        // loop words and tables of the search, and (k > 1) the staging of the reorder; cum = 0 for beam 0 of an example, -inf for
+        // the others, nothing finished
+        e->beam_max_len = max_len;
+        CHK(ensure(e, e->beam_ws, 3 * 1024 + 3 * 1024 * BEAM_MAX_K + (size_t)4 * max_len * B));
+        if (r.beam > 1) {
+            const size_t fl = (size_t)e->cfg.num_layers * B * 3 * max_len * 64;
+            CHK(ensure(e, e->kstage, fl));
+            CHK(ensure(e, e->vstage, fl));
+        }
+        e->h_beam.assign(2048, 0.f);         // (a member: alive until the copy has run; words 1024 .. 2047 are fin = 0)
+        for (int row = 0; row < B; ++row) e->h_beam[row] = row % r.beam == 0 ? 0.f : -INFINITY;
+        HIPCHK(hipMemcpyAsync(e->beam_ws.p, e->h_beam.data(), 2048 * sizeof(float), hipMemcpyHostToDevice, s));
+    }
     HIPCHK(hipEventRecord(e->ev_phase[0], s));
     // loop state (the prefill's arg-max already records token 0 and publishes ticket 1)
     __atomic_store_n(e->h_progress, 0ull, __ATOMIC_RELEASE);
@@ -164,7 +239,7 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
     HIPCHK(hipMemsetAsync(e->d_nseen, 0, 3 * sizeof(int32_t), s));       // n_seen, arrive, ticket
     HIPCHK(hipMemsetAsync(e->d_seen, 0, 1024 * sizeof(int32_t), s));
     e->h_params[0] = max_len;
-    e->h_params[1] = stop_id;
+    e->h_params[1] = r.beam && r.ignore_stop ? -1 : stop_id;        // (beam search: no token is the stop id, so nothing ever finishes)
     HIPCHK(hipMemcpyAsync(e->d_params, e->h_params, 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
 #ifdef MELLOW_DEVPROBE
     static const bool dev_dead = getenv("MELLOW_DEV_DEAD_BLOCKS") != nullptr;    // developer probe: launch-chain floor of a step
@@ -176,8 +251,10 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
     // row never reached are -1 in the token record.
     StepMode m;
     m.logits = m.sample = r.on;         // the sampler reads the full logits rows
-    m.logprob = r.out_logprob != nullptr;
-    m.early_exit = dev_dead || (!r.ignore_stop && e->da.RB > 1);
+    m.logprob = r.out_logprob != nullptr && !r.beam;
+    m.beam = r.beam;
+    if (r.beam) m.logits = true;        // the select reads the full logits rows; every row runs every step: no early exit, no migration
+    m.early_exit = !r.beam && (dev_dead || (!r.ignore_stop && e->da.RB > 1));
     m.migrate = m.early_exit && !dev_dead && e->opt.row_migration;   // option "row_migration" = 0: block exit without repacking (developer A/B)
     if (m.logprob) {
         // the head's partial sums and the record; columns that are never computed stay exactly 0.0
@@ -270,6 +347,7 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
     }
     HIPCHK(hipEventRecord(e->ev_phase[3], s));
     HIPCHK(hipGetLastError());
+    if (r.beam) return finish_beam_pass(e, r, B, steps_done, first_ms);
     // host-side length bookkeeping (reference wrapper.py:247-254) on the engine-owned record
     std::vector<int32_t> toks((size_t)B * max_len);
     HIPCHK(hipMemcpyAsync(r.out_tokens, e->out_tok.p, toks.size() * sizeof(int32_t), hipMemcpyDefault, s));
@@ -399,6 +477,36 @@ int mellow_generate_q(mellow_engine_t* e, const float* audio1, const float* audi
                       float* first_token_ms) {
     return generate(e, {audio1, audio2, n_samples, input_ids, B, 1, Q, max_len, stop_id, ignore_stop, do_sample != 0, top_p, temperature, seed, row_offset,
                         out_tokens, out_logprob, out_len, out_steps, first_token_ms}, DOOR_Q);
+}
+
+// k beams per example from ONE encode and ONE prefill per example (include/mellow_hip.h states the semantics; beam.hip the kernels).
+// The step graph is one of its own: the mode is part of the key (the select replaces the arg-max, the reorder follows the head).
+int mellow_generate_beam(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples, const int32_t* input_ids,
+                         int B, int k, int max_len, int stop_id, int ignore_stop, int32_t* out_parent, int32_t* out_token,
+                         float* out_lp, float* out_cum, int32_t* out_steps, float* first_token_ms) {
+    GenRequest r{audio1, audio2, n_samples, input_ids, B, k, 1, max_len, stop_id, ignore_stop, false, 1.f, 1.f, 0, 0,
+                 out_token, out_lp, nullptr, out_steps, first_token_ms};
+    r.beam = k; r.out_parent = out_parent; r.out_cum = out_cum;
+    if (k < 1) return fail("mellow_generate_beam takes 1 to %d beams per example (got k = %d)", BEAM_MAX_K, k);      // (before the n >= 1 rule words it as n)
+    return generate(e, r, DOOR_BEAM | DOOR_SCORED);
+}
+
+int mellow_beam_select(mellow_engine_t* e, const float* logits, const float* cum, const int32_t* fin, int B, int k, int stop_id,
+                       int32_t* out_parent, int32_t* out_token, float* out_cum, float* out_lp) {
+    if (!e || !e->finalized) return fail("engine not finalized");
+    if (!logits || !cum || !fin || !out_parent || !out_token || !out_cum || !out_lp || B <= 0) return fail("bad argument");
+    if (k < 1 || k > BEAM_MAX_K) return fail("mellow_beam_select takes 1 to %d beams per example (got k = %d)", BEAM_MAX_K, k);
+    if ((int64_t)B * k > kPassRows) return fail("mellow_beam_select takes at most 1024 rows per call: B * k = %d * %d", B, k);
+    if (e->cfg.vocab_size != SAMPLE_MAX_V) return fail("the beam select is built for a vocabulary of %d (engine: %d)", SAMPLE_MAX_V, e->cfg.vocab_size);
+    HIPCHK(hipSetDevice(e->device));
+    CHK(ensure(e, e->beam_ws, 3 * 1024 + 3 * 1024 * BEAM_MAX_K));
+    BeamArgs g = beam_args(e, B * k, k);       // (the survivor words only: the outputs are the caller's)
+    g.logits = logits; g.cum_in = cum; g.fin_in = fin; g.cum_state = nullptr; g.fin_state = nullptr; g.stop_id = stop_id;
+    g.out_parent = out_parent; g.out_token = out_token; g.out_cum = out_cum; g.out_lp = out_lp;
+    launch_beam_select(g, B, DecArgs(), nullptr, nullptr, nullptr, e->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return 0;
 }
 
 int mellow_sample_logits(mellow_engine_t* e, const float* logits, int B, const int32_t* row_ids, int step, float top_p,

@@ -4,7 +4,8 @@
 //   engine_weights.cpp  mellow_engine_finalize: every reference checkpoint key -> device layouts (P / PB / P16 / e4m3, composed decode weights)
 //   engine_encoder.cpp  GEMM dispatch, front-end + HTSAT encoder (A1-A13), the taps mellow_logmel / mellow_encode / mellow_resample
 //   engine_lm.cpp       KV pages, LM prefill (A15), the decode step and its per-call mode, mellow_prefix / lm taps, scoring
-//   engine_generate.cpp the generation loop on top of it (A16): request + checks, passes, step graphs, the mellow_generate* entry points
+//   engine_generate.cpp the generation loop on top of it (A16): request + checks, passes, step graphs, the mellow_generate* entry points,
+//                       beam search (mellow_generate_beam, mellow_beam_select)
 //   engine_dev.cpp      developer entry points (GEMM timing / debug taps, kernel stamps)
 // The engine object (below): `Options` + `Weights` are what a fork shares, each copied by one assignment; everything else is one
 // context's own -- stream, events, workspaces (`Buf` frees itself), KV pages, loop words, the decode-graph cache (`StepGraphs`).
@@ -135,6 +136,7 @@ struct StepMode {
     bool logprob = false;        // head / arg-max / sampler in their LSE forms, log-probs recorded next to the tokens
     bool early_exit = false;     // per-row-block early exit (DecArgs::blk_live)
     bool migrate = false;        // ... with row migration (DecArgs::row_of_slot)
+    int beam = 0;                // k >= 1: beam search -- the select (beam.hip) in place of the arg-max, and for k > 1 the two K/V reorder launches after it
 };
 
 // One execution context.  `opt` and `w` are what a fork shares with its parent (copied whole by mellow_engine_fork); the rest is its own.
@@ -209,7 +211,7 @@ struct mellow_engine {
     // d_params, the sampling parameters in d_sparams).  generate_pass (engine_generate.cpp) captures, ensure_lm invalidates.
     struct LOCAL StepGraphs {
         struct Key {
-            std::array<uintptr_t, 9> v{};       // all zero: no capture (a pass has at least one row)
+            std::array<uintptr_t, 14> v{};       // all zero: no capture (a pass has at least one row)
             static Key of(const mellow_engine* e, int B);      // from the engine as configured for the pass (below the engine)
             bool operator==(const Key& k) const { return v == k.v; }
         };
@@ -281,6 +283,12 @@ struct mellow_engine {
     // [layer][examples][3][Tp][64] -- the prefill writes them here, kv_fanout_kernel copies them to the pages of every answer row
     // (source and destination never alias) -- and the source-row table of launch_dec_load_rows with its host staging
     Buf kprefix, vprefix, nseq_rows;
+    // mellow_generate_beam, created on first use: the loop words of the search (cum [1024] | fin [1024] | survivors per row [1024] |
+    // survivor values, tokens, increments [1024][8] each | tables parent, token, lp, cum [max_len][rows] each), its host staging, and
+    // the K/V staging of the reorder [layer][rows][3][max_len][64] per tensor (k > 1)
+    Buf beam_ws, kstage, vstage;
+    int beam_max_len = 0;                     // max_len the tables of beam_ws are laid out for
+    std::vector<float> h_beam;
     Buf lm_xq;                                // mellow_generate_q: the LM input of the tail prefill, [rows][prefix_len - P][hidden] (run_prefill_q)
     std::vector<int32_t> h_nseq_rows;
     int kv_B = 0, kv_Tmax = 0;                // current page geometry
@@ -319,7 +327,12 @@ inline mellow_engine::StepGraphs::Key mellow_engine::StepGraphs::Key::of(const m
                 (uintptr_t)e->da.row_of_slot,      // row table: the DecArgs of every launch, and whether dec_compact is in the step
                 (uintptr_t)e->mode.logprob,        // LSE forms of the head and of the arg-max / sampler
                 (uintptr_t)e->da.cand_sum,         // partial sums: DecArgs of the head and of the arg-max / sampler
-                (uintptr_t)(e->mode.logprob ? e->out_lp.p : nullptr)}};      // log-prob record: LoopArgs of the arg-max / sampler
+                (uintptr_t)(e->mode.logprob ? e->out_lp.p : nullptr),        // log-prob record: LoopArgs of the arg-max / sampler
+                (uintptr_t)e->mode.beam,           // beam search: the select in place of the arg-max, the reorder launches (k > 1)
+                (uintptr_t)(e->mode.beam ? e->beam_ws.p : nullptr),          // ... its loop words and tables: BeamArgs, the reorder's parent table
+                (uintptr_t)(e->mode.beam ? e->beam_max_len : 0),             // ... the table offsets inside beam_ws
+                (uintptr_t)(e->mode.beam > 1 ? e->kstage.p : nullptr),       // ... the staging buffers of the reorder
+                (uintptr_t)(e->mode.beam > 1 ? e->vstage.p : nullptr)}};
 }
 static_assert(!std::is_copy_constructible<mellow_engine::Buf>::value, "a Buf owns its device memory: it moves, it is never copied");
 static_assert(std::is_copy_assignable<mellow_engine::Weights>::value && std::is_copy_assignable<mellow_engine::Options>::value, "a fork copies these by assignment: no owning member (Buf, StepGraphs) belongs in them");
@@ -379,6 +392,8 @@ LoopArgs loop_args(mellow_engine* e);
 // sets e->mode and the DecArgs fields logits, cand_sum, blk_live, blk_snap, row_of_slot from it (cand_sum must be allocated for logprob)
 void apply_step_mode(mellow_engine* e, const StepMode& m);
 int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec);
+// the words of beam_ws (engine_internal.h, the member's comment) as the select takes them, tables laid out for e->beam_max_len
+BeamArgs beam_args(mellow_engine* e, int N, int k);
 // n > 1 (mellow_generate_n; fp32 pages only): the layers run on the B examples and write K/V to kprefix / vprefix; the fan-out and
 // everything from the last prefix row on (last layer, head, first token) run on B * n rows
 int run_prefill(mellow_engine* e, int B, int T, const RecordArgs* rec, bool all_positions = false, int n = 1);

@@ -132,6 +132,18 @@ LoopArgs loop_args(mellow_engine* e) {
     return lp;
 }
 
+BeamArgs beam_args(mellow_engine* e, int N, int k) {
+    float* w = e->beam_ws.p;
+    int32_t* wi = reinterpret_cast<int32_t*>(w);
+    const size_t tab = (size_t)e->beam_max_len * N, t0 = 3 * 1024 + 3 * 1024 * BEAM_MAX_K;
+    BeamArgs g;
+    g.logits = e->da.logits; g.ld = e->cfg.vocab_size; g.k = k; g.N = N;
+    g.cum_in = g.cum_state = w; g.fin_in = g.fin_state = wi + 1024; g.cand_n = wi + 2048;
+    g.cand_c = w + 3 * 1024; g.cand_tok = wi + 3 * 1024 + 1024 * BEAM_MAX_K; g.cand_lp = w + 3 * 1024 + 2 * 1024 * BEAM_MAX_K;
+    g.out_parent = wi + t0; g.out_token = wi + t0 + tab; g.out_lp = w + t0 + 2 * tab; g.out_cum = w + t0 + 3 * tab;
+    return g;
+}
+
 // final norm (+ pending down slabs) + lm_head with fused per-tile arg-max candidates -> dlogits, d_tokens
 int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec) {
     const int NT = e->cfg.vocab_size / 32, Bp = e->da.rows;
@@ -142,7 +154,10 @@ int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec)
       const DecW h = e->w.head_w();
       launch_dec_lm_head(dh(1), h.p, e->w.lm_head.KP / 8, e->cfg.vocab_size, e->stream, h.scale); }
     { ProfScope ps(e, PF_MISC, 0, 0);
-      if (e->mode.sample) {        // mellow_generate_sampled: the head stored the logits (da.logits); draw instead of the arg-max
+      if (e->mode.beam) {          // mellow_generate_beam: the head stored the logits; the k best continuations per example
+          const LoopArgs lp = loop_args(e);
+          launch_beam_select(beam_args(e, B, e->mode.beam), B / e->mode.beam, dh(2), e->d_tokens, e->w.embed, &lp, e->stream);
+      } else if (e->mode.sample) {        // mellow_generate_sampled: the head stored the logits (da.logits); draw instead of the arg-max
           SampleArgs sa;
           sa.logits = e->da.logits; sa.ld = e->cfg.vocab_size; sa.prm = e->d_sparams;
           launch_dec_sample(sa, dh(2), B, e->d_tokens, e->w.embed, (rec && rec->embed_next) ? 1 : 0, rec ? loop_args(e) : LoopArgs(),
@@ -430,6 +445,11 @@ int enqueue_decode_layer_range(mellow_engine* e, int B, int l_begin, int l_end, 
 int enqueue_decode_layers(mellow_engine* e, int B, const RecordArgs* rec) {
     CHK(enqueue_decode_layer_range(e, B, 0, e->cfg.num_layers, true));
     CHK(run_lm_head(e, B, DEC_KC_DOWN, rec));
+    if (e->mode.beam > 1) {      // every surviving row owns its parent's K/V before the next step's attention reads it
+        ProfScope ps(e, PF_MISC, 0, 0);
+        launch_beam_reorder(e->kcache.p, e->vcache.p, e->kstage.p, e->vstage.p, beam_args(e, B, e->mode.beam).out_parent, e->d_pos, e->d_params,
+                            e->cfg.prefix_len, e->cfg.num_layers, B, e->mode.beam, e->kv_B, e->kv_Tmax, e->stream);
+    }
     return 0;
 }
 

@@ -293,6 +293,32 @@ void launch_dec_sample(const SampleArgs& sa, const DecArgs& a, int B, int32_t* t
                        const LoopArgs& loop, hipStream_t s);
 // the same draw on caller rows, no loop state (mellow_sample_logits)
 void launch_sample_logits(const SampleArgs& sa, int B, int32_t* tokens, hipStream_t s);
+// Beam search (beam.hip; include/mellow_hip.h mellow_generate_beam states the exact definition).  N = B * k rows, row b * k + j =
+// beam j of example b.
+constexpr int BEAM_MAX_K = 8;
+struct BeamArgs {
+    const float* logits = nullptr;       // [N][ld] fp32 (ld = SAMPLE_MAX_V: the row tiling of the sampler)
+    int64_t ld = 0;
+    const float* cum_in = nullptr;       // [N] summed log-probs of the rows
+    const int32_t* fin_in = nullptr;     // [N] 0/1
+    float* cum_state = nullptr;          // loop: [N], rewritten by the merge (the same words as cum_in / fin_in); taps: unused
+    int32_t* fin_state = nullptr;
+    int k = 1, N = 0;
+    int stop_id = 0;                     // taps only: the loop reads LoopArgs::params[1]
+    // the rows' survivors, written by the row stage and read by the merge: [N][BEAM_MAX_K] each and the count per row [N]
+    float* cand_c = nullptr; int32_t* cand_tok = nullptr; float* cand_lp = nullptr; int32_t* cand_n = nullptr;
+    // loop: tables [max_len][N], written at row (*d_pos - T0 + 1); taps: [N]
+    int32_t* out_parent = nullptr; int32_t* out_token = nullptr; float* out_lp = nullptr; float* out_cum = nullptr;
+};
+// the selection of one step for B examples.  loop != null: in place of the arg-max of the decode step, with its bookkeeping (the
+// published count is the number of rows finished AFTER this step; LoopArgs::seen_stop / blk_* / row_of_slot are not used);
+// loop == null: the four outputs only (mellow_beam_select; a, tokens and embed are not read)
+void launch_beam_select(const BeamArgs& g, int B, const DecArgs& a, int32_t* tokens, const float* embed, const LoopArgs* loop, hipStream_t s);
+// after the selection of decode step s >= 1: every row whose parent (parent_tab[s][r], s = *d_pos - T0 + 1) is another row of its
+// example gets the parent's K/V at positions [T0, *d_pos] -- gathered into k_stage / v_stage [layers][N][3][params[0]][64], then
+// scattered into the row's own pages [layers][Bp][3][Tmax][64].  Two launches of fixed grid; k = 1 launches nothing.
+void launch_beam_reorder(float* k_pages, float* v_pages, float* k_stage, float* v_stage, const int32_t* parent_tab, const int32_t* d_pos,
+                         const int32_t* params, int T0, int layers, int N, int k, int Bp, int Tmax, hipStream_t s);
 // after the arg-max of a step (early-exit mode only): if the rows that have not produced the stop id yet fit into fewer 32-row
 // blocks than are live, move them (their next-step residual rows) to the lowest slots, rewrite row_of_slot / blk_left / blk_live
 void launch_dec_compact(const DecArgs& a, int B, const LoopArgs& loop, hipStream_t s);

@@ -41,7 +41,7 @@ class EngineError(RuntimeError):
 _lib = None
 # symbols added without a new ABI minor (include/mellow_hip.h): detected by lookup, so that a library built before them still loads
 _ADDED_UNDER_MINOR_4 = ("mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse", "mellow_generate_n",
-                        "mellow_generate_q")
+                        "mellow_generate_q", "mellow_generate_beam", "mellow_beam_select")
 
 
 def load_library(path: Optional[str] = None):
@@ -77,6 +77,8 @@ def load_library(path: Optional[str] = None):
                                    P(C.c_int32), P(cf)]),
         "mellow_generate_q": (ci, [vp, vp, vp, i64, vp, ci, ci, ci, ci, cf, cf, C.c_uint64, C.c_int32, ci, ci, vp, vp, P(C.c_int32),
                                    P(C.c_int32), P(cf)]),
+        "mellow_generate_beam": (ci, [vp, vp, vp, i64, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, P(C.c_int32), P(cf)]),
+        "mellow_beam_select": (ci, [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp]),
         "mellow_sample_logits": (ci, [vp, vp, ci, vp, ci, cf, cf, C.c_uint64, vp]),
         "mellow_logmel": (ci, [vp, vp, ci, i64, ci, vp]),
         "mellow_encode": (ci, [vp, vp, ci, i64, vp]),
@@ -133,7 +135,7 @@ EXPORTED_SYMBOLS = (
     "mellow_engine_num_required", "mellow_engine_required_key", "mellow_generate", "mellow_generate_sampled", "mellow_sample_logits", "mellow_logmel",
     "mellow_encode", "mellow_prefix", "mellow_lm_prefill", "mellow_lm_decode_step", "mellow_argmax", "mellow_embed_tokens", "mellow_lm_forward_logits",
     "mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse", "mellow_generate_n", "mellow_generate_q",
-    "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
+    "mellow_generate_beam", "mellow_beam_select", "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
     "mellow_prof_num_families", "mellow_prof_family_name", "mellow_prof_get", "mellow_last_phase_ms", "mellow_last_steps_enqueued", "mellow_last_row_repacks", "mellow_stft_is_fft", "mellow_prefill_parts", "mellow_abi_minor",
     "mellow_resample", "mellow_engine_set_precision", "mellow_engine_set_option", "mellow_engine_describe", "mellow_debug_gemm_fp8", "mellow_debug_gemm_f32", "mellow_debug_dec_head", "mellow_set_graph", "mellow_host_window_map", "mellow_host_pack_weight", "mellow_host_rope_tables",
 )
@@ -169,6 +171,70 @@ def plan_nseq_passes(B: int, n: int, row_offset: int = 0):
         raise ValueError(f"num_return_sequences = {n} exceeds the {NSEQ_PASS_ROWS} answer rows one pass of the engine takes")
     per = NSEQ_PASS_ROWS // n
     return [(lo, min(B, lo + per), row_offset + lo * n) for lo in range(0, B, per)]
+
+
+BEAM_MAX_K = 8                 # beams per example mellow_generate_beam takes
+BEAM_STAGE_ROWS = 65536        # B * k * max_len its K/V staging takes (1.5 GB per tensor)
+
+
+def check_beam_request(B: int, k: int, max_len: int, m: int = 1):
+    """the argument rules of a beam call that need no engine (the C entry repeats the first three)"""
+    B, k, max_len, m = int(B), int(k), int(max_len), int(m)
+    if k < 1 or k > BEAM_MAX_K:
+        raise ValueError(f"num_beams must be 1 .. {BEAM_MAX_K} (got {k})")
+    if m < 1 or m > k:
+        raise ValueError(f"num_return_sequences must be 1 .. num_beams = {k} with beam search (got {m})")
+    if B * k > NSEQ_PASS_ROWS:
+        raise ValueError(f"{B} examples x {k} beams = {B * k} rows exceed the {NSEQ_PASS_ROWS} one call takes: split the examples "
+                         "over several calls")
+    if k > 1 and B * k * max_len > BEAM_STAGE_ROWS:
+        raise ValueError(f"{B} examples x {k} beams x max_len {max_len} = {B * k * max_len} exceeds the {BEAM_STAGE_ROWS} rows x "
+                         "positions of K/V one beam call stages (1.5 GB per tensor): split the examples or lower max_len")
+
+
+def backtrack_beams(parent, token, lp, k: int):
+    """The sequences a beam search ended with, from its tables.  parent / token int [steps][N] and lp float [steps][N] as
+    mellow_generate_beam records them (N = B * k, row b * k + j = beam j of example b; parent[s][r] = the beam INDEX 0 .. k - 1
+    inside r's example that row r continued at step s).  -> (tokens int32 [N][steps], token_logprobs float64 [N][steps]): row r is
+    the history of the beam that sits in row r after the last step."""
+    parent, token, lp = np.asarray(parent), np.asarray(token), np.asarray(lp, dtype=np.float64)
+    steps, N = token.shape
+    k = int(k)
+    if k < 1 or N % k != 0 or parent.shape != token.shape or lp.shape != token.shape:
+        raise ValueError(f"tables of shape {parent.shape} / {token.shape} / {lp.shape} are not [steps][B * {k}]")
+    if steps and (int(parent.min()) < 0 or int(parent.max()) >= k):
+        raise ValueError(f"a parent index outside 0 .. {k - 1}")
+    toks = np.zeros((N, steps), dtype=np.int32)
+    lps = np.zeros((N, steps), dtype=np.float64)
+    base = np.arange(N) // k * k
+    cur = np.arange(N)
+    for s in range(steps - 1, -1, -1):
+        toks[:, s] = token[s, cur]
+        lps[:, s] = lp[s, cur]
+        cur = base + parent[s, cur]
+    return toks, lps
+
+
+def rank_beams(tokens, token_logprobs, cum, k: int, stop_id: int, length_penalty: float = 1.0, ignore_stop: bool = False):
+    """The final ranking of a beam search, on the host in fp64: tokens [N][steps] / token_logprobs [N][steps] from backtrack_beams,
+    cum [N] the hypotheses' summed log-probs.  A hypothesis holds its tokens up to and INCLUDING its first stop id (or all `steps`);
+    score = logprob / tokens ** length_penalty; an example's hypotheses are sorted by score descending, then beam index.
+    -> (order int [B][k] of beam indices, lengths int32 [N] = tokens before the stop id, counts int32 [N] = tokens of the hypothesis,
+    scores float64 [N]), the last three by row."""
+    tokens = np.asarray(tokens)
+    N, steps = tokens.shape
+    k = int(k)
+    lengths = np.full((N,), steps, dtype=np.int32)
+    if not ignore_stop:
+        hit = tokens == int(stop_id)
+        lengths = np.where(hit.any(axis=1), hit.argmax(axis=1), steps).astype(np.int32)
+    counts = np.minimum(lengths + 1, steps).astype(np.int32)
+    scores = np.asarray(cum, dtype=np.float64) / np.maximum(counts, 1).astype(np.float64) ** float(length_penalty)
+    order = np.zeros((N // k, k), dtype=np.int64)
+    for b in range(N // k):
+        sc = scores[b * k:(b + 1) * k]
+        order[b] = sorted(range(k), key=lambda j: (-sc[j] if sc[j] == sc[j] else np.inf, j))      # (a NaN score ranks last)
+    return order, lengths, counts, scores
 
 
 def _ptr(t: torch.Tensor) -> C.c_void_p:
@@ -337,7 +403,8 @@ class Engine:
     # ---- hot path ----------------------------------------------------------------------------------
     def generate(self, audio1, audio2, input_ids, max_len: int, top_p: float = 0.8, temperature: float = 1.0,
                  stop_id: int = 0, ignore_stop: bool = False, do_sample: bool = False, seed: Optional[int] = None,
-                 row_offset: int = 0, return_logprobs: bool = False, num_return_sequences: int = 1):
+                 row_offset: int = 0, return_logprobs: bool = False, num_return_sequences: int = 1,
+                 num_beams: Optional[int] = None, length_penalty: float = 1.0):
         """-> (tokens int32 [B, steps] on host, lengths [B], steps, first_token_ms)
         num_return_sequences = n > 1 (needs do_sample=True): n sampled answers per example from one encode and one prefill per
         example (mellow_generate_n).  Every array has B * n rows, row b * n + j = answer j of example b, and holds what this call
@@ -354,10 +421,23 @@ class Engine:
         input_ids of shape [B][Q][text_len] (3-D): Q questions about every example from one encode and one prefill of the clips'
         positions per example (mellow_generate_q).  Every array has B * Q rows, row b * Q + j = question j of example b, and holds
         what this call returns for the B * Q expanded examples (audio rows repeated Q times, ids flattened) with the same seed and
-        row_offset (bit-equal in "f32").  At most 1024 rows per call; not together with num_return_sequences > 1."""
+        row_offset (bit-equal in "f32").  At most 1024 rows per call; not together with num_return_sequences > 1.
+        num_beams = k (1 .. 8; None: not a beam call): beam search (mellow_generate_beam; include/mellow_hip.h states the search).
+        The m = num_return_sequences <= k best hypotheses per example are returned, m rows per example, best first: an example's
+        hypotheses are ranked by score = logprob / tokens ** length_penalty (tokens counts the stop id), then beam index.  tokens
+        [B * m, steps] hold a hypothesis up to its stop id and the stop id from there on; lengths as in the greedy call.
+        return_logprobs=True appends token_logprobs [B * m, steps] (0.0 after the stop id) and scores float64 [B * m].  Not
+        together with do_sample or several questions per example.  `last_beam` keeps the raw tables of the call."""
         import time
         t_in = time.perf_counter()
         nseq = int(num_return_sequences)
+        if num_beams is not None:
+            if do_sample:
+                raise ValueError("num_beams and do_sample=True do not combine: beam search is deterministic")
+            if (input_ids.ndim if hasattr(input_ids, "ndim") else np.ndim(input_ids)) == 3:
+                raise ValueError("num_beams and several questions per example do not combine: ask each question in a call of its own")
+            return self._generate_beam(audio1, audio2, input_ids, int(max_len), int(num_beams), nseq, float(length_penalty),
+                                       int(stop_id), bool(ignore_stop), bool(return_logprobs), t_in)
         if (input_ids.ndim if hasattr(input_ids, "ndim") else np.ndim(input_ids)) == 3:
             if nseq != 1:
                 raise ValueError("num_return_sequences > 1 and several questions per example do not combine: ask each question in a "
@@ -440,6 +520,59 @@ class Engine:
         self.last_first_token_host_ms = t_up + ftm0
         res = (toks, lens, steps_all, ftm0)
         return res + (lps,) if return_logprobs else res
+
+    def _generate_beam(self, audio1, audio2, input_ids, max_len, k, m, length_penalty, stop_id, ignore_stop, return_logprobs, t_in):
+        """generate(num_beams=k): one mellow_generate_beam call, then the backtracking and the final ranking on the host"""
+        import time
+        a1, a2 = torch.as_tensor(audio1), torch.as_tensor(audio2)
+        check_beam_request(a1.shape[0], k, max_len, m)
+        if k > 1 and getattr(self, "precision", None) == "fp8":
+            raise ValueError('num_beams > 1 is not available with precision="fp8": the bf16 K/V pages of that mode have no fan-out')
+        self._need("mellow_generate_beam")
+        a1, a2, ids = self._f32(a1), self._f32(a2), self._prompt_ids(input_ids)
+        B, ns = a1.shape
+        assert a2.shape == a1.shape and ids.shape == (B, spec.TEXT_LEN), (a1.shape, a2.shape, ids.shape)
+        N = B * k
+        par = np.zeros((max_len, N), dtype=np.int32)
+        tok = np.zeros((max_len, N), dtype=np.int32)
+        lp = np.zeros((max_len, N), dtype=np.float32)
+        cum = np.zeros((N,), dtype=np.float32)
+        self._sync_inputs()
+        t_up = (time.perf_counter() - t_in) * 1e3
+        steps, ftm = C.c_int32(0), C.c_float(0.0)
+        vp = C.c_void_p
+        self._chk(self.lib.mellow_generate_beam(self.h, _ptr(a1), _ptr(a2), ns, _ptr(ids), B, k, max_len, stop_id, 1 if ignore_stop else 0,
+                                                vp(par.ctypes.data), vp(tok.ctypes.data), vp(lp.ctypes.data), vp(cum.ctypes.data),
+                                                C.byref(steps), C.byref(ftm)))
+        st = int(steps.value)
+        par, tok, lp = par[:st], tok[:st], lp[:st]
+        self.last_beam = {"parent": par, "token": tok, "lp": lp, "cum": cum, "k": k}
+        toks, lps = backtrack_beams(par, tok, lp, k)
+        order, lengths, counts, scores = rank_beams(toks, lps, cum, k, stop_id, length_penalty, ignore_stop)
+        rows = (np.arange(B)[:, None] * k + order[:, :m]).reshape(-1)
+        self.last_first_token_host_ms = t_up + float(ftm.value)
+        res = (toks[rows], lengths[rows], st, float(ftm.value))
+        if return_logprobs:
+            res = res + (lps[rows].astype(np.float32), scores[rows])
+        self.last_beam.update(rows=rows, logprob=cum[rows].astype(np.float64))
+        return res
+
+    def beam_select(self, logits, cum, fin, k: int, stop_id: int = 0):
+        """One selection step of the beam search on caller data (numeric tap, mellow_beam_select): logits [B * k][vocab], cum
+        [B * k], fin [B * k] -> dict of parent / token int32 [B * k], cum / lp float32 [B * k] (row b * k + j = new beam j)."""
+        self._need("mellow_beam_select")
+        lg, cu, fi = self._f32(logits), self._f32(cum), self._i32(fin)
+        N, k = lg.shape[0], int(k)
+        if k < 1 or N % k != 0 or cu.shape != (N,) or fi.shape != (N,):
+            raise ValueError(f"logits {tuple(lg.shape)}, cum {tuple(cu.shape)}, fin {tuple(fi.shape)} are not B * {k} rows")
+        par = torch.empty((N,), dtype=torch.int32, device=self.tdev)
+        tok = torch.empty((N,), dtype=torch.int32, device=self.tdev)
+        oc = torch.empty((N,), dtype=torch.float32, device=self.tdev)
+        ol = torch.empty((N,), dtype=torch.float32, device=self.tdev)
+        self._sync_inputs()
+        self._chk(self.lib.mellow_beam_select(self.h, _ptr(lg), _ptr(cu), _ptr(fi), N // k, k, int(stop_id), _ptr(par), _ptr(tok),
+                                              _ptr(oc), _ptr(ol)))
+        return {"parent": par.cpu().numpy(), "token": tok.cpu().numpy(), "cum": oc.cpu().numpy(), "lp": ol.cpu().numpy()}
 
     def _generate_multiq(self, audio1, audio2, input_ids, max_len, top_p, temperature, stop_id, ignore_stop, do_sample, seed, row_offset,
                          return_logprobs, t_in):

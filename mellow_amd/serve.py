@@ -64,7 +64,8 @@ class EnginePool:
         With do_sample=True batch k samples as rows row_offset + (rows of the batches before it) of one concatenated list,
         so the result does not depend on how many contexts run the batches or which one gets which (num_return_sequences=n: every
         example counts n rows; input_ids [B][Q][text_len]: every example counts Q rows).
-        Every keyword of Engine.generate passes through (return_logprobs=True: five values per batch)."""
+        Every keyword of Engine.generate passes through (return_logprobs=True: five values per batch; num_beams=k with
+        length_penalty / num_return_sequences: a beam search per batch, deterministic, so no row offset is involved)."""
         kws = [kw] * len(batches)
         if kw.get("do_sample"):
             off, kws = int(kw.get("row_offset", 0)), []

@@ -327,7 +327,7 @@ class MellowWrapper:
 
     def generate(self, examples, max_len, top_p, temperature, stop_token="<|endoftext|>", audio_resample=True, *,
                  do_sample: bool = False, seed: Optional[int] = None, return_logprobs: bool = False,
-                 num_return_sequences: int = 1):
+                 num_return_sequences: int = 1, num_beams: int = 1, length_penalty: float = 1.0):
         r"""Produces text response for the given audio files and text prompts
         examples: (list<list>) each example is [audio path 1, audio path 2, text prompt]; the text prompt may be a list or tuple of
                      prompts, several questions about the one pair of clips (module docstring).  If any example has a list, the
@@ -344,6 +344,14 @@ class MellowWrapper:
         num_return_sequences: (int) n > 1 (needs do_sample=True, else ValueError): n sampled answers per example from one encoder
                      pass and one prefill per example; the result holds, per example, a list of n strings (or of n dicts with
                      return_logprobs=True).  1 (default): one answer per example, exactly as without the keyword.
+        num_beams: (int) k > 1 (at most 8): beam search with k beams per example from one encoder pass and one prefill per example,
+                     deterministic.  The answer is the best hypothesis by score = logprob / tokens ** length_penalty (tokens counts
+                     the stop token); with num_return_sequences = m <= k the result holds, per example, a list of the m best, best
+                     first.  With return_logprobs=True the dicts also carry "score".  ValueError together with do_sample=True, with
+                     a list of prompts, or for m > k; NotImplementedError under data parallelism with more than one rank.
+                     1 (default): the call without the keyword.
+        length_penalty: (float) exponent of the hypothesis length in the final ranking (0: rank by logprob alone); the beams compete
+                     on the raw logprob during the search.
 
         With `data_parallel=True` (or MELLOW_DATA_PARALLEL=1) under an initialised torch.distributed group (one process per
         GPU, every rank calling with the same examples) the examples are sharded contiguously over the ranks, each rank ingests
@@ -357,6 +365,12 @@ class MellowWrapper:
         nseq = int(num_return_sequences)
         if nseq < 1:
             raise ValueError(f"num_return_sequences must be >= 1 (got {nseq})")
+        k = int(num_beams)
+        if k < 1:
+            raise ValueError(f"num_beams must be >= 1 (got {k})")
+        if k > 1:
+            return self._generate_beams(examples, audio_paths1, audio_paths2, text_prompts, max_len, stop_token, audio_resample,
+                                        do_sample, return_logprobs, k, nseq, float(length_penalty))
         if nseq > 1 and not do_sample:
             raise ValueError("num_return_sequences > 1 needs do_sample=True: greedy answers of one example are all the same")
         if nseq > 1024:
@@ -396,6 +410,42 @@ class MellowWrapper:
         return self._generate_batch(audio1, audio2, ids, entry_length=max_len, top_p=top_p,
                                     temperature=temperature, stop_token=stop_token, n_total=n, do_sample=do_sample,
                                     seed=seed, row_offset=lo * nseq, return_logprobs=return_logprobs, nseq=nseq)
+
+    def _generate_beams(self, examples, audio_paths1, audio_paths2, text_prompts, max_len, stop_token, audio_resample, do_sample,
+                        return_logprobs, k, m, length_penalty):
+        """generate(num_beams=k > 1): one engine call on every example; the m best hypotheses per example, best first"""
+        from .engine import check_beam_request
+        if do_sample:
+            raise ValueError("num_beams > 1 and do_sample=True do not combine: beam search is deterministic")
+        if any(isinstance(tp, (list, tuple)) for tp in text_prompts):
+            raise ValueError("num_beams > 1 and question lists do not combine: ask each question in a call of its own")
+        if m > k:
+            raise ValueError(f"num_return_sequences = {m} exceeds num_beams = {k}: a beam search ends with k hypotheses")
+        if self._dp()[1] > 1:
+            raise NotImplementedError("beam search is not sharded over data-parallel ranks: call generate on one rank (or with "
+                                      "data_parallel off)")
+        n = len(examples)
+        if n == 0:
+            raise RuntimeError("torch.cat(): expected a non-empty list of Tensors")
+        if getattr(self.model, "precision", None) == "fp8":
+            raise ValueError('num_beams > 1 is not available with precision="fp8": the bf16 K/V pages of that mode have no fan-out')
+        entry_length = self._clamp_max_len(int(max_len))
+        check_beam_request(n, k, entry_length, m)
+        stop_id = self.tokenizer.encode(stop_token)[0]
+        audio1 = self.preprocess_audio(audio_paths1, resample=audio_resample)
+        audio2 = self.preprocess_audio(audio_paths2, resample=audio_resample)
+        ids = self.preprocess_text(text_prompts)["input_ids"]
+        kw = dict(max_len=entry_length, stop_id=stop_id, num_beams=k, length_penalty=length_penalty, num_return_sequences=m)
+        if return_logprobs:
+            toks, lens, steps, ftm, logprobs, scores = self.model.generate(audio1, audio2, ids, return_logprobs=True, **kw)
+            res = self._scored_results(toks, logprobs, stop_id)
+            for r, sc in zip(res, scores):
+                r["score"] = float(sc)
+        else:
+            toks, lens, steps, ftm = self.model.generate(audio1, audio2, ids, **kw)
+            res = [self.tokenizer.decode(x).split("<|endoftext|>")[0] for x in np.asarray(toks)]
+        self.last_first_token_ms = ftm
+        return res if m == 1 else [res[i:i + m] for i in range(0, len(res), m)]
 
     def _generate_questions(self, audio_paths1, audio_paths2, text_prompts, max_len, top_p, temperature, stop_token, audio_resample,
                             do_sample, seed, return_logprobs, nseq):
