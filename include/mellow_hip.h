@@ -54,8 +54,10 @@ extern "C" {
  *     mellow_generate_scored and mellow_debug_dec_head_lse (log-probs of the generated tokens) were added the same way, and so
  *     was mellow_generate_n (n sampled answers per example from one encode and one prefill), and then mellow_generate_q (several
  *     questions per example from one encode and one prefill of the clips' positions), and then mellow_generate_beam with its tap
- *     mellow_beam_select (beam search inside the decode step). */
-#define MELLOW_ABI_MINOR 4
+ *     mellow_beam_select (beam search inside the decode step).
+ *  5: the attention taps on host data, mellow_debug_prefill_attn and mellow_debug_window_attn.  No existing symbol or struct
+ *     changed; a binding that must also load a minor-4 library detects them by symbol lookup. */
+#define MELLOW_ABI_MINOR 5
 
 typedef struct mellow_engine mellow_engine_t;
 
@@ -374,15 +376,39 @@ int  mellow_debug_tap(mellow_engine_t* e, const char* name, float* out, int64_t 
 
 /* Numeric taps on HOST data (work on any engine, finalised or not): C[M][N] = A[M][K] . W[N][K]^T through one GEMM kernel.
  * iters > 0 and ms2 != NULL: ms2[0] / ms2[1] receive the average milliseconds of the operand pre-pass / of the GEMM.
- *   mellow_debug_gemm_f32: mode 0 = the exact fp32 MFMA kernel (no pre-pass), 9 / 6 = the bf16x3 kernel on pre-split rows with
- *     all nine / the six largest partial products, 16 = the fused six-product kernel MELLOW_PRECISION_F32X3 runs (A split in
- *     registers, no pre-pass).  K % 32 == 0, N % 4 == 0.
+ *   mellow_debug_gemm_f32: mode 0 = the exact fp32 MFMA kernel (no pre-pass), 16 / 17 = the six-product f32x3 kernels
+ *     MELLOW_PRECISION_F32X3 runs: 16 splits A in registers (no pre-pass), 17 takes A pre-split in APB order by a pre-pass and
+ *     stages both operands by LDS-DMA.  Any other mode is an error.  K % 32 == 0, N % 4 == 0.
  *   mellow_debug_gemm_fp8: the MELLOW_PRECISION_FP8 GEMM -- A quantised per row and W per row to OCP e4m3 (scale =
  *     amax / 448, round to nearest even), exact products, fp32 accumulation.  K % 64 == 0, N % 4 == 0. */
 int  mellow_debug_gemm_f32(mellow_engine_t* e, int mode, const float* A, int M, int K, const float* W, int N, float* C,
                            int iters, float* ms2);
 int  mellow_debug_gemm_fp8(mellow_engine_t* e, const float* A, int M, int K, const float* W, int N, float* C,
                            int iters, float* ms2);
+/* Attention taps on HOST data (work on any engine, finalised or not): ONE launch of an attention kernel of the engine on the
+ * caller's arrays, through the launcher the engine itself calls.  The device output is filled with 0xFF bytes before the launch
+ * and returned whole, so that a caller sees every byte the kernel did not write:
+ *   out_form 0  fp32 rows: M + 32 rows of `width` floats, the real rows first (out_capacity >= (M + 32) * width * 4 bytes);
+ *   out_form 1  the raw APB image the f32x3 GEMMs take as their pre-split A operand (three bf16 pieces per element, 16-byte
+ *               slots in the order of mellow_amd/csrc/common.h): roundup(M, 128) rows, 6 bytes per element
+ *               (out_capacity >= roundup(M, 128) * width * 6 bytes).
+ * out_capacity is in bytes.  Every argument the engine itself never passes is an error, and nothing is launched.
+ *
+ * Causal GQA prefill attention (9 query heads of 64 on 3 kv heads; width = 576, M = B * (T - qpos0)):
+ *   q host f32 [B][T - qpos0][576], k / v host f32 pages [B][3][Tmax][64] (positions >= T are never read).
+ *   variant 0 = the exact fp32 MFMA kernel, 1 = the f32x3 kernel (operands split exactly in three bf16), 2 = operands rounded once
+ *   to bf16, fp32 pages, 3 = the same on bf16 pages and bf16 q rows (q, k, v are rounded to bf16 on the device first).
+ *   qpos0 = 0: the whole-sequence launch.  qpos0 > 0 (a multiple of 32, < T): the launch for the queries at positions [qpos0, T)
+ *   only, variants 0 and 1.  out_form 1: variants 0 and 1.
+ *   Errors: Tmax < T, qpos0 % 32 != 0, qpos0 >= T, qpos0 > 0 or out_form 1 with variant 2 or 3, too small a capacity. */
+int  mellow_debug_prefill_attn(mellow_engine_t* e, int variant, const float* q, const float* k, const float* v, int B, int T,
+                               int Tmax, int qpos0, int out_form, void* out, int64_t out_capacity);
+/* Swin window attention (windows of 64 tokens, head_dim 24; width = C): qkv host f32 [M][3 C] rows in window order, bias host
+ *   f32 [nH][64][64], mask host f32 [nW][64][64] or NULL (window w takes mask w % nW).  in16 != 0: qkv is rounded to bf16 rows on
+ *   the device first and the bf16-input kernel runs (out_form 0 only).
+ *   Errors: M % 64 != 0, C != 24 * nH, nH not in {4, 8, 16, 32}, a mask with nW <= 0, in16 with out_form 1, too small a capacity. */
+int  mellow_debug_window_attn(mellow_engine_t* e, const float* qkv, int M, int C, int nH, const float* bias, const float* mask,
+                              int nW, int in16, int out_form, void* out, int64_t out_capacity);
 /* The decode step's lm_head kernel on caller-supplied rows (dev): logits[B][vocab] = x[B][hidden] . lm_head^T with the engine's
  * own head weights (the e4m3 copy in MELLOW_PRECISION_FP8; act_fp8 != 0 then also quantises x inside the kernel: one scale per
  * batch row and 72-column slice, fp8 matrix pipe).  Invalidates the decode state of an earlier prefill. */

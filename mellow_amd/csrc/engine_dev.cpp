@@ -142,6 +142,96 @@ int mellow_debug_gemm_fp8(mellow_engine_t* e, const float* A, int M, int K, cons
     return 0;
 }
 
+// ---- attention taps on host data (include/mellow_hip.h): one launch of an existing launcher on buffers of the call's own ------------
+// what the two taps share: the output buffer, filled with 0xFF bytes before the launch and returned whole
+struct AttnTapOut {
+    mellow_engine::Buf buf;
+    size_t bytes = 0;
+};
+// plain form: M + 32 rows of `width` floats; APB form: the image of rup(M, 128) rows, 6 bytes per element
+static int attn_tap_out(mellow_engine* e, AttnTapOut& o, int64_t M, int width, int out_form, int64_t out_capacity) {
+    o.bytes = out_form ? (size_t)rup((int)M, 128) * width * 6 : (size_t)(M + 32) * width * 4;
+    if (out_capacity < (int64_t)o.bytes) return fail("out_capacity %lld is below the %lld bytes this call returns", (long long)out_capacity, (long long)o.bytes);
+    CHK(ensure(e, o.buf, (o.bytes + 3) / 4));
+    HIPCHK(hipMemsetAsync(o.buf.p, 0xFF, o.bytes, e->stream));
+    return 0;
+}
+static int attn_tap_finish(mellow_engine* e, const AttnTapOut& o, void* out) {
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(out, o.buf.p, o.bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+// n host floats -> a device buffer; to16: then rounded to bf16 by launch_kv_to_bf16 into a second buffer, which *dev then addresses
+static int attn_tap_in(mellow_engine* e, mellow_engine::Buf& b32, mellow_engine::Buf& b16, const float* src, size_t n, bool to16, const float** dev) {
+    CHK(ensure(e, b32, n));
+    HIPCHK(hipMemcpy(b32.p, src, n * 4, hipMemcpyHostToDevice));
+    *dev = b32.p;
+    if (to16) {
+        CHK(ensure(e, b16, (n + 1) / 2));
+        launch_kv_to_bf16(b32.p, b16.p, (int64_t)n, e->stream);
+        *dev = b16.p;
+    }
+    return 0;
+}
+
+int mellow_debug_prefill_attn(mellow_engine_t* e, int variant, const float* q, const float* k, const float* v, int B, int T, int Tmax,
+                              int qpos0, int out_form, void* out, int64_t out_capacity) {
+    if (!e || !q || !k || !v || !out) return fail("null argument");
+    if (variant < 0 || variant > 3) return fail("variant must be 0 (fp32 MFMA), 1 (f32x3), 2 (bf16 once, fp32 pages) or 3 (bf16 once, bf16 pages): got %d", variant);
+    if (out_form != 0 && out_form != 1) return fail("out_form must be 0 (fp32 rows) or 1 (APB image): got %d", out_form);
+    if (B < 1 || T < 1 || B > 1024 || Tmax > 65536) return fail("B = %d, T = %d, Tmax = %d: 1 <= B <= 1024, 1 <= T, Tmax <= 65536", B, T, Tmax);
+    if (Tmax < T) return fail("Tmax = %d is below T = %d", Tmax, T);
+    if (qpos0 < 0 || qpos0 % 32 != 0 || qpos0 >= T) return fail("qpos0 = %d must be a multiple of 32 in [0, T = %d)", qpos0, T);
+    if (qpos0 > 0 && variant >= 2) return fail("the launch with a past exists for variants 0 and 1 only (got variant %d, qpos0 = %d)", variant, qpos0);
+    if (out_form == 1 && variant >= 2) return fail("the APB output form is launched for variants 0 and 1 only (got variant %d)", variant);
+    const int64_t M = (int64_t)B * (T - qpos0);
+    if (M > (1 << 22)) return fail("B * (T - qpos0) = %lld rows exceed the tap's %d", (long long)M, 1 << 22);
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    const bool p16 = variant == 3;
+    const size_t page_floats = (size_t)B * 3 * Tmax * 64;
+    mellow_engine::Buf bq, bk, bv, bq16, bk16, bv16;
+    const float *dq, *dk, *dv;
+    CHK(attn_tap_in(e, bq, bq16, q, (size_t)M * 576, p16, &dq));
+    CHK(attn_tap_in(e, bk, bk16, k, page_floats, p16, &dk));
+    CHK(attn_tap_in(e, bv, bv16, v, page_floats, p16, &dv));
+    AttnTapOut o;
+    CHK(attn_tap_out(e, o, M, 576, out_form, out_capacity));
+    float* o_rows = out_form ? nullptr : o.buf.p;
+    void* o_apb = out_form ? o.buf.p : nullptr;
+    if (qpos0 > 0) launch_prefill_attention_past(dq, dk, dv, o_rows, o_apb, B, T, Tmax, qpos0, variant == 1, s);
+    else launch_prefill_attention(dq, dk, dv, o_rows, o_apb, B, T, Tmax, variant >= 1, s, nullptr, variant >= 2, p16);
+    return attn_tap_finish(e, o, out);
+}
+
+int mellow_debug_window_attn(mellow_engine_t* e, const float* qkv, int M, int C, int nH, const float* bias, const float* mask, int nW,
+                             int in16, int out_form, void* out, int64_t out_capacity) {
+    if (!e || !qkv || !bias || !out) return fail("null argument");
+    if (out_form != 0 && out_form != 1) return fail("out_form must be 0 (fp32 rows) or 1 (APB image): got %d", out_form);
+    if (M < 64 || M % 64 != 0 || M > (1 << 22)) return fail("M = %d must be a positive multiple of 64 (whole windows), at most %d", M, 1 << 22);
+    if (nH != 4 && nH != 8 && nH != 16 && nH != 32) return fail("nH = %d is not a head count of the encoder (4, 8, 16, 32)", nH);
+    if (C != 24 * nH) return fail("C = %d is not 24 * nH = %d", C, 24 * nH);
+    if (mask && nW <= 0) return fail("a mask needs nW >= 1 (got %d)", nW);
+    if (in16 && out_form == 1) return fail("the engine never launches the bf16-input kernel with the APB output form");
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    mellow_engine::Buf bx, bx16, bb, bm;
+    const float* dx;
+    CHK(attn_tap_in(e, bx, bx16, qkv, (size_t)M * 3 * C, in16 != 0, &dx));
+    CHK(ensure(e, bb, (size_t)nH * 64 * 64));
+    HIPCHK(hipMemcpy(bb.p, bias, (size_t)nH * 64 * 64 * 4, hipMemcpyHostToDevice));
+    if (mask) {
+        CHK(ensure(e, bm, (size_t)nW * 64 * 64));
+        HIPCHK(hipMemcpy(bm.p, mask, (size_t)nW * 64 * 64 * 4, hipMemcpyHostToDevice));
+    }
+    AttnTapOut o;
+    CHK(attn_tap_out(e, o, M, C, out_form, out_capacity));
+    launch_window_attention(dx, out_form ? nullptr : o.buf.p, M, C, nH, bb.p, mask ? bm.p : nullptr, mask ? nW : 1, s, out_form ? o.buf.p : nullptr,
+                            in16 != 0);
+    return attn_tap_finish(e, o, out);
+}
+
 // developer instrumentation (not part of the public header): one CSV line per profiled launch
 __attribute__((visibility("default"))) int mellow_dev_prof_dump(mellow_engine_t* e, const char* path) {
     if (!e || !path) return fail("bad argument");

@@ -42,6 +42,8 @@ _lib = None
 # symbols added without a new ABI minor (include/mellow_hip.h): detected by lookup, so that a library built before them still loads
 _ADDED_UNDER_MINOR_4 = ("mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse", "mellow_generate_n",
                         "mellow_generate_q", "mellow_generate_beam", "mellow_beam_select")
+# symbols of minor 5 (the attention taps on host data): looked up the same way, so that a minor-4 library still loads
+_ADDED_UNDER_MINOR_5 = ("mellow_debug_prefill_attn", "mellow_debug_window_attn")
 
 
 def load_library(path: Optional[str] = None):
@@ -95,6 +97,8 @@ def load_library(path: Optional[str] = None):
         "mellow_debug_tap": (ci, [vp, C.c_char_p, vp, i64, P(i64)]),
         "mellow_debug_gemm_fp8": (ci, [vp, vp, ci, ci, vp, ci, vp, ci, vp]),
         "mellow_debug_gemm_f32": (ci, [vp, ci, vp, ci, ci, vp, ci, vp, ci, vp]),
+        "mellow_debug_prefill_attn": (ci, [vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp, i64]),
+        "mellow_debug_window_attn": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, i64]),
         "mellow_debug_dec_head": (ci, [vp, vp, ci, ci, vp]),
         "mellow_debug_dec_head_lse": (ci, [vp, vp, ci, ci, vp, vp, vp, vp]),
         "mellow_prof_enable": (ci, [vp, ci]),
@@ -117,8 +121,8 @@ def load_library(path: Optional[str] = None):
         "mellow_host_rope_tables": (ci, [cf, ci, ci, P(cf), P(cf)]),
     }
     for name, (res, args) in sig.items():
-        if name in _ADDED_UNDER_MINOR_4 and not hasattr(lib, name):
-            continue                     # an older minor-4 library: the Engine methods that need the symbol raise when called
+        if name in _ADDED_UNDER_MINOR_4 + _ADDED_UNDER_MINOR_5 and not hasattr(lib, name):
+            continue                     # an older library: the Engine methods that need the symbol raise when called
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -137,7 +141,7 @@ EXPORTED_SYMBOLS = (
     "mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse", "mellow_generate_n", "mellow_generate_q",
     "mellow_generate_beam", "mellow_beam_select", "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
     "mellow_prof_num_families", "mellow_prof_family_name", "mellow_prof_get", "mellow_last_phase_ms", "mellow_last_steps_enqueued", "mellow_last_row_repacks", "mellow_stft_is_fft", "mellow_prefill_parts", "mellow_abi_minor",
-    "mellow_resample", "mellow_engine_set_precision", "mellow_engine_set_option", "mellow_engine_describe", "mellow_debug_gemm_fp8", "mellow_debug_gemm_f32", "mellow_debug_dec_head", "mellow_set_graph", "mellow_host_window_map", "mellow_host_pack_weight", "mellow_host_rope_tables",
+    "mellow_resample", "mellow_engine_set_precision", "mellow_engine_set_option", "mellow_engine_describe", "mellow_debug_gemm_fp8", "mellow_debug_gemm_f32", "mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_debug_dec_head", "mellow_set_graph", "mellow_host_window_map", "mellow_host_pack_weight", "mellow_host_rope_tables",
 )
 
 
@@ -802,8 +806,8 @@ class Engine:
         return out
 
     def debug_gemm_f32(self, A: torch.Tensor, W: torch.Tensor, mode: int = 0, iters: int = 0):
-        """C = A . W^T through the exact fp32 MFMA kernel (mode 0) or a bf16x3 split kernel (9 / 6: pre-split rows; 16: the fused
-        kernel the f32x3 mode runs); host tensors."""
+        """C = A . W^T through the exact fp32 MFMA kernel (mode 0) or one of the f32x3 kernels the default mode runs (16: A split in
+        registers; 17: A pre-split in APB order, both operands by LDS-DMA); host tensors."""
         A = A.detach().cpu().contiguous().float()
         W = W.detach().cpu().contiguous().float()
         (M, K), (N, K2) = A.shape, W.shape
@@ -825,6 +829,48 @@ class Engine:
         self._chk(self.lib.mellow_debug_gemm_fp8(self.h, C.c_void_p(A.data_ptr()), M, K, C.c_void_p(W.data_ptr()), N,
                                                  C.c_void_p(out.data_ptr()), int(iters), ms if iters > 0 else None))
         return out, ((ms[0], ms[1]) if iters > 0 else None)
+
+    @staticmethod
+    def _attn_tap_out(M: int, width: int, out_form: int) -> torch.Tensor:
+        """the host buffer an attention tap fills: fp32 [M + 32][width], or the APB image of roundup(M, 128) rows as int32 words"""
+        if out_form == 0:
+            return torch.empty((M + 32, width), dtype=torch.float32)
+        return torch.empty(((M + 127) // 128 * 128 * width * 6 // 4,), dtype=torch.int32)
+
+    def debug_prefill_attn(self, q, k, v, T: int, variant: int = 0, qpos0: int = 0, out_form: int = 0) -> torch.Tensor:
+        """One launch of a causal GQA prefill attention kernel on host data (mellow_debug_prefill_attn): q [B][T - qpos0][576], k / v
+        pages [B][3][Tmax][64].  variant 0 exact fp32, 1 f32x3, 2 bf16 once on fp32 pages, 3 bf16 once on bf16 pages.  -> the whole
+        device output, which held 0xFF bytes before the launch: out_form 0 fp32 [B * (T - qpos0) + 32][576] (real rows first),
+        out_form 1 the raw APB image of roundup(rows, 128) rows as int32 words."""
+        self._need("mellow_debug_prefill_attn")
+        q, k, v = (x.detach().cpu().contiguous().float() for x in (q, k, v))
+        B, T, qpos0 = int(k.shape[0]), int(T), int(qpos0)
+        if k.dim() != 4 or k.shape[1] != 3 or k.shape[3] != 64 or v.shape != k.shape:
+            raise ValueError(f"k {tuple(k.shape)} / v {tuple(v.shape)} are not pages [B][3][Tmax][64]")
+        if q.dim() != 3 or q.shape[0] != B or q.shape[1] != T - qpos0 or q.shape[2] != 576:
+            raise ValueError(f"q {tuple(q.shape)} is not [B = {B}][T - qpos0 = {T - qpos0}][576]")
+        out = self._attn_tap_out(B * q.shape[1], 576, int(out_form))
+        self._chk(self.lib.mellow_debug_prefill_attn(self.h, int(variant), _ptr(q), _ptr(k), _ptr(v), B, T, int(k.shape[2]), qpos0,
+                                                     int(out_form), _ptr(out), out.numel() * 4))
+        return out
+
+    def debug_window_attn(self, qkv, bias, mask=None, in16: bool = False, out_form: int = 0) -> torch.Tensor:
+        """One launch of the Swin window attention kernel on host data (mellow_debug_window_attn): qkv [M][3 C] rows in window order,
+        bias [nH][64][64], mask [nW][64][64] or None; in16: qkv rounded to bf16 rows on the device, the bf16-input kernel.  -> the
+        whole device output as debug_prefill_attn returns it (width C)."""
+        self._need("mellow_debug_window_attn")
+        qkv, bias = qkv.detach().cpu().contiguous().float(), bias.detach().cpu().contiguous().float()
+        mask = None if mask is None else mask.detach().cpu().contiguous().float()
+        if qkv.dim() != 2 or qkv.shape[1] % 3 or bias.dim() != 3 or tuple(bias.shape[1:]) != (64, 64):
+            raise ValueError(f"qkv {tuple(qkv.shape)} / bias {tuple(bias.shape)} are not [M][3 C] / [nH][64][64]")
+        if mask is not None and (mask.dim() != 3 or tuple(mask.shape[1:]) != (64, 64)):
+            raise ValueError(f"mask {tuple(mask.shape)} is not [nW][64][64]")
+        M, Cw, nH = int(qkv.shape[0]), int(qkv.shape[1]) // 3, int(bias.shape[0])
+        out = self._attn_tap_out(M, Cw, int(out_form))
+        self._chk(self.lib.mellow_debug_window_attn(self.h, _ptr(qkv), M, Cw, nH, _ptr(bias), None if mask is None else _ptr(mask),
+                                                    0 if mask is None else int(mask.shape[0]), 1 if in16 else 0, int(out_form),
+                                                    _ptr(out), out.numel() * 4))
+        return out
 
     def debug_dec_head(self, x: torch.Tensor, act_fp8: bool = False) -> torch.Tensor:
         """The decode step's lm_head kernel on the rows x [B, hidden] (device tensor) -> logits [B, vocab]."""

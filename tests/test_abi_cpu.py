@@ -34,6 +34,25 @@ def test_library_exports_every_declared_symbol(lib):
     assert lib.mellow_abi_version() == E.ABI_VERSION
 
 
+def test_attention_taps_are_declared_bound_and_came_with_minor_5(lib):
+    hdr = open(os.path.join(ROOT, "include", "mellow_hip.h")).read()
+    assert lib.mellow_abi_minor() == 5 and re.search(r"#define MELLOW_ABI_MINOR 5\b", hdr)
+    for name in ("mellow_debug_prefill_attn", "mellow_debug_window_attn"):
+        assert re.search(r"\bint\s+%s\s*\(" % name, hdr), name
+        assert name in E.EXPORTED_SYMBOLS and name in E._ADDED_UNDER_MINOR_5
+        fn = getattr(lib, name)
+        assert fn.restype is ctypes.c_int and len(fn.argtypes) == 12 and fn.argtypes[-1] is ctypes.c_int64
+        # host code only: a null engine is refused before any device is touched
+        assert fn(*[None if t is ctypes.c_void_p else t(1) for t in fn.argtypes]) != 0
+        assert "null argument" in lib.mellow_last_error().decode()
+    # a library that predates them still loads; the Engine methods then say what is missing
+    e = object.__new__(E.Engine)
+    e.lib, e.h = type("OldLib", (), {})(), None
+    for call in (lambda: e.debug_prefill_attn(None, None, None, 1), lambda: e.debug_window_attn(None, None)):
+        with pytest.raises(E.EngineError, match="predates mellow_debug_"):
+            call()
+
+
 def test_required_keys_are_the_reference_state_dict_keys(lib):
     from mellow_amd import spec
     layout = spec.state_dict_layout()

@@ -35,7 +35,7 @@ def test_header_declares_and_library_exports_the_beam_symbols():
         assert fn.restype is ctypes.c_int and len(fn.argtypes) == nargs
     assert lib.mellow_generate_beam.argtypes[5:10] == [ctypes.c_int] * 5          # B, k, max_len, stop_id, ignore_stop
     assert lib.mellow_beam_select.argtypes[4:7] == [ctypes.c_int] * 3             # B, k, stop_id
-    assert lib.mellow_abi_minor() == 4                         # added under the same minor: detected by symbol lookup
+    assert lib.mellow_abi_minor() == 5                         # the current minor; added under minor 4: detected by symbol lookup
     assert "65536" in hdr and "NaN candidate ranks as the arg-max kernel ranks" in hdr
 
 
