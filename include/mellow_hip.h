@@ -54,7 +54,8 @@ extern "C" {
  *     mellow_generate_scored and mellow_debug_dec_head_lse (log-probs of the generated tokens) were added the same way, and so
  *     was mellow_generate_n (n sampled answers per example from one encode and one prefill), and then mellow_generate_q (several
  *     questions per example from one encode and one prefill of the clips' positions), and then mellow_generate_beam with its tap
- *     mellow_beam_select (beam search inside the decode step).
+ *     mellow_beam_select (beam search inside the decode step), and then mellow_generate_rules with its tap mellow_logit_rules_apply
+ *     (repetition controls: logit rules inside the decode step) -- added while the minor was 5, detected by symbol lookup all the same.
  *  5: the attention taps on host data, mellow_debug_prefill_attn and mellow_debug_window_attn.  No existing symbol or struct
  *     changed; a binding that must also load a minor-4 library detects them by symbol lookup. */
 #define MELLOW_ABI_MINOR 5
@@ -296,6 +297,53 @@ int  mellow_generate_beam(mellow_engine_t* e, const float* audio1, const float* 
  * Added under minor 4 with mellow_generate_beam. */
 int  mellow_beam_select(mellow_engine_t* e, const float* logits, const float* cum, const int32_t* fin, int B, int k, int stop_id,
                         int32_t* out_parent, int32_t* out_token, float* out_cum, float* out_lp);
+/* Repetition controls: rules that edit a row's fp32 logits on the device, inside the decode step, between the lm_head and the kernel
+ * that picks the token -- for the prefill's first token as for every decode step, and for every picker (arg-max, sampler, beam select).
+ *
+ * Definition.  A row that has generated tokens h[0 .. s) is about to choose token s (s = 0 at the prefill's head).  The history is the
+ * GENERATED tokens only (the prompt enters the model as embeddings and is not part of it); a beam row's history is its hypothesis --
+ * what backtracking the tables gives for the row -- not the past of the slot it sits in.  l[v] are the raw fp32 logits.  Four rules,
+ * applied in this order:
+ *   1. repetition_penalty t (finite, > 0; 1 = off): for every DISTINCT token v of h, l[v] = l[v] < 0 ? l[v] * t : l[v] / t -- once per
+ *      token however often it occurred; one correctly rounded fp32 multiplication or division.
+ *   2. logit_bias: an optional dense vector bias[vocab], the same for all rows of the call: l[v] = l[v] + bias[v] (one fp32 addition).
+ *      Values are finite or -inf (a suppressed token); NaN and +inf are the caller's error (the Python bindings reject them).
+ *   3. no_repeat_ngram_size n (>= 0; 0 = off): if s >= n - 1, then for every i in [0, s - n] with h[i .. i + n - 2] == h[s - n + 1 .. s - 1]:
+ *      l[h[i + n - 1]] = -inf.  n = 1 bans every token of the history.
+ *   4. min_new_tokens m (>= 0; 0 = off): if s < m and the call's stop_id is >= 0: l[stop_id] = -inf.
+ * Every picker then reads the processed row: the arg-max keeps its order (a NaN is the maximum, lowest index on ties), the sampler
+ * applies temperature and nucleus to the processed row, the beam select forms its log-softmax from it.  A recorded log-prob
+ * (mellow_generate_scored, _n, _q, the lp table of mellow_generate_beam) is then the log-softmax of the PROCESSED row at temperature 1:
+ * the distribution the token was chosen from, in which a banned token has probability 0.  With rules on it is therefore NOT the number
+ * mellow_score returns for the same answer.  A row in which every token is banned is the caller's error: it is not detected, the
+ * result is token 0 with a NaN log-prob.
+ *
+ * mellow_generate_rules arms the rules for the NEXT mellow_generate* call on this context (mellow_generate, _sampled, _scored, _n, _q,
+ * _beam all honour them); NULL disarms.  That call takes them at entry and clears them whatever its outcome, so a call after it runs
+ * without rules unless they are armed again.  A fork has rules of its own, initially none.  logit_bias (host or device memory, or
+ * NULL) is copied when the rules are armed.  A struct with t = 1, n = 0, m = 0 and no bias is still "on": the rules launch runs as the
+ * identity (tokens are those of the call without rules; log-probs agree to the rounding of another summation order).  A call with
+ * rules takes max_len <= 8192 (the history one row stages).  A call without armed rules launches exactly what it launched before
+ * these symbols existed.
+ * Errors (host code, before any device is touched): a `size` other than sizeof(mellow_logit_rules_t), t not finite or <= 0, negative
+ * n or m; then a null or unfinalized engine; then a vocabulary other than 49152 (the row tiling of the sampler).
+ * Added while the minor was 5 without raising it: a binding detects the two symbols by lookup. */
+typedef struct mellow_logit_rules {
+    int32_t size;                 /* sizeof(mellow_logit_rules_t) */
+    float   repetition_penalty;   /* finite, > 0; 1 = off */
+    int32_t no_repeat_ngram_size; /* >= 0; 0 = off */
+    int32_t min_new_tokens;       /* >= 0; 0 = off */
+    const float* logit_bias;      /* [vocab] fp32, host or device, or null; copied when armed */
+} mellow_logit_rules_t;
+int  mellow_generate_rules(mellow_engine_t* e, const mellow_logit_rules_t* rules);
+/* The same rules on caller data, no loop state (numeric tap): logits dev f32 [B][vocab], edited in place; history dev i32 [B][ld]
+ * (ld <= 8192) with hist_len dev i32 [B] tokens of every row (each row has its own s, clamped to [0, ld]); stop_id as in a
+ * generate call.  cand_val / cand_idx dev [B][vocab / 32] receive, per 32-column tile of the processed row, its maximum and the
+ * lowest index attaining it (the arg-max order); cand_sum dev f32 [B][vocab / 32] (may be NULL) the tile's sum of exp(l - cand_val),
+ * exactly 0 for a tile whose maximum is -inf -- the partials the greedy arg-max and the log-prob merges of a step read.  Disarms rules
+ * armed on the context (it uses the context's bias buffer).  Errors as above, and a null buffer, B <= 0 or ld outside [0, 8192]. */
+int  mellow_logit_rules_apply(mellow_engine_t* e, const mellow_logit_rules_t* rules, float* logits, int B, const int32_t* history, int ld,
+                              const int32_t* hist_len, int stop_id, float* cand_val, int32_t* cand_idx, float* cand_sum);
 /* The same draw on caller logits, no loop state (numeric tap): logits dev [B][vocab], row_ids dev i32 [B] (global row index
  * of each row; NULL = 0..B-1), step = t above -> tokens dev i32 [B]. */
 int  mellow_sample_logits(mellow_engine_t* e, const float* logits, int B, const int32_t* row_ids, int step, float top_p,

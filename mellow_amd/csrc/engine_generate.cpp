@@ -23,6 +23,7 @@ struct GenRequest {
     int beam = 0;
     int32_t* out_parent = nullptr;
     float* out_cum = nullptr;
+    LogitRules rules;                            // repetition controls (mellow_generate_rules): taken from the context at entry, the same for every pass
     int rows() const { return examples * n * q; }
     // rows [r0, r0 + nb) of an n = 1, q = 1 request as a request of their own; a row's random stream follows its index in the whole call
     GenRequest pass(int r0, int nb, int text_len, int32_t* steps, float* ftm) const {
@@ -51,6 +52,41 @@ static void stage_sampling(mellow_engine_t* e, float top_p, float temperature, u
     uint32_t* w = e->h_sparams;
     w[SMP_SEED_LO] = (uint32_t)seed; w[SMP_SEED_HI] = (uint32_t)(seed >> 32); w[SMP_ROW_OFF] = (uint32_t)row_offset;
     memcpy(&w[SMP_TOP_P], &top_p, 4); memcpy(&w[SMP_TEMP], &temperature, 4); w[SMP_STEP] = (uint32_t)step;
+}
+
+// The value rules of a mellow_logit_rules_t, each once (mellow_generate_rules and mellow_logit_rules_apply): host code only, no
+// engine and no device needed.
+static int check_rules(const mellow_logit_rules_t* r) {
+    if (r->size != (int32_t)sizeof(mellow_logit_rules_t))
+        return fail("mellow_logit_rules_t.size is %d, this library's struct has %d bytes", (int)r->size, (int)sizeof(mellow_logit_rules_t));
+    if (!std::isfinite(r->repetition_penalty) || !(r->repetition_penalty > 0.f))
+        return fail("repetition_penalty must be finite and > 0 (got %g); 1 is off", (double)r->repetition_penalty);
+    if (r->no_repeat_ngram_size < 0) return fail("no_repeat_ngram_size must be >= 0 (got %d); 0 is off", (int)r->no_repeat_ngram_size);
+    if (r->min_new_tokens < 0) return fail("min_new_tokens must be >= 0 (got %d); 0 is off", (int)r->min_new_tokens);
+    return 0;
+}
+
+// a checked struct -> the context: the values, and the bias copied (from host or device memory) into the context's own buffer
+static int load_rules(mellow_engine_t* e, const mellow_logit_rules_t* r, LogitRules* out) {
+    if (e->cfg.vocab_size != SAMPLE_MAX_V) return fail("the logit rules are built for a vocabulary of %d (engine: %d)", SAMPLE_MAX_V, e->cfg.vocab_size);
+    HIPCHK(hipSetDevice(e->device));
+    CHK(ensure(e, e->rules_bias, SAMPLE_MAX_V));
+    if (r->logit_bias) {
+        HIPCHK(hipMemcpyAsync(e->rules_bias.p, r->logit_bias, (size_t)SAMPLE_MAX_V * sizeof(float), hipMemcpyDefault, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));         // the caller's vector is free again on return
+    }
+    out->on = true; out->theta = r->repetition_penalty; out->ngram = r->no_repeat_ngram_size; out->min_new = r->min_new_tokens;
+    out->bias = r->logit_bias != nullptr;
+    return 0;
+}
+
+// the value block a rules launch reads
+static int stage_rules(mellow_engine_t* e, const LogitRules& r, int stop_id) {
+    uint32_t* w = e->h_rparams;
+    memcpy(&w[RUL_THETA], &r.theta, 4);
+    w[RUL_NGRAM] = (uint32_t)r.ngram; w[RUL_MIN_NEW] = (uint32_t)r.min_new; w[RUL_BIAS_ON] = r.bias ? 1u : 0u; w[RUL_STOP] = (uint32_t)stop_id;
+    HIPCHK(hipMemcpyAsync(e->d_rparams, e->h_rparams, sizeof(e->h_rparams), hipMemcpyHostToDevice, e->stream));
+    return 0;
 }
 
 // Every argument rule of the six entry points, each once.
@@ -96,6 +132,10 @@ static int check_request(mellow_engine_t* e, const GenRequest& r, int door) {
     if (r.on) {
         CHK(check_sampling(e, r.top_p, r.temperature));
         if (r.row_offset < 0) return fail("row_offset must be >= 0");
+    }
+    if (r.rules.on) {
+        if (e->cfg.vocab_size != SAMPLE_MAX_V) return fail("the logit rules are built for a vocabulary of %d (engine: %d)", SAMPLE_MAX_V, e->cfg.vocab_size);
+        if (r.max_len > RULES_MAX_HIST) return fail("a call with logit rules takes max_len <= %d, the history one row stages (got %d)", RULES_MAX_HIST, r.max_len);
     }
     return 0;
 }
@@ -254,6 +294,7 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
     m.logprob = r.out_logprob != nullptr && !r.beam;
     m.beam = r.beam;
     if (r.beam) m.logits = true;        // the select reads the full logits rows; every row runs every step: no early exit, no migration
+    m.rules = r.rules.on;               // dec_logit_rules_kernel edits the stored rows: the head stores them (apply_step_mode)
     m.early_exit = !r.beam && (dev_dead || (!r.ignore_stop && e->da.RB > 1));
     m.migrate = m.early_exit && !dev_dead && e->opt.row_migration;   // option "row_migration" = 0: block exit without repacking (developer A/B)
     if (m.logprob) {
@@ -262,6 +303,11 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
         CHK(ensure(e, e->out_lp, (size_t)Bp * max_len));
         HIPCHK(hipMemsetAsync(e->out_lp.p, 0, (size_t)Bp * max_len * sizeof(float), s));
     }
+    if (m.rules) {
+        // the bias buffer exists whether or not this call has a bias: a captured launch holds its address (StepGraphs::Key)
+        CHK(ensure(e, e->rules_bias, SAMPLE_MAX_V));
+        if (r.beam) CHK(ensure(e, e->rules_hist, (size_t)2 * B * max_len));
+    }
     // the pass runs in its mode; the taps' defaults are back on every way out (the taps never sample, record nor exit early)
     struct ModeScope { mellow_engine* e; ~ModeScope() { apply_step_mode(e, StepMode()); } } mode_scope{e};
     apply_step_mode(e, m);
@@ -269,6 +315,7 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
         stage_sampling(e, r.top_p, r.temperature, r.seed, r.row_offset, 0);
         HIPCHK(hipMemcpyAsync(e->d_sparams, e->h_sparams, sizeof(e->h_sparams), hipMemcpyHostToDevice, s));
     }
+    if (r.rules.on) CHK(stage_rules(e, r.rules, stop_id));
     if (dev_dead) {
         HIPCHK(hipMemsetAsync(e->d_blk_left, 0, 96 * sizeof(int32_t), s));
     } else if (m.early_exit) {
@@ -389,7 +436,9 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
 // independent, the token record of every pass lands at its rows of `out_tokens`, a pass that stopped before the longest one is
 // padded with -1 (never computed), and the reference's stop rule -- the loop ends at the first step at which EVERY row has
 // produced the stop id -- is the maximum over the passes (a row's own length never depends on other rows).
-static int generate(mellow_engine_t* e, const GenRequest& r, int door = 0) {
+static int generate(mellow_engine_t* e, const GenRequest& req, int door = 0) {
+    GenRequest r = req;
+    if (e) { r.rules = e->rules_armed; e->rules_armed = LogitRules(); }      // armed rules serve this call only, whatever its outcome
     CHK(check_request(e, r, door));
     if (r.rows() <= kPassRows) return generate_pass(e, r);      // (always so for n > 1 and, through mellow_generate_q, for Q > 1: check_request)
     const int B = r.examples, max_len = r.max_len;
@@ -487,8 +536,42 @@ int mellow_generate_beam(mellow_engine_t* e, const float* audio1, const float* a
     GenRequest r{audio1, audio2, n_samples, input_ids, B, k, 1, max_len, stop_id, ignore_stop, false, 1.f, 1.f, 0, 0,
                  out_token, out_lp, nullptr, out_steps, first_token_ms};
     r.beam = k; r.out_parent = out_parent; r.out_cum = out_cum;
-    if (k < 1) return fail("mellow_generate_beam takes 1 to %d beams per example (got k = %d)", BEAM_MAX_K, k);      // (before the n >= 1 rule words it as n)
+    if (k < 1) {      // (before the n >= 1 rule words it as n)
+        if (e) e->rules_armed = LogitRules();
+        return fail("mellow_generate_beam takes 1 to %d beams per example (got k = %d)", BEAM_MAX_K, k);
+    }
     return generate(e, r, DOOR_BEAM | DOOR_SCORED);
+}
+
+int mellow_generate_rules(mellow_engine_t* e, const mellow_logit_rules_t* rules) {
+    if (rules) CHK(check_rules(rules));
+    if (!e || !e->finalized) return fail("engine not finalized");
+    e->rules_armed = LogitRules();
+    if (!rules) return 0;
+    LogitRules a;
+    CHK(load_rules(e, rules, &a));
+    e->rules_armed = a;
+    return 0;
+}
+
+int mellow_logit_rules_apply(mellow_engine_t* e, const mellow_logit_rules_t* rules, float* logits, int B, const int32_t* history, int ld,
+                             const int32_t* hist_len, int stop_id, float* cand_val, int32_t* cand_idx, float* cand_sum) {
+    if (rules) CHK(check_rules(rules));
+    if (!e || !e->finalized) return fail("engine not finalized");
+    if (!rules || !logits || !hist_len || !cand_val || !cand_idx || B <= 0 || ld < 0 || (ld > 0 && !history)) return fail("bad argument");
+    if (ld > RULES_MAX_HIST) return fail("mellow_logit_rules_apply takes histories of at most %d tokens (ld = %d)", RULES_MAX_HIST, ld);
+    e->rules_armed = LogitRules();          // the tap uses the context's bias buffer: rules armed before it are gone
+    LogitRules a;
+    CHK(load_rules(e, rules, &a));
+    CHK(stage_rules(e, a, stop_id));
+    RulesArgs g;
+    g.logits = logits; g.ld = e->cfg.vocab_size; g.prm = e->d_rparams; g.bias = e->rules_bias.p;
+    g.cand_val = cand_val; g.cand_idx = cand_idx; g.cand_sum = cand_sum;
+    g.hist = history; g.hist_ld = ld; g.hist_len = hist_len;
+    launch_dec_logit_rules(g, B, e->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return 0;
 }
 
 int mellow_beam_select(mellow_engine_t* e, const float* logits, const float* cum, const int32_t* fin, int B, int k, int stop_id,

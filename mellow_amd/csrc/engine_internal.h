@@ -137,6 +137,15 @@ struct StepMode {
     bool early_exit = false;     // per-row-block early exit (DecArgs::blk_live)
     bool migrate = false;        // ... with row migration (DecArgs::row_of_slot)
     int beam = 0;                // k >= 1: beam search -- the select (beam.hip) in place of the arg-max, and for k > 1 the two K/V reorder launches after it
+    bool rules = false;          // repetition controls: dec_logit_rules_kernel between the head and the picker (forces `logits` on)
+};
+// The repetition controls of one generation call (include/mellow_hip.h, mellow_generate_rules): armed on the context, taken into the
+// call's GenRequest at entry.  The bias itself lives in the context's rules_bias buffer.
+struct LogitRules {
+    bool on = false;
+    float theta = 1.f;
+    int ngram = 0, min_new = 0;
+    bool bias = false;
 };
 
 // One execution context.  `opt` and `w` are what a fork shares with its parent (copied whole by mellow_engine_fork); the rest is its own.
@@ -211,7 +220,7 @@ struct mellow_engine {
     // d_params, the sampling parameters in d_sparams).  generate_pass (engine_generate.cpp) captures, ensure_lm invalidates.
     struct LOCAL StepGraphs {
         struct Key {
-            std::array<uintptr_t, 14> v{};       // all zero: no capture (a pass has at least one row)
+            std::array<uintptr_t, 17> v{};       // all zero: no capture (a pass has at least one row)
             static Key of(const mellow_engine* e, int B);      // from the engine as configured for the pass (below the engine)
             bool operator==(const Key& k) const { return v == k.v; }
         };
@@ -271,6 +280,12 @@ struct mellow_engine {
     int32_t h_params[2] = {0, 0};              // staging of d_params {max_len, stop id}
     uint32_t* d_sparams = nullptr;             // sampling parameter block (kernels.h SMP_*): graph replays serve any seed / top_p / T
     uint32_t h_sparams[SMP_WORDS] = {0};       // ... its staging
+    uint32_t* d_rparams = nullptr;             // rule parameter block (kernels.h RUL_*): graph replays serve any penalty / n-gram size / minimum / bias on-off
+    uint32_t h_rparams[RUL_WORDS] = {0};       // ... its staging
+    LogitRules rules_armed;                    // mellow_generate_rules: what the NEXT mellow_generate* call on this context takes (and clears)
+    // repetition controls, created on first use: the call's dense logit bias [vocab] (a copy: no caller pointer is ever captured),
+    // and the ping-pong history of a beam call [2][rows][max_len] int32 (logit_rules.hip)
+    Buf rules_bias, rules_hist;
     StepMode mode;                             // what apply_step_mode last set (run_lm_head, loop_args and StepGraphs::Key::of read it)
     int32_t h_blk[64] = {0};                   // staging of d_blk_left[32] | d_blk_live[32]
     std::vector<int32_t> h_ident;              // staging of d_row_of_slot
@@ -332,7 +347,10 @@ inline mellow_engine::StepGraphs::Key mellow_engine::StepGraphs::Key::of(const m
                 (uintptr_t)(e->mode.beam ? e->beam_ws.p : nullptr),          // ... its loop words and tables: BeamArgs, the reorder's parent table
                 (uintptr_t)(e->mode.beam ? e->beam_max_len : 0),             // ... the table offsets inside beam_ws
                 (uintptr_t)(e->mode.beam > 1 ? e->kstage.p : nullptr),       // ... the staging buffers of the reorder
-                (uintptr_t)(e->mode.beam > 1 ? e->vstage.p : nullptr)}};
+                (uintptr_t)(e->mode.beam > 1 ? e->vstage.p : nullptr),
+                (uintptr_t)e->mode.rules,          // repetition controls: dec_logit_rules_kernel in the step; the head with its logits store
+                (uintptr_t)(e->mode.rules ? e->rules_bias.p : nullptr),                     // ... the bias buffer: RulesArgs
+                (uintptr_t)(e->mode.rules && e->mode.beam ? e->rules_hist.p : nullptr)}};   // ... the beam rows' history buffer: RulesArgs
 }
 static_assert(!std::is_copy_constructible<mellow_engine::Buf>::value, "a Buf owns its device memory: it moves, it is never copied");
 static_assert(std::is_copy_assignable<mellow_engine::Weights>::value && std::is_copy_assignable<mellow_engine::Options>::value, "a fork copies these by assignment: no owning member (Buf, StepGraphs) belongs in them");
@@ -394,6 +412,8 @@ void apply_step_mode(mellow_engine* e, const StepMode& m);
 int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec);
 // the words of beam_ws (engine_internal.h, the member's comment) as the select takes them, tables laid out for e->beam_max_len
 BeamArgs beam_args(mellow_engine* e, int N, int k);
+// the rules launch of a generation step on B rows, from the engine as apply_step_mode configured it (engine_lm.cpp)
+RulesArgs rules_args(mellow_engine* e, int B);
 // n > 1 (mellow_generate_n; fp32 pages only): the layers run on the B examples and write K/V to kprefix / vprefix; the fan-out and
 // everything from the last prefix row on (last layer, head, first token) run on B * n rows
 int run_prefill(mellow_engine* e, int B, int T, const RecordArgs* rec, bool all_positions = false, int n = 1);

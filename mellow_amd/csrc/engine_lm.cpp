@@ -100,7 +100,8 @@ int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end, int prefill
 void apply_step_mode(mellow_engine* e, const StepMode& m) {
     e->mode = m;
     DecArgs& a = e->da;
-    a.logits = m.logits ? e->dlogits.p : nullptr;      // (off: generation's arg-max needs the candidates only, no 6 MB store per step)
+    e->mode.logits = m.logits || m.rules;              // the rules edit the stored rows
+    a.logits = e->mode.logits ? e->dlogits.p : nullptr;      // (off: generation's arg-max needs the candidates only, no 6 MB store per step)
     a.cand_sum = m.logprob ? e->cand_sum.p : nullptr;
     a.blk_live = m.early_exit ? e->d_blk_live : nullptr;
     a.blk_snap = e->d_blk_live + 32;
@@ -144,6 +145,23 @@ BeamArgs beam_args(mellow_engine* e, int N, int k) {
     return g;
 }
 
+RulesArgs rules_args(mellow_engine* e, int B) {
+    const LoopArgs lp = loop_args(e);
+    RulesArgs g;
+    g.logits = e->da.logits; g.ld = e->cfg.vocab_size; g.prm = e->d_rparams; g.bias = e->rules_bias.p;
+    g.cand_val = e->da.cand_val; g.cand_idx = e->da.cand_idx; g.cand_sum = e->da.cand_sum;
+    g.d_pos = e->d_pos; g.params = lp.params; g.T0 = lp.T0;
+    g.row_of_slot = lp.row_of_slot; g.blk_snap = lp.blk_snap;
+    if (e->mode.beam) {
+        const BeamArgs bm = beam_args(e, B, e->mode.beam);
+        g.beam_hist = reinterpret_cast<int32_t*>(e->rules_hist.p); g.hist_ld = e->beam_max_len;
+        g.parent_tab = bm.out_parent; g.token_tab = bm.out_token; g.N = B; g.k = e->mode.beam;
+    } else {
+        g.hist = lp.out_tokens;
+    }
+    return g;
+}
+
 // final norm (+ pending down slabs) + lm_head with fused per-tile arg-max candidates -> dlogits, d_tokens
 int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec) {
     const int NT = e->cfg.vocab_size / 32, Bp = e->da.rows;
@@ -153,6 +171,10 @@ int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec)
     { ProfScope ps(e, PF_SKINNY, 2.0 * Bp * 576.0 * e->cfg.vocab_size, 576.0 * e->cfg.vocab_size * 4);
       const DecW h = e->w.head_w();
       launch_dec_lm_head(dh(1), h.p, e->w.lm_head.KP / 8, e->cfg.vocab_size, e->stream, h.scale); }
+    if (e->mode.rules && rec) {      // repetition controls: the row's logits and tile partials are edited before any picker reads them
+        ProfScope ps(e, PF_MISC, 0, 2.0 * B * e->cfg.vocab_size * 4);
+        launch_dec_logit_rules(rules_args(e, B), B, e->stream);
+    }
     { ProfScope ps(e, PF_MISC, 0, 0);
       if (e->mode.beam) {          // mellow_generate_beam: the head stored the logits; the k best continuations per example
           const LoopArgs lp = loop_args(e);

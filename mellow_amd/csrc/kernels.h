@@ -319,6 +319,38 @@ void launch_beam_select(const BeamArgs& g, int B, const DecArgs& a, int32_t* tok
 // scattered into the row's own pages [layers][Bp][3][Tmax][64].  Two launches of fixed grid; k = 1 launches nothing.
 void launch_beam_reorder(float* k_pages, float* v_pages, float* k_stage, float* v_stage, const int32_t* parent_tab, const int32_t* d_pos,
                          const int32_t* params, int T0, int layers, int N, int k, int Bp, int Tmax, hipStream_t s);
+// Repetition controls (logit_rules.hip; include/mellow_hip.h mellow_generate_rules states the exact definition): one launch that
+// edits every live row's logits from the row's own history and forms the row's tile partials (cand_val / cand_idx / cand_sum) anew,
+// so that the arg-max, the sampler, the beam select and the LSE merges that follow run unchanged on the processed row.  The rule
+// values live in a device block the host fills per call, so a captured step serves any of them:
+// prm = {bits of the repetition penalty, no_repeat_ngram_size, min_new_tokens, bias on / off, stop id}.
+enum { RUL_THETA = 0, RUL_NGRAM, RUL_MIN_NEW, RUL_BIAS_ON, RUL_STOP, RUL_WORDS = 8 };
+constexpr int RULES_MAX_HIST = 8192;     // history tokens the kernel stages in LDS (32 KiB): the largest max_len of a call with rules
+struct RulesArgs {
+    float* logits = nullptr;             // [slots][ld] fp32, edited in place (ld = SAMPLE_MAX_V: the row tiling of the sampler)
+    int64_t ld = 0;
+    const uint32_t* prm = nullptr;       // device block of RUL_WORDS words
+    const float* bias = nullptr;         // [ld] fp32, read when prm[RUL_BIAS_ON] != 0
+    float* cand_val = nullptr; int32_t* cand_idx = nullptr;   // [slots][ld / 32], rewritten
+    float* cand_sum = nullptr;           // [slots][ld / 32] or null
+    // the history of a row, one of three sources:
+    //   tap (hist_len != null): hist [slots][hist_ld], hist_len [slots];
+    //   loop: hist = the token record [rows][params[0]], columns [0, s) with s = *d_pos - T0 + 1;
+    //   beam loop (beam_hist != null): beam_hist [2][N][hist_ld], half s & 1 built at step s from half (s - 1) & 1 of the parent row
+    //   (parent_tab / token_tab [params[0]][N]: the select's tables) -- a beam row's history is its hypothesis, not its slot's past
+    const int32_t* hist = nullptr;
+    int hist_ld = 0;
+    const int32_t* hist_len = nullptr;
+    const int32_t* d_pos = nullptr;
+    const int32_t* params = nullptr;     // device {max_len, stop_id} (LoopArgs::params)
+    int T0 = 0;
+    const int32_t* row_of_slot = nullptr;   // as in LoopArgs: logits and partials are addressed by slot, the history by example
+    const int32_t* blk_snap = nullptr;
+    int32_t* beam_hist = nullptr;
+    const int32_t* parent_tab = nullptr; const int32_t* token_tab = nullptr;
+    int N = 0, k = 1;
+};
+void launch_dec_logit_rules(const RulesArgs& g, int B, hipStream_t s);
 // after the arg-max of a step (early-exit mode only): if the rows that have not produced the stop id yet fit into fewer 32-row
 // blocks than are live, move them (their next-step residual rows) to the lowest slots, rewrite row_of_slot / blk_left / blk_live
 void launch_dec_compact(const DecArgs& a, int B, const LoopArgs& loop, hipStream_t s);

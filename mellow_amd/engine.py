@@ -34,6 +34,12 @@ class MellowConfig(C.Structure):
     ]
 
 
+class LogitRules(C.Structure):
+    """mellow_logit_rules_t (include/mellow_hip.h)"""
+    _fields_ = [("size", C.c_int32), ("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int32),
+                ("min_new_tokens", C.c_int32), ("logit_bias", C.c_void_p)]
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -43,7 +49,7 @@ _lib = None
 _ADDED_UNDER_MINOR_4 = ("mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse", "mellow_generate_n",
                         "mellow_generate_q", "mellow_generate_beam", "mellow_beam_select")
 # symbols of minor 5 (the attention taps on host data): looked up the same way, so that a minor-4 library still loads
-_ADDED_UNDER_MINOR_5 = ("mellow_debug_prefill_attn", "mellow_debug_window_attn")
+_ADDED_UNDER_MINOR_5 = ("mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_generate_rules", "mellow_logit_rules_apply")
 
 
 def load_library(path: Optional[str] = None):
@@ -82,6 +88,8 @@ def load_library(path: Optional[str] = None):
         "mellow_generate_beam": (ci, [vp, vp, vp, i64, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, P(C.c_int32), P(cf)]),
         "mellow_beam_select": (ci, [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp]),
         "mellow_sample_logits": (ci, [vp, vp, ci, vp, ci, cf, cf, C.c_uint64, vp]),
+        "mellow_generate_rules": (ci, [vp, P(LogitRules)]),
+        "mellow_logit_rules_apply": (ci, [vp, P(LogitRules), vp, ci, vp, ci, vp, ci, vp, vp, vp]),
         "mellow_logmel": (ci, [vp, vp, ci, i64, ci, vp]),
         "mellow_encode": (ci, [vp, vp, ci, i64, vp]),
         "mellow_prefix": (ci, [vp, vp, vp, i64, vp, ci, vp]),
@@ -139,7 +147,7 @@ EXPORTED_SYMBOLS = (
     "mellow_engine_num_required", "mellow_engine_required_key", "mellow_generate", "mellow_generate_sampled", "mellow_sample_logits", "mellow_logmel",
     "mellow_encode", "mellow_prefix", "mellow_lm_prefill", "mellow_lm_decode_step", "mellow_argmax", "mellow_embed_tokens", "mellow_lm_forward_logits",
     "mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse", "mellow_generate_n", "mellow_generate_q",
-    "mellow_generate_beam", "mellow_beam_select", "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
+    "mellow_generate_beam", "mellow_beam_select", "mellow_generate_rules", "mellow_logit_rules_apply", "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
     "mellow_prof_num_families", "mellow_prof_family_name", "mellow_prof_get", "mellow_last_phase_ms", "mellow_last_steps_enqueued", "mellow_last_row_repacks", "mellow_stft_is_fft", "mellow_prefill_parts", "mellow_abi_minor",
     "mellow_resample", "mellow_engine_set_precision", "mellow_engine_set_option", "mellow_engine_describe", "mellow_debug_gemm_fp8", "mellow_debug_gemm_f32", "mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_debug_dec_head", "mellow_set_graph", "mellow_host_window_map", "mellow_host_pack_weight", "mellow_host_rope_tables",
 )
@@ -175,6 +183,32 @@ def plan_nseq_passes(B: int, n: int, row_offset: int = 0):
         raise ValueError(f"num_return_sequences = {n} exceeds the {NSEQ_PASS_ROWS} answer rows one pass of the engine takes")
     per = NSEQ_PASS_ROWS // n
     return [(lo, min(B, lo + per), row_offset + lo * n) for lo in range(0, B, per)]
+
+
+RULES_MAX_LEN = 8192           # max_len of a call with logit rules (the history one row stages)
+
+
+def check_logit_rules(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, logit_bias=None, vocab: Optional[int] = None):
+    """The value rules of the repetition controls that need no engine (the C entry repeats the first three).  -> (penalty, n, m,
+    bias as a dense float32 [vocab] array or None)."""
+    import math
+    t = float(repetition_penalty)
+    if not math.isfinite(t) or t <= 0.0:
+        raise ValueError(f"repetition_penalty must be finite and > 0 (got {repetition_penalty}); 1 is off")
+    n, m = int(no_repeat_ngram_size), int(min_new_tokens)
+    if n < 0:
+        raise ValueError(f"no_repeat_ngram_size must be >= 0 (got {n}); 0 is off")
+    if m < 0:
+        raise ValueError(f"min_new_tokens must be >= 0 (got {m}); 0 is off")
+    bias = None
+    if logit_bias is not None:
+        bias = np.ascontiguousarray(torch.as_tensor(logit_bias).detach().cpu().numpy() if isinstance(logit_bias, torch.Tensor)
+                                    else logit_bias, dtype=np.float32).reshape(-1)
+        if vocab is not None and bias.shape[0] != int(vocab):
+            raise ValueError(f"logit_bias must hold one value per token of the vocabulary ({int(vocab)}), got {bias.shape[0]}")
+        if np.isnan(bias).any() or np.isposinf(bias).any():
+            raise ValueError("logit_bias values must be finite or -inf (NaN and +inf are refused)")
+    return t, n, m, bias
 
 
 BEAM_MAX_K = 8                 # beams per example mellow_generate_beam takes
@@ -408,7 +442,8 @@ class Engine:
     def generate(self, audio1, audio2, input_ids, max_len: int, top_p: float = 0.8, temperature: float = 1.0,
                  stop_id: int = 0, ignore_stop: bool = False, do_sample: bool = False, seed: Optional[int] = None,
                  row_offset: int = 0, return_logprobs: bool = False, num_return_sequences: int = 1,
-                 num_beams: Optional[int] = None, length_penalty: float = 1.0):
+                 num_beams: Optional[int] = None, length_penalty: float = 1.0, repetition_penalty: float = 1.0,
+                 no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, logit_bias=None, _arm_neutral_rules: bool = False):
         """-> (tokens int32 [B, steps] on host, lengths [B], steps, first_token_ms)
         num_return_sequences = n > 1 (needs do_sample=True): n sampled answers per example from one encode and one prefill per
         example (mellow_generate_n).  Every array has B * n rows, row b * n + j = answer j of example b, and holds what this call
@@ -431,10 +466,16 @@ class Engine:
         hypotheses are ranked by score = logprob / tokens ** length_penalty (tokens counts the stop id), then beam index.  tokens
         [B * m, steps] hold a hypothesis up to its stop id and the stop id from there on; lengths as in the greedy call.
         return_logprobs=True appends token_logprobs [B * m, steps] (0.0 after the stop id) and scores float64 [B * m].  Not
-        together with do_sample or several questions per example.  `last_beam` keeps the raw tables of the call."""
+        together with do_sample or several questions per example.  `last_beam` keeps the raw tables of the call.
+        repetition_penalty / no_repeat_ngram_size / min_new_tokens / logit_bias (dense float [vocab], finite or -inf): the repetition
+        controls of include/mellow_hip.h (mellow_generate_rules), applied to every row's logits on the device before the token is
+        chosen, whatever chooses it (arg-max, sampler, beam select); the history is the row's generated tokens.  With any of them
+        set, a returned log-prob is that of the processed distribution, not the number score() returns.  All at their neutral
+        values: nothing is armed and the call is the one without these keywords."""
         import time
         t_in = time.perf_counter()
         nseq = int(num_return_sequences)
+        self._rules = self._make_rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, logit_bias, _arm_neutral_rules, int(max_len))
         if num_beams is not None:
             if do_sample:
                 raise ValueError("num_beams and do_sample=True do not combine: beam search is deterministic")
@@ -469,15 +510,18 @@ class Engine:
         if return_logprobs:
             self._need("mellow_generate_scored")
             lp = torch.empty((B, max_len), dtype=torch.float32, device=self.tdev)
+            self._arm()
             self._chk(self.lib.mellow_generate_scored(self.h, _ptr(a1), _ptr(a2), n, _ptr(ids), B, int(max_len), 1 if do_sample else 0,
                                                       float(top_p), float(temperature), _seed64(seed) if do_sample else 0,
                                                       int(row_offset) if do_sample else 0, int(stop_id), 1 if ignore_stop else 0,
                                                       _ptr(out), _ptr(lp), lens, C.byref(steps), C.byref(ftm)))
         elif do_sample:
+            self._arm()
             self._chk(self.lib.mellow_generate_sampled(self.h, _ptr(a1), _ptr(a2), n, _ptr(ids), B, int(max_len), float(top_p),
                                                        float(temperature), _seed64(seed), int(row_offset), int(stop_id),
                                                        1 if ignore_stop else 0, _ptr(out), lens, C.byref(steps), C.byref(ftm)))
         else:
+            self._arm()
             self._chk(self.lib.mellow_generate(self.h, _ptr(a1), _ptr(a2), n, _ptr(ids), B, int(max_len), float(top_p),
                                                float(temperature), int(stop_id), 1 if ignore_stop else 0, _ptr(out),
                                                lens, C.byref(steps), C.byref(ftm)))
@@ -485,6 +529,55 @@ class Engine:
         self.last_first_token_host_ms = t_up + float(ftm.value)
         res = (toks, np.asarray(list(lens), dtype=np.int32), int(steps.value), float(ftm.value))
         return res + (lp.cpu().numpy()[:, : steps.value],) if return_logprobs else res
+
+    def _make_rules(self, repetition_penalty, no_repeat_ngram_size, min_new_tokens, logit_bias, arm_neutral, max_len):
+        """the struct _arm() hands to mellow_generate_rules before every C call of this generate(), or None: nothing to arm"""
+        t, n, m, bias = check_logit_rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, logit_bias,
+                                          None if logit_bias is None else self.lm.vocab_size)
+        if t == 1.0 and n == 0 and m == 0 and bias is None and not arm_neutral:
+            return None
+        if m > max_len:
+            raise ValueError(f"min_new_tokens = {m} exceeds max_len = {max_len}")
+        if max_len > RULES_MAX_LEN:
+            raise ValueError(f"a call with logit rules takes max_len <= {RULES_MAX_LEN} (got {max_len})")
+        self._need("mellow_generate_rules")
+        r = LogitRules(size=C.sizeof(LogitRules), repetition_penalty=t, no_repeat_ngram_size=n, min_new_tokens=m,
+                       logit_bias=None if bias is None else bias.ctypes.data)
+        r._bias = bias               # keeps the vector alive while the struct points at it
+        return r
+
+    def _arm(self):
+        """arm this call's rules for the next mellow_generate* call (it clears them): before EVERY C call a generate() makes"""
+        r = getattr(self, "_rules", None)
+        if r is not None:
+            self._chk(self.lib.mellow_generate_rules(self.h, C.byref(r)))
+
+    def logit_rules_apply(self, logits, history, hist_len, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
+                          min_new_tokens: int = 0, logit_bias=None, stop_id: int = 0, with_sum: bool = True):
+        """The rules on caller data (numeric tap, mellow_logit_rules_apply): logits [B][vocab], history int [B][ld], hist_len int [B]
+        -> dict of numpy arrays: "logits" [B][vocab] processed, "cand_val" / "cand_idx" [B][vocab / 32] the per-tile maximum and
+        its first index, "cand_sum" [B][vocab / 32] the per-tile sum of exp(l - cand_val) (with_sum=False: absent)."""
+        t, n, m, bias = check_logit_rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, logit_bias, self.lm.vocab_size)
+        self._need("mellow_logit_rules_apply")
+        lg = self._f32(logits).clone()
+        B, V = lg.shape
+        h = self._i32(history).reshape(B, -1)
+        ln = self._i32(hist_len).reshape(-1)
+        if V != self.lm.vocab_size or ln.shape[0] != B:
+            raise ValueError(f"logits {tuple(lg.shape)}, history {tuple(h.shape)}, hist_len {tuple(ln.shape)} do not describe B rows of the vocabulary")
+        ld = int(h.shape[1])
+        cv = torch.empty((B, V // 32), dtype=torch.float32, device=self.tdev)
+        cx = torch.empty((B, V // 32), dtype=torch.int32, device=self.tdev)
+        cs = torch.empty((B, V // 32), dtype=torch.float32, device=self.tdev) if with_sum else None
+        r = LogitRules(size=C.sizeof(LogitRules), repetition_penalty=t, no_repeat_ngram_size=n, min_new_tokens=m,
+                       logit_bias=None if bias is None else bias.ctypes.data)
+        self._sync_inputs()
+        self._chk(self.lib.mellow_logit_rules_apply(self.h, C.byref(r), _ptr(lg), B, _ptr(h) if ld else None, ld, _ptr(ln), int(stop_id),
+                                                    _ptr(cv), _ptr(cx), None if cs is None else _ptr(cs)))
+        out = {"logits": lg.cpu().numpy(), "cand_val": cv.cpu().numpy(), "cand_idx": cx.cpu().numpy()}
+        if cs is not None:
+            out["cand_sum"] = cs.cpu().numpy()
+        return out
 
     def _generate_nseq(self, audio1, audio2, input_ids, max_len, nseq, top_p, temperature, stop_id, ignore_stop, seed, row_offset,
                        return_logprobs, t_in):
@@ -507,6 +600,7 @@ class Engine:
             r0, nr = lo * nseq, (hi - lo) * nseq
             ln = (C.c_int32 * nr)()
             steps, ftm = C.c_int32(0), C.c_float(0.0)
+            self._arm()
             self._chk(self.lib.mellow_generate_n(self.h, _ptr(a1[lo:hi]), _ptr(a2[lo:hi]), ns, _ptr(ids[lo:hi]), hi - lo, nseq, max_len, 1,
                                                  top_p, temperature, seed, off, stop_id, 1 if ignore_stop else 0, _ptr(out[r0:r0 + nr]),
                                                  None if lp is None else _ptr(lp[r0:r0 + nr]), ln, C.byref(steps), C.byref(ftm)))
@@ -545,6 +639,7 @@ class Engine:
         t_up = (time.perf_counter() - t_in) * 1e3
         steps, ftm = C.c_int32(0), C.c_float(0.0)
         vp = C.c_void_p
+        self._arm()
         self._chk(self.lib.mellow_generate_beam(self.h, _ptr(a1), _ptr(a2), ns, _ptr(ids), B, k, max_len, stop_id, 1 if ignore_stop else 0,
                                                 vp(par.ctypes.data), vp(tok.ctypes.data), vp(lp.ctypes.data), vp(cum.ctypes.data),
                                                 C.byref(steps), C.byref(ftm)))
@@ -602,6 +697,7 @@ class Engine:
         t_up = (time.perf_counter() - t_in) * 1e3
         lens = (C.c_int32 * N)()
         steps, ftm = C.c_int32(0), C.c_float(0.0)
+        self._arm()
         self._chk(self.lib.mellow_generate_q(self.h, _ptr(a1), _ptr(a2), ns, _ptr(ids), B, Q, max_len, 1 if do_sample else 0, top_p,
                                              temperature, seed, row_offset, stop_id, 1 if ignore_stop else 0, _ptr(out),
                                              None if lp is None else _ptr(lp), lens, C.byref(steps), C.byref(ftm)))

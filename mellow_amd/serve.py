@@ -65,7 +65,9 @@ class EnginePool:
         so the result does not depend on how many contexts run the batches or which one gets which (num_return_sequences=n: every
         example counts n rows; input_ids [B][Q][text_len]: every example counts Q rows).
         Every keyword of Engine.generate passes through (return_logprobs=True: five values per batch; num_beams=k with
-        length_penalty / num_return_sequences: a beam search per batch, deterministic, so no row offset is involved)."""
+        length_penalty / num_return_sequences: a beam search per batch, deterministic, so no row offset is involved;
+        repetition_penalty / no_repeat_ngram_size / min_new_tokens / logit_bias: the repetition controls, armed by each context for
+        its own calls, the same for every batch)."""
         kws = [kw] * len(batches)
         if kw.get("do_sample"):
             off, kws = int(kw.get("row_offset", 0)), []

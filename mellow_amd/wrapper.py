@@ -270,6 +270,7 @@ class MellowWrapper:
         n_local = int(audio1.shape[0])
         if n_local:
             samp = dict(do_sample=True, seed=seed, row_offset=row_offset) if do_sample else {}
+            samp.update(getattr(self, "_rules_kw", None) or {})
             if nseq > 1:
                 samp["num_return_sequences"] = nseq
             if return_logprobs:       # (refused under data-parallel sharding by generate(): the gather below carries tokens only)
@@ -327,7 +328,9 @@ class MellowWrapper:
 
     def generate(self, examples, max_len, top_p, temperature, stop_token="<|endoftext|>", audio_resample=True, *,
                  do_sample: bool = False, seed: Optional[int] = None, return_logprobs: bool = False,
-                 num_return_sequences: int = 1, num_beams: int = 1, length_penalty: float = 1.0):
+                 num_return_sequences: int = 1, num_beams: int = 1, length_penalty: float = 1.0, repetition_penalty: float = 1.0,
+                 no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, suppress_tokens: Optional[Sequence[int]] = None,
+                 logit_bias: Optional[dict] = None):
         r"""Produces text response for the given audio files and text prompts
         examples: (list<list>) each example is [audio path 1, audio path 2, text prompt]; the text prompt may be a list or tuple of
                      prompts, several questions about the one pair of clips (module docstring).  If any example has a list, the
@@ -352,6 +355,18 @@ class MellowWrapper:
                      1 (default): the call without the keyword.
         length_penalty: (float) exponent of the hypothesis length in the final ranking (0: rank by logprob alone); the beams compete
                      on the raw logprob during the search.
+        repetition_penalty: (float) t > 0: the logit of every token the answer already holds is divided by t if positive and
+                     multiplied by t if negative, once per distinct token (1, the default: off).
+        no_repeat_ngram_size: (int) n > 0: no n-gram of tokens occurs twice in an answer (0: off).
+        min_new_tokens: (int) the stop token cannot be chosen before an answer holds this many tokens (0: off).
+        suppress_tokens: (list<int>) token ids that are never chosen.
+        logit_bias: (dict) {token id: float added to that token's logit}; -inf suppresses the token.
+                     These five work with every other keyword (do_sample, return_logprobs, num_return_sequences, question lists,
+                     num_beams, data parallelism: the rules are per call and the same on every rank) and run on the device, on the
+                     generated tokens of each answer (the prompt is not part of the history).  With any of them set, a returned
+                     log-prob is that of the processed distribution the token was chosen from -- no longer what `score` returns.
+                     ValueError for t <= 0 or not finite, a negative n or m, an id outside the vocabulary, a NaN or +inf bias, or
+                     min_new_tokens > max_len.  All at their defaults: the call without the keywords.
 
         With `data_parallel=True` (or MELLOW_DATA_PARALLEL=1) under an initialised torch.distributed group (one process per
         GPU, every rank calling with the same examples) the examples are sharded contiguously over the ranks, each rank ingests
@@ -362,6 +377,7 @@ class MellowWrapper:
             audio_paths1.append(ap1)
             audio_paths2.append(ap2)
             text_prompts.append(tp)
+        self._rules_kw = self._rules_keywords(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, logit_bias, max_len)
         nseq = int(num_return_sequences)
         if nseq < 1:
             raise ValueError(f"num_return_sequences must be >= 1 (got {nseq})")
@@ -395,6 +411,10 @@ class MellowWrapper:
             extra = repr(("sample", seed, float(top_p), float(temperature))).encode()
             if nseq > 1:
                 extra += repr(("nseq", nseq)).encode()
+        if self._rules_kw:      # the rules are per call and the same on every rank: a mismatch is refused by the same exchange
+            import hashlib
+            extra += repr(sorted((k, hashlib.sha1(np.ascontiguousarray(v).tobytes()).hexdigest() if k == "logit_bias" else v)
+                                 for k, v in self._rules_kw.items())).encode()
         lo, hi = 0, n
         if world > 1:
             from .dist import shard_range
@@ -410,6 +430,35 @@ class MellowWrapper:
         return self._generate_batch(audio1, audio2, ids, entry_length=max_len, top_p=top_p,
                                     temperature=temperature, stop_token=stop_token, n_total=n, do_sample=do_sample,
                                     seed=seed, row_offset=lo * nseq, return_logprobs=return_logprobs, nseq=nseq)
+
+    def _rules_keywords(self, repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, logit_bias, max_len):
+        """The repetition controls of a generate() call as keywords of Engine.generate: only those that differ from their neutral
+        value, so a call that sets none passes none.  suppress_tokens and logit_bias are merged into one dense vector."""
+        from .engine import check_logit_rules
+        t, n, m, _ = check_logit_rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens)
+        if m > int(max_len):
+            raise ValueError(f"min_new_tokens = {m} exceeds max_len = {int(max_len)}")
+        kw = {}
+        if t != 1.0:
+            kw["repetition_penalty"] = t
+        if n:
+            kw["no_repeat_ngram_size"] = n
+        if m:
+            kw["min_new_tokens"] = m
+        entries = [(tok, val) for tok, val in (logit_bias or {}).items()] + [(tok, -math.inf) for tok in (suppress_tokens or [])]
+        if entries:
+            lm = getattr(self.model, "lm", None) or LMConfig.load()
+            V = int(lm.vocab_size)
+            dense = np.zeros((V,), dtype=np.float32)
+            for tok, val in entries:
+                if isinstance(tok, bool) or int(tok) != tok or not 0 <= int(tok) < V:
+                    raise ValueError(f"token id {tok!r} is outside the vocabulary [0, {V})")
+                val = float(val)
+                if math.isnan(val) or val == math.inf:
+                    raise ValueError(f"logit_bias[{int(tok)}] = {val}: values must be finite or -inf")
+                dense[int(tok)] += np.float32(val)          # (a suppressed token stays suppressed: -inf + finite = -inf)
+            kw["logit_bias"] = dense
+        return kw
 
     def _generate_beams(self, examples, audio_paths1, audio_paths2, text_prompts, max_len, stop_token, audio_resample, do_sample,
                         return_logprobs, k, m, length_penalty):
@@ -436,6 +485,7 @@ class MellowWrapper:
         audio2 = self.preprocess_audio(audio_paths2, resample=audio_resample)
         ids = self.preprocess_text(text_prompts)["input_ids"]
         kw = dict(max_len=entry_length, stop_id=stop_id, num_beams=k, length_penalty=length_penalty, num_return_sequences=m)
+        kw.update(getattr(self, "_rules_kw", None) or {})
         if return_logprobs:
             toks, lens, steps, ftm, logprobs, scores = self.model.generate(audio1, audio2, ids, return_logprobs=True, **kw)
             res = self._scored_results(toks, logprobs, stop_id)
