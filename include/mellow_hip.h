@@ -55,7 +55,8 @@ extern "C" {
  *     was mellow_generate_n (n sampled answers per example from one encode and one prefill), and then mellow_generate_q (several
  *     questions per example from one encode and one prefill of the clips' positions), and then mellow_generate_beam with its tap
  *     mellow_beam_select (beam search inside the decode step), and then mellow_generate_rules with its tap mellow_logit_rules_apply
- *     (repetition controls: logit rules inside the decode step) -- added while the minor was 5, detected by symbol lookup all the same.
+ *     (repetition controls: logit rules inside the decode step), and then mellow_generate_guidance with its tap mellow_guidance_apply
+ *     (contrastive guidance inside the decode step) -- added while the minor was 5, detected by symbol lookup all the same.
  *  5: the attention taps on host data, mellow_debug_prefill_attn and mellow_debug_window_attn.  No existing symbol or struct
  *     changed; a binding that must also load a minor-4 library detects them by symbol lookup. */
 #define MELLOW_ABI_MINOR 5
@@ -344,6 +345,46 @@ int  mellow_generate_rules(mellow_engine_t* e, const mellow_logit_rules_t* rules
  * armed on the context (it uses the context's bias buffer).  Errors as above, and a null buffer, B <= 0 or ld outside [0, 8192]. */
 int  mellow_logit_rules_apply(mellow_engine_t* e, const mellow_logit_rules_t* rules, float* logits, int B, const int32_t* history, int ld,
                               const int32_t* hist_len, int stop_id, float* cand_val, int32_t* cand_idx, float* cand_sum);
+/* Contrastive (classifier-free) guidance: the step's distribution is contrasted with that of a NEGATIVE input on the device, inside
+ * the decode step, between the lm_head and the rules launch / the kernel that picks the token -- for the prefill's first token as for
+ * every decode step.
+ *
+ * Definition.  A guided call on P examples runs 2 * P rows: row 2i is example i (the conditional row), row 2i + 1 its negative (the same
+ * question over silence, over the swapped pair, over another pair: the caller's choice; the two are ordinary rows of the batch for the
+ * encoder, the prefill, the K/V pages and the decode layers).  Per step and pair, with l_c, l_u the fp32 logits of the two rows and s
+ * the scale:
+ *     lse_x = m_x + log(sum_v exp(l_x[v] - m_x)),  m_x = max_v l_x[v]          (x = c, u)
+ *     a[v]  = l_c[v] - lse_c;  b[v] = l_u[v] - lse_u
+ *     g[v]  = b[v] + s * (a[v] - b[v])
+ * (the form of Hugging Face's unbatched classifier-free guidance processor: s = 1 gives the conditional log-softmax, s = 0 the
+ * negative's, s > 1 moves away from the negative).  g is written to BOTH rows of the pair and the per-tile partials of both rows are
+ * formed anew from it, so everything downstream sees two identical rows: the repetition controls, if armed, run after the guidance
+ * (on g, with the pair's common history), then the arg-max or the sampler.  Both rows therefore get the same token and both K/V
+ * histories advance with the answer actually produced.  A recorded log-prob is that of the processed distribution the token was
+ * chosen from (the log-softmax of g, after the rules if armed), not the number mellow_score returns.  The sampler's random stream of
+ * pair i is that of global row `row_offset + i` -- the PAIR index -- so guided answer i draws from the stream un-guided example i
+ * would, whatever the batch layout.  All arithmetic is fp32 in one fixed order (the bits depend on the inputs only); logits that come
+ * from the head are finite, and the definition says nothing about +-inf or NaN inputs.
+ *
+ * mellow_generate_guidance arms the scale for the NEXT mellow_generate* call on this context; that call takes it at entry and clears
+ * it whatever its outcome.  A fork has its own, initially none.  Scale 1 arms nothing (and disarms).  Honoured by mellow_generate,
+ * _sampled and _scored (and by _n with n = 1 and _q with Q = 1, which are those calls), with and without armed rules: their B is then
+ * the ROW count 2 * P and must be even; every output holds all rows, rows 2i and 2i + 1 equal.  A call of more than 1024 rows splits
+ * at an even row and its row offset advances by pairs.  Refused with a message, and disarmed, by mellow_generate_n with n > 1,
+ * mellow_generate_q with Q > 1 and mellow_generate_beam.  Guidance needs no K/V fan-out: it is available in every precision.  A
+ * guided call runs without row migration (a pair's rows stay neighbours); per-block early exit stays.  A call without armed guidance
+ * launches exactly what it launched before these symbols existed.  Not built yet: beams, n > 1, question lists, sharding pairs over
+ * data-parallel ranks.  Measured cost: 32 pairs take about 30 us (3 %) more per decode step than the un-guided call of
+ * the same 64 rows, 28 us with rules armed on both.
+ * Errors: a scale that is not finite (host code, before any device is touched); then a null or unfinalized engine.
+ * Added while the minor was 5 without raising it: a binding detects the two symbols by lookup. */
+int  mellow_generate_guidance(mellow_engine_t* e, float scale);
+/* The same combination on caller data, no loop state (numeric tap): logits dev f32 [2 * P][vocab], rows 2i / 2i + 1 the conditional and
+ * the negative row of pair i, both overwritten in place with g.  cand_val / cand_idx dev [2 * P][vocab / 32] receive, per 32-column tile
+ * of g, its maximum and the lowest index attaining it (the arg-max order); cand_sum dev f32 [2 * P][vocab / 32] (may be NULL) the tile's
+ * sum of exp(g - cand_val).  Any finite scale, 1 included.  Leaves guidance armed on the context as it is.  Errors as above, and a null
+ * buffer, P <= 0 or a vocabulary other than 49152. */
+int  mellow_guidance_apply(mellow_engine_t* e, float scale, float* logits, int P, float* cand_val, int32_t* cand_idx, float* cand_sum);
 /* The same draw on caller logits, no loop state (numeric tap): logits dev [B][vocab], row_ids dev i32 [B] (global row index
  * of each row; NULL = 0..B-1), step = t above -> tokens dev i32 [B]. */
 int  mellow_sample_logits(mellow_engine_t* e, const float* logits, int B, const int32_t* row_ids, int step, float top_p,

@@ -305,6 +305,7 @@ int alloc_state_words(mellow_engine* e) {
     e->d_params = e->d_tokens + 1032;
     e->d_sparams = reinterpret_cast<uint32_t*>(e->d_tokens + 1536);     // SMP_WORDS
     e->d_rparams = reinterpret_cast<uint32_t*>(e->d_tokens + 1552);     // RUL_WORDS
+    e->d_gparams = reinterpret_cast<uint32_t*>(e->d_tokens + 1560);     // GDN_WORDS
     e->d_blk_left = e->d_tokens + 1040;
     e->d_blk_live = e->d_tokens + 1072;
     e->d_seen = e->d_tokens + 2048;

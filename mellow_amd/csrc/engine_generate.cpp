@@ -24,12 +24,13 @@ struct GenRequest {
     int32_t* out_parent = nullptr;
     float* out_cum = nullptr;
     LogitRules rules;                            // repetition controls (mellow_generate_rules): taken from the context at entry, the same for every pass
+    Guidance guide;                              // contrastive guidance (mellow_generate_guidance): likewise; rows 2p and 2p + 1 are then pair p
     int rows() const { return examples * n * q; }
     // rows [r0, r0 + nb) of an n = 1, q = 1 request as a request of their own; a row's random stream follows its index in the whole call
     GenRequest pass(int r0, int nb, int text_len, int32_t* steps, float* ftm) const {
         GenRequest p = *this;
         p.audio1 += (size_t)r0 * n_samples; p.audio2 += (size_t)r0 * n_samples; p.input_ids += (size_t)r0 * text_len;
-        p.examples = nb; p.row_offset += r0;
+        p.examples = nb; p.row_offset += guide.on ? r0 >> 1 : r0;      // (guided: r0 is even, and the streams go by pair)
         p.out_tokens += (size_t)r0 * max_len;
         if (out_logprob) p.out_logprob += (size_t)r0 * max_len;
         if (out_len) p.out_len += r0;
@@ -89,9 +90,21 @@ static int stage_rules(mellow_engine_t* e, const LogitRules& r, int stop_id) {
     return 0;
 }
 
+// the value block a guidance launch reads
+static int stage_guidance(mellow_engine_t* e, float scale) {
+    memcpy(&e->h_gparams[GDN_SCALE], &scale, 4);
+    HIPCHK(hipMemcpyAsync(e->d_gparams, e->h_gparams, sizeof(e->h_gparams), hipMemcpyHostToDevice, e->stream));
+    return 0;
+}
+
 // Every argument rule of the six entry points, each once.
 static int check_request(mellow_engine_t* e, const GenRequest& r, int door) {
     if (!e || !e->finalized) return fail("engine not finalized");
+    if (r.guide.on) {      // (first: whatever else is wrong with such a call, this is what its caller has to hear)
+        if (r.beam) return fail("guidance is armed (mellow_generate_guidance): mellow_generate_beam does not take it (beam search over pairs is not built)");
+        if (r.n > 1) return fail("guidance is armed (mellow_generate_guidance): mellow_generate_n with n > 1 does not take it (pass every pair n times to mellow_generate_sampled)");
+        if (r.q > 1) return fail("guidance is armed (mellow_generate_guidance): mellow_generate_q with Q > 1 does not take it (pass a pair per question to mellow_generate)");
+    }
     if (r.n < 1) return fail("n must be >= 1 (got %d)", r.n);
     if (r.q < 1) return fail("Q must be >= 1 (got %d)", r.q);
     if (r.n > 1 && r.q > 1) return fail("internal: n and Q are never both above 1");
@@ -132,6 +145,10 @@ static int check_request(mellow_engine_t* e, const GenRequest& r, int door) {
     if (r.on) {
         CHK(check_sampling(e, r.top_p, r.temperature));
         if (r.row_offset < 0) return fail("row_offset must be >= 0");
+    }
+    if (r.guide.on) {
+        if (e->cfg.vocab_size != SAMPLE_MAX_V) return fail("the guidance kernel is built for a vocabulary of %d (engine: %d)", SAMPLE_MAX_V, e->cfg.vocab_size);
+        if (r.examples % 2 != 0) return fail("guidance is armed (mellow_generate_guidance): B counts rows, conditional and negative interleaved, and must be even (got %d)", r.examples);
     }
     if (r.rules.on) {
         if (e->cfg.vocab_size != SAMPLE_MAX_V) return fail("the logit rules are built for a vocabulary of %d (engine: %d)", SAMPLE_MAX_V, e->cfg.vocab_size);
@@ -295,8 +312,11 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
     m.beam = r.beam;
     if (r.beam) m.logits = true;        // the select reads the full logits rows; every row runs every step: no early exit, no migration
     m.rules = r.rules.on;               // dec_logit_rules_kernel edits the stored rows: the head stores them (apply_step_mode)
+    m.guide = r.guide.on;               // dec_guidance_kernel combines the stored rows of a pair: the head stores them (apply_step_mode)
     m.early_exit = !r.beam && (dev_dead || (!r.ignore_stop && e->da.RB > 1));
-    m.migrate = m.early_exit && !dev_dead && e->opt.row_migration;   // option "row_migration" = 0: block exit without repacking (developer A/B)
+    // a guided call runs without migration (a pair's rows stay neighbours in slots 2p, 2p + 1); block exit stays: both rows of a
+    // pair get the same token, so they finish at the same step, and a pair never straddles a 32-row block
+    m.migrate = m.early_exit && !dev_dead && e->opt.row_migration && !m.guide;   // option "row_migration" = 0: block exit without repacking (developer A/B)
     if (m.logprob) {
         // the head's partial sums and the record; columns that are never computed stay exactly 0.0
         CHK(ensure(e, e->cand_sum, (size_t)Bp * (e->cfg.vocab_size / 32)));
@@ -316,6 +336,7 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
         HIPCHK(hipMemcpyAsync(e->d_sparams, e->h_sparams, sizeof(e->h_sparams), hipMemcpyHostToDevice, s));
     }
     if (r.rules.on) CHK(stage_rules(e, r.rules, stop_id));
+    if (r.guide.on) CHK(stage_guidance(e, r.guide.scale));
     if (dev_dead) {
         HIPCHK(hipMemsetAsync(e->d_blk_left, 0, 96 * sizeof(int32_t), s));
     } else if (m.early_exit) {
@@ -439,6 +460,7 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
 static int generate(mellow_engine_t* e, const GenRequest& req, int door = 0) {
     GenRequest r = req;
     if (e) { r.rules = e->rules_armed; e->rules_armed = LogitRules(); }      // armed rules serve this call only, whatever its outcome
+    if (e) { r.guide = e->guide_armed; e->guide_armed = Guidance(); }        // ... and so does armed guidance
     CHK(check_request(e, r, door));
     if (r.rows() <= kPassRows) return generate_pass(e, r);      // (always so for n > 1 and, through mellow_generate_q, for Q > 1: check_request)
     const int B = r.examples, max_len = r.max_len;
@@ -537,7 +559,7 @@ int mellow_generate_beam(mellow_engine_t* e, const float* audio1, const float* a
                  out_token, out_lp, nullptr, out_steps, first_token_ms};
     r.beam = k; r.out_parent = out_parent; r.out_cum = out_cum;
     if (k < 1) {      // (before the n >= 1 rule words it as n)
-        if (e) e->rules_armed = LogitRules();
+        if (e) { e->rules_armed = LogitRules(); e->guide_armed = Guidance(); }
         return fail("mellow_generate_beam takes 1 to %d beams per example (got k = %d)", BEAM_MAX_K, k);
     }
     return generate(e, r, DOOR_BEAM | DOOR_SCORED);
@@ -551,6 +573,31 @@ int mellow_generate_rules(mellow_engine_t* e, const mellow_logit_rules_t* rules)
     LogitRules a;
     CHK(load_rules(e, rules, &a));
     e->rules_armed = a;
+    return 0;
+}
+
+int mellow_generate_guidance(mellow_engine_t* e, float scale) {
+    if (!std::isfinite(scale)) return fail("guidance scale must be finite (got %g); 1 is off", (double)scale);
+    if (!e || !e->finalized) return fail("engine not finalized");
+    e->guide_armed = Guidance();
+    if (scale == 1.f) return 0;          // the conditional distribution itself: nothing to arm
+    e->guide_armed.on = true; e->guide_armed.scale = scale;
+    return 0;
+}
+
+int mellow_guidance_apply(mellow_engine_t* e, float scale, float* logits, int P, float* cand_val, int32_t* cand_idx, float* cand_sum) {
+    if (!std::isfinite(scale)) return fail("guidance scale must be finite (got %g)", (double)scale);
+    if (!e || !e->finalized) return fail("engine not finalized");
+    if (!logits || !cand_val || !cand_idx || P <= 0) return fail("bad argument");
+    if (e->cfg.vocab_size != SAMPLE_MAX_V) return fail("the guidance kernel is built for a vocabulary of %d (engine: %d)", SAMPLE_MAX_V, e->cfg.vocab_size);
+    HIPCHK(hipSetDevice(e->device));
+    CHK(stage_guidance(e, scale));
+    GuideArgs g;
+    g.logits = logits; g.ld = e->cfg.vocab_size; g.prm = e->d_gparams;
+    g.cand_val = cand_val; g.cand_idx = cand_idx; g.cand_sum = cand_sum;
+    launch_dec_guidance(g, P, e->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->stream));
     return 0;
 }
 

@@ -138,6 +138,13 @@ struct StepMode {
     bool migrate = false;        // ... with row migration (DecArgs::row_of_slot)
     int beam = 0;                // k >= 1: beam search -- the select (beam.hip) in place of the arg-max, and for k > 1 the two K/V reorder launches after it
     bool rules = false;          // repetition controls: dec_logit_rules_kernel between the head and the picker (forces `logits` on)
+    bool guide = false;          // contrastive guidance: dec_guidance_kernel after the head, before the rules launch (forces `logits` on; rows 2p, 2p + 1 are a pair)
+};
+// The guidance of one generation call (include/mellow_hip.h, mellow_generate_guidance): armed on the context, taken into the call's
+// GenRequest at entry.
+struct Guidance {
+    bool on = false;
+    float scale = 1.f;
 };
 // The repetition controls of one generation call (include/mellow_hip.h, mellow_generate_rules): armed on the context, taken into the
 // call's GenRequest at entry.  The bias itself lives in the context's rules_bias buffer.
@@ -220,7 +227,7 @@ struct mellow_engine {
     // d_params, the sampling parameters in d_sparams).  generate_pass (engine_generate.cpp) captures, ensure_lm invalidates.
     struct LOCAL StepGraphs {
         struct Key {
-            std::array<uintptr_t, 17> v{};       // all zero: no capture (a pass has at least one row)
+            std::array<uintptr_t, 18> v{};       // all zero: no capture (a pass has at least one row)
             static Key of(const mellow_engine* e, int B);      // from the engine as configured for the pass (below the engine)
             bool operator==(const Key& k) const { return v == k.v; }
         };
@@ -282,6 +289,9 @@ struct mellow_engine {
     uint32_t h_sparams[SMP_WORDS] = {0};       // ... its staging
     uint32_t* d_rparams = nullptr;             // rule parameter block (kernels.h RUL_*): graph replays serve any penalty / n-gram size / minimum / bias on-off
     uint32_t h_rparams[RUL_WORDS] = {0};       // ... its staging
+    uint32_t* d_gparams = nullptr;             // guidance parameter block (kernels.h GDN_*): graph replays serve any scale
+    uint32_t h_gparams[GDN_WORDS] = {0};       // ... its staging
+    Guidance guide_armed;                      // mellow_generate_guidance: what the NEXT mellow_generate* call on this context takes (and clears)
     LogitRules rules_armed;                    // mellow_generate_rules: what the NEXT mellow_generate* call on this context takes (and clears)
     // repetition controls, created on first use: the call's dense logit bias [vocab] (a copy: no caller pointer is ever captured),
     // and the ping-pong history of a beam call [2][rows][max_len] int32 (logit_rules.hip)
@@ -350,7 +360,8 @@ inline mellow_engine::StepGraphs::Key mellow_engine::StepGraphs::Key::of(const m
                 (uintptr_t)(e->mode.beam > 1 ? e->vstage.p : nullptr),
                 (uintptr_t)e->mode.rules,          // repetition controls: dec_logit_rules_kernel in the step; the head with its logits store
                 (uintptr_t)(e->mode.rules ? e->rules_bias.p : nullptr),                     // ... the bias buffer: RulesArgs
-                (uintptr_t)(e->mode.rules && e->mode.beam ? e->rules_hist.p : nullptr)}};   // ... the beam rows' history buffer: RulesArgs
+                (uintptr_t)(e->mode.rules && e->mode.beam ? e->rules_hist.p : nullptr),     // ... the beam rows' history buffer: RulesArgs
+                (uintptr_t)e->mode.guide}};        // contrastive guidance: dec_guidance_kernel in the step; the head with its logits store; the sampler's stream by pair
 }
 static_assert(!std::is_copy_constructible<mellow_engine::Buf>::value, "a Buf owns its device memory: it moves, it is never copied");
 static_assert(std::is_copy_assignable<mellow_engine::Weights>::value && std::is_copy_assignable<mellow_engine::Options>::value, "a fork copies these by assignment: no owning member (Buf, StepGraphs) belongs in them");
@@ -414,6 +425,8 @@ int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec)
 BeamArgs beam_args(mellow_engine* e, int N, int k);
 // the rules launch of a generation step on B rows, from the engine as apply_step_mode configured it (engine_lm.cpp)
 RulesArgs rules_args(mellow_engine* e, int B);
+// the guidance launch of a generation step, from the engine as apply_step_mode configured it (engine_lm.cpp)
+GuideArgs guide_args(mellow_engine* e);
 // n > 1 (mellow_generate_n; fp32 pages only): the layers run on the B examples and write K/V to kprefix / vprefix; the fan-out and
 // everything from the last prefix row on (last layer, head, first token) run on B * n rows
 int run_prefill(mellow_engine* e, int B, int T, const RecordArgs* rec, bool all_positions = false, int n = 1);

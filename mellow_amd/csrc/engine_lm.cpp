@@ -100,7 +100,7 @@ int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end, int prefill
 void apply_step_mode(mellow_engine* e, const StepMode& m) {
     e->mode = m;
     DecArgs& a = e->da;
-    e->mode.logits = m.logits || m.rules;              // the rules edit the stored rows
+    e->mode.logits = m.logits || m.rules || m.guide;   // the rules and the guidance edit the stored rows
     a.logits = e->mode.logits ? e->dlogits.p : nullptr;      // (off: generation's arg-max needs the candidates only, no 6 MB store per step)
     a.cand_sum = m.logprob ? e->cand_sum.p : nullptr;
     a.blk_live = m.early_exit ? e->d_blk_live : nullptr;
@@ -162,6 +162,15 @@ RulesArgs rules_args(mellow_engine* e, int B) {
     return g;
 }
 
+GuideArgs guide_args(mellow_engine* e) {
+    const LoopArgs lp = loop_args(e);
+    GuideArgs g;
+    g.logits = e->da.logits; g.ld = e->cfg.vocab_size; g.prm = e->d_gparams;
+    g.cand_val = e->da.cand_val; g.cand_idx = e->da.cand_idx; g.cand_sum = e->da.cand_sum;
+    g.blk_snap = lp.blk_snap;
+    return g;
+}
+
 // final norm (+ pending down slabs) + lm_head with fused per-tile arg-max candidates -> dlogits, d_tokens
 int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec) {
     const int NT = e->cfg.vocab_size / 32, Bp = e->da.rows;
@@ -171,6 +180,10 @@ int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec)
     { ProfScope ps(e, PF_SKINNY, 2.0 * Bp * 576.0 * e->cfg.vocab_size, 576.0 * e->cfg.vocab_size * 4);
       const DecW h = e->w.head_w();
       launch_dec_lm_head(dh(1), h.p, e->w.lm_head.KP / 8, e->cfg.vocab_size, e->stream, h.scale); }
+    if (e->mode.guide && rec) {      // contrastive guidance: both rows of a pair get the combined row before the rules and any picker read them
+        ProfScope ps(e, PF_MISC, 0, 6.0 * B * e->cfg.vocab_size * 4);
+        launch_dec_guidance(guide_args(e), B / 2, e->stream);
+    }
     if (e->mode.rules && rec) {      // repetition controls: the row's logits and tile partials are edited before any picker reads them
         ProfScope ps(e, PF_MISC, 0, 2.0 * B * e->cfg.vocab_size * 4);
         launch_dec_logit_rules(rules_args(e, B), B, e->stream);
@@ -182,6 +195,7 @@ int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec)
       } else if (e->mode.sample) {        // mellow_generate_sampled: the head stored the logits (da.logits); draw instead of the arg-max
           SampleArgs sa;
           sa.logits = e->da.logits; sa.ld = e->cfg.vocab_size; sa.prm = e->d_sparams;
+          sa.row_shift = e->mode.guide ? 1 : 0;        // a guided pair draws from the stream of its pair index
           launch_dec_sample(sa, dh(2), B, e->d_tokens, e->w.embed, (rec && rec->embed_next) ? 1 : 0, rec ? loop_args(e) : LoopArgs(),
                             e->stream);
       } else {

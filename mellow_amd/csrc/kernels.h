@@ -286,6 +286,7 @@ struct SampleArgs {
     int64_t ld = 0;
     const uint32_t* prm = nullptr;       // device block of SMP_WORDS words
     const int32_t* row_ids = nullptr;    // taps: global row index of each row (null: the row's position)
+    int row_shift = 0;                   // decode step: the stream of row r is that of global row `row offset + (r >> row_shift)`; 1 in a guided call (both rows of pair p draw from the stream of global row p)
 };
 constexpr int SAMPLE_MAX_V = 49152;      // the vocabulary the sampler is built for: 48 values per thread of one 1024-thread workgroup
 // the decode step's sampler: draws from sa.logits (= DecArgs::logits) and then does exactly the bookkeeping of dec_argmax_kernel
@@ -351,6 +352,21 @@ struct RulesArgs {
     int N = 0, k = 1;
 };
 void launch_dec_logit_rules(const RulesArgs& g, int B, hipStream_t s);
+// Contrastive guidance (guidance.hip; include/mellow_hip.h mellow_generate_guidance states the exact definition): rows 2p and 2p + 1
+// are the conditional and the negative row of pair p.  One launch combines the log-softmax of the two rows, g = b + s * (a - b),
+// writes g to BOTH rows and forms both rows' tile partials (cand_val / cand_idx / cand_sum) from it, so that the rules launch, the
+// arg-max, the sampler and the LSE merges that follow run unchanged on two identical rows.  The scale lives in a device block the
+// host fills per call, so a captured step serves any scale: prm = {bits of the scale}.
+enum { GDN_SCALE = 0, GDN_WORDS = 8 };
+struct GuideArgs {
+    float* logits = nullptr;             // [2 * pairs][ld] fp32, edited in place (ld = SAMPLE_MAX_V: the row tiling of the sampler)
+    int64_t ld = 0;
+    const uint32_t* prm = nullptr;       // device block of GDN_WORDS words
+    float* cand_val = nullptr; int32_t* cand_idx = nullptr;   // [2 * pairs][ld / 32], rewritten
+    float* cand_sum = nullptr;           // [2 * pairs][ld / 32] or null
+    const int32_t* blk_snap = nullptr;   // as in LoopArgs (a guided call runs without row migration: slot == row)
+};
+void launch_dec_guidance(const GuideArgs& g, int P /* pairs */, hipStream_t s);
 // after the arg-max of a step (early-exit mode only): if the rows that have not produced the stop id yet fit into fewer 32-row
 // blocks than are live, move them (their next-step residual rows) to the lowest slots, rewrite row_of_slot / blk_left / blk_live
 void launch_dec_compact(const DecArgs& a, int B, const LoopArgs& loop, hipStream_t s);

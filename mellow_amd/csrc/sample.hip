@@ -265,7 +265,7 @@ __global__ __launch_bounds__(SMP_THREADS) void dec_sample_kernel(const SampleArg
     int idx = 0;
     if (!dead) {
         const int step = lp.out_tokens ? *a.d_pos - lp.T0 + 1 : (int)sa.prm[SMP_STEP];
-        idx = sample_row(sa.logits + (int64_t)b * sa.ld, sa.prm, sa.prm[SMP_ROW_OFF] + (uint32_t)row, (uint32_t)step);
+        idx = sample_row(sa.logits + (int64_t)b * sa.ld, sa.prm, sa.prm[SMP_ROW_OFF] + ((uint32_t)row >> sa.row_shift), (uint32_t)step);
     }
     float lse = 0.f;
     if constexpr (LSE) {

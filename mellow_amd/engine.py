@@ -49,7 +49,8 @@ _lib = None
 _ADDED_UNDER_MINOR_4 = ("mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse", "mellow_generate_n",
                         "mellow_generate_q", "mellow_generate_beam", "mellow_beam_select")
 # symbols of minor 5 (the attention taps on host data): looked up the same way, so that a minor-4 library still loads
-_ADDED_UNDER_MINOR_5 = ("mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_generate_rules", "mellow_logit_rules_apply")
+_ADDED_UNDER_MINOR_5 = ("mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_generate_rules", "mellow_logit_rules_apply",
+                        "mellow_generate_guidance", "mellow_guidance_apply")
 
 
 def load_library(path: Optional[str] = None):
@@ -90,6 +91,8 @@ def load_library(path: Optional[str] = None):
         "mellow_sample_logits": (ci, [vp, vp, ci, vp, ci, cf, cf, C.c_uint64, vp]),
         "mellow_generate_rules": (ci, [vp, P(LogitRules)]),
         "mellow_logit_rules_apply": (ci, [vp, P(LogitRules), vp, ci, vp, ci, vp, ci, vp, vp, vp]),
+        "mellow_generate_guidance": (ci, [vp, cf]),
+        "mellow_guidance_apply": (ci, [vp, cf, vp, ci, vp, vp, vp]),
         "mellow_logmel": (ci, [vp, vp, ci, i64, ci, vp]),
         "mellow_encode": (ci, [vp, vp, ci, i64, vp]),
         "mellow_prefix": (ci, [vp, vp, vp, i64, vp, ci, vp]),
@@ -147,7 +150,7 @@ EXPORTED_SYMBOLS = (
     "mellow_engine_num_required", "mellow_engine_required_key", "mellow_generate", "mellow_generate_sampled", "mellow_sample_logits", "mellow_logmel",
     "mellow_encode", "mellow_prefix", "mellow_lm_prefill", "mellow_lm_decode_step", "mellow_argmax", "mellow_embed_tokens", "mellow_lm_forward_logits",
     "mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse", "mellow_generate_n", "mellow_generate_q",
-    "mellow_generate_beam", "mellow_beam_select", "mellow_generate_rules", "mellow_logit_rules_apply", "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
+    "mellow_generate_beam", "mellow_beam_select", "mellow_generate_rules", "mellow_logit_rules_apply", "mellow_generate_guidance", "mellow_guidance_apply", "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
     "mellow_prof_num_families", "mellow_prof_family_name", "mellow_prof_get", "mellow_last_phase_ms", "mellow_last_steps_enqueued", "mellow_last_row_repacks", "mellow_stft_is_fft", "mellow_prefill_parts", "mellow_abi_minor",
     "mellow_resample", "mellow_engine_set_precision", "mellow_engine_set_option", "mellow_engine_describe", "mellow_debug_gemm_fp8", "mellow_debug_gemm_f32", "mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_debug_dec_head", "mellow_set_graph", "mellow_host_window_map", "mellow_host_pack_weight", "mellow_host_rope_tables",
 )
@@ -209,6 +212,15 @@ def check_logit_rules(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_to
         if np.isnan(bias).any() or np.isposinf(bias).any():
             raise ValueError("logit_bias values must be finite or -inf (NaN and +inf are refused)")
     return t, n, m, bias
+
+
+def check_guidance_scale(guidance_scale=1.0) -> float:
+    """The one value rule of contrastive guidance (the C entry repeats it): a finite scale.  1 is off."""
+    import math
+    s = float(guidance_scale)
+    if not math.isfinite(s):
+        raise ValueError(f"guidance_scale must be finite (got {guidance_scale}); 1 is off")
+    return s
 
 
 BEAM_MAX_K = 8                 # beams per example mellow_generate_beam takes
@@ -443,7 +455,8 @@ class Engine:
                  stop_id: int = 0, ignore_stop: bool = False, do_sample: bool = False, seed: Optional[int] = None,
                  row_offset: int = 0, return_logprobs: bool = False, num_return_sequences: int = 1,
                  num_beams: Optional[int] = None, length_penalty: float = 1.0, repetition_penalty: float = 1.0,
-                 no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, logit_bias=None, _arm_neutral_rules: bool = False):
+                 no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, logit_bias=None, _arm_neutral_rules: bool = False,
+                 guidance_scale: float = 1.0, negative=None, keep_negative_rows: bool = False):
         """-> (tokens int32 [B, steps] on host, lengths [B], steps, first_token_ms)
         num_return_sequences = n > 1 (needs do_sample=True): n sampled answers per example from one encode and one prefill per
         example (mellow_generate_n).  Every array has B * n rows, row b * n + j = answer j of example b, and holds what this call
@@ -471,10 +484,30 @@ class Engine:
         controls of include/mellow_hip.h (mellow_generate_rules), applied to every row's logits on the device before the token is
         chosen, whatever chooses it (arg-max, sampler, beam select); the history is the row's generated tokens.  With any of them
         set, a returned log-prob is that of the processed distribution, not the number score() returns.  All at their neutral
-        values: nothing is armed and the call is the one without these keywords."""
+        values: nothing is armed and the call is the one without these keywords.
+        guidance_scale = s != 1 with negative = (audio1, audio2, input_ids) of the same shapes: contrastive guidance (include/mellow_hip.h,
+        mellow_generate_guidance).  Every example runs next to its negative (rows 2i, 2i + 1 of one batch of 2 * B rows); per step the
+        two rows' log-softmax a, b are combined on the device to g = b + s * (a - b), which both rows then choose their token from
+        (after the repetition controls, if set).  The B conditional rows are returned (keep_negative_rows=True: all 2 * B rows, rows
+        2i and 2i + 1 equal).  row_offset counts PAIRS: answer i draws from the stream example i of the un-guided call draws from.  A
+        returned log-prob is that of the processed distribution.  ValueError together with num_beams, num_return_sequences > 1 or
+        3-D input_ids, for a scale that is not finite, or for s != 1 without `negative`.  s = 1 (default): nothing is armed, `negative`
+        is ignored and the call is the one without these keywords."""
         import time
         t_in = time.perf_counter()
         nseq = int(num_return_sequences)
+        gscale = check_guidance_scale(guidance_scale)
+        self._guide = None
+        if gscale != 1.0:
+            if num_beams is not None:
+                raise ValueError("guidance_scale and num_beams do not combine: beam search over pairs is not built")
+            if nseq != 1:
+                raise ValueError("guidance_scale and num_return_sequences > 1 do not combine: repeat the example (and its negative) in the batch")
+            if (input_ids.ndim if hasattr(input_ids, "ndim") else np.ndim(input_ids)) == 3:
+                raise ValueError("guidance_scale and several questions per example do not combine: pass an example per question")
+            if negative is None:
+                raise ValueError(f"guidance_scale = {gscale} needs `negative` = (audio1, audio2, input_ids): the input to contrast with")
+            self._need("mellow_generate_guidance")
         self._rules = self._make_rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, logit_bias, _arm_neutral_rules, int(max_len))
         if num_beams is not None:
             if do_sample:
@@ -498,6 +531,16 @@ class Engine:
             return self._generate_nseq(audio1, audio2, input_ids, int(max_len), nseq, float(top_p), float(temperature), int(stop_id),
                                        bool(ignore_stop), _seed64(seed), int(row_offset), bool(return_logprobs), t_in)
         a1, a2, ids = self._f32(audio1), self._f32(audio2), self._prompt_ids(input_ids)
+        if gscale != 1.0:
+            # rows 2i / 2i + 1 = example i / its negative
+            n1, n2, nids = self._f32(negative[0]), self._f32(negative[1]), self._prompt_ids(negative[2])
+            if n1.shape != a1.shape or n2.shape != a2.shape or nids.shape != ids.shape:
+                raise ValueError(f"`negative` must have the shapes of the inputs: {tuple(n1.shape)}, {tuple(n2.shape)}, {tuple(nids.shape)} "
+                                 f"against {tuple(a1.shape)}, {tuple(a2.shape)}, {tuple(ids.shape)}")
+            a1 = torch.stack((a1, n1), dim=1).reshape(2 * a1.shape[0], -1).contiguous()
+            a2 = torch.stack((a2, n2), dim=1).reshape(2 * a2.shape[0], -1).contiguous()
+            ids = torch.stack((ids, nids), dim=1).reshape(2 * ids.shape[0], -1).contiguous()
+            self._guide = gscale
         B, n = a1.shape
         assert a2.shape == a1.shape and ids.shape == (B, spec.TEXT_LEN), (a1.shape, a2.shape, ids.shape)
         out = torch.empty((B, max_len), dtype=torch.int32, device=self.tdev)
@@ -527,8 +570,9 @@ class Engine:
                                                lens, C.byref(steps), C.byref(ftm)))
         toks = out.cpu().numpy()[:, : steps.value]
         self.last_first_token_host_ms = t_up + float(ftm.value)
-        res = (toks, np.asarray(list(lens), dtype=np.int32), int(steps.value), float(ftm.value))
-        return res + (lp.cpu().numpy()[:, : steps.value],) if return_logprobs else res
+        rows = slice(None, None, 2) if self._guide is not None and not keep_negative_rows else slice(None)      # guided: the conditional rows
+        res = (toks[rows], np.asarray(list(lens), dtype=np.int32)[rows], int(steps.value), float(ftm.value))
+        return res + (lp.cpu().numpy()[rows, : steps.value],) if return_logprobs else res
 
     def _make_rules(self, repetition_penalty, no_repeat_ngram_size, min_new_tokens, logit_bias, arm_neutral, max_len):
         """the struct _arm() hands to mellow_generate_rules before every C call of this generate(), or None: nothing to arm"""
@@ -551,6 +595,9 @@ class Engine:
         r = getattr(self, "_rules", None)
         if r is not None:
             self._chk(self.lib.mellow_generate_rules(self.h, C.byref(r)))
+        g = getattr(self, "_guide", None)
+        if g is not None:
+            self._chk(self.lib.mellow_generate_guidance(self.h, float(g)))
 
     def logit_rules_apply(self, logits, history, hist_len, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
                           min_new_tokens: int = 0, logit_bias=None, stop_id: int = 0, with_sum: bool = True):
@@ -574,6 +621,27 @@ class Engine:
         self._sync_inputs()
         self._chk(self.lib.mellow_logit_rules_apply(self.h, C.byref(r), _ptr(lg), B, _ptr(h) if ld else None, ld, _ptr(ln), int(stop_id),
                                                     _ptr(cv), _ptr(cx), None if cs is None else _ptr(cs)))
+        out = {"logits": lg.cpu().numpy(), "cand_val": cv.cpu().numpy(), "cand_idx": cx.cpu().numpy()}
+        if cs is not None:
+            out["cand_sum"] = cs.cpu().numpy()
+        return out
+
+    def guidance_apply(self, logits, scale: float, with_sum: bool = True):
+        """Contrastive guidance on caller data (numeric tap, mellow_guidance_apply): logits [2 * P][vocab], rows 2i / 2i + 1 the
+        conditional and the negative row of pair i -> dict of numpy arrays: "logits" [2 * P][vocab], both rows of a pair holding g,
+        "cand_val" / "cand_idx" [2 * P][vocab / 32] the per-tile maximum of g and its first index, "cand_sum" [2 * P][vocab / 32] the
+        per-tile sum of exp(g - cand_val) (with_sum=False: absent)."""
+        s = check_guidance_scale(scale)
+        self._need("mellow_guidance_apply")
+        lg = self._f32(logits).clone()
+        R, V = lg.shape
+        if V != self.lm.vocab_size or R < 2 or R % 2:
+            raise ValueError(f"logits {tuple(lg.shape)} do not describe pairs of rows of the vocabulary")
+        cv = torch.empty((R, V // 32), dtype=torch.float32, device=self.tdev)
+        cx = torch.empty((R, V // 32), dtype=torch.int32, device=self.tdev)
+        cs = torch.empty((R, V // 32), dtype=torch.float32, device=self.tdev) if with_sum else None
+        self._sync_inputs()
+        self._chk(self.lib.mellow_guidance_apply(self.h, s, _ptr(lg), R // 2, _ptr(cv), _ptr(cx), None if cs is None else _ptr(cs)))
         out = {"logits": lg.cpu().numpy(), "cand_val": cv.cpu().numpy(), "cand_idx": cx.cpu().numpy()}
         if cs is not None:
             out["cand_sum"] = cs.cpu().numpy()

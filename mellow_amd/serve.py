@@ -56,7 +56,9 @@ class EnginePool:
 
     def _run(self, slot: int, batch, kw):
         with self._locks[slot]:          # one call at a time per context (the C ABI serialises per handle)
-            a1, a2, ids = batch
+            a1, a2, ids = batch[:3]
+            if len(batch) > 3:           # (audio1, audio2, input_ids, negative): the batch's own negative inputs of a guided call
+                kw = dict(kw, negative=batch[3])
             return self.engines[slot].generate(a1, a2, ids, **kw)     # ctypes releases the GIL inside the call
 
     def generate_many(self, batches: Sequence, **kw):
@@ -67,7 +69,9 @@ class EnginePool:
         Every keyword of Engine.generate passes through (return_logprobs=True: five values per batch; num_beams=k with
         length_penalty / num_return_sequences: a beam search per batch, deterministic, so no row offset is involved;
         repetition_penalty / no_repeat_ngram_size / min_new_tokens / logit_bias: the repetition controls, armed by each context for
-        its own calls, the same for every batch)."""
+        its own calls, the same for every batch; guidance_scale with negative=(audio1, audio2, input_ids): contrastive guidance, the
+        scale armed by each context for its own calls -- a `negative` keyword goes to every batch as it is, a batch given as
+        (audio1, audio2, input_ids, negative) brings its own; a guided batch counts its examples, not its rows, towards row_offset)."""
         kws = [kw] * len(batches)
         if kw.get("do_sample"):
             off, kws = int(kw.get("row_offset", 0)), []

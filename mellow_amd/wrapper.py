@@ -271,6 +271,7 @@ class MellowWrapper:
         if n_local:
             samp = dict(do_sample=True, seed=seed, row_offset=row_offset) if do_sample else {}
             samp.update(getattr(self, "_rules_kw", None) or {})
+            samp.update(getattr(self, "_guide_kw", None) or {})
             if nseq > 1:
                 samp["num_return_sequences"] = nseq
             if return_logprobs:       # (refused under data-parallel sharding by generate(): the gather below carries tokens only)
@@ -330,7 +331,7 @@ class MellowWrapper:
                  do_sample: bool = False, seed: Optional[int] = None, return_logprobs: bool = False,
                  num_return_sequences: int = 1, num_beams: int = 1, length_penalty: float = 1.0, repetition_penalty: float = 1.0,
                  no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, suppress_tokens: Optional[Sequence[int]] = None,
-                 logit_bias: Optional[dict] = None):
+                 logit_bias: Optional[dict] = None, guidance_scale: float = 1.0, negative_examples=None):
         r"""Produces text response for the given audio files and text prompts
         examples: (list<list>) each example is [audio path 1, audio path 2, text prompt]; the text prompt may be a list or tuple of
                      prompts, several questions about the one pair of clips (module docstring).  If any example has a list, the
@@ -367,6 +368,18 @@ class MellowWrapper:
                      log-prob is that of the processed distribution the token was chosen from -- no longer what `score` returns.
                      ValueError for t <= 0 or not finite, a negative n or m, an id outside the vocabulary, a NaN or +inf bias, or
                      min_new_tokens > max_len.  All at their defaults: the call without the keywords.
+        guidance_scale: (float) s != 1: contrastive (classifier-free) guidance against `negative_examples`.  Every example is run next
+                     to its negative; at every step the two log-softmax rows a (example) and b (negative) are combined on the device
+                     to b + s * (a - b) and the token is chosen from that, so s > 1 penalises what the model would have said about
+                     the negative as well -- its language prior -- and keeps what the clips contributed.  The result has exactly
+                     the shape of the un-guided call (strings, or dicts with return_logprobs=True; a log-prob is then that of the
+                     combined distribution).  Combines with do_sample / seed, return_logprobs and the five repetition keywords
+                     (which run after the guidance).  ValueError together with num_beams > 1, num_return_sequences > 1 or a list of
+                     prompts, for a scale that is not finite, for s != 1 without negatives, or for a negatives list of another
+                     length; NotImplementedError under data parallelism with more than one rank.  1 (default): the call without
+                     the keyword -- nothing is armed and the negatives are ignored.
+        negative_examples: a list parallel to `examples` of [audio path 1, audio path 2, prompt], or the string "silence": every
+                     example's own prompt over two all-zero clips of the configured length (no file is read).
 
         With `data_parallel=True` (or MELLOW_DATA_PARALLEL=1) under an initialised torch.distributed group (one process per
         GPU, every rank calling with the same examples) the examples are sharded contiguously over the ranks, each rank ingests
@@ -384,6 +397,8 @@ class MellowWrapper:
         k = int(num_beams)
         if k < 1:
             raise ValueError(f"num_beams must be >= 1 (got {k})")
+        gscale, negatives = self._guidance_request(guidance_scale, negative_examples, examples, text_prompts, k, nseq)
+        self._guide_kw = {}
         if k > 1:
             return self._generate_beams(examples, audio_paths1, audio_paths2, text_prompts, max_len, stop_token, audio_resample,
                                         do_sample, return_logprobs, k, nseq, float(length_penalty))
@@ -427,9 +442,50 @@ class MellowWrapper:
         else:
             audio1 = audio2 = torch.zeros((0, 1))
             ids = torch.zeros((0, spec.TEXT_LEN), dtype=torch.int64)
-        return self._generate_batch(audio1, audio2, ids, entry_length=max_len, top_p=top_p,
-                                    temperature=temperature, stop_token=stop_token, n_total=n, do_sample=do_sample,
-                                    seed=seed, row_offset=lo * nseq, return_logprobs=return_logprobs, nseq=nseq)
+        if negatives is not None:       # (one rank: lo, hi = 0, n)
+            if negatives == "silence":      # the examples' own prompts over all-zero clips: nothing is read
+                neg = (torch.zeros_like(audio1), torch.zeros_like(audio2), ids)
+            else:
+                neg = (self.preprocess_audio([e[0] for e in negatives], resample=audio_resample),
+                       self.preprocess_audio([e[1] for e in negatives], resample=audio_resample),
+                       self.preprocess_text([e[2] for e in negatives])["input_ids"])
+            self._guide_kw = dict(guidance_scale=gscale, negative=neg)
+        try:
+            return self._generate_batch(audio1, audio2, ids, entry_length=max_len, top_p=top_p,
+                                        temperature=temperature, stop_token=stop_token, n_total=n, do_sample=do_sample,
+                                        seed=seed, row_offset=lo * nseq, return_logprobs=return_logprobs, nseq=nseq)
+        finally:
+            self._guide_kw = {}         # (the negative clips are not kept alive past the call)
+
+    def _guidance_request(self, guidance_scale, negative_examples, examples, text_prompts, k, nseq):
+        """The keyword rules of guidance_scale / negative_examples -> (scale, negatives): negatives is None for an un-guided call
+        (scale 1: whatever was given is ignored), else "silence" or the checked list."""
+        from .engine import check_guidance_scale
+        s = check_guidance_scale(guidance_scale)
+        if s == 1.0:
+            return s, None
+        if k > 1:
+            raise ValueError("guidance_scale and num_beams > 1 do not combine: beam search over pairs is not built")
+        if nseq > 1:
+            raise ValueError("guidance_scale and num_return_sequences > 1 do not combine: repeat the example (and its negative) in the list")
+        if any(isinstance(tp, (list, tuple)) for tp in text_prompts):
+            raise ValueError("guidance_scale and question lists do not combine: pass an example per question")
+        if negative_examples is None:
+            raise ValueError(f"guidance_scale = {s} needs negative_examples: a list parallel to the examples, or \"silence\"")
+        if isinstance(negative_examples, str):
+            if negative_examples != "silence":
+                raise ValueError(f"negative_examples = {negative_examples!r}: the only string it takes is \"silence\"")
+            negatives = "silence"
+        else:
+            negatives = [list(e) for e in negative_examples]
+            if len(negatives) != len(examples):
+                raise ValueError(f"negative_examples holds {len(negatives)} entries for {len(examples)} examples: one negative per example")
+            if any(len(e) != 3 or isinstance(e[2], (list, tuple)) for e in negatives):
+                raise ValueError("every negative example is [audio path 1, audio path 2, prompt]")
+        if self._dp()[1] > 1:
+            raise NotImplementedError("guided generation is not sharded over data-parallel ranks: call generate on one rank (or with "
+                                      "data_parallel off)")
+        return s, negatives
 
     def _rules_keywords(self, repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, logit_bias, max_len):
         """The repetition controls of a generate() call as keywords of Engine.generate: only those that differ from their neutral

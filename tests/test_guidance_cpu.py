@@ -1,0 +1,288 @@
+"""CPU: contrastive guidance (mellow_generate_guidance, mellow_guidance_apply, Engine.generate(guidance_scale=, negative=),
+MellowWrapper.generate(guidance_scale=, negative_examples=)) as far as it goes without a GPU: the exported symbols, the host-side
+refusals, the fp64 reference of tests/guidance_ref.py against its own limits, the wrapper's keyword rules on a stub engine, and the
+pool's pass-through."""
+import ctypes
+import math
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from mellow_amd import engine as E
+from mellow_amd import spec
+from mellow_amd.wrapper import MellowWrapper
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import guidance_ref as GR  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ("mellow_generate_guidance", "mellow_guidance_apply")
+
+
+def _lib():
+    if not os.path.exists(E.LIB_PATH):
+        from mellow_amd.csrc import build
+        build.build()
+    return E.load_library()
+
+
+def test_header_declares_and_library_exports_the_symbols():
+    hdr = open(os.path.join(ROOT, "include", "mellow_hip.h")).read()
+    lib = _lib()
+    raw = ctypes.CDLL(E.LIB_PATH)
+    for name, nargs in zip(NAMES, (2, 7)):
+        assert re.search(r"\bint\s+%s\s*\(" % name, hdr), name
+        assert name in E.EXPORTED_SYMBOLS and name in E._ADDED_UNDER_MINOR_5
+        assert hasattr(raw, name)
+        fn = getattr(lib, name)
+        assert fn.restype is ctypes.c_int and len(fn.argtypes) == nargs
+    assert lib.mellow_abi_minor() == 5 and re.search(r"#define MELLOW_ABI_MINOR 5\b", hdr)   # detected by symbol lookup, not by the number
+    assert "g[v]  = b[v] + s * (a[v] - b[v])" in hdr                                         # the definition
+    assert "+-inf" in hdr and "row migration" in hdr                                         # what it does not define; the limit
+
+
+def test_refusals_in_host_code():
+    """no GPU here: every one of these returns before a device is touched"""
+    lib = _lib()
+    for bad in (math.nan, math.inf, -math.inf):
+        assert lib.mellow_generate_guidance(None, bad) != 0
+        assert "finite" in lib.mellow_last_error().decode(), bad
+        assert lib.mellow_guidance_apply(None, bad, None, 1, None, None, None) != 0
+        assert "finite" in lib.mellow_last_error().decode(), bad
+    for ok in (3.0, 0.0, 1.0, -0.5):
+        assert lib.mellow_generate_guidance(None, ok) != 0
+        assert "engine not finalized" in lib.mellow_last_error().decode()     # ... as mellow_generate_rules reports it
+        assert lib.mellow_guidance_apply(None, ok, None, 1, None, None, None) != 0
+        assert "engine not finalized" in lib.mellow_last_error().decode()
+
+
+class OldLib:
+    """a library built before mellow_generate_guidance"""
+
+    def mellow_last_error(self):
+        return b""
+
+
+def _bare_engine():
+    e = object.__new__(E.Engine)
+    e.lib, e.h = OldLib(), None
+    e.tdev, e.lm = torch.device("cpu"), E.LMConfig.load()
+    e._sync_inputs = lambda: None
+    return e
+
+
+def test_engine_argument_errors_need_no_gpu():
+    e = _bare_engine()
+    a = np.zeros((2, 8), dtype=np.float32)
+    ids = np.zeros((2, spec.TEXT_LEN), dtype=np.int64)
+    neg = (a, a, ids)
+    V = e.lm.vocab_size
+    for kw in (dict(), dict(do_sample=True, seed=1), dict(return_logprobs=True), dict(keep_negative_rows=True)):
+        with pytest.raises(E.EngineError, match="predates mellow_generate_guidance"):
+            e.generate(a, a, ids, max_len=4, guidance_scale=2.0, negative=neg, **kw)
+    with pytest.raises(E.EngineError, match="predates mellow_guidance_apply"):
+        e.guidance_apply(np.zeros((2, V), dtype=np.float32), 2.0)
+    for kw, word in ((dict(guidance_scale=math.nan, negative=neg), "finite"), (dict(guidance_scale=math.inf, negative=neg), "finite"),
+                     (dict(guidance_scale=-math.inf), "finite"), (dict(guidance_scale=2.0), "negative"),
+                     (dict(guidance_scale=2.0, negative=neg, num_beams=2), "num_beams"),
+                     (dict(guidance_scale=2.0, negative=neg, num_return_sequences=2, do_sample=True, seed=1), "num_return_sequences")):
+        with pytest.raises(ValueError, match=word):
+            e.generate(a, a, ids, max_len=4, **kw)
+    with pytest.raises(ValueError, match="questions"):
+        e.generate(a, a, np.zeros((2, 2, spec.TEXT_LEN), dtype=np.int64), max_len=4, guidance_scale=2.0, negative=neg)
+    with pytest.raises(ValueError, match="finite"):
+        e.guidance_apply(np.zeros((2, V), dtype=np.float32), math.nan)
+    assert E.check_guidance_scale(0) == 0.0 and E.check_guidance_scale(-1.5) == -1.5
+
+
+# ---- the reference against its own limits ---------------------------------------------------------------------------------------------
+def _rows(P, V=256, seed=0):
+    rng = np.random.default_rng(seed)
+    return (rng.standard_normal((2 * P, V)) * np.repeat(rng.uniform(0.3, 8.0, P), 2)[:, None]).astype(np.float32)
+
+
+def test_reference_scale_one_is_the_conditional_and_zero_the_negative():
+    rows = _rows(3)
+    assert np.allclose(GR.guide_rows(rows, 1.0), GR.log_softmax64(rows[0::2]), rtol=0, atol=1e-12)
+    assert np.array_equal(GR.guide_rows(rows, 0.0), GR.log_softmax64(rows[1::2]))
+    assert np.allclose(np.exp(GR.log_softmax64(rows)).sum(-1), 1.0)
+    g = GR.guide(rows[0], rows[1], 3.0)
+    assert g.shape == (256,) and np.allclose(g, 3.0 * GR.log_softmax64(rows[0]) - 2.0 * GR.log_softmax64(rows[1]))
+
+
+def test_reference_identical_rows_give_their_log_softmax_for_any_scale():
+    rows = np.repeat(_rows(2)[0::2], 2, axis=0)
+    for s in (-2.0, 0.0, 0.5, 1.5, 3.0, 10.0):
+        assert np.array_equal(GR.guide_rows(rows, s), GR.log_softmax64(rows[0::2])), s
+    # ... and a constant shift of either row changes nothing (the log-softmax removes it)
+    shifted = _rows(2).astype(np.float64)
+    base = GR.guide_rows(shifted, 2.5)
+    shifted[1::2] += 7.0
+    assert np.allclose(GR.guide_rows(shifted, 2.5), base, rtol=0, atol=1e-11)
+
+
+def test_reference_partials_and_bound():
+    rows = np.array([[0.0] * 31 + [2.0] + [1.0, 3.0, 3.0] + [0.0] * 29], dtype=np.float64)
+    val, idx = GR.tile_partials(rows)
+    assert val.tolist() == [[2.0, 3.0]] and idx.tolist() == [[31, 33]]                       # the first index among equals
+    assert GR.tile_sums64(rows)[0, 0] == pytest.approx(1.0 + 31 * math.exp(-2.0))
+    two = _rows(1)
+    b0, b3 = GR.bound(two, 0.0), GR.bound(two, 3.0)
+    assert b0.shape == (1,) and b3[0] == pytest.approx(5 * b0[0])                            # |s| + |s - 1|: 1 at s = 0, 5 at s = 3
+    assert b0[0] >= 4 * 2.0 ** -23
+
+
+# ---- wrapper ----------------------------------------------------------------------------------------------------------------------------
+class Tok:
+    STOP = 7
+
+    def encode(self, s):
+        return [self.STOP] if s == "<|endoftext|>" else [100 + len(w) for w in s.split()]
+
+    def decode(self, ids):
+        return " ".join("<|endoftext|>" if int(t) == self.STOP else f"t{int(t)}" for t in ids)
+
+
+class StubEngine:
+    tdev = torch.device("cpu")
+
+    def __init__(self):
+        self.calls = []
+
+    def max_new_tokens_limit(self):
+        return 1000
+
+    def generate(self, audio1, audio2, input_ids, max_len, **kw):
+        self.calls.append(dict(kw, max_len=max_len, examples=len(audio1), audio1=audio1, audio2=audio2, input_ids=input_ids))
+        rows = len(audio1) * int(kw.get("num_return_sequences", 1)) * (input_ids.shape[1] if input_ids.ndim == 3 else 1)
+        toks = (1000 + np.arange(rows)[:, None] * 10 + np.arange(max_len)[None, :]).astype(np.int32)
+        res = (toks, np.full(rows, max_len, dtype=np.int32), max_len, 1.5)
+        if kw.get("return_logprobs"):
+            lp = np.full(toks.shape, -0.5, dtype=np.float32)
+            res = res + (lp, np.zeros(rows)) if "num_beams" in kw else res + (lp,)
+        return res
+
+
+def _wrapper():
+    w = MellowWrapper.__new__(MellowWrapper)
+    w.tokenizer, w.model, w._data_parallel = Tok(), StubEngine(), False
+    w.read = []
+
+    def audio(files, resample):
+        w.read += list(files)
+        return torch.stack([torch.full((8,), float(len(f))) for f in files])
+
+    w.preprocess_audio = audio
+    w.preprocess_text = lambda prompts: {"input_ids": torch.stack([torch.full((spec.TEXT_LEN,), len(p), dtype=torch.int64) for p in prompts])}
+    return w
+
+
+EX = [[f"a{i}.wav", f"b{i}.wav", "q" * (i + 1)] for i in range(3)]
+NEGS = [[f"neg{i}.wav", f"negb{i}.wav", "n" * (i + 5)] for i in range(3)]
+GUIDE_KEYS = ("guidance_scale", "negative", "negative_examples", "keep_negative_rows")
+
+
+def test_wrapper_scale_one_passes_no_new_keyword():
+    w = _wrapper()
+    base = w.generate(EX, 5, 0.8, 1.0)
+    same = w.generate(EX, 5, 0.8, 1.0, guidance_scale=1.0, negative_examples=NEGS)
+    also = w.generate(EX, 5, 0.8, 1.0, guidance_scale=1, negative_examples="silence")
+    assert same == base and also == base
+    for c in w.model.calls:
+        assert not any(k in c for k in GUIDE_KEYS)
+        assert sorted(c) == sorted(w.model.calls[0])
+    assert not any(f.startswith("neg") for f in w.read)                        # the negatives are ignored: nothing of them is read
+
+
+def test_wrapper_keyword_errors():
+    w = _wrapper()
+    for kw, word in ((dict(guidance_scale=math.nan, negative_examples=NEGS), "finite"), (dict(guidance_scale=math.inf, negative_examples=NEGS), "finite"),
+                     (dict(guidance_scale=-math.inf, negative_examples="silence"), "finite"),
+                     (dict(guidance_scale=2.0), "negative_examples"), (dict(guidance_scale=2.0, negative_examples=NEGS[:2]), "one negative per example"),
+                     (dict(guidance_scale=2.0, negative_examples=NEGS + NEGS[:1]), "one negative per example"),
+                     (dict(guidance_scale=2.0, negative_examples="noise"), "silence"),
+                     (dict(guidance_scale=2.0, negative_examples=NEGS, num_beams=2), "num_beams"),
+                     (dict(guidance_scale=2.0, negative_examples=NEGS, num_return_sequences=2, do_sample=True, seed=1), "num_return_sequences"),
+                     (dict(guidance_scale=2.0, negative_examples=[["a", "b", ["q1", "q2"]]] * 3), "prompt")):
+        with pytest.raises(ValueError, match=word):
+            w.generate(EX, 5, 0.8, 1.0, **kw)
+    with pytest.raises(ValueError, match="question lists"):
+        w.generate([["a.wav", "b.wav", ["q1", "q2"]]], 5, 0.8, 1.0, guidance_scale=2.0, negative_examples="silence")
+    with pytest.raises(TypeError):
+        w.generate(EX, 5, 0.8, 1.0, "<|endoftext|>", True, False, None, False, 1, 1, 1.0, 1.0, 0, 0, None, None, 2.0)        # keyword-only
+    assert w.model.calls == []
+
+
+def test_wrapper_refuses_guidance_under_data_parallelism():
+    w = _wrapper()
+    w._dp = lambda: (0, 2)
+    with pytest.raises(NotImplementedError, match="data-parallel"):
+        w.generate(EX, 5, 0.8, 1.0, guidance_scale=2.0, negative_examples="silence")
+    assert w.model.calls == []
+
+
+def test_wrapper_silence_hands_over_zero_clips_and_the_own_prompts():
+    w = _wrapper()
+    out = w.generate(EX, 5, 0.8, 1.0, guidance_scale=2.5, negative_examples="silence")
+    assert len(out) == 3 and all(isinstance(t, str) for t in out)              # the shape of the un-guided call
+    (c,) = w.model.calls
+    assert c["guidance_scale"] == 2.5 and "negative_examples" not in c
+    n1, n2, nids = c["negative"]
+    assert tuple(n1.shape) == tuple(c["audio1"].shape) and tuple(n2.shape) == tuple(c["audio2"].shape)
+    assert float(torch.as_tensor(n1).abs().max()) == 0.0 and float(torch.as_tensor(n2).abs().max()) == 0.0
+    assert float(torch.as_tensor(c["audio1"]).abs().min()) > 0.0               # (the stub's clips are not silent)
+    assert torch.equal(torch.as_tensor(nids), torch.as_tensor(c["input_ids"]))
+    assert w.read == [e[0] for e in EX] + [e[1] for e in EX]                   # no file read for the negatives
+    assert w._guide_kw == {}                                                   # nothing kept for the next call
+    w.generate(EX, 5, 0.8, 1.0)
+    assert not any(k in w.model.calls[1] for k in GUIDE_KEYS)
+
+
+def test_wrapper_passes_the_keywords_on_the_greedy_sampled_and_scored_routes():
+    w = _wrapper()
+    rules = dict(repetition_penalty=1.2, no_repeat_ngram_size=3, min_new_tokens=2, suppress_tokens=[5], logit_bias={9: 1.0})
+    plain = w.generate(EX, 5, 0.8, 1.0, return_logprobs=True)
+    g = w.generate(EX, 5, 0.8, 1.0, guidance_scale=3.0, negative_examples=NEGS)
+    s = w.generate(EX, 5, 0.8, 1.0, guidance_scale=3.0, negative_examples=NEGS, do_sample=True, seed=11, **rules)
+    r = w.generate(EX, 5, 0.8, 1.0, guidance_scale=0.5, negative_examples=NEGS, return_logprobs=True, **rules)
+    assert len(w.model.calls) == 4
+    assert [type(x) for x in g] == [str] * 3 and [type(x) for x in s] == [str] * 3
+    assert [sorted(d) for d in r] == [sorted(d) for d in plain]                # dicts of the same keys
+    for c, scale in zip(w.model.calls[1:], (3.0, 3.0, 0.5)):
+        assert c["guidance_scale"] == scale and c["examples"] == 3
+        n1, n2, nids = c["negative"]
+        assert [float(x[0]) for x in n1] == [float(len(e[0])) for e in NEGS] and [float(x[0]) for x in n2] == [float(len(e[1])) for e in NEGS]
+        assert [int(x[0]) for x in nids] == [len(e[2]) for e in NEGS]
+    assert w.model.calls[2]["do_sample"] and w.model.calls[2]["seed"] == 11 and w.model.calls[2]["row_offset"] == 0
+    assert w.model.calls[3]["return_logprobs"]
+    for c in w.model.calls[2:]:
+        assert c["repetition_penalty"] == 1.2 and c["no_repeat_ngram_size"] == 3 and c["min_new_tokens"] == 2
+        assert np.isneginf(c["logit_bias"][5]) and c["logit_bias"][9] == 1.0
+    assert "repetition_penalty" not in w.model.calls[1]
+
+
+def test_pool_passes_the_keywords_through():
+    import threading
+    from concurrent.futures import ThreadPoolExecutor
+    from mellow_amd.serve import EnginePool
+    pool = object.__new__(EnginePool)
+    seen = []
+
+    class Eng:
+        def generate(self, a1, a2, ids, **kw):
+            seen.append(kw)
+            return len(a1)
+
+    pool.engines, pool._locks, pool._pool = [Eng()], [threading.Lock()], ThreadPoolExecutor(max_workers=1)
+    neg = (np.zeros((2, 4)),) * 3
+    own = (np.ones((3, 4)),) * 3
+    batches = [(np.zeros((2, 4)),) * 3, (np.zeros((3, 4)),) * 3 + (own,)]
+    assert pool.generate_many(batches, max_len=4, guidance_scale=2.0, negative=neg, do_sample=True, seed=3, no_repeat_ngram_size=2) == [2, 3]
+    assert all(k["guidance_scale"] == 2.0 and k["no_repeat_ngram_size"] == 2 for k in seen)
+    assert seen[0]["negative"] is neg and seen[1]["negative"] is own           # a batch may bring its own negative
+    assert [k["row_offset"] for k in seen] == [0, 2]                           # pairs count once: the streams go by pair
+    pool._pool.shutdown()
