@@ -56,7 +56,8 @@ extern "C" {
  *     questions per example from one encode and one prefill of the clips' positions), and then mellow_generate_beam with its tap
  *     mellow_beam_select (beam search inside the decode step), and then mellow_generate_rules with its tap mellow_logit_rules_apply
  *     (repetition controls: logit rules inside the decode step), and then mellow_generate_guidance with its tap mellow_guidance_apply
- *     (contrastive guidance inside the decode step) -- added while the minor was 5, detected by symbol lookup all the same.
+ *     (contrastive guidance inside the decode step), and then mellow_generate_top_logprobs with its tap mellow_top_logprobs_apply
+ *     (the k likeliest tokens of every step) -- added while the minor was 5, detected by symbol lookup all the same.
  *  5: the attention taps on host data, mellow_debug_prefill_attn and mellow_debug_window_attn.  No existing symbol or struct
  *     changed; a binding that must also load a minor-4 library detects them by symbol lookup. */
 #define MELLOW_ABI_MINOR 5
@@ -385,6 +386,44 @@ int  mellow_generate_guidance(mellow_engine_t* e, float scale);
  * sum of exp(g - cand_val).  Any finite scale, 1 included.  Leaves guidance armed on the context as it is.  Errors as above, and a null
  * buffer, P <= 0 or a vocabulary other than 49152. */
 int  mellow_guidance_apply(mellow_engine_t* e, float scale, float* logits, int P, float* cand_val, int32_t* cand_idx, float* cand_sum);
+/* Top log-probs: next to the log-prob of the token that was chosen, the k likeliest tokens of every step and their log-probs, found
+ * on the device inside the decode step, between the rules launch and the kernel that picks the token -- for the prefill's first token
+ * as for every decode step.
+ *
+ * Definition.
+ * - The row is a row of fp32 logits l[0..49152), as the picker of that step reads it: after guidance and after the rules, if armed.
+ * - Alternatives 0 .. k-1 are the first k tokens in the order (value descending, index ascending).  A -0 counts as +0, as in the
+ *   sampler's okey.  The selection moves fp32 values only, so it is exact.
+ * - Each alternative's log-prob is l[v] - lse, one fp32 subtraction.
+ * - lse = dec_lse_value(M, S), with M, S merged from the row's (cand_val, cand_sum) partials by dec_lse_max / dec_lse_sum (common.h).
+ *   These are the same functions, in the same order, that dec_sample_kernel<true> uses.  So when the drawn token is among the k, its
+ *   entry is bit-equal to the call's out_logprob.
+ * - The greedy kernel records -log S directly.  There the entry agrees to the rounding of lse, not to the bit.
+ * - A banned token (-inf) ranks last and reports -inf.  If fewer than k tokens are finite, the -inf ones follow by index.
+ * - A row whose M is not finite (a NaN or +inf logit, or every token banned) reports NaN for all k log-probs.  Its ids are
+ *   unspecified, but lie inside [0, vocab).
+ * - 1 <= k <= 20 (TOP_LOGPROBS_MAX_K).  The vocabulary must be 49152, the sampler's row tiling.
+ *
+ * mellow_generate_top_logprobs arms the record for the NEXT mellow_generate* call on this context; that call takes it at entry and
+ * clears it whatever its outcome.  A fork has its own, initially none.  k = 0 disarms.  out_ids i32 / out_lp f32 are [N][max_len][k],
+ * host or device, for the N rows and the max_len of that call's out_tokens (a guided call's 2P rows included, rows 2i and 2i + 1
+ * equal); an entry is -1 / exactly 0.0 wherever out_tokens holds -1.  A call of more than 1024 rows advances through the record pass by
+ * pass, as it does through out_tokens.  Honoured by mellow_generate_scored, and by mellow_generate_n / mellow_generate_q when their
+ * out_logprob is non-NULL, with and without armed rules and guidance, with do_sample 0 or 1, in every precision.  A call that records
+ * no log-probs (mellow_generate, mellow_generate_sampled, _n / _q with a NULL out_logprob) fails with a message and disarms; so does
+ * mellow_generate_beam (top log-probs of a beam hypothesis are not built).  k is part of the captured step's key: a captured graph
+ * never replays with another k.  A call without the arming launches exactly what it launched before these symbols existed.  Measured
+ * cost: at 32 rows about 14 us (k = 5) to 22 us (k = 20) more per decode step, 2 to 3 %.
+ * Errors, host code first, before any device is touched: k outside [0, 20], or a null buffer with k > 0; then a null or unfinalized
+ * engine; then a vocabulary other than 49152; and, inside the call, rows_of_a_pass * max_len * k > 1 << 24 (the record of one pass:
+ * 134 MB).
+ * Added while the minor was 5 without raising it: a binding detects the two symbols by lookup. */
+int  mellow_generate_top_logprobs(mellow_engine_t* e, int k, int32_t* out_ids, float* out_lp);
+/* The same selection on caller data, one launch, no loop state (numeric tap): logits dev f32 [B][vocab]; cand_val / cand_sum dev f32
+ * [B][vocab / 32], the partials as mellow_logit_rules_apply or mellow_guidance_apply return them -> out_ids dev i32 [B][k], out_lp dev
+ * f32 [B][k].  Leaves whatever is armed as it is.  Errors as above (here k = 0 is a bad argument), plus B <= 0 or a null input. */
+int  mellow_top_logprobs_apply(mellow_engine_t* e, const float* logits, const float* cand_val, const float* cand_sum, int B, int k,
+                               int32_t* out_ids, float* out_lp);
 /* The same draw on caller logits, no loop state (numeric tap): logits dev [B][vocab], row_ids dev i32 [B] (global row index
  * of each row; NULL = 0..B-1), step = t above -> tokens dev i32 [B]. */
 int  mellow_sample_logits(mellow_engine_t* e, const float* logits, int B, const int32_t* row_ids, int step, float top_p,

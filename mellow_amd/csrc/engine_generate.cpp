@@ -25,6 +25,7 @@ struct GenRequest {
     float* out_cum = nullptr;
     LogitRules rules;                            // repetition controls (mellow_generate_rules): taken from the context at entry, the same for every pass
     Guidance guide;                              // contrastive guidance (mellow_generate_guidance): likewise; rows 2p and 2p + 1 are then pair p
+    TopLogprobs top;                             // top log-probs (mellow_generate_top_logprobs): likewise; the record [rows][max_len][k] advances with the passes
     int rows() const { return examples * n * q; }
     // rows [r0, r0 + nb) of an n = 1, q = 1 request as a request of their own; a row's random stream follows its index in the whole call
     GenRequest pass(int r0, int nb, int text_len, int32_t* steps, float* ftm) const {
@@ -33,6 +34,7 @@ struct GenRequest {
         p.examples = nb; p.row_offset += guide.on ? r0 >> 1 : r0;      // (guided: r0 is even, and the streams go by pair)
         p.out_tokens += (size_t)r0 * max_len;
         if (out_logprob) p.out_logprob += (size_t)r0 * max_len;
+        if (top.k) { p.top.ids += (size_t)r0 * max_len * top.k; p.top.lp += (size_t)r0 * max_len * top.k; }
         if (out_len) p.out_len += r0;
         p.out_steps = steps; p.first_token_ms = ftm;
         return p;
@@ -41,6 +43,7 @@ struct GenRequest {
 enum { DOOR_SCORED = 1, DOOR_N = 2, DOOR_Q = 4, DOOR_BEAM = 8 };     // what a rule of one entry point needs to know: mellow_generate_scored, mellow_generate_n, mellow_generate_q, mellow_generate_beam
 constexpr int64_t kBeamStageRows = 65536;        // B * k * max_len a beam call may stage: 30 layers x 65536 x 3 x 64 fp32 = 1.5 GB per tensor
 constexpr int kPassRows = 1024;                  // rows of one pass: 32 row blocks of loop state
+constexpr int64_t kTopRecord = 1 << 24;          // rows * max_len * k the top log-probs record of one pass may hold (two buffers of 67 MB)
 
 static int check_sampling(mellow_engine_t* e, float top_p, float temperature) {
     if (e->cfg.vocab_size != SAMPLE_MAX_V) return fail("the sampler is built for a vocabulary of %d (engine: %d)", SAMPLE_MAX_V, e->cfg.vocab_size);
@@ -105,6 +108,10 @@ static int check_request(mellow_engine_t* e, const GenRequest& r, int door) {
         if (r.n > 1) return fail("guidance is armed (mellow_generate_guidance): mellow_generate_n with n > 1 does not take it (pass every pair n times to mellow_generate_sampled)");
         if (r.q > 1) return fail("guidance is armed (mellow_generate_guidance): mellow_generate_q with Q > 1 does not take it (pass a pair per question to mellow_generate)");
     }
+    if (r.top.k) {         // (likewise)
+        if (r.beam) return fail("top log-probs are armed (mellow_generate_top_logprobs): mellow_generate_beam does not take them (top log-probs of a beam hypothesis are not built)");
+        if (!r.out_logprob) return fail("top log-probs are armed (mellow_generate_top_logprobs): this call records no log-probs (use mellow_generate_scored, or mellow_generate_n / mellow_generate_q with an out_logprob)");
+    }
     if (r.n < 1) return fail("n must be >= 1 (got %d)", r.n);
     if (r.q < 1) return fail("Q must be >= 1 (got %d)", r.q);
     if (r.n > 1 && r.q > 1) return fail("internal: n and Q are never both above 1");
@@ -149,6 +156,13 @@ static int check_request(mellow_engine_t* e, const GenRequest& r, int door) {
     if (r.guide.on) {
         if (e->cfg.vocab_size != SAMPLE_MAX_V) return fail("the guidance kernel is built for a vocabulary of %d (engine: %d)", SAMPLE_MAX_V, e->cfg.vocab_size);
         if (r.examples % 2 != 0) return fail("guidance is armed (mellow_generate_guidance): B counts rows, conditional and negative interleaved, and must be even (got %d)", r.examples);
+    }
+    if (r.top.k) {
+        if (e->cfg.vocab_size != SAMPLE_MAX_V) return fail("the top log-probs kernel is built for a vocabulary of %d (engine: %d)", SAMPLE_MAX_V, e->cfg.vocab_size);
+        const int64_t pass_rows = r.rows() < kPassRows ? r.rows() : kPassRows;
+        if (pass_rows * r.max_len * r.top.k > kTopRecord)
+            return fail("the top log-probs record of one pass holds at most %lld entries: rows * max_len * k = %lld * %d * %d (lower k or max_len, or split the examples over several calls)",
+                        (long long)kTopRecord, (long long)pass_rows, r.max_len, r.top.k);
     }
     if (r.rules.on) {
         if (e->cfg.vocab_size != SAMPLE_MAX_V) return fail("the logit rules are built for a vocabulary of %d (engine: %d)", SAMPLE_MAX_V, e->cfg.vocab_size);
@@ -313,6 +327,7 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
     if (r.beam) m.logits = true;        // the select reads the full logits rows; every row runs every step: no early exit, no migration
     m.rules = r.rules.on;               // dec_logit_rules_kernel edits the stored rows: the head stores them (apply_step_mode)
     m.guide = r.guide.on;               // dec_guidance_kernel combines the stored rows of a pair: the head stores them (apply_step_mode)
+    m.top = r.top.k;                    // dec_top_logprobs_kernel reads the stored rows: the head stores them (apply_step_mode)
     m.early_exit = !r.beam && (dev_dead || (!r.ignore_stop && e->da.RB > 1));
     // a guided call runs without migration (a pair's rows stay neighbours in slots 2p, 2p + 1); block exit stays: both rows of a
     // pair get the same token, so they finish at the same step, and a pair never straddles a 32-row block
@@ -322,6 +337,14 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
         CHK(ensure(e, e->cand_sum, (size_t)Bp * (e->cfg.vocab_size / 32)));
         CHK(ensure(e, e->out_lp, (size_t)Bp * max_len));
         HIPCHK(hipMemsetAsync(e->out_lp.p, 0, (size_t)Bp * max_len * sizeof(float), s));
+    }
+    if (m.top) {
+        // the record: -1 / exactly 0.0 wherever no token is recorded
+        const size_t nrec = (size_t)Bp * max_len * m.top;
+        CHK(ensure(e, e->top_ids, nrec));
+        CHK(ensure(e, e->top_lp, nrec));
+        HIPCHK(hipMemsetAsync(e->top_ids.p, 0xff, nrec * sizeof(int32_t), s));
+        HIPCHK(hipMemsetAsync(e->top_lp.p, 0, nrec * sizeof(float), s));
     }
     if (m.rules) {
         // the bias buffer exists whether or not this call has a bias: a captured launch holds its address (StepGraphs::Key)
@@ -421,6 +444,10 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
     HIPCHK(hipMemcpyAsync(r.out_tokens, e->out_tok.p, toks.size() * sizeof(int32_t), hipMemcpyDefault, s));
     HIPCHK(hipMemcpyAsync(toks.data(), e->out_tok.p, toks.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (r.out_logprob) HIPCHK(hipMemcpyAsync(r.out_logprob, e->out_lp.p, toks.size() * sizeof(float), hipMemcpyDefault, s));
+    if (r.top.k) {
+        HIPCHK(hipMemcpyAsync(r.top.ids, e->top_ids.p, toks.size() * r.top.k * sizeof(int32_t), hipMemcpyDefault, s));
+        HIPCHK(hipMemcpyAsync(r.top.lp, e->top_lp.p, toks.size() * r.top.k * sizeof(float), hipMemcpyDefault, s));
+    }
     HIPCHK(hipStreamSynchronize(s));
     CHK(check_bad_id(e));        // a prompt id outside the vocabulary (flagged by prefix_assemble_kernel): the reference raises IndexError
     for (int i = 0; i < 3; ++i) HIPCHK(hipEventElapsedTime(&e->phase_ms[i], e->ev_phase[i], e->ev_phase[i + 1]));
@@ -461,6 +488,7 @@ static int generate(mellow_engine_t* e, const GenRequest& req, int door = 0) {
     GenRequest r = req;
     if (e) { r.rules = e->rules_armed; e->rules_armed = LogitRules(); }      // armed rules serve this call only, whatever its outcome
     if (e) { r.guide = e->guide_armed; e->guide_armed = Guidance(); }        // ... and so does armed guidance
+    if (e) { r.top = e->top_armed; e->top_armed = TopLogprobs(); }           // ... and an armed top log-probs record
     CHK(check_request(e, r, door));
     if (r.rows() <= kPassRows) return generate_pass(e, r);      // (always so for n > 1 and, through mellow_generate_q, for Q > 1: check_request)
     const int B = r.examples, max_len = r.max_len;
@@ -478,10 +506,24 @@ static int generate(mellow_engine_t* e, const GenRequest& req, int door = 0) {
         rep_all += e->last_compactions;
         for (int i = 0; i < 3; ++i) ph[i] += e->phase_ms[i];
     }
+    // `bytes` of every row of a [rows][pitch] record set to `byte`, host or device memory
+    auto fill_rows = [](void* dst, size_t pitch, int byte, size_t bytes, int rows) -> int {
+        hipPointerAttribute_t at;
+        const bool on_device = hipPointerGetAttributes(&at, dst) == hipSuccess && at.type == hipMemoryTypeDevice;
+        if (!on_device) (void)hipGetLastError();            // a plain host pointer is not an error here
+        if (on_device) HIPCHK(hipMemset2D(dst, pitch, byte, bytes, rows));
+        else for (int row = 0; row < rows; ++row) memset(static_cast<char*>(dst) + (size_t)row * pitch, byte, bytes);
+        return 0;
+    };
     // columns a pass never reached (it stopped before the longest pass): -1, like the rows of a block that stopped early
     for (size_t p = 0; p < pass_steps.size(); ++p) {
         const int r0 = (int)p * kPassRows, nb = B - r0 < kPassRows ? B - r0 : kPassRows;
         if (pass_steps[p] >= steps_all) continue;
+        if (r.top.k) {      // the top log-probs record follows the token record: -1 / exactly 0.0
+            const size_t o = ((size_t)r0 * max_len + pass_steps[p]) * r.top.k, wk = (size_t)(steps_all - pass_steps[p]) * r.top.k * 4;
+            CHK(fill_rows(r.top.ids + o, (size_t)max_len * r.top.k * 4, 0xff, wk, nb));
+            CHK(fill_rows(r.top.lp + o, (size_t)max_len * r.top.k * 4, 0, wk, nb));
+        }
         int32_t* dst = r.out_tokens + (size_t)r0 * max_len + pass_steps[p];
         const size_t w = (size_t)(steps_all - pass_steps[p]) * sizeof(int32_t);
         hipPointerAttribute_t at;
@@ -559,7 +601,7 @@ int mellow_generate_beam(mellow_engine_t* e, const float* audio1, const float* a
                  out_token, out_lp, nullptr, out_steps, first_token_ms};
     r.beam = k; r.out_parent = out_parent; r.out_cum = out_cum;
     if (k < 1) {      // (before the n >= 1 rule words it as n)
-        if (e) { e->rules_armed = LogitRules(); e->guide_armed = Guidance(); }
+        if (e) { e->rules_armed = LogitRules(); e->guide_armed = Guidance(); e->top_armed = TopLogprobs(); }
         return fail("mellow_generate_beam takes 1 to %d beams per example (got k = %d)", BEAM_MAX_K, k);
     }
     return generate(e, r, DOOR_BEAM | DOOR_SCORED);
@@ -596,6 +638,34 @@ int mellow_guidance_apply(mellow_engine_t* e, float scale, float* logits, int P,
     g.logits = logits; g.ld = e->cfg.vocab_size; g.prm = e->d_gparams;
     g.cand_val = cand_val; g.cand_idx = cand_idx; g.cand_sum = cand_sum;
     launch_dec_guidance(g, P, e->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+int mellow_generate_top_logprobs(mellow_engine_t* e, int k, int32_t* out_ids, float* out_lp) {
+    if (k < 0 || k > TOP_LOGPROBS_MAX_K) return fail("top log-probs: k must be 0 (off) to %d (got %d)", TOP_LOGPROBS_MAX_K, k);
+    if (k > 0 && (!out_ids || !out_lp)) return fail("top log-probs: null record buffer");
+    if (!e || !e->finalized) return fail("engine not finalized");
+    e->top_armed = TopLogprobs();
+    if (k == 0) return 0;
+    if (e->cfg.vocab_size != SAMPLE_MAX_V) return fail("the top log-probs kernel is built for a vocabulary of %d (engine: %d)", SAMPLE_MAX_V, e->cfg.vocab_size);
+    e->top_armed.k = k; e->top_armed.ids = out_ids; e->top_armed.lp = out_lp;
+    return 0;
+}
+
+int mellow_top_logprobs_apply(mellow_engine_t* e, const float* logits, const float* cand_val, const float* cand_sum, int B, int k,
+                              int32_t* out_ids, float* out_lp) {
+    if (k < 0 || k > TOP_LOGPROBS_MAX_K) return fail("top log-probs: k must be 1 to %d (got %d)", TOP_LOGPROBS_MAX_K, k);
+    if (k > 0 && (!out_ids || !out_lp)) return fail("top log-probs: null record buffer");
+    if (!e || !e->finalized) return fail("engine not finalized");
+    if (e->cfg.vocab_size != SAMPLE_MAX_V) return fail("the top log-probs kernel is built for a vocabulary of %d (engine: %d)", SAMPLE_MAX_V, e->cfg.vocab_size);
+    if (!logits || !cand_val || !cand_sum || B <= 0 || k < 1) return fail("bad argument");
+    HIPCHK(hipSetDevice(e->device));
+    TopArgs g;
+    g.logits = logits; g.ld = e->cfg.vocab_size; g.cand_val = cand_val; g.cand_sum = cand_sum; g.k = k;
+    g.out_ids = out_ids; g.out_lp = out_lp;
+    launch_dec_top_logprobs(g, B, e->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(e->stream));
     return 0;

@@ -139,6 +139,14 @@ struct StepMode {
     int beam = 0;                // k >= 1: beam search -- the select (beam.hip) in place of the arg-max, and for k > 1 the two K/V reorder launches after it
     bool rules = false;          // repetition controls: dec_logit_rules_kernel between the head and the picker (forces `logits` on)
     bool guide = false;          // contrastive guidance: dec_guidance_kernel after the head, before the rules launch (forces `logits` on; rows 2p, 2p + 1 are a pair)
+    int top = 0;                 // k >= 1: dec_top_logprobs_kernel after the rules launch, before the picker (forces `logits` on; needs `logprob`)
+};
+// The top log-probs record of one generation call (include/mellow_hip.h, mellow_generate_top_logprobs): armed on the context, taken
+// into the call's GenRequest at entry.  ids / lp are the caller's [rows][max_len][k], host or device.
+struct TopLogprobs {
+    int k = 0;
+    int32_t* ids = nullptr;
+    float* lp = nullptr;
 };
 // The guidance of one generation call (include/mellow_hip.h, mellow_generate_guidance): armed on the context, taken into the call's
 // GenRequest at entry.
@@ -227,7 +235,7 @@ struct mellow_engine {
     // d_params, the sampling parameters in d_sparams).  generate_pass (engine_generate.cpp) captures, ensure_lm invalidates.
     struct LOCAL StepGraphs {
         struct Key {
-            std::array<uintptr_t, 18> v{};       // all zero: no capture (a pass has at least one row)
+            std::array<uintptr_t, 21> v{};       // all zero: no capture (a pass has at least one row)
             static Key of(const mellow_engine* e, int B);      // from the engine as configured for the pass (below the engine)
             bool operator==(const Key& k) const { return v == k.v; }
         };
@@ -291,6 +299,7 @@ struct mellow_engine {
     uint32_t h_rparams[RUL_WORDS] = {0};       // ... its staging
     uint32_t* d_gparams = nullptr;             // guidance parameter block (kernels.h GDN_*): graph replays serve any scale
     uint32_t h_gparams[GDN_WORDS] = {0};       // ... its staging
+    TopLogprobs top_armed;                     // mellow_generate_top_logprobs: what the NEXT mellow_generate* call on this context takes (and clears)
     Guidance guide_armed;                      // mellow_generate_guidance: what the NEXT mellow_generate* call on this context takes (and clears)
     LogitRules rules_armed;                    // mellow_generate_rules: what the NEXT mellow_generate* call on this context takes (and clears)
     // repetition controls, created on first use: the call's dense logit bias [vocab] (a copy: no caller pointer is ever captured),
@@ -304,6 +313,8 @@ struct mellow_engine {
     // mellow_generate_scored, created on first use: the head's per-tile sums of exponentials [rows][vocab / 32] (DecArgs::cand_sum) and
     // the log-prob record [rows][max_len] (LoopArgs::out_logprob)
     Buf cand_sum, out_lp;
+    // mellow_generate_top_logprobs, created on first use: the record of a pass, ids int32 and log-probs f32, [rows][max_len][k] each
+    Buf top_ids, top_lp;
     // mellow_generate_n (n answers per example from one prefill), created on first use: the prefix K/V of the call's examples
     // [layer][examples][3][Tp][64] -- the prefill writes them here, kv_fanout_kernel copies them to the pages of every answer row
     // (source and destination never alias) -- and the source-row table of launch_dec_load_rows with its host staging
@@ -361,7 +372,10 @@ inline mellow_engine::StepGraphs::Key mellow_engine::StepGraphs::Key::of(const m
                 (uintptr_t)e->mode.rules,          // repetition controls: dec_logit_rules_kernel in the step; the head with its logits store
                 (uintptr_t)(e->mode.rules ? e->rules_bias.p : nullptr),                     // ... the bias buffer: RulesArgs
                 (uintptr_t)(e->mode.rules && e->mode.beam ? e->rules_hist.p : nullptr),     // ... the beam rows' history buffer: RulesArgs
-                (uintptr_t)e->mode.guide}};        // contrastive guidance: dec_guidance_kernel in the step; the head with its logits store; the sampler's stream by pair
+                (uintptr_t)e->mode.guide,          // contrastive guidance: dec_guidance_kernel in the step; the head with its logits store; the sampler's stream by pair
+                (uintptr_t)e->mode.top,            // top log-probs: dec_top_logprobs_kernel in the step and its k (a launch argument); the head with its logits store
+                (uintptr_t)(e->mode.top ? e->top_ids.p : nullptr),           // ... its record: TopArgs
+                (uintptr_t)(e->mode.top ? e->top_lp.p : nullptr)}};
 }
 static_assert(!std::is_copy_constructible<mellow_engine::Buf>::value, "a Buf owns its device memory: it moves, it is never copied");
 static_assert(std::is_copy_assignable<mellow_engine::Weights>::value && std::is_copy_assignable<mellow_engine::Options>::value, "a fork copies these by assignment: no owning member (Buf, StepGraphs) belongs in them");
@@ -427,6 +441,8 @@ BeamArgs beam_args(mellow_engine* e, int N, int k);
 RulesArgs rules_args(mellow_engine* e, int B);
 // the guidance launch of a generation step, from the engine as apply_step_mode configured it (engine_lm.cpp)
 GuideArgs guide_args(mellow_engine* e);
+// the top log-probs launch of a generation step, from the engine as apply_step_mode configured it (engine_lm.cpp)
+TopArgs top_args(mellow_engine* e);
 // n > 1 (mellow_generate_n; fp32 pages only): the layers run on the B examples and write K/V to kprefix / vprefix; the fan-out and
 // everything from the last prefix row on (last layer, head, first token) run on B * n rows
 int run_prefill(mellow_engine* e, int B, int T, const RecordArgs* rec, bool all_positions = false, int n = 1);

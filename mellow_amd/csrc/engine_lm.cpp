@@ -100,7 +100,7 @@ int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end, int prefill
 void apply_step_mode(mellow_engine* e, const StepMode& m) {
     e->mode = m;
     DecArgs& a = e->da;
-    e->mode.logits = m.logits || m.rules || m.guide;   // the rules and the guidance edit the stored rows
+    e->mode.logits = m.logits || m.rules || m.guide || m.top > 0;   // the rules and the guidance edit the stored rows, the top log-probs read them
     a.logits = e->mode.logits ? e->dlogits.p : nullptr;      // (off: generation's arg-max needs the candidates only, no 6 MB store per step)
     a.cand_sum = m.logprob ? e->cand_sum.p : nullptr;
     a.blk_live = m.early_exit ? e->d_blk_live : nullptr;
@@ -171,6 +171,16 @@ GuideArgs guide_args(mellow_engine* e) {
     return g;
 }
 
+TopArgs top_args(mellow_engine* e) {
+    const LoopArgs lp = loop_args(e);
+    TopArgs g;
+    g.logits = e->da.logits; g.ld = e->cfg.vocab_size; g.cand_val = e->da.cand_val; g.cand_sum = e->da.cand_sum; g.k = e->mode.top;
+    g.out_ids = reinterpret_cast<int32_t*>(e->top_ids.p); g.out_lp = e->top_lp.p;
+    g.d_pos = e->d_pos; g.params = lp.params; g.T0 = lp.T0;
+    g.row_of_slot = lp.row_of_slot; g.blk_snap = lp.blk_snap;
+    return g;
+}
+
 // final norm (+ pending down slabs) + lm_head with fused per-tile arg-max candidates -> dlogits, d_tokens
 int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec) {
     const int NT = e->cfg.vocab_size / 32, Bp = e->da.rows;
@@ -187,6 +197,10 @@ int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec)
     if (e->mode.rules && rec) {      // repetition controls: the row's logits and tile partials are edited before any picker reads them
         ProfScope ps(e, PF_MISC, 0, 2.0 * B * e->cfg.vocab_size * 4);
         launch_dec_logit_rules(rules_args(e, B), B, e->stream);
+    }
+    if (e->mode.top && rec) {        // top log-probs: exactly the row the picker below reads, after the guidance and the rules
+        ProfScope ps(e, PF_MISC, 0, 1.0 * B * e->cfg.vocab_size * 4);
+        launch_dec_top_logprobs(top_args(e), B, e->stream);
     }
     { ProfScope ps(e, PF_MISC, 0, 0);
       if (e->mode.beam) {          // mellow_generate_beam: the head stored the logits; the k best continuations per example

@@ -367,6 +367,24 @@ struct GuideArgs {
     const int32_t* blk_snap = nullptr;   // as in LoopArgs (a guided call runs without row migration: slot == row)
 };
 void launch_dec_guidance(const GuideArgs& g, int P /* pairs */, hipStream_t s);
+// The k likeliest tokens of every live row (top_logprobs.hip; include/mellow_hip.h mellow_generate_top_logprobs states the exact
+// definition): one launch after the rules launch and before the picker.  It reads the row and its tile partials and writes the
+// record only.  k is a launch argument, so it is part of the step-graph key.
+constexpr int TOP_LOGPROBS_MAX_K = 20;
+struct TopArgs {
+    const float* logits = nullptr;       // [slots][ld] fp32 (ld = SAMPLE_MAX_V: the row tiling of the sampler)
+    int64_t ld = 0;
+    const float* cand_val = nullptr; const float* cand_sum = nullptr;   // [slots][ld / 32]: the partials the row's log-sum-exp is merged from
+    int k = 0;
+    // loop (d_pos != null): the record [rows][params[0]][k], written at column (*d_pos - T0 + 1) of the slot's example; tap: [slots][k]
+    int32_t* out_ids = nullptr; float* out_lp = nullptr;
+    const int32_t* d_pos = nullptr;
+    const int32_t* params = nullptr;     // device {max_len, stop_id} (LoopArgs::params)
+    int T0 = 0;
+    const int32_t* row_of_slot = nullptr;   // as in LoopArgs: logits and partials are addressed by slot, the record by example
+    const int32_t* blk_snap = nullptr;
+};
+void launch_dec_top_logprobs(const TopArgs& g, int B, hipStream_t s);
 // after the arg-max of a step (early-exit mode only): if the rows that have not produced the stop id yet fit into fewer 32-row
 // blocks than are live, move them (their next-step residual rows) to the lowest slots, rewrite row_of_slot / blk_left / blk_live
 void launch_dec_compact(const DecArgs& a, int B, const LoopArgs& loop, hipStream_t s);

@@ -50,7 +50,7 @@ _ADDED_UNDER_MINOR_4 = ("mellow_lm_score", "mellow_score", "mellow_generate_scor
                         "mellow_generate_q", "mellow_generate_beam", "mellow_beam_select")
 # symbols of minor 5 (the attention taps on host data): looked up the same way, so that a minor-4 library still loads
 _ADDED_UNDER_MINOR_5 = ("mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_generate_rules", "mellow_logit_rules_apply",
-                        "mellow_generate_guidance", "mellow_guidance_apply")
+                        "mellow_generate_guidance", "mellow_guidance_apply", "mellow_generate_top_logprobs", "mellow_top_logprobs_apply")
 
 
 def load_library(path: Optional[str] = None):
@@ -93,6 +93,8 @@ def load_library(path: Optional[str] = None):
         "mellow_logit_rules_apply": (ci, [vp, P(LogitRules), vp, ci, vp, ci, vp, ci, vp, vp, vp]),
         "mellow_generate_guidance": (ci, [vp, cf]),
         "mellow_guidance_apply": (ci, [vp, cf, vp, ci, vp, vp, vp]),
+        "mellow_generate_top_logprobs": (ci, [vp, ci, vp, vp]),
+        "mellow_top_logprobs_apply": (ci, [vp, vp, vp, vp, ci, ci, vp, vp]),
         "mellow_logmel": (ci, [vp, vp, ci, i64, ci, vp]),
         "mellow_encode": (ci, [vp, vp, ci, i64, vp]),
         "mellow_prefix": (ci, [vp, vp, vp, i64, vp, ci, vp]),
@@ -150,7 +152,7 @@ EXPORTED_SYMBOLS = (
     "mellow_engine_num_required", "mellow_engine_required_key", "mellow_generate", "mellow_generate_sampled", "mellow_sample_logits", "mellow_logmel",
     "mellow_encode", "mellow_prefix", "mellow_lm_prefill", "mellow_lm_decode_step", "mellow_argmax", "mellow_embed_tokens", "mellow_lm_forward_logits",
     "mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse", "mellow_generate_n", "mellow_generate_q",
-    "mellow_generate_beam", "mellow_beam_select", "mellow_generate_rules", "mellow_logit_rules_apply", "mellow_generate_guidance", "mellow_guidance_apply", "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
+    "mellow_generate_beam", "mellow_beam_select", "mellow_generate_rules", "mellow_logit_rules_apply", "mellow_generate_guidance", "mellow_guidance_apply", "mellow_generate_top_logprobs", "mellow_top_logprobs_apply", "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
     "mellow_prof_num_families", "mellow_prof_family_name", "mellow_prof_get", "mellow_last_phase_ms", "mellow_last_steps_enqueued", "mellow_last_row_repacks", "mellow_stft_is_fft", "mellow_prefill_parts", "mellow_abi_minor",
     "mellow_resample", "mellow_engine_set_precision", "mellow_engine_set_option", "mellow_engine_describe", "mellow_debug_gemm_fp8", "mellow_debug_gemm_f32", "mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_debug_dec_head", "mellow_set_graph", "mellow_host_window_map", "mellow_host_pack_weight", "mellow_host_rope_tables",
 )
@@ -221,6 +223,17 @@ def check_guidance_scale(guidance_scale=1.0) -> float:
     if not math.isfinite(s):
         raise ValueError(f"guidance_scale must be finite (got {guidance_scale}); 1 is off")
     return s
+
+
+TOP_LOGPROBS_MAX_K = 20        # alternatives per step mellow_generate_top_logprobs records
+
+
+def check_top_logprobs(top_logprobs=0) -> int:
+    """The one value rule of top_logprobs (the C entry repeats it): 0 (off) to 20 alternatives per step."""
+    k = int(top_logprobs)
+    if k < 0 or k > TOP_LOGPROBS_MAX_K:
+        raise ValueError(f"top_logprobs must be 0 (off) to {TOP_LOGPROBS_MAX_K} (got {top_logprobs})")
+    return k
 
 
 BEAM_MAX_K = 8                 # beams per example mellow_generate_beam takes
@@ -456,7 +469,7 @@ class Engine:
                  row_offset: int = 0, return_logprobs: bool = False, num_return_sequences: int = 1,
                  num_beams: Optional[int] = None, length_penalty: float = 1.0, repetition_penalty: float = 1.0,
                  no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, logit_bias=None, _arm_neutral_rules: bool = False,
-                 guidance_scale: float = 1.0, negative=None, keep_negative_rows: bool = False):
+                 guidance_scale: float = 1.0, negative=None, keep_negative_rows: bool = False, top_logprobs: int = 0):
         """-> (tokens int32 [B, steps] on host, lengths [B], steps, first_token_ms)
         num_return_sequences = n > 1 (needs do_sample=True): n sampled answers per example from one encode and one prefill per
         example (mellow_generate_n).  Every array has B * n rows, row b * n + j = answer j of example b, and holds what this call
@@ -492,10 +505,26 @@ class Engine:
         2i and 2i + 1 equal).  row_offset counts PAIRS: answer i draws from the stream example i of the un-guided call draws from.  A
         returned log-prob is that of the processed distribution.  ValueError together with num_beams, num_return_sequences > 1 or
         3-D input_ids, for a scale that is not finite, or for s != 1 without `negative`.  s = 1 (default): nothing is armed, `negative`
-        is ignored and the call is the one without these keywords."""
+        is ignored and the call is the one without these keywords.
+        top_logprobs = k (1 .. 20; needs return_logprobs=True): the k likeliest tokens of every step (include/mellow_hip.h,
+        mellow_generate_top_logprobs), taken on the device from exactly the row the token is chosen from -- after the guidance and the
+        repetition controls, if set; at temperature 1 and without the nucleus, as `logprobs` is.  The result gains two values after
+        logprobs: top_ids int32 [rows, steps, k] and top_logprobs float32 [rows, steps, k], best first (value descending, then index
+        ascending); -1 / exactly 0.0 where tokens is -1.  Guided calls return the conditional rows, or all rows with
+        keep_negative_rows=True.  ValueError with num_beams, without return_logprobs=True, or for k outside [0, 20].  0 (default):
+        nothing is armed and the call is the one without the keyword."""
         import time
         t_in = time.perf_counter()
         nseq = int(num_return_sequences)
+        self._top_k, self._top_cur = 0, None
+        topk = check_top_logprobs(top_logprobs)
+        if topk:
+            if num_beams is not None:
+                raise ValueError("top_logprobs and num_beams do not combine: top log-probs of a beam hypothesis are not built")
+            if not return_logprobs:
+                raise ValueError("top_logprobs needs return_logprobs=True: the alternatives come with the log-prob record")
+            self._need("mellow_generate_top_logprobs")
+        self._top_k = topk
         gscale = check_guidance_scale(guidance_scale)
         self._guide = None
         if gscale != 1.0:
@@ -544,6 +573,7 @@ class Engine:
         B, n = a1.shape
         assert a2.shape == a1.shape and ids.shape == (B, spec.TEXT_LEN), (a1.shape, a2.shape, ids.shape)
         out = torch.empty((B, max_len), dtype=torch.int32, device=self.tdev)
+        top = self._top_record(B, int(max_len))
         self._sync_inputs()
         t_up = (time.perf_counter() - t_in) * 1e3
         lens = (C.c_int32 * B)()
@@ -553,6 +583,7 @@ class Engine:
         if return_logprobs:
             self._need("mellow_generate_scored")
             lp = torch.empty((B, max_len), dtype=torch.float32, device=self.tdev)
+            self._top_cur = top
             self._arm()
             self._chk(self.lib.mellow_generate_scored(self.h, _ptr(a1), _ptr(a2), n, _ptr(ids), B, int(max_len), 1 if do_sample else 0,
                                                       float(top_p), float(temperature), _seed64(seed) if do_sample else 0,
@@ -572,7 +603,19 @@ class Engine:
         self.last_first_token_host_ms = t_up + float(ftm.value)
         rows = slice(None, None, 2) if self._guide is not None and not keep_negative_rows else slice(None)      # guided: the conditional rows
         res = (toks[rows], np.asarray(list(lens), dtype=np.int32)[rows], int(steps.value), float(ftm.value))
-        return res + (lp.cpu().numpy()[rows, : steps.value],) if return_logprobs else res
+        if return_logprobs:
+            res = res + (lp.cpu().numpy()[rows, : steps.value],)
+        if top is not None:
+            res = res + tuple(t.cpu().numpy()[rows, : steps.value] for t in top)
+        return res
+
+    def _top_record(self, rows: int, max_len: int):
+        """the device record (ids int32, log-probs float32, [rows][max_len][k] each) of a generate() with top_logprobs, or None"""
+        k = getattr(self, "_top_k", 0)
+        if not k:
+            return None
+        return (torch.empty((rows, max_len, k), dtype=torch.int32, device=self.tdev),
+                torch.empty((rows, max_len, k), dtype=torch.float32, device=self.tdev))
 
     def _make_rules(self, repetition_penalty, no_repeat_ngram_size, min_new_tokens, logit_bias, arm_neutral, max_len):
         """the struct _arm() hands to mellow_generate_rules before every C call of this generate(), or None: nothing to arm"""
@@ -598,6 +641,10 @@ class Engine:
         g = getattr(self, "_guide", None)
         if g is not None:
             self._chk(self.lib.mellow_generate_guidance(self.h, float(g)))
+        k, cur = getattr(self, "_top_k", 0), getattr(self, "_top_cur", None)
+        if k and cur is not None:        # the rows of the record the next C call fills
+            self._chk(self.lib.mellow_generate_top_logprobs(self.h, int(k), _ptr(cur[0]), _ptr(cur[1])))
+            self._top_cur = None         # (the caller of _arm holds the tensors until its C call has returned)
 
     def logit_rules_apply(self, logits, history, hist_len, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
                           min_new_tokens: int = 0, logit_bias=None, stop_id: int = 0, with_sum: bool = True):
@@ -647,6 +694,24 @@ class Engine:
             out["cand_sum"] = cs.cpu().numpy()
         return out
 
+    def top_logprobs_apply(self, logits, cand_val, cand_sum, k: int):
+        """The k likeliest tokens of caller rows (numeric tap, mellow_top_logprobs_apply): logits [B][vocab], cand_val / cand_sum
+        [B][vocab / 32] the tile partials as logit_rules_apply or guidance_apply return them -> (ids int32 [B][k], lp float32 [B][k])
+        as numpy arrays, best first."""
+        k = check_top_logprobs(k)
+        if k < 1:
+            raise ValueError(f"top_logprobs_apply takes k = 1 to {TOP_LOGPROBS_MAX_K} (got {k})")
+        self._need("mellow_top_logprobs_apply")
+        lg, cv, cs = self._f32(logits), self._f32(cand_val), self._f32(cand_sum)
+        B, V = lg.shape
+        if V != self.lm.vocab_size or cv.shape != (B, V // 32) or cs.shape != (B, V // 32):
+            raise ValueError(f"logits {tuple(lg.shape)}, cand_val {tuple(cv.shape)}, cand_sum {tuple(cs.shape)} do not describe B rows of the vocabulary")
+        ids = torch.empty((B, k), dtype=torch.int32, device=self.tdev)
+        lp = torch.empty((B, k), dtype=torch.float32, device=self.tdev)
+        self._sync_inputs()
+        self._chk(self.lib.mellow_top_logprobs_apply(self.h, _ptr(lg), _ptr(cv), _ptr(cs), B, k, _ptr(ids), _ptr(lp)))
+        return ids.cpu().numpy(), lp.cpu().numpy()
+
     def _generate_nseq(self, audio1, audio2, input_ids, max_len, nseq, top_p, temperature, stop_id, ignore_stop, seed, row_offset,
                        return_logprobs, t_in):
         """generate(num_return_sequences=nseq > 1): one mellow_generate_n call per pass of plan_nseq_passes; a pass that stopped
@@ -660,6 +725,7 @@ class Engine:
         N = B * nseq
         out = torch.empty((N, max_len), dtype=torch.int32, device=self.tdev)
         lp = torch.empty((N, max_len), dtype=torch.float32, device=self.tdev) if return_logprobs else None
+        top = self._top_record(N, max_len)
         self._sync_inputs()
         t_up = (time.perf_counter() - t_in) * 1e3
         lens = np.zeros((N,), dtype=np.int32)
@@ -668,6 +734,7 @@ class Engine:
             r0, nr = lo * nseq, (hi - lo) * nseq
             ln = (C.c_int32 * nr)()
             steps, ftm = C.c_int32(0), C.c_float(0.0)
+            self._top_cur = None if top is None else (top[0][r0:r0 + nr], top[1][r0:r0 + nr])
             self._arm()
             self._chk(self.lib.mellow_generate_n(self.h, _ptr(a1[lo:hi]), _ptr(a2[lo:hi]), ns, _ptr(ids[lo:hi]), hi - lo, nseq, max_len, 1,
                                                  top_p, temperature, seed, off, stop_id, 1 if ignore_stop else 0, _ptr(out[r0:r0 + nr]),
@@ -679,13 +746,19 @@ class Engine:
         steps_all = max(pass_steps)
         toks = out.cpu().numpy()[:, :steps_all].copy()
         lps = lp.cpu().numpy()[:, :steps_all].copy() if return_logprobs else None
+        tops = None if top is None else [t.cpu().numpy()[:, :steps_all].copy() for t in top]
         for (lo, hi, _), st in zip(passes, pass_steps):      # columns a pass never reached: never computed
             toks[lo * nseq:hi * nseq, st:] = -1
             if lps is not None:
                 lps[lo * nseq:hi * nseq, st:] = 0.0
+            if tops is not None:
+                tops[0][lo * nseq:hi * nseq, st:] = -1
+                tops[1][lo * nseq:hi * nseq, st:] = 0.0
         self.last_first_token_host_ms = t_up + ftm0
         res = (toks, lens, steps_all, ftm0)
-        return res + (lps,) if return_logprobs else res
+        if return_logprobs:
+            res = res + (lps,)
+        return res if tops is None else res + tuple(tops)
 
     def _generate_beam(self, audio1, audio2, input_ids, max_len, k, m, length_penalty, stop_id, ignore_stop, return_logprobs, t_in):
         """generate(num_beams=k): one mellow_generate_beam call, then the backtracking and the final ranking on the host"""
@@ -761,6 +834,7 @@ class Engine:
                              "have no fan-out (pass the pair once per question instead)")
         out = torch.empty((N, max_len), dtype=torch.int32, device=self.tdev)
         lp = torch.empty((N, max_len), dtype=torch.float32, device=self.tdev) if return_logprobs else None
+        top = self._top_cur = self._top_record(N, max_len)
         self._sync_inputs()
         t_up = (time.perf_counter() - t_in) * 1e3
         lens = (C.c_int32 * N)()
@@ -772,7 +846,9 @@ class Engine:
         toks = out.cpu().numpy()[:, : steps.value]
         self.last_first_token_host_ms = t_up + float(ftm.value)
         res = (toks, np.asarray(list(lens), dtype=np.int32), int(steps.value), float(ftm.value))
-        return res + (lp.cpu().numpy()[:, : steps.value],) if return_logprobs else res
+        if return_logprobs:
+            res = res + (lp.cpu().numpy()[:, : steps.value],)
+        return res if top is None else res + tuple(t.cpu().numpy()[:, : steps.value] for t in top)
 
     def stft_is_fft(self) -> bool:
         """the STFT runs as an FFT (f32x3 mode, windowed-DFT conv weights) instead of the DFT GEMM"""

@@ -71,7 +71,8 @@ class EnginePool:
         repetition_penalty / no_repeat_ngram_size / min_new_tokens / logit_bias: the repetition controls, armed by each context for
         its own calls, the same for every batch; guidance_scale with negative=(audio1, audio2, input_ids): contrastive guidance, the
         scale armed by each context for its own calls -- a `negative` keyword goes to every batch as it is, a batch given as
-        (audio1, audio2, input_ids, negative) brings its own; a guided batch counts its examples, not its rows, towards row_offset)."""
+        (audio1, audio2, input_ids, negative) brings its own; a guided batch counts its examples, not its rows, towards row_offset;
+        top_logprobs=k with return_logprobs=True: seven values per batch, top_ids and top_logprobs [rows, steps, k] after logprobs)."""
         kws = [kw] * len(batches)
         if kw.get("do_sample"):
             off, kws = int(kw.get("row_offset", 0)), []

@@ -275,11 +275,12 @@ class MellowWrapper:
             if nseq > 1:
                 samp["num_return_sequences"] = nseq
             if return_logprobs:       # (refused under data-parallel sharding by generate(): the gather below carries tokens only)
-                toks, lens, steps, ftm, logprobs = self.model.generate(audio1, audio2, input_ids, max_len=entry_length, top_p=top_p,
-                                                                       temperature=temperature, stop_id=stop_token_index,
-                                                                       return_logprobs=True, **samp)
+                samp.update(getattr(self, "_top_kw", None) or {})
+                toks, lens, steps, ftm, logprobs, *top = self.model.generate(audio1, audio2, input_ids, max_len=entry_length, top_p=top_p,
+                                                                             temperature=temperature, stop_id=stop_token_index,
+                                                                             return_logprobs=True, **samp)
                 self.last_first_token_ms = ftm
-                res = self._scored_results(toks, logprobs, stop_token_index)
+                res = self._scored_results(toks, logprobs, stop_token_index, top if samp.get("top_logprobs") else None)
                 if counts is not None:
                     return self._per_question(res, counts, int(input_ids.shape[1]))
                 return res if nseq == 1 else [res[i:i + nseq] for i in range(0, len(res), nseq)]
@@ -309,12 +310,14 @@ class MellowWrapper:
         """rows of the padded [B][Q] layout -> per example the answers to its own counts[i] questions (the padding is dropped)"""
         return [rows[i * Q:i * Q + int(c)] for i, c in enumerate(counts)]
 
-    def _scored_results(self, toks, logprobs, stop_id: int):
+    def _scored_results(self, toks, logprobs, stop_id: int, top=None):
         """One dict per row of a generate(return_logprobs=True) call.  The counted tokens are those before the row's first stop id
         plus the stop id itself if the row produced it -- score()'s append_stop=True convention, so `logprob` is the number
-        score() gives for `text`; it is their fp32 sum in ascending order."""
+        score() gives for `text`; it is their fp32 sum in ascending order.
+        top = (top_ids [rows, steps, k], top_logprobs [rows, steps, k]) of a call with top_logprobs=k: every dict gains
+        "top_logprobs", one list per counted token of k dicts {"token_id", "token", "logprob"}, best first."""
         out = []
-        for r, lp in zip(np.asarray(toks), np.asarray(logprobs, dtype=np.float32)):
+        for i, (r, lp) in enumerate(zip(np.asarray(toks), np.asarray(logprobs, dtype=np.float32))):
             valid = r >= 0                       # -1 = never computed (wrapper docstring): a prefix of the row is valid
             n_valid = int(valid.sum())
             hit = np.nonzero(r[:n_valid] == stop_id)[0]
@@ -325,13 +328,17 @@ class MellowWrapper:
             out.append({"text": self.tokenizer.decode(r[valid]).split("<|endoftext|>")[0],
                         "token_ids": [int(t) for t in r[:n]], "token_logprobs": [float(x) for x in lp[:n]],
                         "logprob": float(total), "tokens": n})
+            if top is not None:
+                ids, tlp = np.asarray(top[0])[i], np.asarray(top[1], dtype=np.float32)[i]
+                out[-1]["top_logprobs"] = [[{"token_id": int(t), "token": self.tokenizer.decode([int(t)]), "logprob": float(x)}
+                                            for t, x in zip(ids[st], tlp[st])] for st in range(n)]
         return out
 
     def generate(self, examples, max_len, top_p, temperature, stop_token="<|endoftext|>", audio_resample=True, *,
                  do_sample: bool = False, seed: Optional[int] = None, return_logprobs: bool = False,
                  num_return_sequences: int = 1, num_beams: int = 1, length_penalty: float = 1.0, repetition_penalty: float = 1.0,
                  no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, suppress_tokens: Optional[Sequence[int]] = None,
-                 logit_bias: Optional[dict] = None, guidance_scale: float = 1.0, negative_examples=None):
+                 logit_bias: Optional[dict] = None, guidance_scale: float = 1.0, negative_examples=None, top_logprobs: int = 0):
         r"""Produces text response for the given audio files and text prompts
         examples: (list<list>) each example is [audio path 1, audio path 2, text prompt]; the text prompt may be a list or tuple of
                      prompts, several questions about the one pair of clips (module docstring).  If any example has a list, the
@@ -380,6 +387,13 @@ class MellowWrapper:
                      the keyword -- nothing is armed and the negatives are ignored.
         negative_examples: a list parallel to `examples` of [audio path 1, audio path 2, prompt], or the string "silence": every
                      example's own prompt over two all-zero clips of the configured length (no file is read).
+        top_logprobs: (int) k = 1 .. 20 (needs return_logprobs=True): every result dict gains "top_logprobs", one list per counted
+                     token (stop token included) of k dicts {"token_id", "token", "logprob"}, best first: the k likeliest tokens of
+                     the distribution that token was chosen from (the model's log-softmax at temperature 1 without the nucleus,
+                     after the guidance and the repetition keywords if set), found on the device inside the decode step.  With
+                     max_len=1 on a multiple-choice prompt these are the first-token option probabilities.  Works with do_sample,
+                     num_return_sequences, question lists, the five repetition keywords and guidance_scale.  ValueError without
+                     return_logprobs=True, with num_beams > 1, or for k outside [0, 20].  0 (default): the call without the keyword.
 
         With `data_parallel=True` (or MELLOW_DATA_PARALLEL=1) under an initialised torch.distributed group (one process per
         GPU, every rank calling with the same examples) the examples are sharded contiguously over the ranks, each rank ingests
@@ -399,6 +413,7 @@ class MellowWrapper:
             raise ValueError(f"num_beams must be >= 1 (got {k})")
         gscale, negatives = self._guidance_request(guidance_scale, negative_examples, examples, text_prompts, k, nseq)
         self._guide_kw = {}
+        self._top_kw = self._top_request(top_logprobs, return_logprobs, k)
         if k > 1:
             return self._generate_beams(examples, audio_paths1, audio_paths2, text_prompts, max_len, stop_token, audio_resample,
                                         do_sample, return_logprobs, k, nseq, float(length_penalty))
@@ -456,6 +471,19 @@ class MellowWrapper:
                                         seed=seed, row_offset=lo * nseq, return_logprobs=return_logprobs, nseq=nseq)
         finally:
             self._guide_kw = {}         # (the negative clips are not kept alive past the call)
+
+    @staticmethod
+    def _top_request(top_logprobs, return_logprobs, k):
+        """The keyword rules of top_logprobs -> the keyword for Engine.generate ({} for 0: the call without it)."""
+        from .engine import check_top_logprobs
+        t = check_top_logprobs(top_logprobs)
+        if t == 0:
+            return {}
+        if k > 1:
+            raise ValueError("top_logprobs and num_beams > 1 do not combine: top log-probs of a beam hypothesis are not built")
+        if not return_logprobs:
+            raise ValueError("top_logprobs needs return_logprobs=True: the alternatives are part of the result dicts")
+        return dict(top_logprobs=t)
 
     def _guidance_request(self, guidance_scale, negative_examples, examples, text_prompts, k, nseq):
         """The keyword rules of guidance_scale / negative_examples -> (scale, negatives): negatives is None for an un-guided call
