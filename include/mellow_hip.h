@@ -59,7 +59,8 @@ extern "C" {
  *     (contrastive guidance inside the decode step), and then mellow_generate_top_logprobs with its tap mellow_top_logprobs_apply
  *     (the k likeliest tokens of every step) -- added while the minor was 5, detected by symbol lookup all the same.
  *  5: the attention taps on host data, mellow_debug_prefill_attn and mellow_debug_window_attn.  No existing symbol or struct
- *     changed; a binding that must also load a minor-4 library detects them by symbol lookup. */
+ *     changed; a binding that must also load a minor-4 library detects them by symbol lookup.  The GEMM epilogue tap
+ *     mellow_debug_gemm_epi was added later under this same minor, detected by symbol lookup all the same. */
 #define MELLOW_ABI_MINOR 5
 
 typedef struct mellow_engine mellow_engine_t;
@@ -513,6 +514,48 @@ int  mellow_debug_gemm_f32(mellow_engine_t* e, int mode, const float* A, int M, 
                            int iters, float* ms2);
 int  mellow_debug_gemm_fp8(mellow_engine_t* e, const float* A, int M, int K, const float* W, int N, float* C,
                            int iters, float* ms2);
+/* GEMM epilogue tap on HOST data (works on any engine, finalised or not): ONE call of a GEMM launcher the engine itself calls --
+ * kernel 0 launch_gemm (exact fp32 MFMA), 16 launch_gemm_bf16x3_fused (f32x3, A split in registers), 17 launch_split_rows_apb then
+ * launch_gemm_bf16x3_apb (f32x3, both operands by LDS-DMA) -- with the epilogue the descriptor describes, after the weight packing
+ * that epilogue needs (launch_pack_weight / launch_pack_weight_pairs, launch_pack_bf16x3).  mellow_debug_gemm_f32 stays the plain
+ * timing and accuracy tap.  The fp8 kernel, c16, kv16 and the AMX hand-over are not reachable from here.
+ *   A host f32 [M][K]; W host f32 [Nw][K] logical rows (swiglu: rows [0, Nw / 2) gate, [Nw / 2, Nw) up; qkv-rope: 576 q, 192 k,
+ *   192 v rows); bias host f32 [Nw] or NULL; resid host f32 [C rows][N] or NULL; crow_map host i32 [rows_in] or NULL (C row of
+ *   row m = (m / rows_in) * rows_out + crow_map[m % rows_in], a one-to-one map into [0, rows_out), M % rows_in == 0; C rows =
+ *   M / rows_in * rows_out, else M); rs_ssq host f32 [M][rs_parts] or NULL (every accumulator of row m is scaled by
+ *   1 / sqrt(sum_p rs_ssq[m][p] / rs_dim + rs_eps)); rope_cos / rope_sin host f32 [Tmax][32], or both NULL for the tables of
+ *   mellow_host_rope_tables(cfg.rope_theta, 64, Tmax).
+ * Every output the launch can write is filled with 0xFF bytes first and returned whole (capacities in bytes):
+ *   out_c    f32 [C rows + 32][ldc]           (linear with want_c, swiglu with want_c; resid = 2 loads the residual into it first)
+ *   out_c3   the raw APB image of N columns, roundup(M, 128) rows, 6 bytes per element (want_c3)
+ *   out_ssq  f32 [M + 32][N / 64]             (want_ssq: sums of squares of the stored row over each 64-column group)
+ *   out_q    f32 [M + 32][576]                (qkv-rope)
+ *   out_k / out_v  f32 pages [B + 1][3][Tmax][64], B = M / (T - pos0): every position, and one page set of no example
+ * Refused by name, nothing launched: K % 32 != 0 (kernels 0 / 16) or K % 16 != 0 or K < 48 (kernel 17); N not a multiple of 4 in
+ * [rup(Nw, 4), rup(Nw, 128)] (swiglu: N != Nw / 2); want_c3 with linear and N % 64 != 0 or with swiglu and N % 16 != 0; want_c3
+ * or splitk_max with kernel 0; want_ssq without want_c3; ldc < N; pos0 outside [0, T); Tmax < T; M != B * (T - pos0); qkv-rope
+ * with Nw or N != 960; a capacity that is too small. */
+typedef struct mellow_gemm_epi {
+    int32_t size;            /* sizeof(mellow_gemm_epi_t) */
+    int32_t kernel;          /* 0, 16, 17 */
+    int32_t epi;             /* 0 linear, 1 swiglu, 2 qkv-rope */
+    int32_t M, K, Nw, N;     /* Nw logical weight rows, N stored columns */
+    int32_t act;             /* linear: 0 none, 1 GELU, 2 sigmoid */
+    int32_t bias;            /* linear: 0 / 1 */
+    int32_t resid;           /* linear: 0 none, 1 a separate buffer, 2 in place (resid == C) */
+    int32_t rows_in, rows_out;   /* linear, with crow_map */
+    int32_t ldc;             /* linear: floats between C rows, >= N (swiglu: N) */
+    int32_t want_c, want_c3, want_ssq;
+    int32_t rs_parts;        /* with rs_ssq */
+    float rs_dim, rs_eps;
+    int32_t splitk_max;      /* 0 = no workspace; else the engine's 512-tile workspace with sk_tiles = 256 and this sk_max */
+    int32_t no_x3w;          /* keep a K = 96, M >= 8192 launch of kernel 17 on the tile kernel */
+    int32_t T, Tmax, pos0;   /* qkv-rope: pos0 > 0 selects EPI_QKV_ROPE_AT; rows m = b * (T - pos0) + i are positions pos0 + i */
+} mellow_gemm_epi_t;
+int  mellow_debug_gemm_epi(mellow_engine_t* e, const mellow_gemm_epi_t* d, const float* A, const float* W, const float* bias,
+                           const float* resid, const int32_t* crow_map, const float* rs_ssq, const float* rope_cos,
+                           const float* rope_sin, void* out_c, int64_t c_capacity, void* out_c3, int64_t c3_capacity, float* out_ssq,
+                           int64_t ssq_capacity, float* out_q, int64_t q_capacity, float* out_k, float* out_v, int64_t kv_capacity);
 /* Attention taps on HOST data (work on any engine, finalised or not): ONE launch of an attention kernel of the engine on the
  * caller's arrays, through the launcher the engine itself calls.  The device output is filled with 0xFF bytes before the launch
  * and returned whole, so that a caller sees every byte the kernel did not write:

@@ -232,6 +232,188 @@ int mellow_debug_window_attn(mellow_engine_t* e, const float* qkv, int M, int C,
     return attn_tap_finish(e, o, out);
 }
 
+// ---- GEMM epilogue tap on host data (include/mellow_hip.h): one launch of a GEMM launcher with the epilogue the caller describes ------
+// a device buffer of `bytes` bytes, filled with 0xFF or loaded from `src`
+static int gemm_tap_buf(mellow_engine* e, mellow_engine::Buf& b, size_t bytes, const void* src) {
+    CHK(ensure(e, b, (bytes + 3) / 4 + 4));
+    if (src) HIPCHK(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
+    else HIPCHK(hipMemsetAsync(b.p, 0xFF, bytes, e->stream));
+    return 0;
+}
+static int gemm_tap_fetch(void* out, int64_t capacity, const mellow_engine::Buf& b, size_t bytes, const char* name) {
+    if (!out) return fail("%s is null: this launch writes %lld bytes there", name, (long long)bytes);
+    if (capacity < (int64_t)bytes) return fail("%s_capacity %lld is below the %lld bytes this call returns", name, (long long)capacity, (long long)bytes);
+    HIPCHK(hipMemcpy(out, b.p, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int mellow_debug_gemm_epi(mellow_engine_t* e, const mellow_gemm_epi_t* d, const float* A, const float* W, const float* bias,
+                          const float* resid, const int32_t* crow_map, const float* rs_ssq, const float* rope_cos, const float* rope_sin,
+                          void* out_c, int64_t c_capacity, void* out_c3, int64_t c3_capacity, float* out_ssq, int64_t ssq_capacity,
+                          float* out_q, int64_t q_capacity, float* out_k, float* out_v, int64_t kv_capacity) {
+    if (!e || !d || !A || !W) return fail("null argument");
+    if (d->size != (int32_t)sizeof(mellow_gemm_epi_t)) return fail("size = %d is not sizeof(mellow_gemm_epi_t) = %d", d->size, (int)sizeof(mellow_gemm_epi_t));
+    const int kernel = d->kernel, M = d->M, K = d->K, Nw = d->Nw, N = d->N;
+    const bool lin_ = d->epi == 0, swi = d->epi == 1, qkv = d->epi == 2;
+    if (kernel != 0 && kernel != 16 && kernel != 17) return fail("kernel must be 0 (fp32 MFMA), 16 (f32x3, A split in registers) or 17 (f32x3, pre-split A, LDS-DMA): got %d", kernel);
+    if (!lin_ && !swi && !qkv) return fail("epi must be 0 (linear), 1 (swiglu) or 2 (qkv-rope): got %d", d->epi);
+    if (M < 1 || M > (1 << 22)) return fail("M = %d: 1 <= M <= %d", M, 1 << 22);
+    if (K < 1 || K > 65536) return fail("K = %d: 1 <= K <= 65536", K);
+    if (kernel != 17 && K % 32 != 0) return fail("K = %d must be a multiple of 32 for kernel %d", K, kernel);
+    if (kernel == 17 && K % 16 != 0) return fail("K = %d must be a multiple of 16 for kernel 17", K);
+    if (kernel == 17 && K < 48) return fail("K = %d is below the 48 (three k16 stages) kernel 17 needs", K);
+    if (Nw < 1 || Nw > 65536) return fail("Nw = %d: 1 <= Nw <= 65536", Nw);
+    if (swi) {
+        if (Nw % 2 != 0 || N != Nw / 2 || N % 4 != 0) return fail("swiglu: Nw = %d counts gate + up rows and N = %d must be Nw / 2, a multiple of 4", Nw, N);
+    } else if (N % 4 != 0 || N < rup(Nw, 4) || N > rup(Nw, 128)) {
+        return fail("N = %d must be a multiple of 4 with rup(Nw, 4) = %d <= N <= rup(Nw, 128) = %d", N, rup(Nw, 4), rup(Nw, 128));
+    }
+    if ((int64_t)M * K > (1 << 28) || (int64_t)rup(Nw, 128) * K > (1 << 27)) return fail("M * K = %lld or rup(Nw, 128) * K = %lld exceeds the tap's 2^28 / 2^27 elements", (long long)M * K, (long long)rup(Nw, 128) * K);
+    if (d->want_c3 && kernel == 0) return fail("want_c3: kernel 0 hands nothing over in APB order");
+    if (d->splitk_max && kernel == 0) return fail("splitk_max: kernel 0 has no split-K");
+    if (d->splitk_max < 0 || d->splitk_max == 1 || d->splitk_max > 64) return fail("splitk_max = %d: 0 (no workspace) or 2 .. 64", d->splitk_max);
+    if (d->want_ssq && !(lin_ && d->want_c3)) return fail("want_ssq needs want_c3 with the linear epilogue");
+    if (d->want_c3 && lin_ && N % 64 != 0) return fail("want_c3 with the linear epilogue needs N %% 64 == 0 (N = %d)", N);
+    if (d->want_c3 && swi && N % 16 != 0) return fail("want_c3 with swiglu needs N %% 16 == 0 (N = %d)", N);
+    if (d->want_c3 && qkv) return fail("want_c3: the qkv-rope epilogue hands nothing over in APB order");
+    const bool has_rs = rs_ssq != nullptr;
+    if (has_rs && (d->rs_parts < 1 || d->rs_parts > 64 || !(d->rs_dim > 0.f) || !(d->rs_eps >= 0.f)))
+        return fail("rs_ssq needs 1 <= rs_parts <= 64, rs_dim > 0, rs_eps >= 0 (got %d, %g, %g)", d->rs_parts, d->rs_dim, d->rs_eps);
+    int64_t c_rows = M;
+    int64_t ldc = N;
+    if (lin_) {
+        if (d->act < 0 || d->act > 2) return fail("act must be 0 (none), 1 (GELU) or 2 (sigmoid): got %d", d->act);
+        if (d->resid < 0 || d->resid > 2) return fail("resid must be 0 (none), 1 (a separate buffer) or 2 (in place): got %d", d->resid);
+        if (d->resid && !resid) return fail("resid = %d without a residual array", d->resid);
+        if (d->bias && !bias) return fail("bias is set without a bias array");
+        if (!d->want_c && !d->want_c3) return fail("want_c and want_c3 are both 0: the launch would store nothing");
+        if (d->resid == 2 && !d->want_c) return fail("resid = 2 (in place) needs want_c");
+        ldc = d->ldc;
+        if (ldc < N || ldc % 4 != 0 || ldc > 4 * 65536) return fail("ldc = %lld must be a multiple of 4, >= N = %d", (long long)ldc, N);
+        if (crow_map) {
+            if (d->rows_in < 1 || d->rows_out < d->rows_in || M % d->rows_in != 0)
+                return fail("crow_map needs 1 <= rows_in <= rows_out and M %% rows_in == 0 (rows_in = %d, rows_out = %d, M = %d)", d->rows_in, d->rows_out, M);
+            std::vector<char> seen(d->rows_out, 0);
+            for (int i = 0; i < d->rows_in; ++i) {
+                if (crow_map[i] < 0 || crow_map[i] >= d->rows_out || seen[crow_map[i]]) return fail("crow_map[%d] = %d is outside [0, rows_out = %d) or taken twice", i, crow_map[i], d->rows_out);
+                seen[crow_map[i]] = 1;
+            }
+            c_rows = (int64_t)(M / d->rows_in) * d->rows_out;
+        }
+    } else if (swi) {
+        if (!d->want_c && !d->want_c3) return fail("want_c and want_c3 are both 0: the launch would store nothing");
+        if (d->want_c && d->want_c3) return fail("swiglu writes C or the APB image, never both: want_c and want_c3 are both set");
+    }
+    int B = 0, Tq = 0;
+    if (qkv) {
+        if (Nw != 960 || N != 960) return fail("qkv-rope has 9 query and 3 kv heads of 64: Nw = N = 960 (got Nw = %d, N = %d)", Nw, N);
+        if (d->T < 1 || d->Tmax > 65536) return fail("T = %d, Tmax = %d: 1 <= T, Tmax <= 65536", d->T, d->Tmax);
+        if (d->Tmax < d->T) return fail("Tmax = %d is below T = %d", d->Tmax, d->T);
+        if (d->pos0 < 0 || d->pos0 >= d->T) return fail("pos0 = %d must lie in [0, T = %d)", d->pos0, d->T);
+        Tq = d->T - d->pos0;
+        if (M % Tq != 0) return fail("M = %d is not B * (T - pos0) = B * %d", M, Tq);
+        B = M / Tq;
+        if (B > 1024) return fail("M / (T - pos0) = %d examples exceed the tap's 1024", B);
+        if ((rope_cos == nullptr) != (rope_sin == nullptr)) return fail("rope_cos and rope_sin come together or not at all");
+    }
+    // capacities, before anything is launched
+    const size_t c_bytes = (size_t)(c_rows + 32) * ldc * 4;
+    const int parts = N / 64;
+    const size_t c3_bytes = (size_t)rup(M, 128) * N * 6, ssq_bytes = (size_t)(M + 32) * (parts > 0 ? parts : 1) * 4;
+    const size_t q_bytes = (size_t)(M + 32) * 576 * 4, kv_bytes = (size_t)(B + 1) * 3 * d->Tmax * 64 * 4;      // one page set of no example behind the last
+    const bool wc = !qkv && d->want_c, wc3 = !qkv && d->want_c3, wssq = lin_ && d->want_ssq;
+    if (wc && (!out_c || c_capacity < (int64_t)c_bytes)) return fail("c_capacity %lld is below the %lld bytes this call returns (or out_c is null)", (long long)c_capacity, (long long)c_bytes);
+    if (wc3 && (!out_c3 || c3_capacity < (int64_t)c3_bytes)) return fail("c3_capacity %lld is below the %lld bytes this call returns (or out_c3 is null)", (long long)c3_capacity, (long long)c3_bytes);
+    if (wssq && (!out_ssq || ssq_capacity < (int64_t)ssq_bytes)) return fail("ssq_capacity %lld is below the %lld bytes this call returns (or out_ssq is null)", (long long)ssq_capacity, (long long)ssq_bytes);
+    if (qkv && (!out_q || q_capacity < (int64_t)q_bytes)) return fail("q_capacity %lld is below the %lld bytes this call returns (or out_q is null)", (long long)q_capacity, (long long)q_bytes);
+    if (qkv && (!out_k || !out_v || kv_capacity < (int64_t)kv_bytes)) return fail("kv_capacity %lld is below the %lld bytes each page array takes (or out_k / out_v is null)", (long long)kv_capacity, (long long)kv_bytes);
+
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    const int Nrows = swi ? Nw / 2 : Nw;                 // rows of one logical weight matrix
+    const int Nwp = swi ? 64 * ((Nrows + 31) / 32) : Nw;      // packed rows: pairs come in 64-row groups of 32 gate + 32 up
+    const int NP = rup(Nwp, 128);
+    mellow_engine::Buf bA, bW, bWp, bPB, bA3, bBias, bRes, bMap, bRs, bC, bC3, bSsq, bQ, bKc, bVc, bCos, bSin;
+    CHK(gemm_tap_buf(e, bA, (size_t)M * K * 4, A));
+    CHK(gemm_tap_buf(e, bW, (size_t)Nw * K * 4, W));
+    CHK(ensure(e, bWp, (size_t)NP * K));
+    if (swi) launch_pack_weight_pairs(bW.p, bW.p + (size_t)Nrows * K, Nrows, K, K, bWp.p, NP, K, s);
+    else launch_pack_weight(bW.p, Nw, K, K, bWp.p, NP, K, s);
+    GemmArgs g;
+    g.A = bA.p; g.lda = K; g.M = M; g.K = K; g.Wp = bWp.p; g.Nw = Nwp; g.N = N; g.ldc = ldc;
+    g.epi = lin_ ? EPI_LINEAR : swi ? EPI_SWIGLU : d->pos0 > 0 ? EPI_QKV_ROPE_AT : EPI_QKV_ROPE;
+    if (kernel != 0) {
+        CHK(ensure(e, bPB, (size_t)NP * K * 6 / 4));
+        launch_pack_bf16x3(bWp.p, NP, K, bPB.p, s);
+        g.W8 = reinterpret_cast<const uint8_t*>(bPB.p);
+    }
+    if (kernel == 17) {
+        CHK(ensure(e, bA3, (size_t)rup(M, 128) * K * 6 / 4));
+        g.A8 = reinterpret_cast<const uint8_t*>(bA3.p); g.lda8 = (int64_t)3 * (K >> 3);
+    }
+    if (has_rs) {
+        CHK(gemm_tap_buf(e, bRs, (size_t)M * d->rs_parts * 4, rs_ssq));
+        g.rs_ssq = bRs.p; g.rs_parts = d->rs_parts; g.rs_dim = d->rs_dim; g.rs_eps = d->rs_eps;
+    }
+    if (wc) { CHK(gemm_tap_buf(e, bC, c_bytes, nullptr)); g.C = bC.p; }
+    if (wc3) { CHK(gemm_tap_buf(e, bC3, c3_bytes, nullptr)); g.C3 = bC3.p; }
+    if (wssq) { CHK(gemm_tap_buf(e, bSsq, ssq_bytes, nullptr)); g.ssq_out = bSsq.p; g.ssq_parts = parts; }
+    if (lin_) {
+        g.act = d->act;
+        if (d->bias) {           // the launchers read whole float4 of columns < N: the columns past Nw hold zeros, as the engine's padded biases do
+            std::vector<float> hb(rup(N, 128), 0.f);
+            memcpy(hb.data(), bias, (size_t)Nw * 4);
+            CHK(gemm_tap_buf(e, bBias, hb.size() * 4, hb.data()));
+            g.bias = bBias.p;
+        }
+        if (crow_map) {
+            CHK(gemm_tap_buf(e, bMap, (size_t)d->rows_in * 4, crow_map));
+            g.crow_map = reinterpret_cast<const int32_t*>(bMap.p); g.rows_in = d->rows_in; g.rows_out = d->rows_out;
+        }
+        if (d->resid == 1) {                                // resid host [c_rows][N]
+            CHK(gemm_tap_buf(e, bRes, (size_t)c_rows * N * 4, resid));
+            g.resid = bRes.p; g.ldr = N;
+        } else if (d->resid == 2) {                         // in place: the residual is loaded into C after the fill
+            HIPCHK(hipStreamSynchronize(s));
+            HIPCHK(hipMemcpy2D(bC.p, (size_t)ldc * 4, resid, (size_t)N * 4, (size_t)N * 4, (size_t)c_rows, hipMemcpyHostToDevice));
+            g.resid = bC.p; g.ldr = ldc;
+        }
+    }
+    if (qkv) {
+        CHK(gemm_tap_buf(e, bQ, q_bytes, nullptr));
+        CHK(gemm_tap_buf(e, bKc, kv_bytes, nullptr));
+        CHK(gemm_tap_buf(e, bVc, kv_bytes, nullptr));
+        std::vector<float> hc, hs;
+        if (!rope_cos) {
+            hc.resize((size_t)d->Tmax * 32); hs.resize((size_t)d->Tmax * 32);
+            CHK(mellow_host_rope_tables(e->cfg.rope_theta, 64, d->Tmax, hc.data(), hs.data()));
+        }
+        CHK(gemm_tap_buf(e, bCos, (size_t)d->Tmax * 32 * 4, rope_cos ? rope_cos : hc.data()));
+        CHK(gemm_tap_buf(e, bSin, (size_t)d->Tmax * 32 * 4, rope_sin ? rope_sin : hs.data()));
+        g.q_out = bQ.p; g.k_cache = bKc.p; g.v_cache = bVc.p; g.rope_cos = bCos.p; g.rope_sin = bSin.p;
+        g.T = Tq; g.Tmax = d->Tmax; g.pos0 = d->pos0; g.q_heads = 9; g.kv_heads = 3;
+    }
+    if (d->splitk_max) {         // the engine's own workspace, as with_splitk hands it to the encoder chain
+        CHK(ensure(e, e->sk_ws, (size_t)512 * 16384));
+        g.sk_ws = e->sk_ws.p; g.sk_tiles = 256; g.sk_max = d->splitk_max;
+    }
+    g.no_x3w = d->no_x3w != 0;
+    if (kernel == 0) launch_gemm(g, s);
+    else if (kernel == 16) launch_gemm_bf16x3_fused(g, s);
+    else { launch_split_rows_apb(bA.p, K, M, K, bA3.p, s); launch_gemm_bf16x3_apb(g, s); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    if (wc) CHK(gemm_tap_fetch(out_c, c_capacity, bC, c_bytes, "c"));
+    if (wc3) CHK(gemm_tap_fetch(out_c3, c3_capacity, bC3, c3_bytes, "c3"));
+    if (wssq) CHK(gemm_tap_fetch(out_ssq, ssq_capacity, bSsq, ssq_bytes, "ssq"));
+    if (qkv) {
+        CHK(gemm_tap_fetch(out_q, q_capacity, bQ, q_bytes, "q"));
+        CHK(gemm_tap_fetch(out_k, kv_capacity, bKc, kv_bytes, "kv"));
+        CHK(gemm_tap_fetch(out_v, kv_capacity, bVc, kv_bytes, "kv"));
+    }
+    return 0;
+}
+
 // developer instrumentation (not part of the public header): one CSV line per profiled launch
 __attribute__((visibility("default"))) int mellow_dev_prof_dump(mellow_engine_t* e, const char* path) {
     if (!e || !path) return fail("bad argument");

@@ -40,6 +40,14 @@ class LogitRules(C.Structure):
                 ("min_new_tokens", C.c_int32), ("logit_bias", C.c_void_p)]
 
 
+class GemmEpi(C.Structure):
+    """mellow_gemm_epi_t (include/mellow_hip.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("size", "kernel", "epi", "M", "K", "Nw", "N", "act", "bias", "resid", "rows_in", "rows_out", "ldc",
+                                         "want_c", "want_c3", "want_ssq", "rs_parts")] + \
+               [("rs_dim", C.c_float), ("rs_eps", C.c_float)] + \
+               [(n, C.c_int32) for n in ("splitk_max", "no_x3w", "T", "Tmax", "pos0")]
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -50,7 +58,8 @@ _ADDED_UNDER_MINOR_4 = ("mellow_lm_score", "mellow_score", "mellow_generate_scor
                         "mellow_generate_q", "mellow_generate_beam", "mellow_beam_select")
 # symbols of minor 5 (the attention taps on host data): looked up the same way, so that a minor-4 library still loads
 _ADDED_UNDER_MINOR_5 = ("mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_generate_rules", "mellow_logit_rules_apply",
-                        "mellow_generate_guidance", "mellow_guidance_apply", "mellow_generate_top_logprobs", "mellow_top_logprobs_apply")
+                        "mellow_generate_guidance", "mellow_guidance_apply", "mellow_generate_top_logprobs", "mellow_top_logprobs_apply",
+                        "mellow_debug_gemm_epi")
 
 
 def load_library(path: Optional[str] = None):
@@ -110,6 +119,7 @@ def load_library(path: Optional[str] = None):
         "mellow_debug_tap": (ci, [vp, C.c_char_p, vp, i64, P(i64)]),
         "mellow_debug_gemm_fp8": (ci, [vp, vp, ci, ci, vp, ci, vp, ci, vp]),
         "mellow_debug_gemm_f32": (ci, [vp, ci, vp, ci, ci, vp, ci, vp, ci, vp]),
+        "mellow_debug_gemm_epi": (ci, [vp, P(GemmEpi), vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64]),
         "mellow_debug_prefill_attn": (ci, [vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp, i64]),
         "mellow_debug_window_attn": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, i64]),
         "mellow_debug_dec_head": (ci, [vp, vp, ci, ci, vp]),
@@ -154,7 +164,7 @@ EXPORTED_SYMBOLS = (
     "mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse", "mellow_generate_n", "mellow_generate_q",
     "mellow_generate_beam", "mellow_beam_select", "mellow_generate_rules", "mellow_logit_rules_apply", "mellow_generate_guidance", "mellow_guidance_apply", "mellow_generate_top_logprobs", "mellow_top_logprobs_apply", "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
     "mellow_prof_num_families", "mellow_prof_family_name", "mellow_prof_get", "mellow_last_phase_ms", "mellow_last_steps_enqueued", "mellow_last_row_repacks", "mellow_stft_is_fft", "mellow_prefill_parts", "mellow_abi_minor",
-    "mellow_resample", "mellow_engine_set_precision", "mellow_engine_set_option", "mellow_engine_describe", "mellow_debug_gemm_fp8", "mellow_debug_gemm_f32", "mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_debug_dec_head", "mellow_set_graph", "mellow_host_window_map", "mellow_host_pack_weight", "mellow_host_rope_tables",
+    "mellow_resample", "mellow_engine_set_precision", "mellow_engine_set_option", "mellow_engine_describe", "mellow_debug_gemm_fp8", "mellow_debug_gemm_f32", "mellow_debug_gemm_epi", "mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_debug_dec_head", "mellow_set_graph", "mellow_host_window_map", "mellow_host_pack_weight", "mellow_host_rope_tables",
 )
 
 
@@ -1062,6 +1072,61 @@ class Engine:
         self._chk(self.lib.mellow_debug_gemm_fp8(self.h, C.c_void_p(A.data_ptr()), M, K, C.c_void_p(W.data_ptr()), N,
                                                  C.c_void_p(out.data_ptr()), int(iters), ms if iters > 0 else None))
         return out, ((ms[0], ms[1]) if iters > 0 else None)
+
+    def debug_gemm_epi(self, A, W, kernel: int = 0, epi: str = "linear", N: Optional[int] = None, act: str = "none", bias=None,
+                       resid=None, in_place: bool = False, crow_map=None, rows_out: int = 0, ldc: Optional[int] = None,
+                       want_c: bool = True, want_c3: bool = False, want_ssq: bool = False, rs_ssq=None, rs_dim: float = 1.0,
+                       rs_eps: float = 0.0, splitk_max: int = 0, no_x3w: bool = False, T: int = 1, Tmax: int = 1, pos0: int = 0,
+                       rope=None) -> dict:
+        """One GEMM launch with the epilogue described (mellow_debug_gemm_epi): A [M][K], W [Nw][K] logical rows (swiglu: gate rows then
+        up rows), host tensors.  epi "linear" | "swiglu" | "qkv_rope"; N stored columns (default: Nw rounded up to 4, Nw / 2 for
+        swiglu); resid [C rows][N] with in_place choosing resid == C; crow_map int32 [rows_in] with rows_out; rope = (cos, sin)
+        [Tmax][32] or None for the engine's own tables.  -> dict of the whole device outputs, which held 0xFF bytes before the launch:
+        "c" f32 [C rows + 32][ldc], "c3" the raw APB image as int32 words, "ssq" f32 [M + 32][N / 64], "q" f32 [M + 32][576],
+        "k" / "v" f32 [B + 1][3][Tmax][64]."""
+        self._need("mellow_debug_gemm_epi")
+        f32 = lambda x: None if x is None else torch.as_tensor(x).detach().cpu().contiguous().float()       # noqa: E731
+        A, W, bias, resid, rs_ssq = f32(A), f32(W), f32(bias), f32(resid), f32(rs_ssq)
+        (M, K), Nw = A.shape, int(W.shape[0])
+        assert W.shape[1] == K
+        e = {"linear": 0, "swiglu": 1, "qkv_rope": 2}[epi]
+        if N is None:
+            N = Nw // 2 if e == 1 else (Nw + 3) // 4 * 4
+        d = GemmEpi()
+        d.size, d.kernel, d.epi, d.M, d.K, d.Nw, d.N = C.sizeof(GemmEpi), int(kernel), e, M, K, Nw, int(N)
+        d.act, d.bias = {"none": 0, "gelu": 1, "sigmoid": 2}[act], 0 if bias is None else 1
+        d.resid = 0 if resid is None else (2 if in_place else 1)
+        cmap = None
+        c_rows = M
+        if crow_map is not None:
+            cmap = torch.as_tensor(crow_map).detach().cpu().contiguous().to(torch.int32)
+            d.rows_in, d.rows_out = int(cmap.numel()), int(rows_out)
+            c_rows = M // max(1, d.rows_in) * d.rows_out
+        d.ldc = int(N if ldc is None else ldc)
+        d.want_c, d.want_c3, d.want_ssq = int(bool(want_c)), int(bool(want_c3)), int(bool(want_ssq))
+        if rs_ssq is not None:
+            d.rs_parts, d.rs_dim, d.rs_eps = int(rs_ssq.shape[1]), float(rs_dim), float(rs_eps)
+        d.splitk_max, d.no_x3w, d.T, d.Tmax, d.pos0 = int(splitk_max), int(bool(no_x3w)), int(T), int(Tmax), int(pos0)
+        cos, sin = (None, None) if rope is None else (f32(rope[0]), f32(rope[1]))
+        out = {}
+        if e == 2:
+            B = M // max(1, d.T - d.pos0)
+            out["q"] = torch.empty((M + 32, 576), dtype=torch.float32)
+            out["k"] = torch.empty((B + 1, 3, max(1, d.Tmax), 64), dtype=torch.float32)
+            out["v"] = torch.empty_like(out["k"])
+        else:
+            if want_c:
+                out["c"] = torch.empty((c_rows + 32, max(1, d.ldc)), dtype=torch.float32)
+            if want_c3:
+                out["c3"] = torch.empty(((M + 127) // 128 * 128 * d.N * 6 // 4,), dtype=torch.int32)
+            if want_ssq:
+                out["ssq"] = torch.empty((M + 32, max(1, d.N // 64)), dtype=torch.float32)
+        p = lambda x: None if x is None else _ptr(x)      # noqa: E731
+        nb = lambda k: 0 if k not in out else out[k].numel() * 4      # noqa: E731
+        self._chk(self.lib.mellow_debug_gemm_epi(self.h, C.byref(d), p(A), p(W), p(bias), p(resid), p(cmap), p(rs_ssq), p(cos), p(sin),
+                                                 p(out.get("c")), nb("c"), p(out.get("c3")), nb("c3"), p(out.get("ssq")), nb("ssq"),
+                                                 p(out.get("q")), nb("q"), p(out.get("k")), p(out.get("v")), nb("k")))
+        return out
 
     @staticmethod
     def _attn_tap_out(M: int, width: int, out_form: int) -> torch.Tensor:

@@ -53,6 +53,29 @@ def test_attention_taps_are_declared_bound_and_came_with_minor_5(lib):
             call()
 
 
+def test_gemm_epilogue_tap_is_declared_bound_and_refuses_without_a_device(lib):
+    hdr = open(os.path.join(ROOT, "include", "mellow_hip.h")).read()
+    name = "mellow_debug_gemm_epi"
+    assert re.search(r"\bint\s+%s\s*\(" % name, hdr) and re.search(r"\}\s*mellow_gemm_epi_t;", hdr)
+    assert name in E.EXPORTED_SYMBOLS and name in E._ADDED_UNDER_MINOR_5
+    fn = getattr(lib, name)
+    assert fn.restype is ctypes.c_int and len(fn.argtypes) == 21
+    # the descriptor of the binding is the header's: one 4-byte field per declared member, in the header's order
+    body = re.search(r"typedef struct mellow_gemm_epi \{(.*?)\} mellow_gemm_epi_t;", hdr, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    members = [(t, n.strip()) for t, names in re.findall(r"\b(int32_t|float)\s+([^;]+);", body) for n in names.split(",")]
+    assert [n for _, n in members] == [n for n, _ in E.GemmEpi._fields_]
+    assert all((ct is ctypes.c_float) == (t == "float") for (t, _), (_, ct) in zip(members, E.GemmEpi._fields_))
+    assert ctypes.sizeof(E.GemmEpi) == 4 * len(members)
+    # host code only: a null engine is refused before any device is touched
+    assert fn(*[None if (t is ctypes.c_void_p or hasattr(t, "contents")) else t(1) for t in fn.argtypes]) != 0
+    assert "null argument" in lib.mellow_last_error().decode()
+    e = object.__new__(E.Engine)
+    e.lib, e.h = type("OldLib", (), {})(), None
+    with pytest.raises(E.EngineError, match="predates mellow_debug_gemm_epi"):
+        e.debug_gemm_epi(None, None)
+
+
 def test_required_keys_are_the_reference_state_dict_keys(lib):
     from mellow_amd import spec
     layout = spec.state_dict_layout()
