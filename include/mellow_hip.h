@@ -57,7 +57,8 @@ extern "C" {
  *     mellow_beam_select (beam search inside the decode step), and then mellow_generate_rules with its tap mellow_logit_rules_apply
  *     (repetition controls: logit rules inside the decode step), and then mellow_generate_guidance with its tap mellow_guidance_apply
  *     (contrastive guidance inside the decode step), and then mellow_generate_top_logprobs with its tap mellow_top_logprobs_apply
- *     (the k likeliest tokens of every step) -- added while the minor was 5, detected by symbol lookup all the same.
+ *     (the k likeliest tokens of every step), and then mellow_generate_filters with its tap mellow_sample_logits_filtered (top_k and
+ *     min_p inside the sampler) -- added while the minor was 5, detected by symbol lookup all the same.
  *  5: the attention taps on host data, mellow_debug_prefill_attn and mellow_debug_window_attn.  No existing symbol or struct
  *     changed; a binding that must also load a minor-4 library detects them by symbol lookup.  The GEMM epilogue tap
  *     mellow_debug_gemm_epi was added later under this same minor, detected by symbol lookup all the same. */
@@ -429,6 +430,47 @@ int  mellow_top_logprobs_apply(mellow_engine_t* e, const float* logits, const fl
  * of each row; NULL = 0..B-1), step = t above -> tokens dev i32 [B]. */
 int  mellow_sample_logits(mellow_engine_t* e, const float* logits, int B, const int32_t* row_ids, int step, float top_p,
                           float temperature, uint64_t seed, int32_t* tokens);
+/* Candidate filters of the sampled draw: top_k and min_p next to the nucleus, inside the sampler's launch of the captured step.
+ *
+ * Definition.  Steps 1 - 4 of mellow_generate_sampled become the following; the order is Hugging Face's (temperature, top_k, top_p,
+ * min_p).
+ * 1. z_i = l_i / temperature, exactly as there.  A row with a NaN yields its first NaN index, as there.
+ * 2. top_k = K (K >= 0; 0 is off; K >= 49152 keeps every token).  T is the first K tokens in the order (z descending, index
+ *    ascending).  The set has exactly K members: a tie group on the K-th value is cut by index (Hugging Face would keep the whole
+ *    group; this is the order the nucleus tie-cut and the top log-probs use).  The selection moves fp32 values only, so it is exact.
+ * 3. The nucleus inside T.  q_i = rn(exp(z_i - m) * 2^31), m the row maximum, as there; S_T = sum of q_i over T, an integer sum.
+ *    Token i of T is kept iff the integer mass of the tokens of T strictly before it in the order is
+ *    <= (u64)((double)top_p * (double)S_T).  With K = 0 this is the rule of mellow_generate_sampled, bit for bit.
+ * 4. min_p (in [0, 1]; 0 is off).  Token i is kept iff q_i >= qmin, qmin = rn(min_p * 2^31) (an exact power-of-two scaling, rounded
+ *    once).  The arg-max has q = 2^31 >= qmin, so it is always kept; min_p = 1 keeps exactly the tokens tied at the maximum.
+ *    p_i / p_max does not change under renormalisation, so this is Hugging Face's "p_i >= min_p * p_max after the earlier filters",
+ *    whatever those kept.
+ * 5. The kept set is the intersection of 2 - 4.  It is always a prefix of the order -- whole tie groups, except where an index cut
+ *    ends it -- so one (boundary key, index cut) pair and the q test describe it.  The Gumbel-max draw, the Philox keying (seed,
+ *    global row, step) and the loop bookkeeping are exactly those of mellow_generate_sampled.
+ * Recorded log-probs (out_logprob, top log-probs) stay the model's log-softmax at temperature 1 without any filter.
+ *
+ * mellow_generate_filters arms the filters for the NEXT mellow_generate* call on this context; that call takes them at entry and
+ * clears them whatever its outcome.  A fork has its own, initially none.  NULL disarms, and so does top_k = 0 with min_p = 0 (nothing
+ * is armed).  Honoured by mellow_generate_sampled and by mellow_generate_scored / _n / _q with do_sample != 0, with and without armed
+ * rules, guidance and top log-probs, in every precision; a call of more than 1024 rows applies them in every pass.  A greedy call
+ * (mellow_generate, do_sample == 0) and mellow_generate_beam fail with a message and disarm.  The armed call runs the sampler's
+ * filtered instantiation, which is part of the captured step's key; K and qmin travel in the sampler's parameter block, so one
+ * capture serves every value.  A call without the arming launches exactly what it launched before these symbols existed.
+ * Errors, host code first, before any device is touched: a `size` other than sizeof(mellow_sample_filters_t), top_k < 0, min_p NaN
+ * or outside [0, 1]; then a null or unfinalized engine; then a vocabulary other than 49152.
+ * Added while the minor was 5 without raising it: a binding detects the two symbols by lookup. */
+typedef struct mellow_sample_filters {
+    int32_t size;                 /* sizeof(mellow_sample_filters_t) */
+    int32_t top_k;                /* K >= 0; 0 = off */
+    float   min_p;                /* in [0, 1]; 0 = off */
+} mellow_sample_filters_t;
+int  mellow_generate_filters(mellow_engine_t* e, const mellow_sample_filters_t* f);
+/* The filtered draw on caller logits, no loop state (numeric tap): the arguments of mellow_sample_logits plus the filters (not NULL).
+ * Always the filtered instantiation, also for neutral values (whose tokens are then bit-equal to mellow_sample_logits').  Leaves
+ * whatever is armed as it is.  Errors as above, then those of mellow_sample_logits. */
+int  mellow_sample_logits_filtered(mellow_engine_t* e, const float* logits, int B, const int32_t* row_ids, int step, float top_p,
+                                   float temperature, uint64_t seed, const mellow_sample_filters_t* f, int32_t* tokens);
 
 /* ---- parity taps (same kernels as mellow_generate, stage by stage) ------------------------------- */
 /* A1-A3: htsat.py:864-870.  wav dev [n][n_samples] -> out dev [n][frames][64]; apply_bn=0 gives the

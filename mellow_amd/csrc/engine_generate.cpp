@@ -26,6 +26,7 @@ struct GenRequest {
     LogitRules rules;                            // repetition controls (mellow_generate_rules): taken from the context at entry, the same for every pass
     Guidance guide;                              // contrastive guidance (mellow_generate_guidance): likewise; rows 2p and 2p + 1 are then pair p
     TopLogprobs top;                             // top log-probs (mellow_generate_top_logprobs): likewise; the record [rows][max_len][k] advances with the passes
+    SampleFilters filters;                       // top_k / min_p (mellow_generate_filters): likewise, the same for every pass
     int rows() const { return examples * n * q; }
     // rows [r0, r0 + nb) of an n = 1, q = 1 request as a request of their own; a row's random stream follows its index in the whole call
     GenRequest pass(int r0, int nb, int text_len, int32_t* steps, float* ftm) const {
@@ -52,10 +53,23 @@ static int check_sampling(mellow_engine_t* e, float top_p, float temperature) {
     return 0;
 }
 
-static void stage_sampling(mellow_engine_t* e, float top_p, float temperature, uint64_t seed, int32_t row_offset, int step) {
+// The value rules of a mellow_sample_filters_t, each once (mellow_generate_filters and mellow_sample_logits_filtered): host code
+// only, no engine and no device needed.
+static int check_filters(const mellow_sample_filters_t* f) {
+    if (f->size != (int32_t)sizeof(mellow_sample_filters_t))
+        return fail("mellow_sample_filters_t.size is %d, this library's struct has %d bytes", (int)f->size, (int)sizeof(mellow_sample_filters_t));
+    if (f->top_k < 0) return fail("top_k must be >= 0 (got %d); 0 is off", (int)f->top_k);
+    if (!(f->min_p >= 0.f && f->min_p <= 1.f)) return fail("min_p must be in [0, 1] (got %g); 0 is off", (double)f->min_p);
+    return 0;
+}
+
+static void stage_sampling(mellow_engine_t* e, float top_p, float temperature, uint64_t seed, int32_t row_offset, int step,
+                           const SampleFilters& f = SampleFilters()) {
     uint32_t* w = e->h_sparams;
     w[SMP_SEED_LO] = (uint32_t)seed; w[SMP_SEED_HI] = (uint32_t)(seed >> 32); w[SMP_ROW_OFF] = (uint32_t)row_offset;
     memcpy(&w[SMP_TOP_P], &top_p, 4); memcpy(&w[SMP_TEMP], &temperature, 4); w[SMP_STEP] = (uint32_t)step;
+    w[SMP_TOP_K] = (uint32_t)f.top_k;
+    w[SMP_QMIN] = (uint32_t)std::nearbyint((double)f.min_p * 2147483648.0);      // rn(min_p * 2^31): the product is exact, ties to even as the kernel's q
 }
 
 // The value rules of a mellow_logit_rules_t, each once (mellow_generate_rules and mellow_logit_rules_apply): host code only, no
@@ -111,6 +125,10 @@ static int check_request(mellow_engine_t* e, const GenRequest& r, int door) {
     if (r.top.k) {         // (likewise)
         if (r.beam) return fail("top log-probs are armed (mellow_generate_top_logprobs): mellow_generate_beam does not take them (top log-probs of a beam hypothesis are not built)");
         if (!r.out_logprob) return fail("top log-probs are armed (mellow_generate_top_logprobs): this call records no log-probs (use mellow_generate_scored, or mellow_generate_n / mellow_generate_q with an out_logprob)");
+    }
+    if (r.filters.on) {    // (likewise)
+        if (r.beam) return fail("sample filters are armed (mellow_generate_filters): mellow_generate_beam does not take them (top_k / min_p filter a sampled draw)");
+        if (!r.on) return fail("sample filters are armed (mellow_generate_filters): this call does not sample (use mellow_generate_sampled, or do_sample != 0)");
     }
     if (r.n < 1) return fail("n must be >= 1 (got %d)", r.n);
     if (r.q < 1) return fail("Q must be >= 1 (got %d)", r.q);
@@ -328,6 +346,7 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
     m.rules = r.rules.on;               // dec_logit_rules_kernel edits the stored rows: the head stores them (apply_step_mode)
     m.guide = r.guide.on;               // dec_guidance_kernel combines the stored rows of a pair: the head stores them (apply_step_mode)
     m.top = r.top.k;                    // dec_top_logprobs_kernel reads the stored rows: the head stores them (apply_step_mode)
+    m.filtered = r.filters.on;          // dec_sample_kernel in its filtered instantiation; the values travel in d_sparams
     m.early_exit = !r.beam && (dev_dead || (!r.ignore_stop && e->da.RB > 1));
     // a guided call runs without migration (a pair's rows stay neighbours in slots 2p, 2p + 1); block exit stays: both rows of a
     // pair get the same token, so they finish at the same step, and a pair never straddles a 32-row block
@@ -355,7 +374,7 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
     struct ModeScope { mellow_engine* e; ~ModeScope() { apply_step_mode(e, StepMode()); } } mode_scope{e};
     apply_step_mode(e, m);
     if (r.on) {
-        stage_sampling(e, r.top_p, r.temperature, r.seed, r.row_offset, 0);
+        stage_sampling(e, r.top_p, r.temperature, r.seed, r.row_offset, 0, r.filters);
         HIPCHK(hipMemcpyAsync(e->d_sparams, e->h_sparams, sizeof(e->h_sparams), hipMemcpyHostToDevice, s));
     }
     if (r.rules.on) CHK(stage_rules(e, r.rules, stop_id));
@@ -479,13 +498,14 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
     return 0;
 }
 
-// What mellow_generate_rules / _guidance / _top_logprobs armed on the context serves ONE mellow_generate* call, whatever its outcome:
+// What mellow_generate_rules / _guidance / _top_logprobs / _filters armed on the context serves ONE mellow_generate* call, whatever its outcome:
 // taken into that call's request, cleared on the context
 static void take_armed(mellow_engine_t* e, GenRequest& r) {
     if (!e) return;
     r.rules = e->rules_armed; e->rules_armed = LogitRules();
     r.guide = e->guide_armed; e->guide_armed = Guidance();
     r.top = e->top_armed; e->top_armed = TopLogprobs();
+    r.filters = e->filters_armed; e->filters_armed = SampleFilters();
 }
 
 // The reference's loop (wrapper.py:216-249) takes any number of examples.  One pass of the engine takes up to 1024 rows (32 row
@@ -655,6 +675,16 @@ int mellow_generate_top_logprobs(mellow_engine_t* e, int k, int32_t* out_ids, fl
     return 0;
 }
 
+int mellow_generate_filters(mellow_engine_t* e, const mellow_sample_filters_t* f) {
+    if (f) CHK(check_filters(f));
+    if (!e || !e->finalized) return fail("engine not finalized");
+    e->filters_armed = SampleFilters();
+    if (!f || (f->top_k == 0 && f->min_p == 0.f)) return 0;        // neutral values: nothing to arm
+    if (e->cfg.vocab_size != SAMPLE_MAX_V) return fail("the sampler is built for a vocabulary of %d (engine: %d)", SAMPLE_MAX_V, e->cfg.vocab_size);
+    e->filters_armed.on = true; e->filters_armed.top_k = f->top_k; e->filters_armed.min_p = f->min_p;
+    return 0;
+}
+
 int mellow_top_logprobs_apply(mellow_engine_t* e, const float* logits, const float* cand_val, const float* cand_sum, int B, int k,
                               int32_t* out_ids, float* out_lp) {
     if (k < 0 || k > TOP_LOGPROBS_MAX_K) return fail("top log-probs: k must be 1 to %d (got %d)", TOP_LOGPROBS_MAX_K, k);
@@ -720,6 +750,26 @@ int mellow_sample_logits(mellow_engine_t* e, const float* logits, int B, const i
     HIPCHK(hipMemcpyAsync(e->d_sparams, e->h_sparams, sizeof(e->h_sparams), hipMemcpyHostToDevice, e->stream));
     SampleArgs sa;
     sa.logits = logits; sa.ld = e->cfg.vocab_size; sa.prm = e->d_sparams; sa.row_ids = row_ids;
+    launch_sample_logits(sa, B, tokens, e->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+// the tap of the filtered instantiation: always that instantiation, also for neutral values; what is armed on the context stays
+int mellow_sample_logits_filtered(mellow_engine_t* e, const float* logits, int B, const int32_t* row_ids, int step, float top_p,
+                                  float temperature, uint64_t seed, const mellow_sample_filters_t* f, int32_t* tokens) {
+    if (f) CHK(check_filters(f));
+    if (!e || !e->finalized) return fail("engine not finalized");
+    if (!f || !logits || !tokens || B <= 0) return fail("bad argument");
+    CHK(check_sampling(e, top_p, temperature));
+    HIPCHK(hipSetDevice(e->device));
+    SampleFilters sf;
+    sf.on = true; sf.top_k = f->top_k; sf.min_p = f->min_p;
+    stage_sampling(e, top_p, temperature, seed, 0, step, sf);
+    HIPCHK(hipMemcpyAsync(e->d_sparams, e->h_sparams, sizeof(e->h_sparams), hipMemcpyHostToDevice, e->stream));
+    SampleArgs sa;
+    sa.logits = logits; sa.ld = e->cfg.vocab_size; sa.prm = e->d_sparams; sa.row_ids = row_ids; sa.filtered = true;
     launch_sample_logits(sa, B, tokens, e->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(e->stream));

@@ -139,6 +139,7 @@ struct StepMode {
     int beam = 0;                // k >= 1: beam search -- the select (beam.hip) in place of the arg-max, and for k > 1 the two K/V reorder launches after it
     bool rules = false;          // repetition controls: dec_logit_rules_kernel between the head and the picker (forces `logits` on)
     bool guide = false;          // contrastive guidance: dec_guidance_kernel after the head, before the rules launch (forces `logits` on; rows 2p, 2p + 1 are a pair)
+    bool filtered = false;       // top_k / min_p: dec_sample_kernel in its filtered instantiation (needs `sample`)
     int top = 0;                 // k >= 1: dec_top_logprobs_kernel after the rules launch, before the picker (forces `logits` on; needs `logprob`)
 };
 // The top log-probs record of one generation call (include/mellow_hip.h, mellow_generate_top_logprobs): armed on the context, taken
@@ -147,6 +148,13 @@ struct TopLogprobs {
     int k = 0;
     int32_t* ids = nullptr;
     float* lp = nullptr;
+};
+// The candidate filters of one sampled generation call (include/mellow_hip.h, mellow_generate_filters): armed on the context, taken
+// into the call's GenRequest at entry.
+struct SampleFilters {
+    bool on = false;
+    int top_k = 0;
+    float min_p = 0.f;
 };
 // The guidance of one generation call (include/mellow_hip.h, mellow_generate_guidance): armed on the context, taken into the call's
 // GenRequest at entry.
@@ -235,7 +243,7 @@ struct mellow_engine {
     // d_params, the sampling parameters in d_sparams).  generate_pass (engine_generate.cpp) captures, ensure_lm invalidates.
     struct LOCAL StepGraphs {
         struct Key {
-            std::array<uintptr_t, 21> v{};       // all zero: no capture (a pass has at least one row)
+            std::array<uintptr_t, 22> v{};       // all zero: no capture (a pass has at least one row)
             static Key of(const mellow_engine* e, int B);      // from the engine as configured for the pass (below the engine)
             bool operator==(const Key& k) const { return v == k.v; }
         };
@@ -299,6 +307,7 @@ struct mellow_engine {
     uint32_t h_rparams[RUL_WORDS] = {0};       // ... its staging
     uint32_t* d_gparams = nullptr;             // guidance parameter block (kernels.h GDN_*): graph replays serve any scale
     uint32_t h_gparams[GDN_WORDS] = {0};       // ... its staging
+    SampleFilters filters_armed;               // mellow_generate_filters: what the NEXT mellow_generate* call on this context takes (and clears)
     TopLogprobs top_armed;                     // mellow_generate_top_logprobs: what the NEXT mellow_generate* call on this context takes (and clears)
     Guidance guide_armed;                      // mellow_generate_guidance: what the NEXT mellow_generate* call on this context takes (and clears)
     LogitRules rules_armed;                    // mellow_generate_rules: what the NEXT mellow_generate* call on this context takes (and clears)
@@ -375,7 +384,8 @@ inline mellow_engine::StepGraphs::Key mellow_engine::StepGraphs::Key::of(const m
                 (uintptr_t)e->mode.guide,          // contrastive guidance: dec_guidance_kernel in the step; the head with its logits store; the sampler's stream by pair
                 (uintptr_t)e->mode.top,            // top log-probs: dec_top_logprobs_kernel in the step and its k (a launch argument); the head with its logits store
                 (uintptr_t)(e->mode.top ? e->top_ids.p : nullptr),           // ... its record: TopArgs
-                (uintptr_t)(e->mode.top ? e->top_lp.p : nullptr)}};
+                (uintptr_t)(e->mode.top ? e->top_lp.p : nullptr),
+                (uintptr_t)e->mode.filtered}};     // top_k / min_p: dec_sample_kernel's filtered instantiation (the values are in the SMP_* block)
 }
 static_assert(!std::is_copy_constructible<mellow_engine::Buf>::value, "a Buf owns its device memory: it moves, it is never copied");
 static_assert(std::is_copy_assignable<mellow_engine::Weights>::value && std::is_copy_assignable<mellow_engine::Options>::value, "a fork copies these by assignment: no owning member (Buf, StepGraphs) belongs in them");

@@ -210,6 +210,7 @@ int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec)
           SampleArgs sa;
           sa.logits = e->da.logits; sa.ld = e->cfg.vocab_size; sa.prm = e->d_sparams;
           sa.row_shift = e->mode.guide ? 1 : 0;        // a guided pair draws from the stream of its pair index
+          sa.filtered = e->mode.filtered;
           launch_dec_sample(sa, dh(2), B, e->d_tokens, e->w.embed, (rec && rec->embed_next) ? 1 : 0, rec ? loop_args(e) : LoopArgs(),
                             e->stream);
       } else {

@@ -279,14 +279,16 @@ void launch_dec_argmax(const DecArgs& a, int B, int n_tiles, int32_t* tokens, co
 void launch_dec_lse_tap(const DecArgs& a, int B, int n_tiles, float* out_lse, float* out_max, hipStream_t s);
 // Seeded nucleus sampling (sample.hip; include/mellow_hip.h mellow_generate_sampled states the exact definition).  The
 // parameters live in a device block the host fills per call, so captured graphs serve any seed / top_p / temperature:
-// prm = {lo32(seed), hi32(seed), row offset, bits of top_p, bits of temperature, step (taps only)}.
-enum { SMP_SEED_LO = 0, SMP_SEED_HI, SMP_ROW_OFF, SMP_TOP_P, SMP_TEMP, SMP_STEP, SMP_WORDS = 8 };
+// prm = {lo32(seed), hi32(seed), row offset, bits of top_p, bits of temperature, step (taps only), top_k, qmin = rn(min_p * 2^31)};
+// the last two are read by the filtered instantiations only (mellow_generate_filters), and serve any value likewise.
+enum { SMP_SEED_LO = 0, SMP_SEED_HI, SMP_ROW_OFF, SMP_TOP_P, SMP_TEMP, SMP_STEP, SMP_TOP_K, SMP_QMIN, SMP_WORDS = 8 };
 struct SampleArgs {
     const float* logits = nullptr;       // [rows][ld] fp32
     int64_t ld = 0;
     const uint32_t* prm = nullptr;       // device block of SMP_WORDS words
     const int32_t* row_ids = nullptr;    // taps: global row index of each row (null: the row's position)
     int row_shift = 0;                   // decode step: the stream of row r is that of global row `row offset + (r >> row_shift)`; 1 in a guided call (both rows of pair p draw from the stream of global row p)
+    bool filtered = false;               // the instantiation with top_k / min_p (sample.hip, FILT)
 };
 constexpr int SAMPLE_MAX_V = 49152;      // the vocabulary the sampler is built for: 48 values per thread of one 1024-thread workgroup
 // the decode step's sampler: draws from sa.logits (= DecArgs::logits) and then does exactly the bookkeeping of dec_argmax_kernel

@@ -10,6 +10,16 @@
 //   4. Gumbel-max over the kept tokens: argmax (z + g), g = -log(-log u), u from Philox4x32-10 keyed by (seed) with counter
 //      (index / 4, step, global row, 0); ties to the lowest index.  Noise is only formed for kept tokens.
 // The loop variant then does exactly the bookkeeping of dec_argmax_kernel (decode.hip), which it replaces in the step.
+//
+// The filtered instantiation (FILT; include/mellow_hip.h, mellow_generate_filters) puts two more filters around step 3, in Hugging
+// Face's order top_k, top_p, min_p:
+//   3a. top_k = K: the same select with weight 1 per token and threshold K - 1 finds the K-th key and the count above it; a tie
+//       group on that key larger than its share is cut by the index select.  T = the first K tokens of the order;
+//   3b. the nucleus select runs over T only (every other token, the cut-off part of T's tie group included, is given z = -inf and
+//       with it mass 0), so the first histogram's total is S_T and its tie counts are counts of participants;
+//   3c. min_p: a token is kept iff q >= qmin = rn(min_p * 2^31); q is monotone in z, so the largest failing key is a boundary key.
+// The kept set is a prefix of the order, so one (boundary key, index cut) pair describes it.  Neutral values
+// (K = 0, qmin = 0) give the plain instantiation's draw, bit for bit.
 #include "common.h"
 #include "kernels.h"
 
@@ -34,6 +44,13 @@ __device__ __forceinline__ uint32_t okey(float z) {
 // a copy of a register value the compiler cannot see through: keeps per-pass key / mass arithmetic inside the pass loops
 // (hoisted out, the 48 keys, masses and sign masks of a thread's row slice would be live at once: 128-VGPR budget, spills)
 __device__ __forceinline__ float opaque(float x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+
+// the same for a thread index: an element's index is formed again where it is needed (seen through, the 48 index keys of a thread's
+// slice are hoisted out of the index select's two passes and spilled; the filtered instantiation uses this and runs without them)
+__device__ __forceinline__ int opaque(int x) {
     asm volatile("" : "+v"(x));
     return x;
 }
@@ -139,6 +156,7 @@ __device__ __forceinline__ T block_reduce(T v, Op op, T* red) {
 }
 
 // the draw of one row: returns the token (workgroup-uniform)
+template <bool FILT>
 __device__ __forceinline__ int sample_row(const float* __restrict__ lrow, const uint32_t* __restrict__ prm, uint32_t grow,
                                           uint32_t step) {
     __shared__ SelScratch sh;
@@ -179,7 +197,78 @@ __device__ __forceinline__ int sample_row(const float* __restrict__ lrow, const 
     bool keep_all = !(top_p < 1.0f);
     uint32_t kstar = 0;                  // boundary key: keys above it are kept
     int idx_cut = 0x7fffffff;            // tokens ON the boundary key are kept up to this index
-    if (!keep_all) {
+    if constexpr (FILT) {
+        const uint32_t top_k = prm[SMP_TOP_K], qmin = prm[SMP_QMIN];      // tokens with q < qmin are dropped (min_p)
+        keep_all = true;                 // until a filter sets a boundary (every key is > 0: the neutral pair keeps all, too)
+        if (top_k > 0 && top_k < (uint32_t)SAMPLE_MAX_V) {
+            // T = the first top_k tokens of the order: the pair (kstar, idx_cut)
+            unsigned long long above, mass, thr;
+            radix_select([&](int k, int j, uint32_t& key) { key = okey(opaque(z[k][j])); return true; }, [](int, int) { return 1ull; },
+                         [top_k](unsigned long long) { return (unsigned long long)top_k - 1; }, 24, sh, kstar, above, mass, thr);
+            const unsigned long long c = top_k - above;       // 1 <= c <= mass: the tie group's share
+            if (c < mass) {
+                uint32_t kidx;
+                unsigned long long a2, m2, t2;
+                radix_select([&](int k, int j, uint32_t& key) {
+                                 key = 0xFFFFu - (uint32_t)(4 * (k * SMP_THREADS + opaque(tid)) + j);
+                                 return okey(opaque(z[k][j])) == kstar; },
+                             [](int, int) { return 1ull; }, [c](unsigned long long) { return c - 1; }, 8, sh, kidx, a2, m2, t2);
+                idx_cut = (int)(0xFFFFu - kidx);
+            }
+            keep_all = false;
+            // every token outside T leaves the row (z = -inf: mass 0 in the nucleus below, and never on its boundary key, whose bin
+            // has mass > 0), so the nucleus select and its tie counts see the participants only.  m is in T.
+#pragma unroll
+            for (int k = 0; k < SMP_NV4; ++k)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t key = okey(z[k][j]);
+                    if (!(key > kstar || (key == kstar && 4 * (k * SMP_THREADS + tid) + j <= idx_cut))) z[k][j] = -INFINITY;
+                }
+        }
+        if (top_p < 1.0f) {
+            // the nucleus inside T: the plain select on the masked row.  A boundary it finds lies on or above T's (the tokens below
+            // weigh nothing), and its tie group holds tokens of T only.
+            uint32_t kp;
+            unsigned long long above, mass, thr;
+            if (radix_select([&](int k, int j, uint32_t& key) { key = okey(opaque(z[k][j])); return true; }, q_of,
+                             [&](unsigned long long S) { return top_p > 0.0f ? (unsigned long long)((double)top_p * (double)S) : 0ull; },
+                             24, sh, kp, above, mass, thr)) {
+                kstar = kp; idx_cut = 0x7fffffff; keep_all = false;
+#pragma unroll
+                for (int k = 0; k < SMP_NV4; ++k)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (okey(opaque(z[k][j])) == kstar) qtie_s = (uint32_t)q_of(k, j);   // (every writer stores the same value)
+                __syncthreads();
+                const unsigned long long qt = qtie_s;            // > 0: the boundary bin's mass exceeds thr - above >= 0
+                const unsigned long long n_tie = mass / qt, c = (thr - above) / qt + 1;
+                if (c < n_tie) {
+                    uint32_t kidx;
+                    unsigned long long a2, m2, t2;
+                    radix_select([&](int k, int j, uint32_t& key) {
+                                     key = 0xFFFFu - (uint32_t)(4 * (k * SMP_THREADS + opaque(tid)) + j);
+                                     return okey(opaque(z[k][j])) == kstar; },
+                                 [](int, int) { return 1ull; }, [c](unsigned long long) { return c - 1; }, 8, sh, kidx, a2, m2, t2);
+                    idx_cut = (int)(0xFFFFu - kidx);
+                }
+            }
+        }
+        if (qmin > 0) {
+            // min_p is monotone in z: the largest key that fails q >= qmin, if it lies inside the set kept so far, ends the set above
+            // it (its whole tie group carries the same q)
+            uint32_t kfail = 0;
+#pragma unroll
+            for (int k = 0; k < SMP_NV4; ++k)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t key = okey(opaque(z[k][j]));
+                    if (key >= kstar && key > kfail && q_of(k, j) < qmin) kfail = key;
+                }
+            kfail = block_reduce(kfail, [](uint32_t a, uint32_t b) { return a > b ? a : b; }, reinterpret_cast<uint32_t*>(red_i));
+            if (kfail >= kstar && kfail > 0) { kstar = kfail; idx_cut = -1; keep_all = false; }
+        }
+    } else if (!keep_all) {
         unsigned long long above, mass, thr;
         keep_all = !radix_select([&](int k, int j, uint32_t& key) { key = okey(opaque(z[k][j])); return true; }, q_of,
                                  [&](unsigned long long S) { return top_p > 0.0f ? (unsigned long long)((double)top_p * (double)S) : 0ull; },
@@ -211,7 +300,7 @@ __device__ __forceinline__ int sample_row(const float* __restrict__ lrow, const 
     int bidx = 0x7fffffff;
 #pragma unroll
     for (int k = 0; k < SMP_NV4; ++k) {
-        const int i4 = k * SMP_THREADS + tid;
+        const int i4 = k * SMP_THREADS + (FILT ? opaque(tid) : tid);
         bool kept[4], any = false;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -254,7 +343,7 @@ __device__ __forceinline__ int sample_row(const float* __restrict__ lrow, const 
 // LSE (LoopArgs::out_logprob): after the draw, the row's log-sum-exp is merged from the head's (cand_val, cand_sum) partials by the
 // function the arg-max kernel uses (common.h: dec_lse_max / dec_lse_sum -- the raw logits, temperature 1, no nucleus), the drawn
 // token's logit is read from the logits row the head stored, and logit - lse is recorded where the token is.
-template <bool LSE>
+template <bool LSE, bool FILT>
 __global__ __launch_bounds__(SMP_THREADS) void dec_sample_kernel(const SampleArgs sa, const DecArgs a, int32_t* __restrict__ tokens,
                                                                  const float* __restrict__ embed, int write_x, const LoopArgs lp) {
     __shared__ int tok_s;
@@ -265,7 +354,7 @@ __global__ __launch_bounds__(SMP_THREADS) void dec_sample_kernel(const SampleArg
     int idx = 0;
     if (!dead) {
         const int step = lp.out_tokens ? *a.d_pos - lp.T0 + 1 : (int)sa.prm[SMP_STEP];
-        idx = sample_row(sa.logits + (int64_t)b * sa.ld, sa.prm, sa.prm[SMP_ROW_OFF] + ((uint32_t)row >> sa.row_shift), (uint32_t)step);
+        idx = sample_row<FILT>(sa.logits + (int64_t)b * sa.ld, sa.prm, sa.prm[SMP_ROW_OFF] + ((uint32_t)row >> sa.row_shift), (uint32_t)step);
     }
     float lse = 0.f;
     if constexpr (LSE) {
@@ -316,23 +405,25 @@ __global__ __launch_bounds__(SMP_THREADS) void dec_sample_kernel(const SampleArg
     }
 }
 
+template <bool FILT>
 __global__ __launch_bounds__(SMP_THREADS) void sample_logits_kernel(const SampleArgs sa, int32_t* __restrict__ tokens) {
     const int b = blockIdx.x;
     const uint32_t grow = sa.prm[SMP_ROW_OFF] + (uint32_t)(sa.row_ids ? sa.row_ids[b] : b);
-    const int idx = sample_row(sa.logits + (int64_t)b * sa.ld, sa.prm, grow, sa.prm[SMP_STEP]);
+    const int idx = sample_row<FILT>(sa.logits + (int64_t)b * sa.ld, sa.prm, grow, sa.prm[SMP_STEP]);
     if (threadIdx.x == 0) tokens[b] = idx;
 }
 
 void launch_dec_sample(const SampleArgs& sa, const DecArgs& a, int B, int32_t* tokens, const float* embed, int write_x,
                        const LoopArgs& loop, hipStream_t s) {
-    if (loop.out_logprob != nullptr && a.cand_sum != nullptr)
-        hipLaunchKernelGGL(dec_sample_kernel<true>, dim3(B), dim3(SMP_THREADS), 0, s, sa, a, tokens, embed, write_x, loop);
-    else
-        hipLaunchKernelGGL(dec_sample_kernel<false>, dim3(B), dim3(SMP_THREADS), 0, s, sa, a, tokens, embed, write_x, loop);
+    const bool lse = loop.out_logprob != nullptr && a.cand_sum != nullptr;
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(B), dim3(SMP_THREADS), 0, s, sa, a, tokens, embed, write_x, loop); };
+    if (sa.filtered) { if (lse) go(dec_sample_kernel<true, true>); else go(dec_sample_kernel<false, true>); }
+    else { if (lse) go(dec_sample_kernel<true, false>); else go(dec_sample_kernel<false, false>); }
 }
 
 void launch_sample_logits(const SampleArgs& sa, int B, int32_t* tokens, hipStream_t s) {
-    hipLaunchKernelGGL(sample_logits_kernel, dim3(B), dim3(SMP_THREADS), 0, s, sa, tokens);
+    if (sa.filtered) hipLaunchKernelGGL(sample_logits_kernel<true>, dim3(B), dim3(SMP_THREADS), 0, s, sa, tokens);
+    else hipLaunchKernelGGL(sample_logits_kernel<false>, dim3(B), dim3(SMP_THREADS), 0, s, sa, tokens);
 }
 
 }  // namespace mellow

@@ -40,6 +40,11 @@ class LogitRules(C.Structure):
                 ("min_new_tokens", C.c_int32), ("logit_bias", C.c_void_p)]
 
 
+class SampleFilters(C.Structure):
+    """mellow_sample_filters_t (include/mellow_hip.h)"""
+    _fields_ = [("size", C.c_int32), ("top_k", C.c_int32), ("min_p", C.c_float)]
+
+
 class GemmEpi(C.Structure):
     """mellow_gemm_epi_t (include/mellow_hip.h)"""
     _fields_ = [(n, C.c_int32) for n in ("size", "kernel", "epi", "M", "K", "Nw", "N", "act", "bias", "resid", "rows_in", "rows_out", "ldc",
@@ -59,7 +64,7 @@ _ADDED_UNDER_MINOR_4 = ("mellow_lm_score", "mellow_score", "mellow_generate_scor
 # symbols of minor 5 (the attention taps on host data): looked up the same way, so that a minor-4 library still loads
 _ADDED_UNDER_MINOR_5 = ("mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_generate_rules", "mellow_logit_rules_apply",
                         "mellow_generate_guidance", "mellow_guidance_apply", "mellow_generate_top_logprobs", "mellow_top_logprobs_apply",
-                        "mellow_debug_gemm_epi")
+                        "mellow_debug_gemm_epi", "mellow_generate_filters", "mellow_sample_logits_filtered")
 
 
 def load_library(path: Optional[str] = None):
@@ -98,6 +103,8 @@ def load_library(path: Optional[str] = None):
         "mellow_generate_beam": (ci, [vp, vp, vp, i64, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, P(C.c_int32), P(cf)]),
         "mellow_beam_select": (ci, [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp]),
         "mellow_sample_logits": (ci, [vp, vp, ci, vp, ci, cf, cf, C.c_uint64, vp]),
+        "mellow_generate_filters": (ci, [vp, P(SampleFilters)]),
+        "mellow_sample_logits_filtered": (ci, [vp, vp, ci, vp, ci, cf, cf, C.c_uint64, P(SampleFilters), vp]),
         "mellow_generate_rules": (ci, [vp, P(LogitRules)]),
         "mellow_logit_rules_apply": (ci, [vp, P(LogitRules), vp, ci, vp, ci, vp, ci, vp, vp, vp]),
         "mellow_generate_guidance": (ci, [vp, cf]),
@@ -162,7 +169,7 @@ EXPORTED_SYMBOLS = (
     "mellow_engine_num_required", "mellow_engine_required_key", "mellow_generate", "mellow_generate_sampled", "mellow_sample_logits", "mellow_logmel",
     "mellow_encode", "mellow_prefix", "mellow_lm_prefill", "mellow_lm_decode_step", "mellow_argmax", "mellow_embed_tokens", "mellow_lm_forward_logits",
     "mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse", "mellow_generate_n", "mellow_generate_q",
-    "mellow_generate_beam", "mellow_beam_select", "mellow_generate_rules", "mellow_logit_rules_apply", "mellow_generate_guidance", "mellow_guidance_apply", "mellow_generate_top_logprobs", "mellow_top_logprobs_apply", "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
+    "mellow_generate_beam", "mellow_beam_select", "mellow_generate_rules", "mellow_logit_rules_apply", "mellow_generate_guidance", "mellow_guidance_apply", "mellow_generate_top_logprobs", "mellow_top_logprobs_apply", "mellow_generate_filters", "mellow_sample_logits_filtered", "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
     "mellow_prof_num_families", "mellow_prof_family_name", "mellow_prof_get", "mellow_last_phase_ms", "mellow_last_steps_enqueued", "mellow_last_row_repacks", "mellow_stft_is_fft", "mellow_prefill_parts", "mellow_abi_minor",
     "mellow_resample", "mellow_engine_set_precision", "mellow_engine_set_option", "mellow_engine_describe", "mellow_debug_gemm_fp8", "mellow_debug_gemm_f32", "mellow_debug_gemm_epi", "mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_debug_dec_head", "mellow_set_graph", "mellow_host_window_map", "mellow_host_pack_weight", "mellow_host_rope_tables",
 )
@@ -246,6 +253,21 @@ def check_top_logprobs(top_logprobs=0) -> int:
     return k
 
 
+def check_sample_filters(top_k=0, min_p=0.0):
+    """The value rules of the sampler's candidate filters (the C entry repeats them): top_k >= 0 (0 is off), min_p in [0, 1] (0 is
+    off).  -> (top_k, min_p)"""
+    k, p = int(top_k), float(min_p)
+    if k != top_k:
+        raise ValueError(f"top_k must be an integer >= 0 (got {top_k}); 0 is off")
+    if k < 0:
+        raise ValueError(f"top_k must be >= 0 (got {top_k}); 0 is off")
+    if k > 0x7fffffff:
+        k = 0x7fffffff                 # (any K >= the vocabulary keeps every token)
+    if not (0.0 <= p <= 1.0):
+        raise ValueError(f"min_p must be in [0, 1] (got {min_p}); 0 is off")
+    return k, p
+
+
 BEAM_MAX_K = 8                 # beams per example mellow_generate_beam takes
 BEAM_STAGE_ROWS = 65536        # B * k * max_len its K/V staging takes (1.5 GB per tensor)
 
@@ -321,12 +343,13 @@ def has_question_axis(input_ids) -> bool:
 
 class _CallOptions:
     """What one generate() call arms before EVERY C call it makes (an armed record serves the next mellow_generate* call only): the
-    rules struct or None (it keeps its bias vector alive), the guidance scale or None, the k of top_logprobs.  Built once per call
-    and handed to the route that runs it; nothing of a call is kept on the engine."""
-    __slots__ = ("rules", "guide", "top_k")
+    rules struct or None (it keeps its bias vector alive), the guidance scale or None, the k of top_logprobs, the sampler's filters
+    struct (top_k / min_p of the draw) or None.  Built once per call and handed to the route that runs it; nothing of a call is kept
+    on the engine."""
+    __slots__ = ("rules", "guide", "top_k", "filters")
 
-    def __init__(self, rules, guide, top_k):
-        self.rules, self.guide, self.top_k = rules, guide, top_k
+    def __init__(self, rules, guide, top_k, filters=None):
+        self.rules, self.guide, self.top_k, self.filters = rules, guide, top_k, filters
 
     def arm(self, engine, top):
         """arm the engine's context for its next C call; top = the rows of the top record that call fills (ids, log-probs), or None"""
@@ -336,6 +359,8 @@ class _CallOptions:
             engine._chk(engine.lib.mellow_generate_guidance(engine.h, float(self.guide)))
         if self.top_k and top is not None:
             engine._chk(engine.lib.mellow_generate_top_logprobs(engine.h, int(self.top_k), _ptr(top[0]), _ptr(top[1])))
+        if self.filters is not None:
+            engine._chk(engine.lib.mellow_generate_filters(engine.h, C.byref(self.filters)))
 
 
 class Engine:
@@ -503,7 +528,8 @@ class Engine:
                  row_offset: int = 0, return_logprobs: bool = False, num_return_sequences: int = 1,
                  num_beams: Optional[int] = None, length_penalty: float = 1.0, repetition_penalty: float = 1.0,
                  no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, logit_bias=None, _arm_neutral_rules: bool = False,
-                 guidance_scale: float = 1.0, negative=None, keep_negative_rows: bool = False, top_logprobs: int = 0):
+                 guidance_scale: float = 1.0, negative=None, keep_negative_rows: bool = False, top_logprobs: int = 0,
+                 top_k: int = 0, min_p: float = 0.0):
         """-> (tokens int32 [B, steps] on host, lengths [B], steps, first_token_ms)
         num_return_sequences = n > 1 (needs do_sample=True): n sampled answers per example from one encode and one prefill per
         example (mellow_generate_n).  Every array has B * n rows, row b * n + j = answer j of example b, and holds what this call
@@ -546,10 +572,26 @@ class Engine:
         logprobs: top_ids int32 [rows, steps, k] and top_logprobs float32 [rows, steps, k], best first (value descending, then index
         ascending); -1 / exactly 0.0 where tokens is -1.  Guided calls return the conditional rows, or all rows with
         keep_negative_rows=True.  ValueError with num_beams, without return_logprobs=True, or for k outside [0, 20].  0 (default):
-        nothing is armed and the call is the one without the keyword."""
+        nothing is armed and the call is the one without the keyword.
+        top_k = K / min_p = p (need do_sample=True): the sampler's candidate filters next to the nucleus (include/mellow_hip.h,
+        mellow_generate_filters), applied on the device in Hugging Face's order temperature, top_k, top_p, min_p: the K likeliest
+        tokens (ties cut by index), the nucleus inside them, and of those the tokens whose probability is at least p times the
+        likeliest token's.  Seeds, row streams, num_return_sequences, question lists, repetition controls, guidance and the log-prob
+        records (which stay unfiltered) work as without them.  ValueError without do_sample=True, with num_beams, for K < 0 or p
+        outside [0, 1].  Both 0 (default; Hugging Face's top_k = 50 is not adopted): nothing is armed and the call is the one without
+        the keywords."""
         import time
         t_in = time.perf_counter()
         nseq = int(num_return_sequences)
+        fk, fp = check_sample_filters(top_k, min_p)
+        filters = None
+        if fk or fp:
+            if num_beams is not None:
+                raise ValueError("top_k / min_p and num_beams do not combine: they filter a sampled draw, beam search is deterministic")
+            if not do_sample:
+                raise ValueError("top_k / min_p need do_sample=True: they filter the sampled draw, the greedy token is the arg-max whatever they are")
+            self._need("mellow_generate_filters")
+            filters = SampleFilters(size=C.sizeof(SampleFilters), top_k=fk, min_p=fp)
         topk = check_top_logprobs(top_logprobs)
         if topk:
             if num_beams is not None:
@@ -570,7 +612,7 @@ class Engine:
                 raise ValueError(f"guidance_scale = {gscale} needs `negative` = (audio1, audio2, input_ids): the input to contrast with")
             self._need("mellow_generate_guidance")
         opts = _CallOptions(self._make_rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, logit_bias, _arm_neutral_rules, int(max_len)),
-                            gscale if gscale != 1.0 else None, topk)
+                            gscale if gscale != 1.0 else None, topk, filters)
         if num_beams is not None:
             if do_sample:
                 raise ValueError("num_beams and do_sample=True do not combine: beam search is deterministic")
@@ -1018,9 +1060,17 @@ class Engine:
         self._chk(self.lib.mellow_argmax(self.h, _ptr(l), l.shape[0], _ptr(out)))
         return out
 
-    def sample_logits(self, logits, top_p: float, temperature: float, seed: int, step: int, row_ids=None) -> torch.Tensor:
+    def sample_logits(self, logits, top_p: float, temperature: float, seed: int, step: int, row_ids=None, top_k: int = 0,
+                      min_p: float = 0.0, filtered: Optional[bool] = None) -> torch.Tensor:
         """The decode step's draw on caller logits (B, vocab) -> tokens int32 (B,) on the device; row_ids (B,) = the global
-        row index of each row (None: 0..B-1), step = the column of the token record the draw stands for."""
+        row index of each row (None: 0..B-1), step = the column of the token record the draw stands for.  top_k / min_p: the
+        candidate filters (mellow_sample_logits_filtered, the sampler's filtered instantiation); filtered=True runs that
+        instantiation also for neutral values, None (default) only when a filter is set."""
+        fk, fp = check_sample_filters(top_k, min_p)
+        if filtered is None:
+            filtered = bool(fk or fp)
+        elif not filtered and (fk or fp):
+            raise ValueError("filtered=False with top_k / min_p set: the plain draw has no filters")
         l = self._f32(logits)
         if l.dim() != 2 or l.shape[1] != self.lm.vocab_size:
             raise ValueError(f"logits must be (B, {self.lm.vocab_size}), got {tuple(l.shape)}")
@@ -1030,6 +1080,12 @@ class Engine:
         if rid is not None and rid.shape[0] != B:
             raise ValueError(f"row_ids has {rid.shape[0]} entries for {B} rows")
         self._sync_inputs()
+        if filtered:
+            self._need("mellow_sample_logits_filtered")
+            f = SampleFilters(size=C.sizeof(SampleFilters), top_k=fk, min_p=fp)
+            self._chk(self.lib.mellow_sample_logits_filtered(self.h, _ptr(l), B, None if rid is None else _ptr(rid), int(step), float(top_p),
+                                                             float(temperature), _seed64(seed), C.byref(f), _ptr(out)))
+            return out
         self._chk(self.lib.mellow_sample_logits(self.h, _ptr(l), B, None if rid is None else _ptr(rid), int(step), float(top_p),
                                                 float(temperature), _seed64(seed), _ptr(out)))
         return out

@@ -71,7 +71,9 @@ class EnginePool:
         its own calls, the same for every batch; guidance_scale with negative=(audio1, audio2, input_ids): contrastive guidance, the
         scale armed by each context for its own calls -- a `negative` keyword goes to every batch as it is, a batch given as
         (audio1, audio2, input_ids, negative) brings its own; a guided batch counts its examples, not its rows, towards row_offset;
-        top_logprobs=k with return_logprobs=True: seven values per batch, top_ids and top_logprobs [rows, steps, k] after logprobs)."""
+        top_logprobs=k with return_logprobs=True: seven values per batch, top_ids and top_logprobs [rows, steps, k] after logprobs;
+        top_k / min_p with do_sample=True: the sampler's candidate filters, armed by each context for its own calls, the same for
+        every batch)."""
         kws = [kw] * len(batches)
         if kw.get("do_sample"):
             off, kws = int(kw.get("row_offset", 0)), []

@@ -21,6 +21,10 @@ inside the captured decode step -- z = logits / temperature, the nucleus of the 
 softmax mass strictly before it in (z desc, index asc) order is <= top_p), then Gumbel-max with Philox4x32-10 noise keyed by
 (seed, row, step); include/mellow_hip.h mellow_generate_sampled gives the exact definition.  seed=None draws a 63-bit seed from
 `random` (kept as `last_seed`); under data parallelism the seed must be given and equal on every rank.
+Extension (keyword-only): `generate(..., do_sample=True, top_k=K, min_p=p)` adds the two candidate filters users of Hugging Face
+`generate` reach for, inside the same sampler launch and in Hugging Face's order (temperature, top_k, top_p, min_p): only the K
+likeliest tokens, the nucleus inside them, and of those only tokens at least p times as likely as the likeliest
+(include/mellow_hip.h mellow_generate_filters).  Both are off (0) by default: Hugging Face's top_k = 50 is not adopted.
 Extension (keyword-only): `generate(..., do_sample=True, num_return_sequences=n)` returns n sampled answers per example -- a list
 of n strings (with return_logprobs=True: of n dicts, so `max(out[i], key=lambda a: a["logprob"])` re-ranks) -- for self-consistency
 voting or re-ranking.  Log-mel, encoder, projection and the LM prefill run ONCE per example; the prefix K/V is copied to the n answer
@@ -338,7 +342,8 @@ class MellowWrapper:
                  do_sample: bool = False, seed: Optional[int] = None, return_logprobs: bool = False,
                  num_return_sequences: int = 1, num_beams: int = 1, length_penalty: float = 1.0, repetition_penalty: float = 1.0,
                  no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, suppress_tokens: Optional[Sequence[int]] = None,
-                 logit_bias: Optional[dict] = None, guidance_scale: float = 1.0, negative_examples=None, top_logprobs: int = 0):
+                 logit_bias: Optional[dict] = None, guidance_scale: float = 1.0, negative_examples=None, top_logprobs: int = 0,
+                 top_k: int = 0, min_p: float = 0.0):
         r"""Produces text response for the given audio files and text prompts
         examples: (list<list>) each example is [audio path 1, audio path 2, text prompt]; the text prompt may be a list or tuple of
                      prompts, several questions about the one pair of clips (module docstring).  If any example has a list, the
@@ -394,6 +399,16 @@ class MellowWrapper:
                      max_len=1 on a multiple-choice prompt these are the first-token option probabilities.  Works with do_sample,
                      num_return_sequences, question lists, the five repetition keywords and guidance_scale.  ValueError without
                      return_logprobs=True, with num_beams > 1, or for k outside [0, 20].  0 (default): the call without the keyword.
+        top_k: (int) K > 0 (needs do_sample=True): only the K likeliest tokens of a step can be drawn (ties on the K-th value are cut
+                     by token id, so the set has exactly K members).
+        min_p: (float) p in (0, 1] (needs do_sample=True): only tokens whose probability is at least p times the likeliest token's
+                     can be drawn, so the set shrinks when the model is confident and widens when it is not.
+                     Both run on the device inside the sampler, in Hugging Face's order temperature, top_k, top_p, min_p (the
+                     nucleus is taken inside the K tokens), and work with seed, num_return_sequences, question lists, return_logprobs
+                     / top_logprobs (which stay the unfiltered log-softmax), the five repetition keywords, guidance_scale and data
+                     parallelism (the values are per call and the same on every rank).  ValueError without do_sample=True, with
+                     num_beams > 1, for K < 0 or p outside [0, 1].  Both 0 (default -- Hugging Face's top_k = 50 is not adopted):
+                     the call without the keywords.
 
         With `data_parallel=True` (or MELLOW_DATA_PARALLEL=1) under an initialised torch.distributed group (one process per
         GPU, every rank calling with the same examples) the examples are sharded contiguously over the ranks, each rank ingests
@@ -413,6 +428,8 @@ class MellowWrapper:
             raise ValueError(f"num_beams must be >= 1 (got {k})")
         gscale, negatives = self._guidance_request(guidance_scale, negative_examples, examples, text_prompts, k, nseq)
         engine_kw = dict(rules_kw, **self._top_request(top_logprobs, return_logprobs, k))
+        filters_kw = self._filters_request(top_k, min_p, do_sample, k)
+        engine_kw.update(filters_kw)
         if k > 1:
             return self._generate_beams(examples, audio_paths1, audio_paths2, text_prompts, max_len, stop_token, audio_resample,
                                         do_sample, return_logprobs, k, nseq, float(length_penalty), rules_kw)
@@ -444,6 +461,8 @@ class MellowWrapper:
             import hashlib
             extra += repr(sorted((k, hashlib.sha1(np.ascontiguousarray(v).tobytes()).hexdigest() if k == "logit_bias" else v)
                                  for k, v in rules_kw.items())).encode()
+        if filters_kw:    # likewise
+            extra += repr(("filters", filters_kw["top_k"], filters_kw["min_p"])).encode()
         lo, hi = 0, n
         if world > 1:
             from .dist import shard_range
@@ -467,6 +486,19 @@ class MellowWrapper:
         return self._generate_batch(audio1, audio2, ids, entry_length=max_len, top_p=top_p,
                                     temperature=temperature, stop_token=stop_token, n_total=n, do_sample=do_sample,
                                     seed=seed, row_offset=lo * nseq, return_logprobs=return_logprobs, nseq=nseq, engine_kw=engine_kw)
+
+    @staticmethod
+    def _filters_request(top_k, min_p, do_sample, k):
+        """The keyword rules of top_k / min_p -> the keywords for Engine.generate ({} for both off: the call without them)."""
+        from .engine import check_sample_filters
+        fk, fp = check_sample_filters(top_k, min_p)
+        if not fk and not fp:
+            return {}
+        if k > 1:
+            raise ValueError("top_k / min_p and num_beams > 1 do not combine: they filter a sampled draw, beam search is deterministic")
+        if not do_sample:
+            raise ValueError("top_k / min_p need do_sample=True: they filter the sampled draw, greedy decoding takes the arg-max whatever they are")
+        return dict(top_k=fk, min_p=fp)
 
     @staticmethod
     def _top_request(top_logprobs, return_logprobs, k):
