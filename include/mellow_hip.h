@@ -61,7 +61,8 @@ extern "C" {
  *     min_p inside the sampler) -- added while the minor was 5, detected by symbol lookup all the same.
  *  5: the attention taps on host data, mellow_debug_prefill_attn and mellow_debug_window_attn.  No existing symbol or struct
  *     changed; a binding that must also load a minor-4 library detects them by symbol lookup.  The GEMM epilogue tap
- *     mellow_debug_gemm_epi was added later under this same minor, detected by symbol lookup all the same. */
+ *     mellow_debug_gemm_epi was added later under this same minor, detected by symbol lookup all the same, and so was the norm /
+ *     hand-over tap mellow_debug_norm. */
 #define MELLOW_ABI_MINOR 5
 
 typedef struct mellow_engine mellow_engine_t;
@@ -622,6 +623,28 @@ int  mellow_debug_prefill_attn(mellow_engine_t* e, int variant, const float* q, 
  *   Errors: M % 64 != 0, C != 24 * nH, nH not in {4, 8, 16, 32}, a mask with nW <= 0, in16 with out_form 1, too small a capacity. */
 int  mellow_debug_window_attn(mellow_engine_t* e, const float* qkv, int M, int C, int nH, const float* bias, const float* mask,
                               int nW, int in16, int out_form, void* out, int64_t out_capacity);
+/* Norm / hand-over tap on HOST data (works on any engine, finalised or not): ONE launch of a norm launcher of the engine, or of one
+ * of the two stand-alone hand-over producers, on the caller's rows.
+ *   op 0  LayerNorm (eps 1e-5, biased variance): launch_layernorm (form 0) / launch_layernorm_apb (forms 1, 2).  x host f32 [M][C];
+ *         row_map host i32 [ntok] or NULL: output row m reads input row (m / ntok) * ntok + row_map[m % ntok], a permutation of
+ *         [0, ntok), M % ntok == 0.
+ *   op 1  patch-merging LayerNorm: launch_merge_layernorm.  x host f32 [n][R * R][C]; the output has M = n * (R / 2)^2 rows of 4 C
+ *         columns, row (clip, i, j) = the tokens (2i, 2j), (2i+1, 2j), (2i, 2j+1), (2i+1, 2j+1) side by side; w, b host f32 [4 C].
+ *   op 2  RMSNorm w * (x * rsqrt(mean x^2 + eps)): launch_rmsnorm (form 0) / launch_rmsnorm_apb (forms 1, 2).
+ *   op 3  no norm: launch_split_rows_apb (form 1) / launch_quant_mx8 (form 2) on x itself, lda = C; w and b are not read.
+ * The device outputs are filled with 0xFF bytes before the launch and returned whole (capacities in bytes):
+ *   form 0  out = f32 [M + 32][columns]                                          (ops 0, 1, 2)
+ *   form 1  out = the raw APB image: roundup(M, 128) rows, 6 bytes per element    (ops 0, 2, 3)
+ *   form 2  out = the raw AMX image (MXFP8: e4m3 elements in the order of mellow_amd/csrc/common.h): roundup(M, 128) *
+ *           roundup(C, 64) bytes; out_scales = its E8M0 scale bytes: roundup(M, 128) * 8 * KQ bytes, KQ = ceil(ceil(C / 64) / 4)
+ *           (ops 0, 2, 3)
+ * Refused by name, nothing launched: C % 4 != 0; form 0 with more than 1536 columns; ops 0 / 2 in forms 1 / 2 with C % 16 != 0 or
+ * C > 768 (op 2: C > 752, the 96 KiB of LDS launch_rmsnorm_apb asks for); op 3 form 1 with C % 16 != 0; op 3 form 0; op 1 in form
+ * 1 or 2, with an odd R or with M != n * (R / 2)^2; M < 1 or M > 2^22; a null w (ops 0 - 2) or b (ops 0, 1); a row_map that is no
+ * permutation, or with an op other than 0; eps < 0; a capacity that is too small. */
+int  mellow_debug_norm(mellow_engine_t* e, int op, int form, const float* x, int M, int C, const float* w, const float* b, float eps,
+                       const int32_t* row_map, int ntok, int n, int R, void* out, int64_t out_capacity, void* out_scales,
+                       int64_t scales_capacity);
 /* The decode step's lm_head kernel on caller-supplied rows (dev): logits[B][vocab] = x[B][hidden] . lm_head^T with the engine's
  * own head weights (the e4m3 copy in MELLOW_PRECISION_FP8; act_fp8 != 0 then also quantises x inside the kernel: one scale per
  * batch row and 72-column slice, fp8 matrix pipe).  Invalidates the decode state of an earlier prefill. */

@@ -220,7 +220,8 @@ void launch_merge_layernorm(const float* in, float* out, int n, int R, int C, co
 }
 
 // The row-map LayerNorm with its output pre-split in APB order (f32x3 mode: the consumer is an x3q GEMM, common.h).  Same
-// statistics as layernorm_kernel<0> bit for bit (same lane -> column mapping, same reduction order, same expression for y);
+// statistics as layernorm_kernel<0> bit for bit (same lane -> column mapping, same reduction order, same expression for y:
+// tests/test_gpu_norm.py decodes the image and holds it to the plain kernel's rows word for word);
 // a workgroup owns 32 consecutive OUTPUT rows: pass 1 gathers them (one row per wave at a time, coalesced), keeps them in LDS
 // and forms mean / rstd; pass 2 re-reads them from LDS in the (row % 32, k-half) order of an APB slot run, so that every store
 // instruction of a wave writes 1 KiB contiguous (the scheme of rmsnorm_apb_kernel below).  NQ = float4 per lane (C <= 256 NQ).
@@ -341,6 +342,15 @@ void launch_layernorm_apb(const float* in, void* out_apb, int M, int C, const fl
 #undef MELLOW_LN_LAUNCH
 }
 
+// x^2 + y^2 + z^2 + w^2 of one float4 in ONE pinned form, fma(x, x, y y) + fma(z, z, w w).  Written as a plain expression the compiler
+// is free to contract it either way round, and it did: fma(x, x, y y) in rmsnorm_kernel, fma(y, y, x x) in rmsnorm_apb_kernel, so the
+// two kernels' 1/rms differed in the last place on a few rows in a hundred (tests/test_gpu_norm.py).  This is the form rmsnorm_kernel
+// compiled to before: its results are unchanged.
+__device__ __forceinline__ float sumsq4(const float4& v) {
+#pragma clang fp contract(off)
+    const float yy = v.y * v.y, ww = v.w * v.w;
+    return __builtin_fmaf(v.x, v.x, yy) + __builtin_fmaf(v.z, v.z, ww);
+}
 // LlamaRMSNorm (fp32): w * (x * rsqrt(mean(x^2) + eps))
 __global__ __launch_bounds__(256) void rmsnorm_kernel(const float* __restrict__ in, float* __restrict__ out, int64_t M,
                                                       int C, const float* __restrict__ w, float eps) {
@@ -357,7 +367,7 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const float* __restrict__ 
         x[q] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (v < nv) {
             x[q] = src[v];
-            ss += (x[q].x * x[q].x + x[q].y * x[q].y) + (x[q].z * x[q].z + x[q].w * x[q].w);
+            ss += sumsq4(x[q]);
         }
     }
     const float r = 1.0f / sqrtf(wave_sum(ss) / (float)C + eps);
@@ -376,8 +386,17 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const float* __restrict__ 
         }
     }
 }
+// w * (x * r) with each product rounded to fp32 on its own.  HIP's __fmul_rn is a plain product, so it may still be contracted with
+// what consumes it: split3's a - h (common.h) turned the last product into fma(w, x r, -h), and the three pieces then summed to
+// the 48-bit product rounded another way -- one unit in the last place off the plain kernel's row in about 7 % of the elements.
+// With contraction off inside this function the product carries no contract flag and stays a product.
+__device__ __forceinline__ float rms_scaled(float w, float x, float r) {
+#pragma clang fp contract(off)
+    const float xr = x * r;
+    return w * xr;
+}
 // the same arithmetic, output pre-split in APB order.  A workgroup owns 32 consecutive rows.  Pass 1 is the plain kernel's
-// statistic (same lane -> column mapping and reduction order: the same 1/rms bit for bit), one row per wave at a time; pass 2
+// statistic (same lane -> column mapping, sumsq4 and reduction order: the same 1/rms bit for bit), one row per wave at a time; pass 2
 // re-reads the rows (L2-hot) with lane = (row % 32, k-half), the order of an APB slot run, so every store instruction of a
 // wave writes 1 KiB contiguous (a first version that stored from the row-per-wave mapping scattered 16-byte pieces 12 KiB
 // apart and took 2.3x the time of the plain kernel)
@@ -408,7 +427,7 @@ __global__ __launch_bounds__(256) void rmsnorm_apb_kernel(const float* __restric
             if (v < nv) {
                 const float4 x = src[v];
                 dst[v] = x;
-                ss[i] += (x.x * x.x + x.y * x.y) + (x.z * x.z + x.w * x.w);
+                ss[i] += sumsq4(x);
             }
         }
     }
@@ -447,9 +466,8 @@ __global__ __launch_bounds__(256) void rmsnorm_apb_kernel(const float* __restric
         const int col = kt * 16 + kh * 8;
         const float4 x0 = *reinterpret_cast<const float4*>(rows_s + ml * RS + col), x1 = *reinterpret_cast<const float4*>(rows_s + ml * RS + col + 4);
         const float4 w0 = *reinterpret_cast<const float4*>(w + col), w1 = *reinterpret_cast<const float4*>(w + col + 4);
-        const float y[8] = {__fmul_rn(w0.x, __fmul_rn(x0.x, r)), __fmul_rn(w0.y, __fmul_rn(x0.y, r)), __fmul_rn(w0.z, __fmul_rn(x0.z, r)),
-                            __fmul_rn(w0.w, __fmul_rn(x0.w, r)), __fmul_rn(w1.x, __fmul_rn(x1.x, r)), __fmul_rn(w1.y, __fmul_rn(x1.y, r)),
-                            __fmul_rn(w1.z, __fmul_rn(x1.z, r)), __fmul_rn(w1.w, __fmul_rn(x1.w, r))};
+        const float y[8] = {rms_scaled(w0.x, x0.x, r), rms_scaled(w0.y, x0.y, r), rms_scaled(w0.z, x0.z, r), rms_scaled(w0.w, x0.w, r),
+                            rms_scaled(w1.x, x1.x, r), rms_scaled(w1.y, x1.y, r), rms_scaled(w1.z, x1.z, r), rms_scaled(w1.w, x1.w, r)};
         apb_store8(out, m, kt * 2 + kh, KT, y);
     }
 }

@@ -414,6 +414,86 @@ int mellow_debug_gemm_epi(mellow_engine_t* e, const mellow_gemm_epi_t* d, const 
     return 0;
 }
 
+// ---- norm / hand-over tap on host data (include/mellow_hip.h): one launch of a norm launcher, of launch_split_rows_apb or of
+// launch_quant_mx8 on the caller's rows ------------------------------------------------------------------------------------------------
+int mellow_debug_norm(mellow_engine_t* e, int op, int form, const float* x, int M, int C, const float* w, const float* b, float eps,
+                      const int32_t* row_map, int ntok, int n, int R, void* out, int64_t out_capacity, void* out_scales,
+                      int64_t scales_capacity) {
+    if (!e) return fail("null argument");
+    if (op < 0 || op > 3) return fail("op must be 0 (LayerNorm), 1 (merge-LayerNorm), 2 (RMSNorm) or 3 (no norm): got %d", op);
+    if (form < 0 || form > 2) return fail("form must be 0 (fp32 rows), 1 (APB image) or 2 (AMX image + scale bytes): got %d", form);
+    if (op == 1 && form != 0) return fail("merge-LayerNorm has the fp32 form only (got form %d)", form);
+    if (op == 3 && form == 0) return fail("op 3 (no norm) has the APB and AMX forms only: form 0 would launch nothing");
+    if (C < 4 || C % 4 != 0) return fail("C = %d must be a positive multiple of 4", C);
+    int64_t rows = M;              // output rows
+    int width = C;                 // output columns
+    if (op == 1) {
+        if (n < 1 || R < 2 || R % 2 != 0 || R > 4096) return fail("merge-LayerNorm needs n >= 1 and an even R in [2, 4096] (n = %d, R = %d)", n, R);
+        rows = (int64_t)n * (R / 2) * (R / 2);
+        width = 4 * C;
+        if (rows != M) return fail("M = %d is not n * (R / 2)^2 = %lld", M, (long long)rows);
+    }
+    if (M < 1 || rows > (1 << 22)) return fail("M = %lld: 1 <= M <= %d", (long long)rows, 1 << 22);
+    if (rows * width > (1 << 28)) return fail("M * C = %lld exceeds the tap's 2^28 elements", (long long)(rows * width));
+    if (form == 0 && width > 1536) return fail("%d columns exceed the 1536 (LN_MAXV) a row-per-wave norm kernel holds", width);
+    if ((op == 0 || op == 2) && form != 0 && (C % 16 != 0 || C > 768)) return fail("C = %d: the APB / AMX norm kernels need C %% 16 == 0 and C <= 768", C);
+    if (op == 2 && form != 0 && (size_t)32 * (C + 4) * 4 > (size_t)96 * 1024)
+        return fail("C = %d: launch_rmsnorm_apb stages 32 rows of C + 4 floats in the 96 KiB of LDS it asks for (C <= 752)", C);
+    if (op == 3 && form == 1 && C % 16 != 0) return fail("C = %d must be a multiple of 16 for launch_split_rows_apb", C);
+    if (!x || !out) return fail("null argument");
+    if (op != 3 && !w) return fail("w is null");
+    if (op <= 1 && !b) return fail("b is null: LayerNorm has a bias");
+    if (op == 2 && !(eps >= 0.f && eps < INFINITY)) return fail("eps = %g must be finite and >= 0", eps);
+    if (row_map) {
+        if (op != 0) return fail("row_map goes with op 0 (LayerNorm) only");
+        if (ntok < 1 || M % ntok != 0) return fail("row_map needs ntok >= 1 and M %% ntok == 0 (ntok = %d, M = %d)", ntok, M);
+        std::vector<char> seen(ntok, 0);
+        for (int i = 0; i < ntok; ++i) {
+            if (row_map[i] < 0 || row_map[i] >= ntok || seen[row_map[i]]) return fail("row_map[%d] = %d is outside [0, ntok = %d) or taken twice: not a permutation", i, row_map[i], ntok);
+            seen[row_map[i]] = 1;
+        }
+    }
+    // capacities, before anything is launched
+    const int KT64 = (C + 63) / 64, KQ = (KT64 + 3) / 4;
+    const size_t Mp = (size_t)rup((int)rows, 128);
+    const size_t out_bytes = form == 0 ? (size_t)(rows + 32) * width * 4 : form == 1 ? Mp * C * 6 : Mp * rup(C, 64);
+    const size_t sc_bytes = form == 2 ? Mp * 8 * KQ : 0;
+    if (out_capacity < (int64_t)out_bytes) return fail("out_capacity %lld is below the %lld bytes this call returns", (long long)out_capacity, (long long)out_bytes);
+    if (form == 2 && (!out_scales || scales_capacity < (int64_t)sc_bytes))
+        return fail("scales_capacity %lld is below the %lld bytes this call returns (or out_scales is null)", (long long)scales_capacity, (long long)sc_bytes);
+
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    mellow_engine::Buf bx, bw, bb, bmap, bo, bsc;
+    const size_t in_floats = op == 1 ? (size_t)n * R * R * C : (size_t)M * C;
+    CHK(gemm_tap_buf(e, bx, in_floats * 4, x));
+    if (w) CHK(gemm_tap_buf(e, bw, (size_t)width * 4, w));
+    if (b && op <= 1) CHK(gemm_tap_buf(e, bb, (size_t)width * 4, b));
+    if (row_map) CHK(gemm_tap_buf(e, bmap, (size_t)ntok * 4, row_map));
+    CHK(gemm_tap_buf(e, bo, out_bytes, nullptr));
+    if (form == 2) CHK(gemm_tap_buf(e, bsc, sc_bytes, nullptr));
+    const int32_t* dmap = row_map ? reinterpret_cast<const int32_t*>(bmap.p) : nullptr;
+    const int nt = row_map ? ntok : M;
+    void* dsc = form == 2 ? bsc.p : nullptr;
+    if (op == 0) {
+        if (form == 0) launch_layernorm(bx.p, bo.p, M, C, bw.p, bb.p, dmap, nt, s);
+        else launch_layernorm_apb(bx.p, bo.p, M, C, bw.p, bb.p, dmap, nt, s, dsc);
+    } else if (op == 1) {
+        launch_merge_layernorm(bx.p, bo.p, n, R, C, bw.p, bb.p, s);
+    } else if (op == 2) {
+        if (form == 0) launch_rmsnorm(bx.p, bo.p, M, C, bw.p, eps, s);
+        else launch_rmsnorm_apb(bx.p, bo.p, M, C, bw.p, eps, s, dsc);
+    } else {
+        if (form == 1) launch_split_rows_apb(bx.p, C, M, C, bo.p, s);
+        else launch_quant_mx8(bx.p, C, M, C, bo.p, dsc, s);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    CHK(gemm_tap_fetch(out, out_capacity, bo, out_bytes, "out"));
+    if (form == 2) CHK(gemm_tap_fetch(out_scales, scales_capacity, bsc, sc_bytes, "scales"));
+    return 0;
+}
+
 // developer instrumentation (not part of the public header): one CSV line per profiled launch
 __attribute__((visibility("default"))) int mellow_dev_prof_dump(mellow_engine_t* e, const char* path) {
     if (!e || !path) return fail("bad argument");

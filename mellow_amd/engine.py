@@ -64,7 +64,7 @@ _ADDED_UNDER_MINOR_4 = ("mellow_lm_score", "mellow_score", "mellow_generate_scor
 # symbols of minor 5 (the attention taps on host data): looked up the same way, so that a minor-4 library still loads
 _ADDED_UNDER_MINOR_5 = ("mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_generate_rules", "mellow_logit_rules_apply",
                         "mellow_generate_guidance", "mellow_guidance_apply", "mellow_generate_top_logprobs", "mellow_top_logprobs_apply",
-                        "mellow_debug_gemm_epi", "mellow_generate_filters", "mellow_sample_logits_filtered")
+                        "mellow_debug_gemm_epi", "mellow_generate_filters", "mellow_sample_logits_filtered", "mellow_debug_norm")
 
 
 def load_library(path: Optional[str] = None):
@@ -127,6 +127,7 @@ def load_library(path: Optional[str] = None):
         "mellow_debug_gemm_fp8": (ci, [vp, vp, ci, ci, vp, ci, vp, ci, vp]),
         "mellow_debug_gemm_f32": (ci, [vp, ci, vp, ci, ci, vp, ci, vp, ci, vp]),
         "mellow_debug_gemm_epi": (ci, [vp, P(GemmEpi), vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64]),
+        "mellow_debug_norm": (ci, [vp, ci, ci, vp, ci, ci, vp, vp, cf, vp, ci, ci, ci, vp, i64, vp, i64]),
         "mellow_debug_prefill_attn": (ci, [vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp, i64]),
         "mellow_debug_window_attn": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, i64]),
         "mellow_debug_dec_head": (ci, [vp, vp, ci, ci, vp]),
@@ -171,7 +172,7 @@ EXPORTED_SYMBOLS = (
     "mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse", "mellow_generate_n", "mellow_generate_q",
     "mellow_generate_beam", "mellow_beam_select", "mellow_generate_rules", "mellow_logit_rules_apply", "mellow_generate_guidance", "mellow_guidance_apply", "mellow_generate_top_logprobs", "mellow_top_logprobs_apply", "mellow_generate_filters", "mellow_sample_logits_filtered", "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
     "mellow_prof_num_families", "mellow_prof_family_name", "mellow_prof_get", "mellow_last_phase_ms", "mellow_last_steps_enqueued", "mellow_last_row_repacks", "mellow_stft_is_fft", "mellow_prefill_parts", "mellow_abi_minor",
-    "mellow_resample", "mellow_engine_set_precision", "mellow_engine_set_option", "mellow_engine_describe", "mellow_debug_gemm_fp8", "mellow_debug_gemm_f32", "mellow_debug_gemm_epi", "mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_debug_dec_head", "mellow_set_graph", "mellow_host_window_map", "mellow_host_pack_weight", "mellow_host_rope_tables",
+    "mellow_resample", "mellow_engine_set_precision", "mellow_engine_set_option", "mellow_engine_describe", "mellow_debug_gemm_fp8", "mellow_debug_gemm_f32", "mellow_debug_gemm_epi", "mellow_debug_norm", "mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_debug_dec_head", "mellow_set_graph", "mellow_host_window_map", "mellow_host_pack_weight", "mellow_host_rope_tables",
 )
 
 
@@ -1182,6 +1183,48 @@ class Engine:
         self._chk(self.lib.mellow_debug_gemm_epi(self.h, C.byref(d), p(A), p(W), p(bias), p(resid), p(cmap), p(rs_ssq), p(cos), p(sin),
                                                  p(out.get("c")), nb("c"), p(out.get("c3")), nb("c3"), p(out.get("ssq")), nb("ssq"),
                                                  p(out.get("q")), nb("q"), p(out.get("k")), p(out.get("v")), nb("k")))
+        return out
+
+    def debug_norm(self, x, op: str = "layernorm", form: int = 0, w=None, b=None, eps: float = 1e-5, row_map=None, n: int = 0,
+                   R: int = 0) -> dict:
+        """One launch of a norm launcher or of a stand-alone hand-over producer on host rows (mellow_debug_norm).  op "layernorm"
+        (x [M][C], optional row_map int32 [ntok]) | "merge" (x [n][R * R][C] -> n (R / 2)^2 rows of 4 C) | "rmsnorm" (eps) | "none"
+        (launch_split_rows_apb / launch_quant_mx8 on x itself).  form 0 fp32 rows, 1 APB image, 2 AMX image + scale bytes.  -> dict
+        of the whole device outputs, which held 0xFF bytes before the launch: "y" f32 [M + 32][columns], or "apb" the raw image as
+        int32 words, or "amx" uint8 [roundup(M, 128) * roundup(C, 64)] plus "scales" uint8 [roundup(M, 128) * 8 * KQ]."""
+        self._need("mellow_debug_norm")
+        f32 = lambda t: None if t is None else torch.as_tensor(t).detach().cpu().contiguous().float()       # noqa: E731
+        x, w, b = f32(x), f32(w), f32(b)
+        o, form = {"layernorm": 0, "merge": 1, "rmsnorm": 2, "none": 3}[op], int(form)
+        Cc = int(x.shape[-1])
+        if o == 1:
+            if x.dim() != 3 or x.shape[0] != n or x.shape[1] != R * R:
+                raise ValueError(f"x {tuple(x.shape)} is not [n = {n}][R * R = {R * R}][C]")
+            M, width = int(n) * (int(R) // 2) ** 2, 4 * Cc
+        else:
+            if x.dim() != 2:
+                raise ValueError(f"x {tuple(x.shape)} is not [M][C]")
+            M, width = int(x.shape[0]), Cc
+        for name, v in (("w", w), ("b", b)):
+            if v is not None and v.numel() != width:
+                raise ValueError(f"{name} has {v.numel()} elements for {width} columns")
+        rmap = None if row_map is None else torch.as_tensor(row_map).detach().cpu().contiguous().to(torch.int32)
+        Mp = (max(M, 0) + 127) // 128 * 128
+        out = {}
+        if form == 0:
+            out["y"] = torch.empty((max(M, 0) + 32, width), dtype=torch.float32)
+        elif form == 1:
+            out["apb"] = torch.empty((Mp * Cc * 6 // 4,), dtype=torch.int32)
+        else:
+            kt64 = (Cc + 63) // 64
+            out["amx"] = torch.empty((Mp * kt64 * 64,), dtype=torch.uint8)
+            out["scales"] = torch.empty((Mp * 8 * ((kt64 + 3) // 4),), dtype=torch.uint8)
+        main = out.get("y", out.get("apb", out.get("amx")))
+        p = lambda t: None if t is None else _ptr(t)      # noqa: E731
+        nbytes = lambda t: 0 if t is None else t.numel() * t.element_size()      # noqa: E731
+        self._chk(self.lib.mellow_debug_norm(self.h, o, form, p(x), M, Cc, p(w), p(b), float(eps), p(rmap),
+                                             0 if rmap is None else int(rmap.numel()), int(n), int(R), p(main), nbytes(main),
+                                             p(out.get("scales")), nbytes(out.get("scales"))))
         return out
 
     @staticmethod

@@ -76,6 +76,30 @@ def test_gemm_epilogue_tap_is_declared_bound_and_refuses_without_a_device(lib):
         e.debug_gemm_epi(None, None)
 
 
+def test_norm_tap_is_declared_bound_and_refuses_without_a_device(lib):
+    hdr = open(os.path.join(ROOT, "include", "mellow_hip.h")).read()
+    name = "mellow_debug_norm"
+    assert re.search(r"\bint\s+%s\s*\(" % name, hdr)
+    assert name in E.EXPORTED_SYMBOLS and name in E._ADDED_UNDER_MINOR_5
+    assert lib.mellow_abi_minor() == 5          # added under the current minor: found by symbol lookup, not by the number
+    fn = getattr(lib, name)
+    assert fn.restype is ctypes.c_int and len(fn.argtypes) == 17 and fn.argtypes[-1] is ctypes.c_int64 and fn.argtypes[8] is ctypes.c_float
+    # the binding's argument list is the header's: one entry per declared parameter, pointers as pointers
+    decl = re.search(r"int\s+%s\s*\((.*?)\);" % name, hdr, re.S).group(1)
+    params = [a.strip() for a in decl.split(",")]
+    assert len(params) == len(fn.argtypes)
+    for a, t in zip(params, fn.argtypes):
+        want = ctypes.c_void_p if "*" in a else ctypes.c_float if a.startswith("float") else ctypes.c_int64 if a.startswith("int64_t") else ctypes.c_int
+        assert t is want, (a, t)
+    # host code only: a null engine is refused before any device is touched
+    assert fn(*[None if t is ctypes.c_void_p else t(1) for t in fn.argtypes]) != 0
+    assert "null argument" in lib.mellow_last_error().decode()
+    e = object.__new__(E.Engine)
+    e.lib, e.h = type("OldLib", (), {})(), None
+    with pytest.raises(E.EngineError, match="predates mellow_debug_norm"):
+        e.debug_norm(torch.zeros(4, 96))
+
+
 def test_required_keys_are_the_reference_state_dict_keys(lib):
     from mellow_amd import spec
     layout = spec.state_dict_layout()
