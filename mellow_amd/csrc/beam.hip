@@ -19,51 +19,22 @@
 // the copy is never done in place.  Fixed grids, grid-stride loops; the position and the parent table are read from device words.
 #include "common.h"
 #include "kernels.h"
+#include "step_tail.h"
 
 namespace mellow {
 
 namespace {
 
-constexpr int BM_THREADS = 1024, BM_WAVES = BM_THREADS / 64;
-constexpr int BM_NV4 = SAMPLE_MAX_V / 4 / BM_THREADS;      // float4 groups per thread (12)
-static_assert(BM_NV4 * 4 * BM_THREADS == SAMPLE_MAX_V, "row tiling");
 static_assert(BEAM_MAX_K * BEAM_MAX_K <= 64, "one wave ranks an example's survivors");
 
-__device__ __forceinline__ int64_t f32_idx(int rb, int K8, int m, int k) {      // decode.hip's F32-layout index
-    return ((int64_t)rb * K8 + (k >> 3)) * 64 + m + 32 * ((k >> 2) & 1);
-}
+// order key of a candidate value (c carries no -0: the callers add +0).  Unlike the sampler, which has left before it forms a key, the
+// select meets NaN candidates (a NaN logit makes the row's lse NaN): every NaN maps to the one largest key (the arg-max rule: a NaN is
+// the maximum, ties go to the lowest index)
+__device__ __forceinline__ uint32_t ckey(float c) { return c != c ? 0xFFFFFFFFu : order_key(c); }
 
-// order key of a candidate value: a > b <=> ckey(a) > ckey(b) for non-NaN values (c carries no -0: the callers add +0), equal keys
-// <=> equal values; every NaN maps to the one largest key (the arg-max rule: a NaN is the maximum, ties go to the lowest index)
-__device__ __forceinline__ uint32_t ckey(float c) {
-    if (c != c) return 0xFFFFFFFFu;
-    const uint32_t u = __float_as_uint(c);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// a copy of a register value the compiler cannot see through: keeps the key arithmetic inside the round loop (hoisted out, the
-// 48 keys of a thread's row slice would be live next to the 48 logits: 128-VGPR budget of a 1024-thread workgroup)
-__device__ __forceinline__ float opaque(float x) {
-    asm volatile("" : "+v"(x));
-    return x;
-}
-
-template <typename T, typename Op>
-__device__ __forceinline__ T block_reduce(T v, Op op, T* red) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_xor(v, off, 64));
-    if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
-    T r = red[0];
-    for (int w = 1; w < BM_WAVES; ++w) r = op(r, red[w]);
-    __syncthreads();
-    return r;
-}
-
-__global__ __launch_bounds__(BM_THREADS) void beam_rows_kernel(const BeamArgs g, const int32_t* __restrict__ params) {
-    __shared__ float red_f[BM_WAVES];
-    __shared__ unsigned long long red_u[BM_WAVES];
+__global__ __launch_bounds__(ROW_THREADS) void beam_rows_kernel(const BeamArgs g, const int32_t* __restrict__ params) {
+    __shared__ float red_f[ROW_WAVES];
+    __shared__ unsigned long long red_u[ROW_WAVES];
     const int r = blockIdx.x, tid = threadIdx.x;
     const float cum = g.cum_in[r];
     float* cc = g.cand_c + (int64_t)r * BEAM_MAX_K;
@@ -77,11 +48,11 @@ __global__ __launch_bounds__(BM_THREADS) void beam_rows_kernel(const BeamArgs g,
         return;
     }
     const float* __restrict__ lrow = g.logits + (int64_t)r * g.ld;
-    float l[BM_NV4][4];
+    float l[ROW_NV4][4];
     float m = -INFINITY;
 #pragma unroll
-    for (int k = 0; k < BM_NV4; ++k) {
-        const float4 v = reinterpret_cast<const float4*>(lrow)[k * BM_THREADS + tid];
+    for (int k = 0; k < ROW_NV4; ++k) {
+        const float4 v = reinterpret_cast<const float4*>(lrow)[k * ROW_THREADS + tid];
         l[k][0] = v.x; l[k][1] = v.y; l[k][2] = v.z; l[k][3] = v.w;
 #pragma unroll
         for (int j = 0; j < 4; ++j) m = fmaxf(m, l[k][j]);
@@ -91,7 +62,7 @@ __global__ __launch_bounds__(BM_THREADS) void beam_rows_kernel(const BeamArgs g,
     // in ascending order.  A NaN logit makes S, and with it lse and every candidate of the row, NaN.
     float s = 0.f;
 #pragma unroll
-    for (int k = 0; k < BM_NV4; ++k)
+    for (int k = 0; k < ROW_NV4; ++k)
 #pragma unroll
         for (int j = 0; j < 4; ++j) s += expf(l[k][j] - M);
     const float S = block_reduce(s, [](float a, float b) { return a + b; }, red_f);
@@ -106,11 +77,11 @@ __global__ __launch_bounds__(BM_THREADS) void beam_rows_kernel(const BeamArgs g,
         const uint32_t pkey = (uint32_t)(prev >> 32), pinv = (uint32_t)prev;
         uint32_t bkey = 0u, binv = 0u;
 #pragma unroll
-        for (int k = 0; k < BM_NV4; ++k)
+        for (int k = 0; k < ROW_NV4; ++k)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const uint32_t key = ckey(cum + (opaque(l[k][j]) - lse) + 0.0f);
-                const uint32_t inv = (uint32_t)(0x7fffffff - (4 * (k * BM_THREADS + tid) + j));
+                const uint32_t inv = (uint32_t)(0x7fffffff - (4 * (k * ROW_THREADS + tid) + j));
                 if ((key < pkey || (key == pkey && inv < pinv)) && (key > bkey || (key == bkey && inv > binv))) { bkey = key; binv = inv; }
             }
         unsigned long long best = ((unsigned long long)bkey << 32) | binv;
@@ -125,8 +96,9 @@ __global__ __launch_bounds__(BM_THREADS) void beam_rows_kernel(const BeamArgs g,
     }
 }
 
-// LOOP: the bookkeeping of dec_argmax_kernel for the k new beams of the example (tables at the step's row, cum / fin, embedding
-// gather, finished count, publish).  The tap (LOOP = false) writes the four outputs [N] and nothing else.
+// LOOP: the step's bookkeeping for the k new beams of the example: its own tables at the step's row, cum / fin and the finished
+// count, then the publish and the embedding gather of the step epilogue (step_tail.h).  The tap (LOOP = false) writes the four
+// outputs [N] and nothing else.
 template <bool LOOP>
 __global__ __launch_bounds__(64) void beam_merge_kernel(const BeamArgs g, const DecArgs a, int32_t* __restrict__ tokens,
                                                         const float* __restrict__ embed, const LoopArgs lp) {
@@ -181,26 +153,14 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(const BeamArgs g, const 
         const int nfin = __popcll(__ballot(fin));
         if (lane == 0) {
             // the finished count of a step is formed anew (it can fall): every example adds its own, the last arrival takes the
-            // total and leaves the word at 0 for the next step.  Ordering as in dec_argmax_kernel: this wave's atomics must have
-            // been performed before its arrival is counted -- a drained vmcnt is enough for device-scope atomics.
+            // total and leaves the word at 0 for the next step
             if (nfin) atomicAdd(lp.n_seen, nfin);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (atomicAdd(lp.arrive, 1) == (int)gridDim.x - 1) {
-                *lp.arrive = 0;
-                const int t = *lp.ticket + 1;
-                *lp.ticket = t;
-                const int ns = atomicExch(lp.n_seen, 0);
-                __hip_atomic_store(lp.host_progress, ((unsigned long long)(unsigned)t << 32) | (unsigned)ns, __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_SYSTEM);
-            }
+            step_publish(lp, [n_seen = lp.n_seen] { return atomicExch(n_seen, 0); });
         }
         // embed[token] of every new beam: the next step's residual row
         for (int j = 0; j < k; ++j) {
             const int row = b * k + j, t = min(max(sel_tok[j], 0), SAMPLE_MAX_V - 1);
-            for (int i = lane; i < 144; i += 64) {
-                const float4 e = reinterpret_cast<const float4*>(embed + (int64_t)t * 576)[i];
-                reinterpret_cast<float4*>(a.xmidF)[f32_idx(row >> 5, 72, row & 31, i * 4)] = e;
-            }
+            for (int i = lane; i < 144; i += 64) step_embed_gather(embed, t, a, row, i);
         }
     }
 }
@@ -242,7 +202,7 @@ __global__ __launch_bounds__(256) void beam_kv_move_kernel(float4* __restrict__ 
 
 void launch_beam_select(const BeamArgs& g, int B, const DecArgs& a, int32_t* tokens, const float* embed, const LoopArgs* loop, hipStream_t s) {
     if (B <= 0 || g.k < 1 || g.k > BEAM_MAX_K || g.ld != SAMPLE_MAX_V) return;      // (the engine never asks for these)
-    hipLaunchKernelGGL(beam_rows_kernel, dim3(B * g.k), dim3(BM_THREADS), 0, s, g, loop ? loop->params : nullptr);
+    hipLaunchKernelGGL(beam_rows_kernel, dim3(B * g.k), dim3(ROW_THREADS), 0, s, g, loop ? loop->params : nullptr);
     if (loop) hipLaunchKernelGGL(beam_merge_kernel<true>, dim3(B), dim3(64), 0, s, g, a, tokens, embed, *loop);
     else hipLaunchKernelGGL(beam_merge_kernel<false>, dim3(B), dim3(64), 0, s, g, a, tokens, embed, LoopArgs());
 }

@@ -21,7 +21,7 @@ LIBDIR = os.path.join(PKG, "lib")
 OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(LIBDIR, "libmellow_hip.so")
 SOURCES = ["gemm_f32.hip", "gemm_fp8.hip", "gemm_bf16x3.hip", "decode.hip", "prefill_attn.hip", "encoder.hip", "stft_fft.hip", "sample.hip", "score.hip", "beam.hip", "logit_rules.hip", "guidance.hip", "top_logprobs.hip", "engine.cpp", "engine_weights.cpp", "engine_encoder.cpp", "engine_lm.cpp", "engine_generate.cpp", "engine_dev.cpp"]
-HEADERS = ["common.h", "kernels.h", "gemm_epilogue.h", "prefill_attn_f32.inc", "engine_internal.h", os.path.join("..", "..", "include", "mellow_hip.h")]
+HEADERS = ["common.h", "kernels.h", "step_tail.h", "gemm_epilogue.h", "prefill_attn_f32.inc", "engine_internal.h", os.path.join("..", "..", "include", "mellow_hip.h")]
 ARCH = "gfx950"
 FLAGS = (["-DMELLOW_KDEBUG"] if os.environ.get("MELLOW_KDEBUG") else []) + os.environ.get("MELLOW_EXTRA_FLAGS", "").split() + ["-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable", "-x", "hip"]
@@ -79,7 +79,7 @@ def build(force=False, verbose=False, out=None, objdir=None):
         r = subprocess.run(cmd, capture_output=True, text=True)
         return sp, r
 
-    with cf.ThreadPoolExecutor(max_workers=max(1, min(len(jobs), os.cpu_count() or 1))) as ex:
+    with cf.ThreadPoolExecutor(max_workers=max(1, min(len(jobs), int(os.environ.get("MAX_JOBS", 16))))) as ex:
         for sp, r in ex.map(cc, jobs):
             if r.returncode != 0:
                 sys.stderr.write(r.stdout + r.stderr)

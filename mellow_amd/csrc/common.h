@@ -231,6 +231,11 @@ __device__ __forceinline__ void amx_store16(i32x4* img, uint8_t* sc, int64_t m, 
     if (h == 0) sc[amx_scale_byte(m, s, j, KQ)] = (uint8_t)e;
 }
 
+// F32-layout float4 index of (row m of row-block rb, columns k..k+3, k % 4 == 0) for an activation with K8 k-tiles
+__device__ __forceinline__ int64_t f32_idx(int rb, int K8, int m, int k) {
+    return ((int64_t)rb * K8 + (k >> 3)) * 64 + m + 32 * ((k >> 2) & 1);
+}
+
 // XCD-aware block remap (8 XCDs, block b runs on XCD b % 8): logical ids that are consecutive land on
 // the same XCD so tiles sharing an operand panel hit one L2.  Bijective for any block count.
 __device__ __forceinline__ int xcd_remap(int b, int nb) {

@@ -22,6 +22,7 @@
 //     consumers in a fixed order.
 #include "common.h"
 #include "kernels.h"
+#include "step_tail.h"
 #include <cstdio>
 #include <mutex>
 #include <set>
@@ -158,10 +159,6 @@ __device__ __forceinline__ f32x16 mfma4(f32x16 acc, float4 w, float4 x) {
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w.z, x.z, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w.w, x.w, acc, 0, 0, 0);
     return acc;
-}
-// F32-layout float4 index of (row m of row-block rb, columns k..k+3, k % 4 == 0) for an activation with K8 k-tiles
-__device__ __forceinline__ int64_t f32_idx(int rb, int K8, int m, int k) {
-    return ((int64_t)rb * K8 + (k >> 3)) * 64 + m + 32 * ((k >> 2) & 1);
 }
 
 // ----------------------------------------------------------------------------------------------------
@@ -2004,10 +2001,7 @@ __global__ __launch_bounds__(256) void dec_argmax_kernel(const float* __restrict
     __shared__ int tok_s;
     __shared__ float lse_sh[4];
     const int b = blockIdx.x, tid = threadIdx.x;
-    // a slot whose whole block has stopped (or that is empty after a repack) computes nothing any more, but still takes part
-    // in the step's arrival count
-    const int row = lp.row_of_slot ? lp.row_of_slot[b] : b;         // the example in this slot
-    const bool dead = (lp.blk_snap && lp.blk_snap[b >> 5] == 0) || row < 0;      // workgroup-uniform; written by an EARLIER launch
+    const auto [row, dead] = step_slot(lp.row_of_slot, lp.blk_snap, b);      // a dead slot still takes part in the step's arrival count
     float best = -INFINITY;
     int idx = 0x7fffffff;
     if (!dead) {
@@ -2046,40 +2040,16 @@ __global__ __launch_bounds__(256) void dec_argmax_kernel(const float* __restrict
         }
         if (lp.out_tokens) {
             if (!dead) {
-                const int max_len = lp.params[0], stop_id = lp.params[1];
-                const int step = *a.d_pos - lp.T0 + 1;
-                if (step >= 0 && step < max_len) lp.out_tokens[(int64_t)row * max_len + step] = idx;
-                if constexpr (LSE) {
-                    if (step >= 0 && step < max_len) lp.out_logprob[(int64_t)row * max_len + step] = -dec_lse_log(S);
-                }
-                if (idx == stop_id && lp.seen_stop[row] == 0) {
-                    lp.seen_stop[row] = 1;
-                    atomicAdd(lp.n_seen, 1);
-                    if (lp.blk_left && atomicSub(lp.blk_left + (b >> 5), 1) == 1) lp.blk_live[b >> 5] = 0;   // from the NEXT step on
-                }
+                if constexpr (LSE) step_record(lp, a, b, row, idx, [S] { return -dec_lse_log(S); });
+                else step_record(lp, a, b, row, idx);
             }
-            // the last row of this launch publishes the step: ticket = arg-max launches so far, low word = rows stopped.
-            // Ordering: this row's n_seen / blk_left atomics must have been performed before its arrival is counted -- a drained
-            // vmcnt is enough for device-scope atomics (no cache write-back: a __threadfence() here cost ~3 us per step).  The
-            // host reads only the progress word itself before the stream is synchronised, so its store needs no release.
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (atomicAdd(lp.arrive, 1) == (int)gridDim.x - 1) {
-                *lp.arrive = 0;
-                const int t = *lp.ticket + 1;
-                *lp.ticket = t;
-                const int ns = atomicAdd(lp.n_seen, 0);
-                __hip_atomic_store(lp.host_progress, ((unsigned long long)(unsigned)t << 32) | (unsigned)ns, __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_SYSTEM);
-            }
+            step_publish(lp, [n_seen = lp.n_seen] { return atomicAdd(n_seen, 0); });
         }
     }
     if (dead) return;
     if (write_x) {
         __syncthreads();
-        if (tid < 144) {
-            const float4 e = reinterpret_cast<const float4*>(embed + (int64_t)tok_s * 576)[tid];
-            reinterpret_cast<float4*>(a.xmidF)[f32_idx(b >> 5, 72, b & 31, tid * 4)] = e;
-        }
+        if (tid < 144) step_embed_gather(embed, tok_s, a, b, tid);
     }
     kspan(a.dbg_seq, 1);
 }
@@ -2213,10 +2183,7 @@ __global__ __launch_bounds__(192) void dec_load_rows_kernel(const DecArgs a, con
     // caller-supplied ids are clamped to the table (an out-of-range id must not become a wild read; the Python
     // binding rejects it with an IndexError before it gets here)
     const int64_t src = row_ids ? (int64_t)min(max(row_ids[b], 0), n_src - 1) : (int64_t)b * T_last + (T_last - 1);
-    if (tid < 144) {
-        const float4 e = reinterpret_cast<const float4*>(in + src * ld)[tid];
-        reinterpret_cast<float4*>(a.xmidF)[f32_idx(b >> 5, 72, b & 31, tid * 4)] = e;
-    }
+    if (tid < 144) step_store_x(a.xmidF, b, tid, reinterpret_cast<const float4*>(in + src * ld)[tid]);
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------

@@ -14,58 +14,39 @@
 // pair leave the kernel bit-identical.  Logits are finite (they come from the head); +-inf inputs are outside the definition.
 #include "common.h"
 #include "kernels.h"
+#include "step_tail.h"
 
 namespace mellow {
 
 namespace {
 
-constexpr int GD_THREADS = 1024, GD_WAVES = GD_THREADS / 64;
-constexpr int GD_NV4 = SAMPLE_MAX_V / 4 / GD_THREADS;      // float4 groups per thread and row (12)
-constexpr int GD_TILES = SAMPLE_MAX_V / 32;                // 32-column tiles of a row (1536)
-static_assert(GD_NV4 * 4 * GD_THREADS == SAMPLE_MAX_V, "row tiling");
-static_assert(GD_THREADS % 8 == 0 && GD_TILES == GD_NV4 * (GD_THREADS / 8), "a tile is the float4 groups of eight neighbouring lanes");
-
-// butterfly over the wave, then the waves' values in wave order: every thread returns the same bits
-template <typename Op>
-__device__ __forceinline__ float gd_block_reduce(float v, Op op, float* red) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_xor(v, off, 64));
-    if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
-    float r = red[0];
-#pragma unroll
-    for (int w = 1; w < GD_WAVES; ++w) r = op(r, red[w]);
-    __syncthreads();            // (red is rewritten by the next reduction)
-    return r;
-}
-
 // log-sum-exp of one row: m + log(sum exp(l - m)), m the row's maximum
 __device__ __forceinline__ float gd_row_lse(const float* __restrict__ lrow, float* red) {
     const int tid = threadIdx.x;
-    float4 v[GD_NV4];
+    float4 v[ROW_NV4];
 #pragma unroll
-    for (int k = 0; k < GD_NV4; ++k) v[k] = reinterpret_cast<const float4*>(lrow)[k * GD_THREADS + tid];
+    for (int k = 0; k < ROW_NV4; ++k) v[k] = reinterpret_cast<const float4*>(lrow)[k * ROW_THREADS + tid];
     float m = -INFINITY;
 #pragma unroll
-    for (int k = 0; k < GD_NV4; ++k) m = fmaxf(fmaxf(fmaxf(fmaxf(m, v[k].x), v[k].y), v[k].z), v[k].w);
-    m = gd_block_reduce(m, [](float a, float b) { return fmaxf(a, b); }, red);
+    for (int k = 0; k < ROW_NV4; ++k) m = fmaxf(fmaxf(fmaxf(fmaxf(m, v[k].x), v[k].y), v[k].z), v[k].w);
+    m = block_reduce(m, [](float a, float b) { return fmaxf(a, b); }, red);
     float s = 0.f;
 #pragma unroll
-    for (int k = 0; k < GD_NV4; ++k) {
+    for (int k = 0; k < ROW_NV4; ++k) {
         s += expf(v[k].x - m);
         s += expf(v[k].y - m);
         s += expf(v[k].z - m);
         s += expf(v[k].w - m);
     }
-    s = gd_block_reduce(s, [](float a, float b) { return a + b; }, red);
+    s = block_reduce(s, [](float a, float b) { return a + b; }, red);
     return m + logf(s);
 }
 
-__global__ __launch_bounds__(GD_THREADS) void dec_guidance_kernel(const GuideArgs g) {
-    __shared__ float red[GD_WAVES];
+__global__ __launch_bounds__(ROW_THREADS) void dec_guidance_kernel(const GuideArgs g) {
+    __shared__ float red[ROW_WAVES];
     const int p = blockIdx.x, tid = threadIdx.x;
-    if (g.blk_snap && g.blk_snap[(2 * p) >> 5] == 0) return;         // workgroup-uniform; written by an EARLIER launch.  A pair never straddles a row block
+    // (a guided call runs without row migration: no slot table, so not step_slot; a pair never straddles a row block)
+    if (g.blk_snap && g.blk_snap[(2 * p) >> 5] == 0) return;         // workgroup-uniform; written by an EARLIER launch
     const float scale = __uint_as_float(g.prm[GDN_SCALE]);
     float* __restrict__ rc = g.logits + (int64_t)(2 * p) * g.ld;     // conditional row
     float* __restrict__ ru = rc + g.ld;                              // negative row
@@ -75,10 +56,10 @@ __global__ __launch_bounds__(GD_THREADS) void dec_guidance_kernel(const GuideArg
     const float lse_u = gd_row_lse(ru, red);
 
     // ---- pass 2: combine, store to both rows, tile partials -----------------------------------------------------------------------
-    const int64_t cb_c = (int64_t)(2 * p) * GD_TILES, cb_u = cb_c + GD_TILES;
+    const int64_t cb_c = (int64_t)(2 * p) * ROW_TILES, cb_u = cb_c + ROW_TILES;
 #pragma unroll 2
-    for (int k = 0; k < GD_NV4; ++k) {
-        const int i4 = k * GD_THREADS + tid;
+    for (int k = 0; k < ROW_NV4; ++k) {
+        const int i4 = k * ROW_THREADS + tid;
         const float4 c4 = reinterpret_cast<const float4*>(rc)[i4];
         const float4 u4 = reinterpret_cast<const float4*>(ru)[i4];
         const float lc[4] = {c4.x, c4.y, c4.z, c4.w}, lu[4] = {u4.x, u4.y, u4.z, u4.w};
@@ -91,25 +72,9 @@ __global__ __launch_bounds__(GD_THREADS) void dec_guidance_kernel(const GuideArg
         const float4 o = make_float4(v[0], v[1], v[2], v[3]);
         reinterpret_cast<float4*>(rc)[i4] = o;
         reinterpret_cast<float4*>(ru)[i4] = o;
-        // the tile's best (value, lowest index): own four in ascending index, then the eight lanes of the tile
-        float bv = v[0];
-        int bx = 4 * i4;
-#pragma unroll
-        for (int j = 1; j < 4; ++j)
-            if (arg_better(v[j], 4 * i4 + j, bv, bx)) { bv = v[j]; bx = 4 * i4 + j; }
-#pragma unroll
-        for (int off = 1; off < 8; off <<= 1) {
-            const float ov = __shfl_xor(bv, off, 64);
-            const int ox = __shfl_xor(bx, off, 64);
-            if (arg_better(ov, ox, bv, bx)) { bv = ov; bx = ox; }
-        }
+        const auto [bv, bx] = tile_best(v, i4);
         if (g.cand_sum) {
-            // sum exp(g - max) of the tile: a thread's four in ascending order, then a butterfly (both partners form the same sum)
-            float ps = 0.f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) ps += expf(v[j] - bv);
-#pragma unroll
-            for (int off = 1; off < 8; off <<= 1) ps += __shfl_xor(ps, off, 64);
+            const float ps = tile_sum8(tile_exp4(v, bv));            // (no -inf guard: g is finite)
             if ((tid & 7) == 0) {
                 g.cand_sum[cb_c + (i4 >> 3)] = ps;
                 g.cand_sum[cb_u + (i4 >> 3)] = ps;
@@ -128,7 +93,7 @@ __global__ __launch_bounds__(GD_THREADS) void dec_guidance_kernel(const GuideArg
 
 void launch_dec_guidance(const GuideArgs& g, int P, hipStream_t s) {
     if (P <= 0 || g.ld != SAMPLE_MAX_V) return;      // (the engine never asks for these)
-    hipLaunchKernelGGL(dec_guidance_kernel, dim3(P), dim3(GD_THREADS), 0, s, g);
+    hipLaunchKernelGGL(dec_guidance_kernel, dim3(P), dim3(ROW_THREADS), 0, s, g);
 }
 
 }  // namespace mellow

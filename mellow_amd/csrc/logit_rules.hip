@@ -15,27 +15,22 @@
 // No float atomics and no arrival order anywhere: the bits depend on the inputs only.
 #include "common.h"
 #include "kernels.h"
+#include "step_tail.h"
 
 namespace mellow {
 
 namespace {
 
-constexpr int RL_THREADS = 1024;
-constexpr int RL_NV4 = SAMPLE_MAX_V / 4 / RL_THREADS;      // float4 groups per thread (12)
-constexpr int RL_WORDS = SAMPLE_MAX_V / 32;                // words of one bitmap = 32-column tiles of a row (1536)
-static_assert(RL_NV4 * 4 * RL_THREADS == SAMPLE_MAX_V, "row tiling");
-static_assert(RL_THREADS % 8 == 0 && RL_WORDS == RL_NV4 * (RL_THREADS / 8), "a tile is the float4 groups of eight neighbouring lanes");
-
 __device__ __forceinline__ void mark(uint32_t* map, int t) {
     if ((unsigned)t < (unsigned)SAMPLE_MAX_V) atomicOr(&map[t >> 5], 1u << (t & 31));      // (an id outside the vocabulary marks nothing)
 }
 
-__global__ __launch_bounds__(RL_THREADS) void dec_logit_rules_kernel(const RulesArgs g) {
+__global__ __launch_bounds__(ROW_THREADS) void dec_logit_rules_kernel(const RulesArgs g) {
     __shared__ int32_t hist[RULES_MAX_HIST];
-    __shared__ uint32_t pen[RL_WORDS], ban[RL_WORDS];
+    __shared__ uint32_t pen[ROW_TILES], ban[ROW_TILES];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int row = g.row_of_slot ? g.row_of_slot[b] : b;             // the example in this slot
-    if ((g.blk_snap && g.blk_snap[b >> 5] == 0) || row < 0) return;   // workgroup-uniform; written by an EARLIER launch
+    const auto [row, dead] = step_slot(g.row_of_slot, g.blk_snap, b);
+    if (dead) return;
 
     const float theta = __uint_as_float(g.prm[RUL_THETA]);
     const int n = (int)g.prm[RUL_NGRAM], min_new = (int)g.prm[RUL_MIN_NEW], stop_id = (int)g.prm[RUL_STOP];
@@ -46,7 +41,7 @@ __global__ __launch_bounds__(RL_THREADS) void dec_logit_rules_kernel(const Rules
     if (g.hist_len) {                                                 // tap: caller rows, a length per row
         s = min(max(g.hist_len[b], 0), min(g.hist_ld, RULES_MAX_HIST));
         const int32_t* __restrict__ h = g.hist + (int64_t)b * g.hist_ld;
-        for (int i = tid; i < s; i += RL_THREADS) hist[i] = h[i];
+        for (int i = tid; i < s; i += ROW_THREADS) hist[i] = h[i];
     } else {
         const int max_len = min(g.params[0], RULES_MAX_HIST);
         s = min(max(*g.d_pos - g.T0 + 1, 0), max_len);
@@ -57,7 +52,7 @@ __global__ __launch_bounds__(RL_THREADS) void dec_logit_rules_kernel(const Rules
                 const int pr = row / g.k * g.k + min(max(g.parent_tab[(int64_t)(s - 1) * g.N + row], 0), g.k - 1);
                 const int32_t* __restrict__ src = g.beam_hist + ((int64_t)((s - 1) & 1) * g.N + pr) * g.hist_ld;
                 int32_t* __restrict__ dst = g.beam_hist + ((int64_t)(s & 1) * g.N + row) * g.hist_ld;
-                for (int i = tid; i < s; i += RL_THREADS) {
+                for (int i = tid; i < s; i += ROW_THREADS) {
                     const int32_t t = i < s - 1 ? src[i] : g.token_tab[(int64_t)(s - 1) * g.N + row];
                     hist[i] = t;
                     dst[i] = t;
@@ -65,17 +60,17 @@ __global__ __launch_bounds__(RL_THREADS) void dec_logit_rules_kernel(const Rules
             }
         } else {
             const int32_t* __restrict__ h = g.hist + (int64_t)row * g.params[0];      // the token record: columns [0, s) are written
-            for (int i = tid; i < s; i += RL_THREADS) hist[i] = h[i];
+            for (int i = tid; i < s; i += ROW_THREADS) hist[i] = h[i];
         }
     }
-    for (int i = tid; i < RL_WORDS; i += RL_THREADS) { pen[i] = 0u; ban[i] = 0u; }
+    for (int i = tid; i < ROW_TILES; i += ROW_THREADS) { pen[i] = 0u; ban[i] = 0u; }
     __syncthreads();
 
     // ---- 2. the two sets --------------------------------------------------------------------------------------------------------
-    for (int i = tid; i < s; i += RL_THREADS) mark(pen, hist[i]);
+    for (int i = tid; i < s; i += ROW_THREADS) mark(pen, hist[i]);
     if (n > 0 && s >= n - 1) {
         // position i starts an (n - 1)-gram equal to the last n - 1 tokens: the token after it would repeat an n-gram
-        for (int i = tid; i <= s - n; i += RL_THREADS) {
+        for (int i = tid; i <= s - n; i += ROW_THREADS) {
             bool eq = true;
             for (int j = 0; j < n - 1 && eq; ++j) eq = hist[i + j] == hist[s - n + 1 + j];
             if (eq) mark(ban, hist[i + n - 1]);
@@ -86,10 +81,10 @@ __global__ __launch_bounds__(RL_THREADS) void dec_logit_rules_kernel(const Rules
 
     // ---- 3. apply, 4. tile partials ---------------------------------------------------------------------------------------------
     float* __restrict__ lrow = g.logits + (int64_t)b * g.ld;
-    const int64_t cbase = (int64_t)b * RL_WORDS;
+    const int64_t cbase = (int64_t)b * ROW_TILES;
 #pragma unroll 2
-    for (int k = 0; k < RL_NV4; ++k) {
-        const int i4 = k * RL_THREADS + tid;
+    for (int k = 0; k < ROW_NV4; ++k) {
+        const int i4 = k * ROW_THREADS + tid;
         const float4 v4 = reinterpret_cast<const float4*>(lrow)[i4];
         float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
         if (bias_on) b4 = reinterpret_cast<const float4*>(g.bias)[i4];
@@ -107,28 +102,12 @@ __global__ __launch_bounds__(RL_THREADS) void dec_logit_rules_kernel(const Rules
             changed |= __float_as_uint(x) != __float_as_uint(in[j]);
         }
         if (changed) reinterpret_cast<float4*>(lrow)[i4] = make_float4(v[0], v[1], v[2], v[3]);
-        // the tile's best (value, lowest index): own four in ascending index, then the eight lanes of the tile
-        float bv = v[0];
-        int bx = 4 * i4;
-#pragma unroll
-        for (int j = 1; j < 4; ++j)
-            if (arg_better(v[j], 4 * i4 + j, bv, bx)) { bv = v[j]; bx = 4 * i4 + j; }
-#pragma unroll
-        for (int off = 1; off < 8; off <<= 1) {
-            const float ov = __shfl_xor(bv, off, 64);
-            const int ox = __shfl_xor(bx, off, 64);
-            if (arg_better(ov, ox, bv, bx)) { bv = ov; bx = ox; }
-        }
+        const auto [bv, bx] = tile_best(v, i4);
         if (g.cand_sum) {
-            // sum exp(l - max) of the tile: a thread's four in ascending order, then a butterfly (both partners form the same sum).
-            // A tile whose maximum is -inf (banned whole) sums to exactly 0: no exp(-inf - -inf)
+            // a tile whose maximum is -inf (banned whole) sums to exactly 0: no exp(-inf - -inf)
             float ps = 0.f;
-            if (bv > -INFINITY || bv != bv) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) ps += expf(v[j] - bv);
-            }
-#pragma unroll
-            for (int off = 1; off < 8; off <<= 1) ps += __shfl_xor(ps, off, 64);
+            if (bv > -INFINITY || bv != bv) ps = tile_exp4(v, bv);
+            ps = tile_sum8(ps);
             if ((tid & 7) == 0) g.cand_sum[cbase + (i4 >> 3)] = ps;
         }
         if ((tid & 7) == 0) {
@@ -142,7 +121,7 @@ __global__ __launch_bounds__(RL_THREADS) void dec_logit_rules_kernel(const Rules
 
 void launch_dec_logit_rules(const RulesArgs& g, int B, hipStream_t s) {
     if (B <= 0 || g.ld != SAMPLE_MAX_V) return;      // (the engine never asks for these)
-    hipLaunchKernelGGL(dec_logit_rules_kernel, dim3(B), dim3(RL_THREADS), 0, s, g);
+    hipLaunchKernelGGL(dec_logit_rules_kernel, dim3(B), dim3(ROW_THREADS), 0, s, g);
 }
 
 }  // namespace mellow

@@ -9,7 +9,7 @@
 //      integer mass) finds the boundary key; ties on that key are cut by index with a second select over the index (counts);
 //   4. Gumbel-max over the kept tokens: argmax (z + g), g = -log(-log u), u from Philox4x32-10 keyed by (seed) with counter
 //      (index / 4, step, global row, 0); ties to the lowest index.  Noise is only formed for kept tokens.
-// The loop variant then does exactly the bookkeeping of dec_argmax_kernel (decode.hip), which it replaces in the step.
+// The loop variant then runs the step epilogue (step_tail.h) as dec_argmax_kernel (decode.hip) does, which it replaces in the step.
 //
 // The filtered instantiation (FILT; include/mellow_hip.h, mellow_generate_filters) puts two more filters around step 3, in Hugging
 // Face's order top_k, top_p, min_p:
@@ -22,38 +22,14 @@
 // (K = 0, qmin = 0) give the plain instantiation's draw, bit for bit.
 #include "common.h"
 #include "kernels.h"
+#include "step_tail.h"
 
 namespace mellow {
 
 namespace {
 
-constexpr int SMP_THREADS = 1024, SMP_WAVES = SMP_THREADS / 64;
-constexpr int SMP_NV4 = SAMPLE_MAX_V / 4 / SMP_THREADS;      // float4 groups per thread (12)
-static_assert(SMP_NV4 * 4 * SMP_THREADS == SAMPLE_MAX_V, "row tiling");
-
-__device__ __forceinline__ int64_t f32_idx(int rb, int K8, int m, int k) {      // decode.hip's F32-layout index
-    return ((int64_t)rb * K8 + (k >> 3)) * 64 + m + 32 * ((k >> 2) & 1);
-}
-
-// order-preserving key: a > b (as floats, no NaN) <=> okey(a) > okey(b); equal keys <=> equal values (z carries no -0)
-__device__ __forceinline__ uint32_t okey(float z) {
-    const uint32_t u = __float_as_uint(z);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// a copy of a register value the compiler cannot see through: keeps per-pass key / mass arithmetic inside the pass loops
-// (hoisted out, the 48 keys, masses and sign masks of a thread's row slice would be live at once: 128-VGPR budget, spills)
-__device__ __forceinline__ float opaque(float x) {
-    asm volatile("" : "+v"(x));
-    return x;
-}
-
-// the same for a thread index: an element's index is formed again where it is needed (seen through, the 48 index keys of a thread's
-// slice are hoisted out of the index select's two passes and spilled; the filtered instantiation uses this and runs without them)
-__device__ __forceinline__ int opaque(int x) {
-    asm volatile("" : "+v"(x));
-    return x;
-}
+// (the keys of this file are order_key(z) as it stands: z carries no -0, sample_row adds +0 where it forms z, and a row with a NaN
+// has left before any key is formed)
 
 // Philox4x32-10 (Salmon et al., SC'11; Random123's constants)
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
@@ -69,7 +45,7 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
 }
 
 struct SelScratch {
-    unsigned long long hist[SMP_WAVES][256];   // per-wave histograms (integer adds: order-free)
+    unsigned long long hist[ROW_WAVES][256];   // per-wave histograms (integer adds: order-free)
     unsigned long long bin[256];
     uint32_t digit;
     unsigned long long above, mass;
@@ -88,10 +64,10 @@ __device__ __forceinline__ bool radix_select(KeyF key_of, WF w_of, ThrF thr_of, 
     uint32_t prefix = 0, pmask = shift_hi + 8 >= 32 ? 0u : ~0u << (shift_hi + 8);
     unsigned long long above = 0, mass = 0, thr = 0;
     for (int shift = shift_hi; shift >= 0; shift -= 8) {
-        for (int i = tid; i < SMP_WAVES * 256; i += SMP_THREADS) (&sh.hist[0][0])[i] = 0ull;
+        for (int i = tid; i < ROW_WAVES * 256; i += ROW_THREADS) (&sh.hist[0][0])[i] = 0ull;
         __syncthreads();
 #pragma unroll
-        for (int k = 0; k < SMP_NV4; ++k)
+        for (int k = 0; k < ROW_NV4; ++k)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 uint32_t key;
@@ -103,7 +79,7 @@ __device__ __forceinline__ bool radix_select(KeyF key_of, WF w_of, ThrF thr_of, 
         __syncthreads();
         if (tid < 256) {
             unsigned long long s = 0;
-            for (int w = 0; w < SMP_WAVES; ++w) s += sh.hist[w][tid];
+            for (int w = 0; w < ROW_WAVES; ++w) s += sh.hist[w][tid];
             sh.bin[tid] = s;
         }
         __syncthreads();
@@ -142,37 +118,24 @@ __device__ __forceinline__ bool radix_select(KeyF key_of, WF w_of, ThrF thr_of, 
     return true;
 }
 
-template <typename T, typename Op>
-__device__ __forceinline__ T block_reduce(T v, Op op, T* red) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_xor(v, off, 64));
-    if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
-    T r = red[0];
-    for (int w = 1; w < SMP_WAVES; ++w) r = op(r, red[w]);
-    __syncthreads();
-    return r;
-}
-
 // the draw of one row: returns the token (workgroup-uniform)
 template <bool FILT>
 __device__ __forceinline__ int sample_row(const float* __restrict__ lrow, const uint32_t* __restrict__ prm, uint32_t grow,
                                           uint32_t step) {
     __shared__ SelScratch sh;
-    __shared__ float red_f[SMP_WAVES];
-    __shared__ int red_i[SMP_WAVES];
+    __shared__ float red_f[ROW_WAVES];
+    __shared__ int red_i[ROW_WAVES];
     __shared__ uint32_t qtie_s;
     const int tid = threadIdx.x;
     const uint32_t seed_lo = prm[SMP_SEED_LO], seed_hi = prm[SMP_SEED_HI];
     const float top_p = __uint_as_float(prm[SMP_TOP_P]), temp = __uint_as_float(prm[SMP_TEMP]);
 
-    float z[SMP_NV4][4];
+    float z[ROW_NV4][4];
     int nan_idx = 0x7fffffff;
     float m = -INFINITY;
 #pragma unroll
-    for (int k = 0; k < SMP_NV4; ++k) {
-        const int i4 = k * SMP_THREADS + tid;
+    for (int k = 0; k < ROW_NV4; ++k) {
+        const int i4 = k * ROW_THREADS + tid;
         const float4 v = reinterpret_cast<const float4*>(lrow)[i4];
         const float vv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -203,15 +166,15 @@ __device__ __forceinline__ int sample_row(const float* __restrict__ lrow, const 
         if (top_k > 0 && top_k < (uint32_t)SAMPLE_MAX_V) {
             // T = the first top_k tokens of the order: the pair (kstar, idx_cut)
             unsigned long long above, mass, thr;
-            radix_select([&](int k, int j, uint32_t& key) { key = okey(opaque(z[k][j])); return true; }, [](int, int) { return 1ull; },
+            radix_select([&](int k, int j, uint32_t& key) { key = order_key(opaque(z[k][j])); return true; }, [](int, int) { return 1ull; },
                          [top_k](unsigned long long) { return (unsigned long long)top_k - 1; }, 24, sh, kstar, above, mass, thr);
             const unsigned long long c = top_k - above;       // 1 <= c <= mass: the tie group's share
             if (c < mass) {
                 uint32_t kidx;
                 unsigned long long a2, m2, t2;
                 radix_select([&](int k, int j, uint32_t& key) {
-                                 key = 0xFFFFu - (uint32_t)(4 * (k * SMP_THREADS + opaque(tid)) + j);
-                                 return okey(opaque(z[k][j])) == kstar; },
+                                 key = 0xFFFFu - (uint32_t)(4 * (k * ROW_THREADS + opaque(tid)) + j);
+                                 return order_key(opaque(z[k][j])) == kstar; },
                              [](int, int) { return 1ull; }, [c](unsigned long long) { return c - 1; }, 8, sh, kidx, a2, m2, t2);
                 idx_cut = (int)(0xFFFFu - kidx);
             }
@@ -219,11 +182,11 @@ __device__ __forceinline__ int sample_row(const float* __restrict__ lrow, const 
             // every token outside T leaves the row (z = -inf: mass 0 in the nucleus below, and never on its boundary key, whose bin
             // has mass > 0), so the nucleus select and its tie counts see the participants only.  m is in T.
 #pragma unroll
-            for (int k = 0; k < SMP_NV4; ++k)
+            for (int k = 0; k < ROW_NV4; ++k)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const uint32_t key = okey(z[k][j]);
-                    if (!(key > kstar || (key == kstar && 4 * (k * SMP_THREADS + tid) + j <= idx_cut))) z[k][j] = -INFINITY;
+                    const uint32_t key = order_key(z[k][j]);
+                    if (!(key > kstar || (key == kstar && 4 * (k * ROW_THREADS + tid) + j <= idx_cut))) z[k][j] = -INFINITY;
                 }
         }
         if (top_p < 1.0f) {
@@ -231,15 +194,15 @@ __device__ __forceinline__ int sample_row(const float* __restrict__ lrow, const 
             // weigh nothing), and its tie group holds tokens of T only.
             uint32_t kp;
             unsigned long long above, mass, thr;
-            if (radix_select([&](int k, int j, uint32_t& key) { key = okey(opaque(z[k][j])); return true; }, q_of,
+            if (radix_select([&](int k, int j, uint32_t& key) { key = order_key(opaque(z[k][j])); return true; }, q_of,
                              [&](unsigned long long S) { return top_p > 0.0f ? (unsigned long long)((double)top_p * (double)S) : 0ull; },
                              24, sh, kp, above, mass, thr)) {
                 kstar = kp; idx_cut = 0x7fffffff; keep_all = false;
 #pragma unroll
-                for (int k = 0; k < SMP_NV4; ++k)
+                for (int k = 0; k < ROW_NV4; ++k)
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
-                        if (okey(opaque(z[k][j])) == kstar) qtie_s = (uint32_t)q_of(k, j);   // (every writer stores the same value)
+                        if (order_key(opaque(z[k][j])) == kstar) qtie_s = (uint32_t)q_of(k, j);   // (every writer stores the same value)
                 __syncthreads();
                 const unsigned long long qt = qtie_s;            // > 0: the boundary bin's mass exceeds thr - above >= 0
                 const unsigned long long n_tie = mass / qt, c = (thr - above) / qt + 1;
@@ -247,8 +210,8 @@ __device__ __forceinline__ int sample_row(const float* __restrict__ lrow, const 
                     uint32_t kidx;
                     unsigned long long a2, m2, t2;
                     radix_select([&](int k, int j, uint32_t& key) {
-                                     key = 0xFFFFu - (uint32_t)(4 * (k * SMP_THREADS + opaque(tid)) + j);
-                                     return okey(opaque(z[k][j])) == kstar; },
+                                     key = 0xFFFFu - (uint32_t)(4 * (k * ROW_THREADS + opaque(tid)) + j);
+                                     return order_key(opaque(z[k][j])) == kstar; },
                                  [](int, int) { return 1ull; }, [c](unsigned long long) { return c - 1; }, 8, sh, kidx, a2, m2, t2);
                     idx_cut = (int)(0xFFFFu - kidx);
                 }
@@ -259,10 +222,10 @@ __device__ __forceinline__ int sample_row(const float* __restrict__ lrow, const 
             // it (its whole tie group carries the same q)
             uint32_t kfail = 0;
 #pragma unroll
-            for (int k = 0; k < SMP_NV4; ++k)
+            for (int k = 0; k < ROW_NV4; ++k)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const uint32_t key = okey(opaque(z[k][j]));
+                    const uint32_t key = order_key(opaque(z[k][j]));
                     if (key >= kstar && key > kfail && q_of(k, j) < qmin) kfail = key;
                 }
             kfail = block_reduce(kfail, [](uint32_t a, uint32_t b) { return a > b ? a : b; }, reinterpret_cast<uint32_t*>(red_i));
@@ -270,16 +233,16 @@ __device__ __forceinline__ int sample_row(const float* __restrict__ lrow, const 
         }
     } else if (!keep_all) {
         unsigned long long above, mass, thr;
-        keep_all = !radix_select([&](int k, int j, uint32_t& key) { key = okey(opaque(z[k][j])); return true; }, q_of,
+        keep_all = !radix_select([&](int k, int j, uint32_t& key) { key = order_key(opaque(z[k][j])); return true; }, q_of,
                                  [&](unsigned long long S) { return top_p > 0.0f ? (unsigned long long)((double)top_p * (double)S) : 0ull; },
                                  24, sh, kstar, above, mass, thr);
         if (!keep_all) {
             // the tokens on kstar all carry the same q (same z): the first c of them by index are kept
 #pragma unroll
-            for (int k = 0; k < SMP_NV4; ++k)
+            for (int k = 0; k < ROW_NV4; ++k)
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    if (okey(opaque(z[k][j])) == kstar) qtie_s = (uint32_t)q_of(k, j);   // (every writer stores the same value)
+                    if (order_key(opaque(z[k][j])) == kstar) qtie_s = (uint32_t)q_of(k, j);   // (every writer stores the same value)
             __syncthreads();
             const unsigned long long qt = qtie_s;            // > 0: the boundary bin's mass exceeds thr - above >= 0
             const unsigned long long n_tie = mass / qt, c = (thr - above) / qt + 1;
@@ -287,8 +250,8 @@ __device__ __forceinline__ int sample_row(const float* __restrict__ lrow, const 
                 uint32_t kidx;
                 unsigned long long a2, m2, t2;
                 radix_select([&](int k, int j, uint32_t& key) {
-                                 key = 0xFFFFu - (uint32_t)(4 * (k * SMP_THREADS + tid) + j);
-                                 return okey(opaque(z[k][j])) == kstar; },
+                                 key = 0xFFFFu - (uint32_t)(4 * (k * ROW_THREADS + tid) + j);
+                                 return order_key(opaque(z[k][j])) == kstar; },
                              [](int, int) { return 1ull; }, [c](unsigned long long) { return c - 1; }, 8, sh, kidx, a2, m2, t2);
                 idx_cut = (int)(0xFFFFu - kidx);
             }
@@ -299,12 +262,12 @@ __device__ __forceinline__ int sample_row(const float* __restrict__ lrow, const 
     float best = -INFINITY;
     int bidx = 0x7fffffff;
 #pragma unroll
-    for (int k = 0; k < SMP_NV4; ++k) {
-        const int i4 = k * SMP_THREADS + (FILT ? opaque(tid) : tid);
+    for (int k = 0; k < ROW_NV4; ++k) {
+        const int i4 = k * ROW_THREADS + (FILT ? opaque(tid) : tid);
         bool kept[4], any = false;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const uint32_t key = okey(opaque(z[k][j]));
+            const uint32_t key = order_key(opaque(z[k][j]));
             kept[j] = (keep_all || key > kstar || (key == kstar && 4 * i4 + j <= idx_cut));
             any |= kept[j];
         }
@@ -330,7 +293,7 @@ __device__ __forceinline__ int sample_row(const float* __restrict__ lrow, const 
     if ((tid & 63) == 0) { red_f[tid >> 6] = best; red_i[tid >> 6] = bidx; }
     __syncthreads();
     best = red_f[0]; bidx = red_i[0];
-    for (int w = 1; w < SMP_WAVES; ++w)
+    for (int w = 1; w < ROW_WAVES; ++w)
         if (red_f[w] > best || (red_f[w] == best && red_i[w] < bidx)) { best = red_f[w]; bidx = red_i[w]; }
     __syncthreads();
     return min(max(bidx, 0), SAMPLE_MAX_V - 1);
@@ -338,19 +301,17 @@ __device__ __forceinline__ int sample_row(const float* __restrict__ lrow, const 
 
 }  // namespace
 
-// the decode step's sampler: replaces dec_argmax_kernel when sampling is on; after the draw the loop bookkeeping below is
-// dec_argmax_kernel's, line for line (decode.hip: dead-slot rule, token record, stop counts, arrival / publish, embedding gather)
+// the decode step's sampler: replaces dec_argmax_kernel when sampling is on; after the draw it runs the step epilogue (step_tail.h)
 // LSE (LoopArgs::out_logprob): after the draw, the row's log-sum-exp is merged from the head's (cand_val, cand_sum) partials by the
 // function the arg-max kernel uses (common.h: dec_lse_max / dec_lse_sum -- the raw logits, temperature 1, no nucleus), the drawn
 // token's logit is read from the logits row the head stored, and logit - lse is recorded where the token is.
 template <bool LSE, bool FILT>
-__global__ __launch_bounds__(SMP_THREADS) void dec_sample_kernel(const SampleArgs sa, const DecArgs a, int32_t* __restrict__ tokens,
+__global__ __launch_bounds__(ROW_THREADS) void dec_sample_kernel(const SampleArgs sa, const DecArgs a, int32_t* __restrict__ tokens,
                                                                  const float* __restrict__ embed, int write_x, const LoopArgs lp) {
     __shared__ int tok_s;
     __shared__ float lse_sh[4];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int row = lp.row_of_slot ? lp.row_of_slot[b] : b;         // the example in this slot
-    const bool dead = (lp.blk_snap && lp.blk_snap[b >> 5] == 0) || row < 0;      // workgroup-uniform; written by an EARLIER launch
+    const auto [row, dead] = step_slot(lp.row_of_slot, lp.blk_snap, b);
     int idx = 0;
     if (!dead) {
         const int step = lp.out_tokens ? *a.d_pos - lp.T0 + 1 : (int)sa.prm[SMP_STEP];
@@ -371,42 +332,23 @@ __global__ __launch_bounds__(SMP_THREADS) void dec_sample_kernel(const SampleArg
         }
         if (lp.out_tokens) {
             if (!dead) {
-                const int max_len = lp.params[0], stop_id = lp.params[1];
-                const int step = *a.d_pos - lp.T0 + 1;
-                if (step >= 0 && step < max_len) lp.out_tokens[(int64_t)row * max_len + step] = idx;
-                if constexpr (LSE) {
-                    if (step >= 0 && step < max_len) lp.out_logprob[(int64_t)row * max_len + step] = sa.logits[(int64_t)b * sa.ld + idx] - lse;
-                }
-                if (idx == stop_id && lp.seen_stop[row] == 0) {
-                    lp.seen_stop[row] = 1;
-                    atomicAdd(lp.n_seen, 1);
-                    if (lp.blk_left && atomicSub(lp.blk_left + (b >> 5), 1) == 1) lp.blk_live[b >> 5] = 0;   // from the NEXT step on
-                }
+                if constexpr (LSE)
+                    step_record(lp, a, b, row, idx, [=, logits = sa.logits, ld = sa.ld] { return logits[(int64_t)b * ld + idx] - lse; });
+                else
+                    step_record(lp, a, b, row, idx);
             }
-            // publish exactly as dec_argmax_kernel does (its comment gives the ordering argument)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (atomicAdd(lp.arrive, 1) == (int)gridDim.x - 1) {
-                *lp.arrive = 0;
-                const int t = *lp.ticket + 1;
-                *lp.ticket = t;
-                const int ns = atomicAdd(lp.n_seen, 0);
-                __hip_atomic_store(lp.host_progress, ((unsigned long long)(unsigned)t << 32) | (unsigned)ns, __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_SYSTEM);
-            }
+            step_publish(lp, [n_seen = lp.n_seen] { return atomicAdd(n_seen, 0); });
         }
     }
     if (dead) return;
     if (write_x) {
         __syncthreads();
-        if (tid < 144) {
-            const float4 e = reinterpret_cast<const float4*>(embed + (int64_t)tok_s * 576)[tid];
-            reinterpret_cast<float4*>(a.xmidF)[f32_idx(b >> 5, 72, b & 31, tid * 4)] = e;
-        }
+        if (tid < 144) step_embed_gather(embed, tok_s, a, b, tid);
     }
 }
 
 template <bool FILT>
-__global__ __launch_bounds__(SMP_THREADS) void sample_logits_kernel(const SampleArgs sa, int32_t* __restrict__ tokens) {
+__global__ __launch_bounds__(ROW_THREADS) void sample_logits_kernel(const SampleArgs sa, int32_t* __restrict__ tokens) {
     const int b = blockIdx.x;
     const uint32_t grow = sa.prm[SMP_ROW_OFF] + (uint32_t)(sa.row_ids ? sa.row_ids[b] : b);
     const int idx = sample_row<FILT>(sa.logits + (int64_t)b * sa.ld, sa.prm, grow, sa.prm[SMP_STEP]);
@@ -416,14 +358,14 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_logits_kernel(const Sample
 void launch_dec_sample(const SampleArgs& sa, const DecArgs& a, int B, int32_t* tokens, const float* embed, int write_x,
                        const LoopArgs& loop, hipStream_t s) {
     const bool lse = loop.out_logprob != nullptr && a.cand_sum != nullptr;
-    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(B), dim3(SMP_THREADS), 0, s, sa, a, tokens, embed, write_x, loop); };
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(B), dim3(ROW_THREADS), 0, s, sa, a, tokens, embed, write_x, loop); };
     if (sa.filtered) { if (lse) go(dec_sample_kernel<true, true>); else go(dec_sample_kernel<false, true>); }
     else { if (lse) go(dec_sample_kernel<true, false>); else go(dec_sample_kernel<false, false>); }
 }
 
 void launch_sample_logits(const SampleArgs& sa, int B, int32_t* tokens, hipStream_t s) {
-    if (sa.filtered) hipLaunchKernelGGL(sample_logits_kernel<true>, dim3(B), dim3(SMP_THREADS), 0, s, sa, tokens);
-    else hipLaunchKernelGGL(sample_logits_kernel<false>, dim3(B), dim3(SMP_THREADS), 0, s, sa, tokens);
+    if (sa.filtered) hipLaunchKernelGGL(sample_logits_kernel<true>, dim3(B), dim3(ROW_THREADS), 0, s, sa, tokens);
+    else hipLaunchKernelGGL(sample_logits_kernel<false>, dim3(B), dim3(ROW_THREADS), 0, s, sa, tokens);
 }
 
 }  // namespace mellow

@@ -17,22 +17,17 @@
 // No atomics: the result depends on the inputs only.
 #include "common.h"
 #include "kernels.h"
+#include "step_tail.h"
 
 namespace mellow {
 
 namespace {
 
-constexpr int TL_THREADS = 1024, TL_WAVES = TL_THREADS / 64;
-constexpr int TL_NV4 = SAMPLE_MAX_V / 4 / TL_THREADS;      // float4 groups per thread (12)
-constexpr int TL_SLOTS = 4 * TL_NV4;                       // values per thread (48)
-static_assert(TL_NV4 * 4 * TL_THREADS == SAMPLE_MAX_V, "row tiling");
-static_assert(TL_WAVES == 16, "the wave results are reduced by one 16-lane DPP row");
+constexpr int TL_SLOTS = 4 * ROW_NV4;                       // values per thread (48)
+static_assert(ROW_WAVES == 16, "the wave results are reduced by one 16-lane DPP row");
 
-// order-preserving key: a > b (as floats, no NaN) <=> tl_key(a) > tl_key(b); -0 has the key of +0
-__device__ __forceinline__ uint32_t tl_key(float z) {
-    const uint32_t u = __float_as_uint(z + 0.0f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+// the order key of a raw logit: these come straight from the head and may be -0, which has to rank as +0 does (+ 0.0f turns it)
+__device__ __forceinline__ uint32_t tl_key(float z) { return order_key(z + 0.0f); }
 
 // 16-lane and 64-lane all-reduces of u32 without LDS traffic (common.h has the float forms and says what the DPP controls do)
 template <int CTRL>
@@ -55,13 +50,13 @@ __device__ __forceinline__ uint32_t tl_wave(uint32_t v) {
     return tl_pick<MAX>((uint32_t)r[0], (uint32_t)r[1]);
 }
 
-__global__ __launch_bounds__(TL_THREADS) void dec_top_logprobs_kernel(const TopArgs g) {
+__global__ __launch_bounds__(ROW_THREADS) void dec_top_logprobs_kernel(const TopArgs g) {
     __shared__ float lse_sh[4];
-    __shared__ uint32_t red_k[2][TL_WAVES], red_i[2][TL_WAVES];
+    __shared__ uint32_t red_k[2][ROW_WAVES], red_i[2][ROW_WAVES];
     __shared__ int win[TOP_LOGPROBS_MAX_K];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int row = g.row_of_slot ? g.row_of_slot[b] : b;             // the example in this slot
-    if ((g.blk_snap && g.blk_snap[b >> 5] == 0) || row < 0) return;   // workgroup-uniform; written by an EARLIER launch
+    const auto [row, dead] = step_slot(g.row_of_slot, g.blk_snap, b);
+    if (dead) return;
     int step = 0, max_len = 1;                                        // the tap: one step, [B][k]
     if (g.d_pos) {
         max_len = g.params[0];
@@ -79,8 +74,8 @@ __global__ __launch_bounds__(TL_THREADS) void dec_top_logprobs_kernel(const TopA
     const float* __restrict__ lrow = g.logits + (int64_t)b * g.ld;
     uint32_t key[TL_SLOTS];
 #pragma unroll
-    for (int q = 0; q < TL_NV4; ++q) {
-        const float4 v = reinterpret_cast<const float4*>(lrow)[q * TL_THREADS + tid];
+    for (int q = 0; q < ROW_NV4; ++q) {
+        const float4 v = reinterpret_cast<const float4*>(lrow)[q * ROW_THREADS + tid];
         key[4 * q + 0] = tl_key(v.x); key[4 * q + 1] = tl_key(v.y); key[4 * q + 2] = tl_key(v.z); key[4 * q + 3] = tl_key(v.w);
     }
     // the thread's two first elements among the slots `gone` does not mark: (k1, s1) before (k2, s2); a strict compare keeps the
@@ -105,7 +100,7 @@ __global__ __launch_bounds__(TL_THREADS) void dec_top_logprobs_kernel(const TopA
 
     // ---- 3. k rounds ---------------------------------------------------------------------------------------------------------------
     for (int r = 0; r < k; ++r) {
-        const uint32_t idx = (uint32_t)(((s1 >> 2) * TL_THREADS + tid) * 4 + (s1 & 3));
+        const uint32_t idx = (uint32_t)(((s1 >> 2) * ROW_THREADS + tid) * 4 + (s1 & 3));
         const uint32_t wk = tl_wave<true>(k1);
         const uint32_t wi = tl_wave<false>(k1 == wk ? idx : 0xFFFFFFFFu);
         if ((tid & 63) == 0) { red_k[r & 1][tid >> 6] = wk; red_i[r & 1][tid >> 6] = wi; }
@@ -135,7 +130,7 @@ __global__ __launch_bounds__(TL_THREADS) void dec_top_logprobs_kernel(const TopA
 
 void launch_dec_top_logprobs(const TopArgs& g, int B, hipStream_t s) {
     if (B <= 0 || g.ld != SAMPLE_MAX_V || g.k < 1 || g.k > TOP_LOGPROBS_MAX_K) return;      // (the engine never asks for these)
-    hipLaunchKernelGGL(dec_top_logprobs_kernel, dim3(B), dim3(TL_THREADS), 0, s, g);
+    hipLaunchKernelGGL(dec_top_logprobs_kernel, dim3(B), dim3(ROW_THREADS), 0, s, g);
 }
 
 }  // namespace mellow

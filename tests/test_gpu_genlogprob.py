@@ -204,6 +204,37 @@ def test_logprobs_follow_their_example_through_row_migration(engine, synth_sd):
         assert np.isfinite(lp).all() and (lp[t >= 0] <= 0).all()
 
 
+def test_three_pickers_share_the_step_bookkeeping(engine):
+    """The arg-max, the sampler and the beam merge run the same step epilogue (token / log-prob record, stop count, block-exit countdown,
+    publish, embedding gather).  B = 33 is two row blocks; the stop id is chosen as in the migration test above, so rows stop at
+    different steps, a block empties and rows migrate.  A sampler at top_p = 0 keeps the arg-max alone, and one beam is the greedy
+    search: the three calls must tell the same story.  The greedy log-prob is -log S, the sampler's and the beam's l[id] - lse:
+    2e-4 is the bound test_gpu_beam.py holds the two forms to."""
+    B, ML = 33, 12
+    a1, a2, ids = synth.make_batch(B)
+    free, *_ = engine.generate(a1, a2, ids, max_len=ML, stop_id=0, ignore_stop=True)
+    vals, counts = np.unique(free[:, 1:6], return_counts=True)
+    stop = int(vals[np.argmax(counts)])                 # the most frequent early token: several rows stop early
+    gt, gl, gs, _, glp = engine.generate(a1, a2, ids, max_len=ML, stop_id=stop, return_logprobs=True)
+    reps_g = engine.last_row_repacks()
+    st, sl, ss, _, slp = engine.generate(a1, a2, ids, max_len=ML, stop_id=stop, return_logprobs=True, do_sample=True, top_p=0.0, seed=5)
+    reps_s = engine.last_row_repacks()
+    bt, bl, bs, _, blp, _ = engine.generate(a1, a2, ids, max_len=ML, stop_id=stop, return_logprobs=True, num_beams=1)
+    d_s = float(np.abs(slp - glp).max())
+    d_b = 0.0
+    for r in range(B):
+        n = min(int(gl[r]) + 1, gs)                      # up to and including the row's stop id: a finished beam is frozen after it
+        assert np.array_equal(bt[r, :n], gt[r, :n]), r
+        d_b = max(d_b, float(np.abs(blp[r, :n] - glp[r, :n]).max()))
+    print(f"[{engine.precision}] stop id {stop}: steps {gs} / {ss} / {bs}, repacks {reps_g} / {reps_s}, rows dropped {int((gt == -1).any(1).sum())}; "
+          f"max|lp - greedy lp|: sampled {d_s:.3e}, one beam {d_b:.3e}")
+    assert reps_g >= 1 and reps_s >= 1, "no row repack happened: pick a stop id that stops more rows"
+    assert np.array_equal(st, gt) and np.array_equal(sl, gl) and ss == gs        # (the -1 columns of dropped rows included)
+    assert d_s <= 2e-4
+    assert bs == gs and np.array_equal(bl, gl) and bt.shape == gt.shape
+    assert d_b <= 2e-4
+
+
 @pytest.mark.parametrize("engine", ["f32"], indirect=True)
 def test_scored_batches_beyond_1024_rows_pad_every_record(engine, golden_dir):
     """A scored batch of more than 1024 rows runs as passes (tests/test_gpu_parity.py test_batches_beyond_1024_rows_run_as_passes has
