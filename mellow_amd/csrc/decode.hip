@@ -56,46 +56,46 @@ void set_kernel_debug_buffer(uint64_t* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g
 // softmax weights: exp(x) = 2^(x*log2 e) on the hardware v_exp_f32 (x <= 0 here; ~1e-6 relative, far inside the fp32
 // summation-order noise of a 64..700-key softmax); exp(-inf) = 0 exactly
 __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
-// A/B switches for developer builds (tools/ab_build.sh): -DMELLOW_NO_BLK_EXIT, -DMELLOW_NO_NT
-#ifdef MELLOW_NO_BLK_EXIT
-#define MELLOW_BLK_EXIT(RB)
-#else
 #define MELLOW_BLK_EXIT(RB) if (BLK) { if (a.blk_live[RB] == 0) return; }   // BLK: compile-time (a run-time null test costs 0.26 us per launch)
-#endif
 // streamed-once operands (weights, KV pages): non-temporal loads (`global_load_dwordx4 ... nt`).  Each of these lines is read
 // by exactly one workgroup per step, so keeping it in L2 buys nothing, and the nt policy shortens issue -> landed by ~18 %
 // on this part (MI355X_MICROARCH.md, row nt-weights)
 __device__ __forceinline__ float4 ldg_nt(const float4* p) {
-#ifdef MELLOW_NO_NT
-    return *p;
-#else
     const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
     return make_float4(v[0], v[1], v[2], v[3]);
-#endif
 }
 // Decode weights in e4m3 (BASELINE config 5, `W8` variants of the GEMM kernels): the SAME slot order as the fp32 layouts
 // (one float4 slot = one 4-byte word of four e4m3 values), one scale per packed weight row, applied to the reduced output.
 // W8 == 1: the values are widened to fp32 in registers and multiplied on the fp32 matrix pipe, the activations stay fp32
-// (MELLOW_FP8_DECODE_ACT=0: the form the weight pin of the parity suite runs); W8 == 2, the mode's default: see ldw8 below.
-template <bool W8>
-__device__ __forceinline__ float4 ldw(const float* __restrict__ Wp, int64_t slot) {
-    if constexpr (W8) {
-        const uint32_t u = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(Wp) + slot);
-        const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8(u, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(u, true);
-        return make_float4(lo[0], lo[1], hi[0], hi[1]);
-    } else {
-        return ldg_nt(reinterpret_cast<const float4*>(Wp) + slot);
+// (MELLOW_FP8_DECODE_ACT=0: the form the weight pin of the parity suite runs).
+// W8 == 2 ("A8"), the mode's default: the e4m3 words go to the fp8 matrix pipe as they are (v_mfma_f32_32x32x16_fp8_fp8 /
+// 16x16x32) and the ACTIVATIONS are quantised to e4m3 in the consumer's registers, right after the fp32 fragments have landed:
+// one scale per (batch row, k-slice of the wave) = amax / 448 of the values the wave holds for that row, applied to the wave's
+// accumulators before the cross-wave reduction -- finer than a per-row scale and free of any cross-workgroup statistic.  No
+// repacking: a lane's e4m3 word of k-tile t and of k-tile t+1 form the 8-byte A operand, and the activation fragments of the same
+// two tiles (same lane -> same k positions) the B operand; the contraction only needs A and B to agree on which k a byte holds.
+//
+// WFrag: a lane's weight words of N k-tiles in the mode's form -- fp32 quads (W8 == 0; W8 == 1: widened by the load) or the
+// e4m3 words (W8 == 2).  load() fetches ONE k-tile: every kernel interleaves it with the activation loads of the same tile in a
+// load block of its own (the o_proj clamps the slot per tile), and the products below take the fragment whole.
+template <int N, int W8>
+struct WFrag {
+    using word = std::conditional_t<W8 == 2, uint32_t, float4>;
+    word t[N];
+    static __device__ __forceinline__ word load(const float* __restrict__ Wp, int64_t slot) {
+        if constexpr (W8 == 0) {
+            return ldg_nt(reinterpret_cast<const float4*>(Wp) + slot);
+        } else {
+            const uint32_t u = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(Wp) + slot);
+            if constexpr (W8 == 2) {
+                return u;
+            } else {
+                const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8(u, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(u, true);
+                return make_float4(lo[0], lo[1], hi[0], hi[1]);
+            }
+        }
     }
-}
-// W8 == 2 ("A8"): the e4m3 words go to the fp8 matrix pipe as they are (v_mfma_f32_32x32x16_fp8_fp8 / 16x16x32) and the
-// ACTIVATIONS are quantised to e4m3 in the consumer's registers, right after the fp32 fragments have landed: one scale per
-// (batch row, k-slice of the wave) = amax / 448 of the values the wave holds for that row, applied to the wave's accumulators
-// before the cross-wave reduction -- finer than a per-row scale and free of any cross-workgroup statistic.  No repacking: a
-// lane's e4m3 word of k-tile t and of k-tile t+1 form the 8-byte A operand, and the activation fragments of the same two
-// tiles (same lane -> same k positions) the B operand; the contraction only needs A and B to agree on which k a byte holds.
-__device__ __forceinline__ uint32_t ldw8(const float* __restrict__ Wp, int64_t slot) {
-    return __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(Wp) + slot);
-}
+};
 __device__ __forceinline__ float f4amax(float4 v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
 __device__ __forceinline__ uint32_t q4_e4m3(float4 v, float inv) {
     int w = 0;
@@ -124,33 +124,6 @@ __device__ __forceinline__ void a8_scales(float amax, float& inv, float& sc) {
     inv = amax > 0.f ? 448.0f / amax : 0.f;
     sc = amax * (1.0f / 448.0f);
 }
-// Stores of a kernel's OUTPUT (read by the next launch, on other XCDs).  Developer A/B (tools/ab_build.sh -DMELLOW_ST_MODE=n):
-// 0 plain (write-back in this XCD's L2, flushed by the release at the end of the kernel), 1 non-temporal, 2 write-through (sc0 sc1)
-#ifndef MELLOW_ST_MODE
-#define MELLOW_ST_MODE 0
-#endif
-__device__ __forceinline__ void st_out(float4* p, float4 v) {
-#if MELLOW_ST_MODE == 1
-    __builtin_nontemporal_store(f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4*>(p));
-#elif MELLOW_ST_MODE == 2
-    const f32x4 r = {v.x, v.y, v.z, v.w};
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(p), "v"(r) : "memory");
-#else
-    *p = v;
-#endif
-}
-// A field of the by-value argument struct that only the EPILOGUE needs is otherwise fetched by a scalar load right where it is
-// used -- after the reduction barrier, followed at once by s_waitcnt lgkmcnt(0): a cold scalar-cache miss (the argument block's
-// lines beyond the preloaded dwords) on the critical tail of every launch, sometimes two in a row.  Naming the value in an empty
-// asm right after the kernel's vector loads have been ISSUED makes the compiler fetch it there, where the wait hides behind the
-// loads that are in flight anyway.  MEASURED (round 4, same box, tools/ab_run.sh): 46.89 ms of decode per 63 steps with the hoist
-// against 46.83 without (B = 64: 68.7 against 68.35) -- those scalar loads hit the scalar cache and cost nothing where they are;
-// the wait in front of the load block costs a little.  Off; -DMELLOW_HOIST_ON keeps the A/B.
-#ifdef MELLOW_HOIST_ON
-#define MELLOW_HOIST(x) asm volatile("" ::"s"(x))
-#else
-#define MELLOW_HOIST(x) ((void)0)
-#endif
 __device__ __forceinline__ float4 f4add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float f4ssq(float4 v) { return (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w); }
 __device__ __forceinline__ f32x16 mfma4(f32x16 acc, float4 w, float4 x) {
@@ -160,6 +133,92 @@ __device__ __forceinline__ f32x16 mfma4(f32x16 acc, float4 w, float4 x) {
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w.w, x.w, acc, 0, 0, 0);
     return acc;
 }
+__device__ __forceinline__ f32x4 mfma4s(f32x4 acc, float4 w, float4 x) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, x.x, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, x.y, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, x.z, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, x.w, acc, 0, 0, 0);
+    return acc;
+}
+// One wave's slice of a 32-row weight tile against its 32 batch rows: acc += W[:, slice] x[slice].  W8 == 2 quantises the slice
+// of each batch row (lanes m and m + 32 hold it) and scales the WHOLE accumulator: acc holds nothing but this slice (zeros on entry).
+template <int N, int W8>
+__device__ __forceinline__ f32x16 slice_mma32(f32x16 acc, const WFrag<N, W8>& w, const float4 (&x)[N]) {
+    if constexpr (W8 == 2) {
+        float am = 0.f, inv, sc;
+#pragma unroll
+        for (int i = 0; i < N; ++i) am = fmaxf(am, f4amax(x[i]));
+        a8_scales(half_max(am), inv, sc);
+        uint32_t xq[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) xq[i] = q4_e4m3(x[i], inv);
+        acc = mfma8_32<N>(acc, w.t, xq);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] *= sc;
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; ++i) acc = mfma4(acc, w.t[i], x[i]);
+    }
+    return acc;
+}
+// The same for a 16-row weight tile and 16 batch rows (v_mfma_f32_16x16x4_f32 / 16x16x32 fp8): a batch row's values of the
+// slice sit in the four lanes m + 16 q, hence the swz_xor16 step of the amax.
+template <int N, int W8>
+__device__ __forceinline__ f32x4 slice_mma16(f32x4 acc, const WFrag<N, W8>& w, const float4 (&x)[N]) {
+    if constexpr (W8 == 2) {
+        float am = 0.f, inv, sc;
+#pragma unroll
+        for (int i = 0; i < N; ++i) am = fmaxf(am, f4amax(x[i]));
+        am = fmaxf(am, swz_xor16(am));
+        a8_scales(half_max(am), inv, sc);
+        uint32_t xq[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) xq[i] = q4_e4m3(x[i], inv);
+        acc = mfma8_16<N>(acc, w.t, xq);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[r] *= sc;
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; ++i) acc = mfma4s(acc, w.t[i], x[i]);
+    }
+    return acc;
+}
+// Cross-wave reduction through LDS, red[wave][row of ROWS][lane].  A wave parks its accumulators (register r of lane l = row
+// r0 + r) with reduce_store; after the barrier red_sum adds one (row, lane) over the waves -- wave 0's partial first, then
+// waves 1, 2, ... in ascending order: the summation order of every build.
+typedef __attribute__((address_space(3))) float lds_f32;      // the helpers take `red` as an LDS pointer: through a generic one the
+#define MELLOW_LDS(p) ((lds_f32*)(p))                         // index arithmetic is canonicalised in 64 bits and the reads pair worse
+template <typename V>
+__device__ __forceinline__ void reduce_store(lds_f32* row0_lane, V acc) {
+#pragma unroll
+    for (int r = 0; r < (int)(sizeof(V) / sizeof(float)); ++r) row0_lane[r * 64] = acc[r];
+}
+template <int WAVES, int ROWS>
+__device__ __forceinline__ float red_sum(const lds_f32* red, int r, int lane) {
+    float s = red[r * 64 + lane];
+#pragma unroll
+    for (int wv = 1; wv < WAVES; ++wv) s += red[(wv * ROWS + r) * 64 + lane];
+    return s;
+}
+// The 256-thread epilogue of a 32 x 32 tile: thread (mm = tid % 32, hh = tid / 32 % 2, gq = tid / 64 % 4) owns batch row mm and
+// the four columns epi_col .. + 3 of the tile (accumulator registers 4 gq .. 4 gq + 3 of lane mm + 32 hh).
+template <int WAVES>
+__device__ __forceinline__ float4 reduce32(const lds_f32* red, int tid) {
+    const int mm = tid & 31, hh = (tid >> 5) & 1, gq = (tid >> 6) & 3;
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {            // (red_sum's index with the parent's association: (row * 64 + mm) + 32 hh pairs the reads as before)
+        const int r = 4 * gq + j;
+        float sacc = red[r * 64 + mm + 32 * hh];
+#pragma unroll
+        for (int wv = 1; wv < WAVES; ++wv) sacc += red[(wv * 16 + r) * 64 + mm + 32 * hh];
+        v[j] = sacc;
+    }
+    return make_float4(v[0], v[1], v[2], v[3]);
+}
+__device__ __forceinline__ int epi_col(int nt, int tid) { return nt * 32 + 8 * ((tid >> 6) & 3) + 4 * ((tid >> 5) & 1); }
+// e4m3 weights: the scales of the four packed rows sc[0 .. 3] on a thread's four reduced values
+__device__ __forceinline__ float4 f4scale(float4 v, const float* __restrict__ sc) { return make_float4(v.x * sc[0], v.y * sc[1], v.z * sc[2], v.w * sc[3]); }
 
 // ----------------------------------------------------------------------------------------------------
 // f32x3 mode (the engine's default): the decode GEMMs on the bf16 matrix pipe at fp32 accuracy.  Every fp32 operand value is
@@ -283,18 +342,15 @@ __global__ __launch_bounds__(QKV_THREADS) void dec_qkv_kernel(const float* __res
         const int64_t wslot = ((int64_t)nt * K8p + k8_0) * 64 + lane;
         const float4* xb = reinterpret_cast<const float4*>(xmidF_p) + ((int64_t)rb * 72 + k8_0) * 64 + lane;
         const float4* sb = reinterpret_cast<const float4*>(dslabF_p) + ((int64_t)rb * 72 + k8_0) * 64 + lane;
-        float4 w[KPW], x[KPW], sl[KPW][KCD > 0 ? KCD : 1];
-        uint32_t w8[KPW];
+        WFrag<KPW, W8> w;
+        float4 x[KPW], sl[KPW][KCD > 0 ? KCD : 1];
 #pragma unroll
         for (int i = 0; i < KPW; ++i) {
-            if constexpr (W8 == 2) w8[i] = ldw8(Wp, wslot + i * 64);
-            else w[i] = ldw<W8 != 0>(Wp, wslot + i * 64);
+            w.t[i] = w.load(Wp, wslot + i * 64);
             x[i] = xb[i * 64];
 #pragma unroll
             for (int s = 0; s < KCD; ++s) sl[i][s] = sb[(int64_t)s * a.slabF_stride4 + i * 64];
         }
-        MELLOW_HOIST(a.pq); MELLOW_HOIST(a.rows); MELLOW_HOIST(a.ssq1); MELLOW_HOIST(a.xnewR);
-        if (W8) MELLOW_HOIST(wscale);
         __builtin_amdgcn_sched_barrier(0);
         f32x16 acc;
 #pragma unroll
@@ -302,36 +358,21 @@ __global__ __launch_bounds__(QKV_THREADS) void dec_qkv_kernel(const float* __res
         float ssp = 0.f;
 #pragma unroll
         for (int i = 0; i < KPW; ++i) {
-            float4 xv = x[i];
 #pragma unroll
-            for (int s = 0; s < KCD; ++s) xv = f4add(xv, sl[i][s]);
-            if constexpr (W8 == 2) x[i] = xv;            // quantised below, once the wave's slice of the row is known
-            else acc = mfma4(acc, w[i], xv);
+            for (int s = 0; s < KCD; ++s) x[i] = f4add(x[i], sl[i][s]);
             // side jobs of two n-tiles (the workgroups of one k-chunk see every row of x_new on these 72 columns):
             //   nt == 0: partial sum of squares per row (the attention's RMS statistic)
             //   nt == 1: x_new row-major (the o_proj's residual operand)
-            if (nt == 0) ssp += f4ssq(xv);
+            if (nt == 0) ssp += f4ssq(x[i]);
             if (nt == 1)
-                *reinterpret_cast<float4*>(a.xnewR + ((int64_t)rb * 32 + (lane & 31)) * 576 + (k8_0 + i) * 8 + (lane >> 5) * 4) = xv;
+                *reinterpret_cast<float4*>(a.xnewR + ((int64_t)rb * 32 + (lane & 31)) * 576 + (k8_0 + i) * 8 + (lane >> 5) * 4) = x[i];
         }
-        if constexpr (W8 == 2) {
-            float am = 0.f, inv, sc;
-#pragma unroll
-            for (int i = 0; i < KPW; ++i) am = fmaxf(am, f4amax(x[i]));
-            a8_scales(half_max(am), inv, sc);
-            uint32_t xq[KPW];
-#pragma unroll
-            for (int i = 0; i < KPW; ++i) xq[i] = q4_e4m3(x[i], inv);
-            acc = mfma8_32<KPW>(acc, w8, xq);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] *= sc;
-        }
+        acc = slice_mma32<KPW, W8>(acc, w, x);
         if (nt == 0) {
             ssp = half_sum(ssp);                 // the two k-halves of a row sit in lanes m and m + 32
             if (lane < 32) ssq_s[wave * 32 + lane] = ssp;
         }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) red[(wave * 16 + r) * 64 + lane] = acc[r];
+        reduce_store(MELLOW_LDS(red) + wave * 16 * 64 + lane, acc);
     }
     __syncthreads();
     if (nt == 0 && tid < 32)
@@ -342,23 +383,10 @@ __global__ __launch_bounds__(QKV_THREADS) void dec_qkv_kernel(const float* __res
         a.ssq1[((int64_t)rb * 32 + tid) * DEC_KC_QKV + kc] = ssum;
     }
     if (tid >= 256) return;                              // (QW = 9 only) the epilogue is 256 threads wide; no barrier follows
-    const int mm = tid & 31, hh = (tid >> 5) & 1, gq = tid >> 6;
-    float v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int r = 4 * gq + j;
-        float sacc = red[r * 64 + mm + 32 * hh];
-#pragma unroll
-        for (int wv = 1; wv < QW; ++wv) sacc += red[(wv * 16 + r) * 64 + mm + 32 * hh];
-        v[j] = sacc;
-    }
-    const int n = nt * 32 + 8 * gq + 4 * hh;
-    if (W8) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] *= wscale[n + j];
-    }
-    if (n < 960)
-        *reinterpret_cast<float4*>(a.pq + ((int64_t)kc * a.rows + rb * 32 + mm) * 960 + n) = make_float4(v[0], v[1], v[2], v[3]);
+    const int mm = tid & 31, n = epi_col(nt, tid);
+    float4 v = reduce32<QW>(MELLOW_LDS(red), tid);
+    if (W8) v = f4scale(v, wscale + n);
+    if (n < 960) *reinterpret_cast<float4*>(a.pq + ((int64_t)kc * a.rows + rb * 32 + mm) * 960 + n) = v;
     kspan(a.dbg_seq, 1);
 }
 
@@ -368,9 +396,6 @@ __global__ __launch_bounds__(QKV_THREADS) void dec_qkv_kernel(const float* __res
 //     per-wave online softmax over an interleaved set of 4-key groups; partial (m, l, o) per split.
 //     Split sp owns key groups [sp*gs, (sp+1)*gs) (the last split: everything from sp*gs on, plus the new key).
 // ----------------------------------------------------------------------------------------------------
-#ifndef MELLOW_DA_ABL
-#define MELLOW_DA_ABL 0      // developer ablation (wrong results, timing only): 1 no K/V page loads, 2 no score / softmax / PV loop, 4 no slab prologue loads
-#endif
 #ifndef MELLOW_DA_WAVES
 #define MELLOW_DA_WAVES 8
 #define MELLOW_DA_G 7
@@ -504,7 +529,7 @@ __global__ __launch_bounds__(NW * 64, ONE ? 2 : (KV16 && MELLOW_DA16_MFMA && DA_
     if (tid < 80) {
 #pragma unroll
         for (int s = 0; s < NPQ; ++s)
-            sl4[s] = (MELLOW_DA_ABL & 4) ? make_float4(0.1f * s, 0.2f, 0.3f, 0.4f) : *reinterpret_cast<const float4*>(prow + (int64_t)s * rows_p * 960);
+            sl4[s] = float4(*reinterpret_cast<const float4*>(prow + (int64_t)s * rows_p * 960));      // (copied as a value: the loads keep their place between the address steps)
         if (!FUSED) {
             sq4[0] = reinterpret_cast<const float4*>(a.ssq1 + (int64_t)b * DEC_KC_QKV)[0];
             sq4[1] = reinterpret_cast<const float4*>(a.ssq1 + (int64_t)b * DEC_KC_QKV)[1];
@@ -536,25 +561,19 @@ __global__ __launch_bounds__(NW * 64, ONE ? 2 : (KV16 && MELLOW_DA16_MFMA && DA_
         const i32x4* kp = reinterpret_cast<const i32x4*>(reinterpret_cast<const uint16_t*>(kpage) + (int64_t)tc * 64 + hf * 32);
 #pragma unroll
         for (int st = 0; st < 4; ++st)
-            kq[st] = (MELLOW_DA_ABL & 1) ? i32x4{tc, 0x3c003c00, st, 0x3c003c00} : (MELLOW_DA16_KNT ? __builtin_nontemporal_load(kp + st) : kp[st]);
+            kq[st] = MELLOW_DA16_KNT ? __builtin_nontemporal_load(kp + st) : kp[st];
     };
     auto load_vgroup = [&](int g0, int u) {
         const int gi = mf_group(g0, u);
         const int tc = min(gi * 4 + sub, Tmax - 1);
-        vq[u] = (MELLOW_DA_ABL & 1) ? u32x2{0x3c003c00u, (unsigned)tc}
-                                    : __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(reinterpret_cast<const uint16_t*>(vpage) + (int64_t)tc * 64 + quad * 4));
+        vq[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(reinterpret_cast<const uint16_t*>(vpage) + (int64_t)tc * 64 + quad * 4));
     };
     float4 k4[MF ? 1 : DA_G], v4[MF ? 1 : DA_G];
     auto load_group = [&](int u) {
         const int gi = gbeg + wave + u * DA_WAVES;
         const int tc = min(gi * 4 + sub, Tmax - 1);               // inside the page; validity is decided later
-        if (MELLOW_DA_ABL & 1) {
-            k4[u] = make_float4(0.01f * tc, 0.02f, 0.03f, 0.04f);
-            v4[u] = make_float4(0.01f, 0.02f * tc, 0.03f, 0.04f);
-        } else {
-            k4[u] = ld_kv<KV16>(kpage, (int64_t)tc * 64 + quad * 4);
-            v4[u] = ld_kv<KV16>(vpage, (int64_t)tc * 64 + quad * 4);
-        }
+        k4[u] = ld_kv<KV16>(kpage, (int64_t)tc * 64 + quad * 4);
+        v4[u] = ld_kv<KV16>(vpage, (int64_t)tc * 64 + quad * 4);
     };
     const int g_first_mf = gbeg + wave;                           // virtual wave wave + NW j starts at group g_first_mf + NW j
     if constexpr (MF) {
@@ -565,8 +584,6 @@ __global__ __launch_bounds__(NW * 64, ONE ? 2 : (KV16 && MELLOW_DA16_MFMA && DA_
 #pragma unroll
         for (int u = 0; u < DA_G1; ++u) load_group(u);
     }
-    MELLOW_HOIST(a.attF16); MELLOW_HOIST(a.att_ml); MELLOW_HOIST(a.RB); MELLOW_HOIST(a.eps);
-    if (FUSED) MELLOW_HOIST(a.xnewR);
     __builtin_amdgcn_sched_barrier(0);
     kstamp(1, 1, dbg);
 
@@ -699,7 +716,7 @@ _Pragma("unroll")                                                               
             l_run[hh] = l_run[hh] * alpha + lsum;                                                                        \
         }                                                                                                                \
     }
-    const int g_first = gbeg + wave, g_stop = (MELLOW_DA_ABL & 2) ? gbeg : gend;
+    const int g_first = gbeg + wave, g_stop = gend;
 #define MELLOW_DA_RELOAD(g0)                                                                                             \
     {                                                                                                                    \
         _Pragma("unroll") for (int u = 0; u < DA_G; ++u) {                                                               \
@@ -862,7 +879,7 @@ _Pragma("unroll")                                                               
             const int head = 3 * g + hh, k = head * 64 + dq * 4;
             const int rb = b >> 5, m = b & 31;
             const int64_t o4 = ((((int64_t)sp * a.RB + rb) * 36 + (k >> 4)) * 2 + (m >> 4)) * 64 + (m & 15) + 16 * ((k >> 2) & 3);
-            st_out(reinterpret_cast<float4*>(a.attF16) + o4, O);
+            *(reinterpret_cast<float4*>(a.attF16) + o4) = O;
             if (dq == 0)      // (m, l) of this split: [head][row][split] pairs, so that the o_proj reads both splits of a row with one 16-byte load
                 *reinterpret_cast<float2*>(a.att_ml + (((int64_t)head * a.rows + b) * TS + sp) * 2) = make_float2(M, L);
         }
@@ -943,20 +960,15 @@ __global__ __launch_bounds__(OP_WAVES * 64) void dec_oproj_kernel(const float* _
     float4 xres = make_float4(0.f, 0.f, 0.f, 0.f);
     if (erow_ok) xres = *reinterpret_cast<const float4*>(xnewR_p + erow * 576 + nt * 16 + enq * 4);
 
-    float4 w[TPW], os[TPW][TS];
-    uint32_t w8[TPW];
+    WFrag<TPW, W8> w;
+    float4 os[TPW][TS];
     float ms[TPW][TS], ls[TPW][TS];
     const int64_t row = (int64_t)rb * 32 + mh * 16 + ml;
 #pragma unroll
     for (int i = 0; i < TPW; ++i) {
         const int t = wave + OP_WAVES * i, tc = t < K16 ? t : K16 - 1;     // clamped: out-of-range tiles get zero weights
-        if constexpr (W8 == 2) {
-            w8[i] = ldw8(Wp16, wslot + (int64_t)tc * 64);
-            if (t >= K16) w8[i] = 0u;
-        } else {
-            w[i] = ldw<W8 != 0>(Wp16, wslot + (int64_t)tc * 64);
-            if (t >= K16) w[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+        w.t[i] = w.load(Wp16, wslot + (int64_t)tc * 64);
+        if (t >= K16) { if constexpr (W8 == 2) w.t[i] = 0u; else w.t[i] = make_float4(0.f, 0.f, 0.f, 0.f); }
         const int h = tc >> 2;                                        // tile = 16 k of head h
 #pragma unroll
         for (int s = 0; s < TS; ++s) {
@@ -977,10 +989,9 @@ __global__ __launch_bounds__(OP_WAVES * 64) void dec_oproj_kernel(const float* _
             }
         }
     }
-    MELLOW_HOIST(a.xmidF); MELLOW_HOIST(a.xmidF16); MELLOW_HOIST(a.ssq);
-    if (W8) MELLOW_HOIST(wscale);
     __builtin_amdgcn_sched_barrier(0);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    float4 xm[TPW];
 #pragma unroll
     for (int i = 0; i < TPW; ++i) {
         // merge the key splits: x = sum_s f_s o_s / sum_s f_s l_s, f_s = exp(m_s - max m)
@@ -996,48 +1007,20 @@ __global__ __launch_bounds__(OP_WAVES * 64) void dec_oproj_kernel(const float* _
             O.x += os[i][s].x * f; O.y += os[i][s].y * f; O.z += os[i][s].z * f; O.w += os[i][s].w * f;
         }
         const float inv = 1.0f / L;
-        if constexpr (W8 == 2) {
-            os[i][0] = make_float4(O.x * inv, O.y * inv, O.z * inv, O.w * inv);      // the merged activation, quantised below
-        } else {
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[i].x, O.x * inv, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[i].y, O.y * inv, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[i].z, O.z * inv, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[i].w, O.w * inv, acc, 0, 0, 0);
-        }
+        xm[i] = make_float4(O.x * inv, O.y * inv, O.z * inv, O.w * inv);      // the merged activation
     }
-    if constexpr (W8 == 2) {
-        // a batch row's values of this wave's k-tiles sit in the four lanes ml + 16 q
-        float am = 0.f, inv, sc;
-#pragma unroll
-        for (int i = 0; i < TPW; ++i) am = fmaxf(am, f4amax(os[i][0]));
-        am = fmaxf(am, swz_xor16(am));
-        a8_scales(half_max(am), inv, sc);
-        uint32_t xq[TPW];
-#pragma unroll
-        for (int i = 0; i < TPW; ++i) xq[i] = q4_e4m3(os[i][0], inv);
-        acc = mfma8_16<TPW>(acc, w8, xq);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[r] *= sc;
-    }
+    acc = slice_mma16<TPW, W8>(acc, w, xm);
     // D[i = n_local = 4*(lane>>4) + r][j = m_local = lane&15]
-#pragma unroll
-    for (int r = 0; r < 4; ++r) red[(wave * 4 + r) * 64 + lane] = acc[r];
+    reduce_store(MELLOW_LDS(red) + wave * 4 * 64 + lane, acc);
     __syncthreads();
     if (tid < 64 && erow_ok) {
         // columns n = 4*enq + r live in registers r = 0..3 of lane em + 16*enq
         const int src_lane = em + 16 * enq;
-        float v[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int wv = 0; wv < OP_WAVES; ++wv)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] += red[(wv * 4 + r) * 64 + src_lane];
-        if (W8) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] *= wscale[nt * 16 + enq * 4 + r];
-        }
-        const float4 y = make_float4(xres.x + v[0], xres.y + v[1], xres.z + v[2], xres.w + v[3]);
         const int k = nt * 16 + enq * 4;
-        st_out(reinterpret_cast<float4*>(a.xmidF) + f32_idx(rb, 72, mh * 16 + em, k), y);
+        float4 v = make_float4(red_sum<OP_WAVES, 4>(MELLOW_LDS(red), 0, src_lane), red_sum<OP_WAVES, 4>(MELLOW_LDS(red), 1, src_lane), red_sum<OP_WAVES, 4>(MELLOW_LDS(red), 2, src_lane), red_sum<OP_WAVES, 4>(MELLOW_LDS(red), 3, src_lane));
+        if (W8) v = f4scale(v, wscale + k);
+        const float4 y = f4add(xres, v);
+        *(reinterpret_cast<float4*>(a.xmidF) + f32_idx(rb, 72, mh * 16 + em, k)) = y;
         if (a.xmid3_32) {                  // f32x3 layer kernels: x_mid pre-split for the q/k/v part (F3-32) and for gate/up (F3-16)
             const F3Quad yq = f3_split4(y), yo = f3_partner(yq);      // threads (enq, enq ^ 1) hold the halves of one slot
             if (!(enq & 1)) {
@@ -1045,7 +1028,7 @@ __global__ __launch_bounds__(OP_WAVES * 64) void dec_oproj_kernel(const float* _
                 f3_store8(a.xmid3_16, f3_16_slot(rb, 18, mh * 16 + em, k), yq, yo);
             }
         } else
-        st_out(reinterpret_cast<float4*>(a.xmidF16) + (((int64_t)rb * 36 + nt) * 2 + mh) * 64 + em + 16 * enq, y);
+        *(reinterpret_cast<float4*>(a.xmidF16) + (((int64_t)rb * 36 + nt) * 2 + mh) * 64 + em + 16 * enq) = y;
         float ss = f4ssq(y);
         ss += dpp_mov<0xB1>(ss);             // sum over the quad (the 4 column groups of one row)
         ss += dpp_mov<0x4E>(ss);
@@ -1079,63 +1062,34 @@ __global__ __launch_bounds__(LM_WAVES * 64) void dec_fullk_kernel(const float* _
     const int k8_0 = wave * KPW;
     const int64_t wslot = ((int64_t)nt * K8p + k8_0) * 64 + lane;
     const float4* xp = reinterpret_cast<const float4*>(XF) + ((int64_t)rb * 72 + k8_0) * 64 + lane;
-    float4 w[KPW], x[KPW];
-    uint32_t w8[KPW];
+    WFrag<KPW, W8> w;
+    float4 x[KPW];
     const bool dbg = tid == 0 && nt == 0 && rb == 0;
     const int dslot = 5;
     kstamp(dslot, 0, dbg);
 #pragma unroll
     for (int i = 0; i < KPW; ++i) {
-        if constexpr (W8 == 2) w8[i] = ldw8(Wp, wslot + i * 64);
-        else w[i] = ldw<W8 != 0>(Wp, wslot + i * 64);
+        w.t[i] = w.load(Wp, wslot + i * 64);
         x[i] = xp[i * 64];
     }
-    MELLOW_HOIST(a.logits); MELLOW_HOIST(a.cand_val); MELLOW_HOIST(a.cand_idx); MELLOW_HOIST(N);
-    if (W8) MELLOW_HOIST(wscale);
     __builtin_amdgcn_sched_barrier(0);
     kstamp(dslot, 1, dbg);
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    if constexpr (W8 == 2) {
-        float am = 0.f, inv, sc;
-#pragma unroll
-        for (int i = 0; i < KPW; ++i) am = fmaxf(am, f4amax(x[i]));
-        a8_scales(half_max(am), inv, sc);
-        uint32_t xq[KPW];
-#pragma unroll
-        for (int i = 0; i < KPW; ++i) xq[i] = q4_e4m3(x[i], inv);
-        acc = mfma8_32<KPW>(acc, w8, xq);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] *= sc;
-    } else {
-#pragma unroll
-        for (int i = 0; i < KPW; ++i) acc = mfma4(acc, w[i], x[i]);
-    }
+    acc = slice_mma32<KPW, W8>(acc, w, x);
     kstamp(dslot, 2, dbg && acc[0] == acc[0]);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) red[(wave * 16 + r) * 64 + lane] = acc[r];
+    reduce_store(MELLOW_LDS(red) + wave * 16 * 64 + lane, acc);
     __syncthreads();
     kstamp(dslot, 3, dbg);
     const bool epi = tid < 256;             // the epilogue is 256 threads wide (more waves only with MELLOW_LM_WAVES > 4)
-    const int mm = tid & 31, hh = (tid >> 5) & 1, gq = (tid >> 6) & 3;
-    float v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int r = 4 * gq + j;
-        float sacc = red[r * 64 + mm + 32 * hh];
-#pragma unroll
-        for (int wv = 1; wv < LM_WAVES; ++wv) sacc += red[(wv * 16 + r) * 64 + mm + 32 * hh];      // fixed order
-        v[j] = sacc;
-    }
+    const int mm = tid & 31, n = epi_col(nt, tid);
+    float4 v4 = reduce32<LM_WAVES>(MELLOW_LDS(red), tid);
     {
-        const int n = nt * 32 + 8 * gq + 4 * hh;
-        if (W8) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] *= wscale[n + j];
-        }
+        if (W8) v4 = f4scale(v4, wscale + n);
+        const float v[4] = {v4.x, v4.y, v4.z, v4.w};
         const int64_t row = (int64_t)rb * 32 + mm;
-        if (epi && a.logits && n < N) *reinterpret_cast<float4*>(a.logits + row * N + n) = make_float4(v[0], v[1], v[2], v[3]);
+        if (epi && a.logits && n < N) *reinterpret_cast<float4*>(a.logits + row * N + n) = v4;
         // best (value, lowest index) of this 32-column tile per row (torch.argmax tie rule)
         __syncthreads();
         float bv = v[0];
@@ -1448,8 +1402,8 @@ __device__ __forceinline__ void q3_body(const float4* __restrict__ wp4, const i3
                     v[j] = sacc;
                 }
                 const float4 o = make_float4(v[0], v[1], v[2], v[3]);
-                if (side) st_out(reinterpret_cast<float4*>(a.dslabF) + (int64_t)slab * a.slabF_stride4 + f32_idx(rb, 72, mm, n), o);
-                else st_out(reinterpret_cast<float4*>(a.pq + ((int64_t)slab * a.rows + rb * 32 + mm) * 960 + n), o);
+                if (side) *(reinterpret_cast<float4*>(a.dslabF) + (int64_t)slab * a.slabF_stride4 + f32_idx(rb, 72, mm, n)) = o;
+                else *reinterpret_cast<float4*>(a.pq + ((int64_t)slab * a.rows + rb * 32 + mm) * 960 + n) = o;
             }
         }
     }
@@ -1483,9 +1437,6 @@ __global__ __launch_bounds__(Q3W * 64) void dec_qkv2x3_kernel(const float* __res
 #ifndef MELLOW_GU3_WAVES
 #define MELLOW_GU3_WAVES 6
 #endif
-#ifndef MELLOW_G3_ABL
-#define MELLOW_G3_ABL 0       // developer ablation (wrong results, timing only): 1 no pre-split store of h, 2 no MFMAs, 4 no activation loads, 8 no weight split, 16 no fp32 store of h
-#endif
 constexpr int GU3W = MELLOW_GU3_WAVES;
 // K4b (f32x3, any number of row blocks): see dec_gateup16_kernel.  x3 = x_mid in F3-16 (18 pairs x 2 row halves per block).
 // Writes h both as fp32 (guF: the last layer's fp32 down projection reads it) and pre-split (h3, F3-32 with 96 pairs).
@@ -1513,19 +1464,16 @@ __global__ __launch_bounds__(GU3W * 64) void dec_gateup3_kernel(const float* __r
 #pragma unroll
         for (int p = 0; p < NP; ++p)
 #pragma unroll
-            for (int c = 0; c < 6; ++c) xq[0][p][c / 3][c % 3] = (MELLOW_G3_ABL & 4) ? i32x4{c, p, 1, 2} : xsrc[(p * 6 + c) * 64];          // block 0, requested with the weights
+            for (int c = 0; c < 6; ++c) xq[0][p][c / 3][c % 3] = xsrc[(p * 6 + c) * 64];          // block 0, requested with the weights
         if (RBM == 2 && RB_p > 1) {              // a two-block pass: both blocks' fragments at once
 #pragma unroll
             for (int p = 0; p < NP; ++p)
 #pragma unroll
-                for (int c = 0; c < 6; ++c) xq[1][p][c / 3][c % 3] = (MELLOW_G3_ABL & 4) ? i32x4{c, p, 3, 2} : xsrc[RBS + (p * 6 + c) * 64];
+                for (int c = 0; c < 6; ++c) xq[1][p][c / 3][c % 3] = xsrc[RBS + (p * 6 + c) * 64];
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            if (MELLOW_G3_ABL & 8) { wp[p][0] = __builtin_bit_cast(i32x4, w[2 * p]); wp[p][1] = __builtin_bit_cast(i32x4, w[2 * p + 1]); wp[p][2] = wp[p][0]; }
-            else split_pair(w[2 * p], w[2 * p + 1], wp[p][0], wp[p][1], wp[p][2]);
-        }
+        for (int p = 0; p < NP; ++p) split_pair(w[2 * p], w[2 * p + 1], wp[p][0], wp[p][1], wp[p][2]);
     }
     for (int rb0 = 0; rb0 < RB_p; rb0 += RBM) {
         const int gn = min(RBM, RB_p - rb0);
@@ -1567,7 +1515,6 @@ __global__ __launch_bounds__(GU3W * 64) void dec_gateup3_kernel(const float* __r
                 }
 #pragma unroll
                 for (int p = 0; p < NP; ++p) {
-                    if (MELLOW_G3_ABL & 2) { acc0[g][0] += __int_as_float(wp[p][0][0] ^ xq[g & 1][p][0][0][0]); acc1[g][1] += __int_as_float(wp[p][2][1] ^ xq[g & 1][p][1][2][1]); continue; }
                     // the two row halves are independent accumulator chains: term by term, alternating (a dependent MFMA waits ~2x its issue time)
 #define MELLOW_G3_TERM(PW, PX) MELLOW_BF16S(wp[p][PW], xq[g & 1][p][0][PX], acc0[g]); MELLOW_BF16S(wp[p][PW], xq[g & 1][p][1][PX], acc1[g]);
                     MELLOW_G3_TERM(2, 0) MELLOW_G3_TERM(0, 2) MELLOW_G3_TERM(1, 1) MELLOW_G3_TERM(1, 0) MELLOW_G3_TERM(0, 1) MELLOW_G3_TERM(0, 0)
@@ -1610,9 +1557,9 @@ __global__ __launch_bounds__(GU3W * 64) void dec_gateup3_kernel(const float* __r
                 h[r] = __fmul_rn(siluf_(gv * r2), uv * r2);
             }
             const float4 hv = make_float4(h[0], h[1], h[2], h[3]);
-            if (!(MELLOW_G3_ABL & 16)) st_out(reinterpret_cast<float4*>(a.guF) + ((int64_t)rb * 192 + nt) * 64 + m + 32 * q, hv);
+            *(reinterpret_cast<float4*>(a.guF) + ((int64_t)rb * 192 + nt) * 64 + m + 32 * q) = hv;
             const F3Quad hq = f3_split4(hv), ho = f3_partner(hq);     // threads (q = 0, q = 1) of a row hold the halves of one slot
-            if (!(MELLOW_G3_ABL & 1) && q == 0) f3_store8(a.h3, f3_32_slot(rb, 96, m, 8 * nt), hq, ho);
+            if (q == 0) f3_store8(a.h3, f3_32_slot(rb, 96, m, 8 * nt), hq, ho);
         }
     }
     kspan(a.dbg_seq, 1);
@@ -1645,12 +1592,11 @@ __global__ __launch_bounds__(GU_WAVES * 64) void dec_gateup16_kernel(const float
     const float4* xp = reinterpret_cast<const float4*>(xF16) + (((int64_t)rb * 36 + t0) * 2) * 64 + lane;
     // epilogue thread (m = tid>>1, q = tid&1), tid < 64: its row's 36 sum-of-squares partials, issued up front
     const float4* sq = reinterpret_cast<const float4*>(ssq_in + ((int64_t)rb * 32 + ((tid >> 1) & 31)) * 40);
-    float4 w[TPW], x0[TPW], x1[TPW], s4[9];
-    uint32_t w8[TPW];
+    WFrag<TPW, W8> w;
+    float4 x0[TPW], x1[TPW], s4[9];
 #pragma unroll
     for (int i = 0; i < TPW; ++i) {
-        if constexpr (W8 == 2) w8[i] = ldw8(Wp16, wslot + i * 64);
-        else w[i] = ldw<W8 != 0>(Wp16, wslot + i * 64);
+        w.t[i] = w.load(Wp16, wslot + i * 64);
         x0[i] = xp[(i * 2) * 64];
         x1[i] = xp[(i * 2 + 1) * 64];
     }
@@ -1658,43 +1604,12 @@ __global__ __launch_bounds__(GU_WAVES * 64) void dec_gateup16_kernel(const float
 #pragma unroll
         for (int j = 0; j < 9; ++j) s4[j] = sq[j];
     }
-    MELLOW_HOIST(a.eps); MELLOW_HOIST(a.guF);
-    if (W8) MELLOW_HOIST(wscale);
     __builtin_amdgcn_sched_barrier(0);
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (W8 == 2) {
-        // rows 0..15 (x0) and 16..31 (x1): a row's values of this wave's k-tiles sit in the four lanes (m % 16) + 16 q
-        float am0 = 0.f, am1 = 0.f, inv0, sc0, inv1, sc1;
-#pragma unroll
-        for (int i = 0; i < TPW; ++i) { am0 = fmaxf(am0, f4amax(x0[i])); am1 = fmaxf(am1, f4amax(x1[i])); }
-        am0 = fmaxf(am0, swz_xor16(am0)); am1 = fmaxf(am1, swz_xor16(am1));
-        a8_scales(half_max(am0), inv0, sc0);
-        a8_scales(half_max(am1), inv1, sc1);
-        uint32_t q0[TPW], q1[TPW];
-#pragma unroll
-        for (int i = 0; i < TPW; ++i) { q0[i] = q4_e4m3(x0[i], inv0); q1[i] = q4_e4m3(x1[i], inv1); }
-        acc0 = mfma8_16<TPW>(acc0, w8, q0);
-        acc1 = mfma8_16<TPW>(acc1, w8, q1);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { acc0[r] *= sc0; acc1[r] *= sc1; }
-    } else {
-#pragma unroll
-    for (int i = 0; i < TPW; ++i) {
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[i].x, x0[i].x, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[i].x, x1[i].x, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[i].y, x0[i].y, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[i].y, x1[i].y, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[i].z, x0[i].z, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[i].z, x1[i].z, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[i].w, x0[i].w, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[i].w, x1[i].w, acc1, 0, 0, 0);
-    }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        red[(wave * 8 + r) * 64 + lane] = acc0[r];
-        red[(wave * 8 + 4 + r) * 64 + lane] = acc1[r];
-    }
+    // rows 0..15 (x0) and 16..31 (x1) of the block against the same weight fragment
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 acc0 = slice_mma16<TPW, W8>(zero, w, x0), acc1 = slice_mma16<TPW, W8>(zero, w, x1);
+    reduce_store(MELLOW_LDS(red) + wave * 8 * 64 + lane, acc0);
+    reduce_store(MELLOW_LDS(red) + (wave * 8 + 4) * 64 + lane, acc1);
     __syncthreads();
     if (tid < 64) {
         // D[i = tile row 4*(lane>>4) + r][j = batch row lane&15], accumulator (m>>4).  Tile rows 0..7 = gate of hidden
@@ -1709,17 +1624,12 @@ __global__ __launch_bounds__(GU_WAVES * 64) void dec_gateup16_kernel(const float
         float h[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            float gv = red[(rbase + r) * 64 + gl], uv = red[(rbase + r) * 64 + ul];
-#pragma unroll
-            for (int wv = 1; wv < GU_WAVES; ++wv) {                       // fixed order
-                gv += red[(wv * 8 + rbase + r) * 64 + gl];
-                uv += red[(wv * 8 + rbase + r) * 64 + ul];
-            }
+            float gv = red_sum<GU_WAVES, 8>(MELLOW_LDS(red), rbase + r, gl), uv = red_sum<GU_WAVES, 8>(MELLOW_LDS(red), rbase + r, ul);
             if (W8) { gv *= wscale[nt * 16 + 4 * q + r]; uv *= wscale[nt * 16 + 8 + 4 * q + r]; }     // packed tile rows
             h[r] = __fmul_rn(siluf_(gv * r2), uv * r2);
         }
         // hidden unit k = 8*nt + 4*q + r: down k-tile nt, F32-layout lane' = m + 32*q
-        st_out(reinterpret_cast<float4*>(a.guF) + ((int64_t)rb * 192 + nt) * 64 + m + 32 * q, make_float4(h[0], h[1], h[2], h[3]));
+        *(reinterpret_cast<float4*>(a.guF) + ((int64_t)rb * 192 + nt) * 64 + m + 32 * q) = make_float4(h[0], h[1], h[2], h[3]);
     }
     kspan(a.dbg_seq, 1);
 }
@@ -1749,58 +1659,28 @@ __global__ __launch_bounds__(DN_WAVES * 64) void dec_down_kernel(const float* __
     const float4* hp = reinterpret_cast<const float4*>(guF_p) + ((int64_t)rb * 192 + k8_0) * 64 + lane;
     const bool dbg = tid == 0 && nt == 0 && kc == 0 && rb == 0;
     kstamp(4, 0, dbg);
-    float4 w[KPW], h4[KPW];
-    uint32_t w8[KPW];
+    WFrag<KPW, W8> w;
+    float4 h4[KPW];
 #pragma unroll
     for (int i = 0; i < KPW; ++i) {
-        if constexpr (W8 == 2) w8[i] = ldw8(Wp, wslot + i * 64);
-        else w[i] = ldw<W8 != 0>(Wp, wslot + i * 64);
+        w.t[i] = w.load(Wp, wslot + i * 64);
         h4[i] = hp[i * 64];
     }
-    MELLOW_HOIST(a.dslabF); MELLOW_HOIST(a.slabF_stride4);
-    if (W8) MELLOW_HOIST(wscale);
     __builtin_amdgcn_sched_barrier(0);
     kstamp(4, 1, dbg);
     f32x16 acc;
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-    if constexpr (W8 == 2) {
-        float am = 0.f, inv, sc;
-#pragma unroll
-        for (int i = 0; i < KPW; ++i) am = fmaxf(am, f4amax(h4[i]));
-        a8_scales(half_max(am), inv, sc);
-        uint32_t xq[KPW];
-#pragma unroll
-        for (int i = 0; i < KPW; ++i) xq[i] = q4_e4m3(h4[i], inv);
-        acc = mfma8_32<KPW>(acc, w8, xq);
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[q] *= sc;
-    } else {
-#pragma unroll
-        for (int i = 0; i < KPW; ++i) acc = mfma4(acc, w[i], h4[i]);
-    }
+    acc = slice_mma32<KPW, W8>(acc, w, h4);
     kstamp(4, 2, dbg && acc[0] == acc[0]);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) red[(wave * 16 + q) * 64 + lane] = acc[q];
+    reduce_store(MELLOW_LDS(red) + wave * 16 * 64 + lane, acc);
     __syncthreads();
     kstamp(4, 3, dbg);
     if (tid < 256) {
-        const int mm = tid & 31, hh = (tid >> 5) & 1, gq = tid >> 6;
-        float v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int q = 4 * gq + j;
-            float sacc = 0.f;
-#pragma unroll
-            for (int wv = 0; wv < DN_WAVES; ++wv) sacc += red[(wv * 16 + q) * 64 + mm + 32 * hh];
-            v[j] = sacc;
-        }
-        const int n = nt * 32 + 8 * gq + 4 * hh;
-        if (W8) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] *= wscale[n + j];
-        }
-        reinterpret_cast<float4*>(a.dslabF)[(int64_t)kc * a.slabF_stride4 + f32_idx(rb, 72, mm, n)] = make_float4(v[0], v[1], v[2], v[3]);
+        const int mm = tid & 31, n = epi_col(nt, tid);
+        float4 v = reduce32<DN_WAVES>(MELLOW_LDS(red), tid);
+        if (W8) v = f4scale(v, wscale + n);
+        reinterpret_cast<float4*>(a.dslabF)[(int64_t)kc * a.slabF_stride4 + f32_idx(rb, 72, mm, n)] = v;
     }
     kstamp(4, 4, dbg);
     kspan(a.dbg_seq, 1);
@@ -1821,7 +1701,7 @@ __global__ __launch_bounds__(DN_WAVES * 64) void dec_down_kernel(const float* __
 // Operands: Wx = W' (P-layout, K8x k-tiles per n-tile), Wh = W' Wd (K8h k-tiles per n-tile), Wd = the down weight (192 k-tiles).
 //   fp32 (W8 == 0): Wx and Wh are the two column ranges of ONE matrix [30][72 + 192] (K8x = K8h = Q2_K8)
 //   e4m3 (W8 != 0): three separately quantised matrices (the q/k/v copy of the unfused layer, the composed one, the down copy),
-//                   one scale per packed row each: sc_x, sc_h, sc_d; W8 == 2 also quantises x_mid / h per wave slice (see ldw8)
+//                   one scale per packed row each: sc_x, sc_h, sc_d; W8 == 2 also quantises x_mid / h per wave slice (see WFrag)
 template <bool BLK, int Q2W, int W8>
 __global__ __launch_bounds__(Q2W * 64) void dec_qkv2_kernel(const float* __restrict__ Wx, const float* __restrict__ Wh,
                                                             const float* __restrict__ Wd, const float* __restrict__ xmidF_p,
@@ -1848,32 +1728,15 @@ __global__ __launch_bounds__(Q2W * 64) void dec_qkv2_kernel(const float* __restr
         const int k8_0 = slab * 36 + wave * XT;
         const int64_t wslot = ((int64_t)nt * K8x + k8_0) * 64 + lane;
         const float4* xb = reinterpret_cast<const float4*>(xmidF_p) + ((int64_t)rb * 72 + k8_0) * 64 + lane;
-        float4 w[XT], x[XT];
-        uint32_t w8[XT];
+        WFrag<XT, W8> w;
+        float4 x[XT];
 #pragma unroll
         for (int i = 0; i < XT; ++i) {
-            if constexpr (W8 == 2) w8[i] = ldw8(Wx, wslot + i * 64);
-            else w[i] = ldw<W8 != 0>(Wx, wslot + i * 64);
+            w.t[i] = w.load(Wx, wslot + i * 64);
             x[i] = xb[i * 64];
         }
-        MELLOW_HOIST(a.pq); MELLOW_HOIST(a.rows);
-        if (W8) MELLOW_HOIST(sc_x);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (W8 == 2) {
-            float am = 0.f, inv, sc;
-#pragma unroll
-            for (int i = 0; i < XT; ++i) am = fmaxf(am, f4amax(x[i]));
-            a8_scales(half_max(am), inv, sc);
-            uint32_t xq[XT];
-#pragma unroll
-            for (int i = 0; i < XT; ++i) xq[i] = q4_e4m3(x[i], inv);
-            acc = mfma8_32<XT>(acc, w8, xq);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] *= sc;
-        } else {
-#pragma unroll
-            for (int i = 0; i < XT; ++i) acc = mfma4(acc, w[i], x[i]);
-        }
+        acc = slice_mma32<XT, W8>(acc, w, x);
     } else {                   // h part
         const int idx = b - 60, hc = idx / 48;
         nt = idx % 48;
@@ -1884,59 +1747,28 @@ __global__ __launch_bounds__(Q2W * 64) void dec_qkv2_kernel(const float* __restr
         const float* wbase = side ? Wd : Wh;
         const int64_t wslot = side ? ((int64_t)(nt - 30) * 192 + k8_0) * 64 + lane : ((int64_t)nt * K8h + k8_0) * 64 + lane;
         const float4* hp = reinterpret_cast<const float4*>(guF_p) + ((int64_t)rb * 192 + k8_0) * 64 + lane;
-        float4 w[HT], h4[HT];
-        uint32_t w8[HT];
+        WFrag<HT, W8> w;
+        float4 h4[HT];
 #pragma unroll
         for (int i = 0; i < HT; ++i) {
-            if constexpr (W8 == 2) w8[i] = ldw8(wbase, wslot + i * 64);
-            else w[i] = ldw<W8 != 0>(wbase, wslot + i * 64);
+            w.t[i] = w.load(wbase, wslot + i * 64);
             h4[i] = hp[i * 64];
         }
-        MELLOW_HOIST(a.pq); MELLOW_HOIST(a.rows); MELLOW_HOIST(a.dslabF); MELLOW_HOIST(a.slabF_stride4);
-        if (W8) MELLOW_HOIST(wsc);
         __builtin_amdgcn_sched_barrier(0);
         kstamp(7, 1, dbg);
-        if constexpr (W8 == 2) {
-            float am = 0.f, inv, sc;
-#pragma unroll
-            for (int i = 0; i < HT; ++i) am = fmaxf(am, f4amax(h4[i]));
-            a8_scales(half_max(am), inv, sc);
-            uint32_t xq[HT];
-#pragma unroll
-            for (int i = 0; i < HT; ++i) xq[i] = q4_e4m3(h4[i], inv);
-            acc = mfma8_32<HT>(acc, w8, xq);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] *= sc;
-        } else {
-#pragma unroll
-            for (int i = 0; i < HT; ++i) acc = mfma4(acc, w[i], h4[i]);
-        }
+        acc = slice_mma32<HT, W8>(acc, w, h4);
         kstamp(7, 2, dbg && acc[0] == acc[0]);
         if (side) nt -= 30;
     }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) red[(wave * 16 + r) * 64 + lane] = acc[r];
+    reduce_store(MELLOW_LDS(red) + wave * 16 * 64 + lane, acc);
     __syncthreads();
     kstamp(7, 3, dbg);
     if (tid < 256) {
-        const int mm = tid & 31, hh = (tid >> 5) & 1, gq = tid >> 6;
-        float v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int q = 4 * gq + j;
-            float sacc = red[q * 64 + mm + 32 * hh];
-#pragma unroll
-            for (int wv = 1; wv < Q2W; ++wv) sacc += red[(wv * 16 + q) * 64 + mm + 32 * hh];      // fixed order
-            v[j] = sacc;
-        }
-        const int n = nt * 32 + 8 * gq + 4 * hh;
-        if (W8) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] *= wsc[n + j];
-        }
-        const float4 o = make_float4(v[0], v[1], v[2], v[3]);
-        if (side) st_out(reinterpret_cast<float4*>(a.dslabF) + (int64_t)slab * a.slabF_stride4 + f32_idx(rb, 72, mm, n), o);
-        else st_out(reinterpret_cast<float4*>(a.pq + ((int64_t)slab * a.rows + rb * 32 + mm) * 960 + n), o);
+        const int mm = tid & 31, n = epi_col(nt, tid);
+        float4 o = reduce32<Q2W>(MELLOW_LDS(red), tid);
+        if (W8) o = f4scale(o, wsc + n);
+        if (side) *(reinterpret_cast<float4*>(a.dslabF) + (int64_t)slab * a.slabF_stride4 + f32_idx(rb, 72, mm, n)) = o;
+        else *reinterpret_cast<float4*>(a.pq + ((int64_t)slab * a.rows + rb * 32 + mm) * 960 + n) = o;
     }
     kstamp(7, 4, dbg);
     kspan(a.dbg_seq, 1);

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Developer tool: a variant of libmellow_hip.so in which ONLY decode.hip is rebuilt with extra -D flags (the other objects come
 # from the release build's cache, mellow_amd/csrc/build/): seconds instead of minutes per variant.
-#   tools/ab_decode.sh nohoist "-DMELLOW_NO_HOIST"   ->  mellow_amd/lib/ab/libmellow_hip_nohoist.so
+#   tools/ab_decode.sh down6 "-DMELLOW_DOWN_WAVES=6"   ->  mellow_amd/lib/ab/libmellow_hip_down6.so
 # Run `python mellow_amd/csrc/build.py` first.  Use with MELLOW_HIP_LIB=... python tools/decode_probe.py, or tools/ab_run.sh.
 # (build.py on a copy of its object cache without decode.hip.o: the copies keep their times, so nothing else is stale)
 set -e
