@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "gemm_tile.h"
 #include "kernels.h"
 
 namespace mellow {
@@ -50,8 +51,7 @@ struct GemmBDev {
     GemmArgs a;
     int gm, gn;
     int ks;                 // split-K: workgroups per output tile (1 = none); tile = L % (gm gn), split = L / (gm gn)
-    int ng = 0;             // x3q, wide outputs (gn % 8 == 0, gn >= 16, no split-K): XCD x owns the n-tiles [x gn/8, (x+1) gn/8) for EVERY row
-                            // panel -- its gn/8 weight tiles stay in its 4 MiB L2 while the panels stream through (below)
+    int ng = 0;             // x3q: the XCD-ownership order of the tiles (gemm_tile.h, tile_decode)
 };
 
 // Split-K for launches that would leave most of the chip idle (<= 256 output tiles: the tail GEMMs of the encoder).  Two
@@ -77,12 +77,7 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(const GemmBDev p) {
     const int tile = blockIdx.x;
     const int pm = tile / p.gn, pn = tile % p.gn;
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    TILE_ZERO_ACC22(acc)
     const f32x4* rs = reinterpret_cast<const f32x4*>(p.a.sk_ws) + ((int64_t)tile * p.ks * 16) * 256 + tid;
     for (int sp = 0; sp < p.ks; ++sp, rs += 16 * 256) {
 #pragma unroll
@@ -110,27 +105,71 @@ static int splitk_for(const GemmArgs& a, int tiles, int KT) {
     return s < 2 ? 1 : s;
 }
 
-#define MELLOW_BF(W, A, ACC) ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, W), __builtin_bit_cast(bf16x8, A), ACC, 0, 0, 0);
+// ---- the six-term product of one k16 tile ------------------------------------------------------------------------------------------
+// Fragments f[tile][piece]: the three bf16 pieces of a wave's two 32-row tiles of an operand.  Term t multiplies weight piece
+// X3_PW[t] by activation piece X3_PA[t]: (2,0) (0,2) (1,1) (1,0) (0,1) (0,0) -- per accumulator the smallest partial products come
+// first, so that they are summed among themselves before they meet the large ones.  The unit is the HALF-term: one weight tile
+// against both activation tiles, into that weight tile's two accumulators.  A term is its two half-terms (term-major: consecutive
+// MFMAs go to four different accumulators, no back-to-back dependence); every kernel of this file issues the same MFMAs in the
+// same order per output element (tests/test_gpu_gemm.py holds kernel 17 == kernel 16 and x3w == the tile kernel to that):
+//   the 24-MFMA burst of a tile        x3_terms(fa, fw, acc, 0, 6)                       gemm_bf16x3f_kernel, gemm_x3p_kernel
+//   x3q                                x3_terms(.., 0, 3), then the six half-terms of terms 3..5 between its six LDS-DMA issues
+//   x3w (one weight tile per wave)     x3_halves(fa, wf, acc, 0, 6): six half-terms, 12 MFMAs
+__device__ __forceinline__ void x3_half(const i32x4 (&fa)[2][3], const i32x4 (&fw)[3], f32x16 (&acc)[2], int t) {
+    constexpr int X3_PW[6] = {2, 0, 1, 1, 0, 0}, X3_PA[6] = {0, 2, 1, 0, 1, 0};
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fw[X3_PW[t]]), __builtin_bit_cast(bf16x8, fa[i][X3_PA[t]]), acc[i], 0, 0, 0);
+}
+__device__ __forceinline__ void x3_halves(const i32x4 (&fa)[2][3], const i32x4 (&fw)[3], f32x16 (&acc)[2], int t0, int t1) {
+#pragma unroll
+    for (int t = t0; t < t1; ++t) x3_half(fa, fw, acc, t);
+}
+__device__ __forceinline__ void x3_terms(const i32x4 (&fa)[2][3], const i32x4 (&fw)[2][3], f32x16 (&acc)[2][2], int t0, int t1) {
+#pragma unroll
+    for (int t = t0; t < t1; ++t) {
+        x3_half(fa, fw[0], acc[0], t);
+        x3_half(fa, fw[1], acc[1], t);
+    }
+}
+// Stage order of a split operand in LDS, 16-byte slots: [piece][32-row tile][lane]; st = the stage at the wave's first tile (2 wm or
+// 2 wn) and its lane.  X3_FRAGS reads both operands' fragments of a k16 tile (x3p, x3q: the kernels name As, Ws, STAGE, wm, wn, lane
+// alike), X3W_FRAGS the A half.  The read loops are macros: as a function filling fa / fw through references the same loop put
+// three more waits into the x3p kernel.
+__device__ __forceinline__ i32x4 x3_frag(const i32x4* st, int t, int pc) { return st[(pc * 4 + t) * 64]; }
+#define X3_FRAGS(ST, FA, FW)                                                                     \
+    {                                                                                            \
+        const i32x4* Ac = As + (ST) * STAGE + (2 * wm) * 64 + lane;                              \
+        const i32x4* Wc = Ws + (ST) * STAGE + (2 * wn) * 64 + lane;                              \
+        _Pragma("unroll") for (int t = 0; t < 2; ++t)                                            \
+            _Pragma("unroll") for (int pc = 0; pc < 3; ++pc) {                                   \
+                FA[t][pc] = x3_frag(Ac, t, pc);                                                  \
+                FW[t][pc] = x3_frag(Wc, t, pc);                                                  \
+            }                                                                                    \
+    }
+constexpr int X3_STAGE = 3 * 4 * 64;                                        // 16-byte slots per operand per k16 stage (12 KiB)
+constexpr int X3_NST = 3;                                                   // x3p, x3q: ring of three stages of both operands
+constexpr size_t X3_LDS = (size_t)2 * X3_NST * X3_STAGE * 16;               // 72 KiB: two workgroups per CU (x3w: six A stages, the same)
 
 // ---- fused variant: A stays fp32 in global memory and in LDS and is split in registers after the fragment read -----------
 // No pre-pass, A traffic identical to the fp32 kernel; only the (pre-split, PB-layout) weight costs 6 bytes per element.
-// stage = one k32: A [k16 2][float4 half 2][m-tile 4][64 lanes] x 16 B = 16 KiB (lane-linear b128 fragment reads),
-//                  W [k16 2][piece 3][n-tile 4][64] x 16 B = 24 KiB; two stages = 80 KiB (dynamic LDS), 2 workgroups per CU.
-template <int EPI, int KS16>
+// stage = one k16: A [float4 half 2][m-tile 4][64 lanes] x 16 B = 8 KiB (lane-linear b128 fragment reads),
+//                  W [piece 3][n-tile 4][64] x 16 B = 12 KiB; two stages = 40 KiB (dynamic LDS).  The short-K kernel (K < 192).
+template <int EPI>
 __global__ __launch_bounds__(256) void gemm_bf16x3f_kernel(const GemmBDev p) {
     constexpr int BM = 128, BN = 128, WN = 2;
-    constexpr int A_STAGE = KS16 * 2 * 4 * 64, W_STAGE = KS16 * 3 * 4 * 64;     // 16-byte slots
-    constexpr int NA = KS16 * 2, NW = KS16 * 3;                             // float4 / 16-byte chunks per thread per stage
+    constexpr int A_STAGE = 2 * 4 * 64, W_STAGE = 3 * 4 * 64;               // 16-byte slots
+    constexpr int NA = 2, NW = 3;                                           // float4 / 16-byte chunks per thread per stage
     extern __shared__ __attribute__((aligned(16))) i32x4 smem_bf[];
     f32x4* As = reinterpret_cast<f32x4*>(smem_bf);                          // [2][A_STAGE]
     i32x4* Ws = smem_bf + 2 * A_STAGE;                                      // [2][W_STAGE]
     const GemmArgs& g = p.a;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    const int L = xcd_remap((int)blockIdx.x, p.gm * p.gn);
-    const int pm = L / p.gn, pn = L % p.gn;
-    const int K16 = g.K >> 4, KT = K16 / KS16;
-    const bool wave_active = (pn * BN + wn * 64) < g.Nw;
+    const TilePos tp = tile_decode<false>(p.gm, p.gn, 1, 0);
+    const int pm = tp.pm, pn = tp.pn;
+    const int KT = g.K >> 4;
+    const bool wave_active = !wave_idle(pn, wn, g.Nw);
     const i32x4* PB = reinterpret_cast<const i32x4*>(g.W8);
 
     const float* a_ptr[NA];
@@ -138,31 +177,25 @@ __global__ __launch_bounds__(256) void gemm_bf16x3f_kernel(const GemmBDev p) {
 #pragma unroll
     for (int q = 0; q < NA; ++q) {
         const int idx = q * 256 + tid;
-        constexpr int CHK = 4 * KS16;                    // float4 chunks per row per stage
-        const int row = (idx / (8 * CHK)) * 8 + (idx & 7);   // 8 consecutive lanes -> 8 rows, next lane bits -> the chunks of a row
-        const int chunk = (idx >> 3) % CHK;              // k = 4 chunk .. 4 chunk + 3 of the stage
+        const int row = (idx / 32) * 8 + (idx & 7);      // 8 consecutive lanes -> 8 rows, next lane bits -> the 4 float4 chunks of a row
+        const int chunk = (idx >> 3) % 4;                // k = 4 chunk .. 4 chunk + 3 of the stage
         int m = pm * BM + row;
         m = m < g.M ? m : g.M - 1;
         a_ptr[q] = g.A + (int64_t)m * g.lda + chunk * 4;
-        const int s16 = chunk >> 2, kh = (chunk >> 1) & 1, half4 = chunk & 1;
-        a_lds[q] = ((s16 * 2 + half4) * 4 + (row >> 5)) * 64 + (row & 31) + 32 * kh;
+        const int kh = (chunk >> 1) & 1, half4 = chunk & 1;
+        a_lds[q] = (half4 * 4 + (row >> 5)) * 64 + (row & 31) + 32 * kh;
     }
     const i32x4* w_ptr[NW];
     int w_lds[NW];
 #pragma unroll
     for (int q = 0; q < NW; ++q) {
         const int c = q * 256 + tid;
-        const int ntl = c / (192 * KS16), rem = c % (192 * KS16), s16 = rem / 192, r2 = rem % 192;
-        w_ptr[q] = PB + ((int64_t)(pn * 4 + ntl) * K16 + s16) * 192 + r2;
-        w_lds[q] = s16 * (3 * 4 * 64) + ((r2 >> 6) * 4 + ntl) * 64 + (r2 & 63);
+        const int ntl = c / 192, r2 = c % 192;           // W: [n-tile][piece][lane] per k16
+        w_ptr[q] = PB + ((int64_t)(pn * 4 + ntl) * KT) * 192 + r2;
+        w_lds[q] = ((r2 >> 6) * 4 + ntl) * 64 + (r2 & 63);
     }
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    TILE_ZERO_ACC22(acc)
 
     f32x4 ra[NA];
     i32x4 rw[NW];
@@ -179,38 +212,22 @@ __global__ __launch_bounds__(256) void gemm_bf16x3f_kernel(const GemmBDev p) {
         const int cur = kt & 1;
         const int ktn = kt + 1 < KT ? kt + 1 : kt;
 #pragma unroll
-        for (int q = 0; q < NA; ++q) ra[q] = *reinterpret_cast<const f32x4*>(a_ptr[q] + ktn * 16 * KS16);
+        for (int q = 0; q < NA; ++q) ra[q] = *reinterpret_cast<const f32x4*>(a_ptr[q] + ktn * 16);
 #pragma unroll
-        for (int q = 0; q < NW; ++q) rw[q] = w_ptr[q][(int64_t)ktn * KS16 * 192];
+        for (int q = 0; q < NW; ++q) rw[q] = w_ptr[q][(int64_t)ktn * 192];
         if (wave_active) {
             const f32x4* Ac = As + cur * A_STAGE + (2 * wm) * 64 + lane;
             const i32x4* Wc = Ws + cur * W_STAGE + (2 * wn) * 64 + lane;
+            i32x4 a[2][3], w[2][3];
 #pragma unroll
-            for (int s16 = 0; s16 < KS16; ++s16) {
-                i32x4 a[2][3], w[2][3];
+            for (int t = 0; t < 2; ++t) {
+                const f32x4 lo = Ac[t * 64], hi = Ac[(4 + t) * 64];
+                const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+                split8(v, a[t][0], a[t][1], a[t][2]);
 #pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    const f32x4 lo = Ac[((s16 * 2 + 0) * 4 + t) * 64], hi = Ac[((s16 * 2 + 1) * 4 + t) * 64];
-                    const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-                    split8(v, a[t][0], a[t][1], a[t][2]);
-#pragma unroll
-                    for (int pc = 0; pc < 3; ++pc) w[t][pc] = Wc[s16 * (3 * 4 * 64) + (pc * 4 + t) * 64];
-                }
-                // term-major: consecutive MFMAs go to four different accumulators (no back-to-back dependence);
-                // per accumulator the order is still smallest partial product first
-#define MELLOW_TERM(PW, PA)                                   \
-                MELLOW_BF(w[0][PW], a[0][PA], acc[0][0])      \
-                MELLOW_BF(w[0][PW], a[1][PA], acc[0][1])      \
-                MELLOW_BF(w[1][PW], a[0][PA], acc[1][0])      \
-                MELLOW_BF(w[1][PW], a[1][PA], acc[1][1])
-                MELLOW_TERM(2, 0)
-                MELLOW_TERM(0, 2)
-                MELLOW_TERM(1, 1)
-                MELLOW_TERM(1, 0)
-                MELLOW_TERM(0, 1)
-                MELLOW_TERM(0, 0)
-#undef MELLOW_TERM
+                for (int pc = 0; pc < 3; ++pc) w[t][pc] = x3_frag(Wc, t, pc);
             }
+            x3_terms(a, w, acc, 0, 6);
         }
 #pragma unroll
         for (int q = 0; q < NA; ++q) As[(cur ^ 1) * A_STAGE + a_lds[q]] = ra[q];
@@ -238,21 +255,18 @@ __global__ __launch_bounds__(256) void gemm_bf16x3f_kernel(const GemmBDev p) {
 // operand split: 206 -- the VALU is not either.  What remains is the one barrier per 24 MFMAs with two waves per SIMD.
 template <int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_x3p_kernel(const GemmBDev p) {
-    constexpr int BM = 128, BN = 128, WN = 2, NST = 3;
-    constexpr int STAGE = 3 * 4 * 64;                                       // 16-byte slots per operand per stage: [piece][tile][lane]
+    constexpr int BM = 128, BN = 128, WN = 2, NST = X3_NST, STAGE = X3_STAGE;
     extern __shared__ __attribute__((aligned(16))) i32x4 smem_bf[];
     i32x4* As = smem_bf;                                                    // [NST][STAGE]  A already split (3 bf16 pieces)
     i32x4* Ws = smem_bf + NST * STAGE;                                      // [NST][STAGE]
     const GemmArgs& g = p.a;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    const int tiles = p.gm * p.gn;
-    const int L = xcd_remap((int)blockIdx.x, tiles * p.ks);
-    const int tile = L % tiles, split = L / tiles;
-    const int pm = tile / p.gn, pn = tile % p.gn;
+    const TilePos tp = tile_decode<true>(p.gm, p.gn, p.ks, 0);
+    const int pm = tp.pm, pn = tp.pn;
     const int KTf = g.K >> 4;
-    const int kt0 = split * KTf / p.ks;
-    const int KT = (split + 1) * KTf / p.ks - kt0;                          // this workgroup's k16 steps (all of them without split-K)
+    const KRange kr = splitk_range(KTf, tp.split, p.ks);
+    const int kt0 = kr.kt0, KT = kr.KT;                                     // this workgroup's k16 steps
     const i32x4* PB = reinterpret_cast<const i32x4*>(g.W8);
 
     // A staging: thread t owns the 8 consecutive k of (row t/2, k-half t%2) of a k16 tile = exactly one lane's share of an MFMA
@@ -274,12 +288,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x3p_kernel(const GemmBDev p) {
         w_lds[q] = ((r2 >> 6) * 4 + ntl) * 64 + (r2 & 63);
     }
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    TILE_ZERO_ACC22(acc)
 
     // two register sets: a tile's global loads are issued two whole iterations before its LDS store (an L2 round trip is
     // longer than one 24-MFMA iteration)
@@ -302,23 +311,6 @@ __global__ __launch_bounds__(256, 2) void gemm_x3p_kernel(const GemmBDev p) {
         As[(ST) * STAGE + 512 + a_lds] = p2_;                                                    \
         _Pragma("unroll") for (int q = 0; q < 3; ++q) Ws[(ST) * STAGE + w_lds[q]] = rw[q];        \
     }
-    // fragments of one k16 tile: a[m-tile][piece], w[n-tile][piece]
-#define X3_FRAGS(ST, FA, FW)                                                                     \
-    {                                                                                            \
-        const i32x4* Ac = As + (ST) * STAGE + (2 * wm) * 64 + lane;                              \
-        const i32x4* Wc = Ws + (ST) * STAGE + (2 * wn) * 64 + lane;                              \
-        _Pragma("unroll") for (int t = 0; t < 2; ++t)                                            \
-            _Pragma("unroll") for (int pc = 0; pc < 3; ++pc) {                                   \
-                FA[t][pc] = Ac[(pc * 4 + t) * 64];                                               \
-                FW[t][pc] = Wc[(pc * 4 + t) * 64];                                               \
-            }                                                                                    \
-    }
-#define X3_TERM(FA, FW, PW, PA)                         \
-    MELLOW_BF(FW[0][PW], FA[0][PA], acc[0][0])          \
-    MELLOW_BF(FW[0][PW], FA[1][PA], acc[0][1])          \
-    MELLOW_BF(FW[1][PW], FA[0][PA], acc[1][0])          \
-    MELLOW_BF(FW[1][PW], FA[1][PA], acc[1][1])
-#define X3_MFMAS(FA, FW) X3_TERM(FA, FW, 2, 0) X3_TERM(FA, FW, 0, 2) X3_TERM(FA, FW, 1, 1) X3_TERM(FA, FW, 1, 0) X3_TERM(FA, FW, 0, 1) X3_TERM(FA, FW, 0, 0)
     // interleave between the MFMA issues: the 12 fragment reads of the next tile first, then the split of the staged tile
     // (VALU) with its 6 LDS writes, then the 5 global loads of the tile after that
 #define X3_SCHED()                                                                               \
@@ -330,13 +322,6 @@ __global__ __launch_bounds__(256, 2) void gemm_x3p_kernel(const GemmBDev p) {
         if (i_ >= 19 && i_ < 24) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);              \
     }
 
-    // the wave raises its priority for the MFMA burst so that the SIMD's other wave does not steal issue slots in the middle
-    // of it (LM shapes +1..5 %, tools/ab_build.sh -DMELLOW_X3_NO_SETPRIO for the A/B)
-#ifdef MELLOW_X3_NO_SETPRIO
-#define X3_PRIO(P)
-#else
-#define X3_PRIO(P) __builtin_amdgcn_s_setprio(P);
-#endif
     i32x4 fa0[2][3], fw0[2][3], fa1[2][3], fw1[2][3];
     X3_GLOAD(0, raA, rwA)
     X3_GLOAD(1, raB, rwB)
@@ -349,21 +334,18 @@ __global__ __launch_bounds__(256, 2) void gemm_x3p_kernel(const GemmBDev p) {
     // iteration t: fragments of tile t+1 (complete since the last barrier) -> registers; MFMAs of tile t; registers (tile t+2,
     // loaded one whole iteration ago) split -> stage (t+2) % 3, whose last readers finished in iteration t-2; loads of tile
     // t+4 -> the same registers (two sets alternate); barrier.  Unrolled by 6: stage indices and register sets are static.
-    // MELLOW_X3_ABL (developer ablation, wrong results): bit 0 no global loads, 1 no barrier, 2 no LDS stores, 3 no fragment
-    // reads in the loop -- what each part costs on top of the 24 MFMAs (tools/README.md)
-#ifndef MELLOW_X3_ABL
-#define MELLOW_X3_ABL 0
-#endif
+    // The wave raises its priority for the MFMA burst so that the SIMD's other wave does not steal issue slots in the middle of
+    // it (LM shapes +1..5 %).
 #define X3_ITER(T, SN, SW, FA, FW, FAN, FWN, ra, rw)                                             \
     if ((T) < KT) {                                                                              \
-        X3_PRIO(2)                                                                               \
-        if (!(MELLOW_X3_ABL & 8)) X3_FRAGS(SN, FAN, FWN)                                         \
-        X3_MFMAS(FA, FW)                                                                         \
-        if (!(MELLOW_X3_ABL & 4)) X3_LSTORE(SW, ra, rw)                                          \
-        if (!(MELLOW_X3_ABL & 1)) X3_GLOAD((T) + 4, ra, rw)                                      \
-        if (!MELLOW_X3_ABL) X3_SCHED()                                                           \
-        X3_PRIO(0)                                                                               \
-        if (!(MELLOW_X3_ABL & 2)) __syncthreads();                                               \
+        __builtin_amdgcn_s_setprio(2);                                                           \
+        X3_FRAGS(SN, FAN, FWN)                                                                   \
+        x3_terms(FA, FW, acc, 0, 6);                                                             \
+        X3_LSTORE(SW, ra, rw)                                                                    \
+        X3_GLOAD((T) + 4, ra, rw)                                                                \
+        X3_SCHED()                                                                               \
+        __builtin_amdgcn_s_setprio(0);                                                           \
+        __syncthreads();                                                                         \
     }
     for (int kt = 0; kt < KT; kt += 6) {
         X3_ITER(kt + 0, 1, 2, fa0, fw0, fa1, fw1, raA, rwA)
@@ -375,13 +357,9 @@ __global__ __launch_bounds__(256, 2) void gemm_x3p_kernel(const GemmBDev p) {
     }
 #undef X3_GLOAD
 #undef X3_LSTORE
-#undef X3_FRAGS
-#undef X3_TERM
-#undef X3_MFMAS
 #undef X3_SCHED
 #undef X3_ITER
-#undef X3_PRIO
-    if (p.ks > 1) return splitk_store(p, acc, tile, split, tid);
+    if (p.ks > 1) return splitk_store(p, acc, tp.tile, tp.split, tid);
     gemm_epilogue<WN, EPI>(g, acc, pm, pn, wm, wn, lane, BM, BN);
 }
 
@@ -392,17 +370,11 @@ __global__ __launch_bounds__(256, 2) void gemm_x3p_kernel(const GemmBDev p) {
 // contiguous), so a stage of either operand is twelve 1-KiB `global_load_lds_dwordx4` (wave-uniform LDS base + lane * 16): no
 // staging registers, no VALU, no ds_write.  Three stages: during iteration t the fragments of tile t+1 are read, tile t+2 is
 // landing and tile t+3 is issued into the stage tile t occupied (its fragments have been in registers since iteration t-1).
-// The LDS-DMA loads are issued from inline asm, which hipcc does not count: the waits are explicit (vmcnt(6): the six loads of
-// tile t+3 may stay in flight across the barrier).
-__device__ __forceinline__ void glds16(const void* base, uint32_t voff, uint32_t lds_addr) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(lds_addr), "s"(base) : "memory");
-}
+// The LDS-DMA loads (gemm_tile.h: glds16, DmaStage) are issued from inline asm, which hipcc does not count: the waits are explicit
+// (vmcnt(6): the six loads of tile t+3 may stay in flight across the barrier).
 template <int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_x3q_kernel(const GemmBDev p) {
-    constexpr int BM = 128, BN = 128, WN = 2, NST = 3;
-    constexpr int STAGE = 3 * 4 * 64;                                       // i32x4 per operand per stage
+    constexpr int BM = 128, BN = 128, WN = 2, NST = X3_NST, STAGE = X3_STAGE;
     extern __shared__ __attribute__((aligned(16))) i32x4 smem_bf[];
     i32x4* As = smem_bf;
     i32x4* Ws = smem_bf + NST * STAGE;
@@ -410,137 +382,57 @@ __global__ __launch_bounds__(256, 2) void gemm_x3q_kernel(const GemmBDev p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
-    const int tiles = p.gm * p.gn;
-    int tile, split, pm, pn;
-    if (p.ng) {
-        // Weight-stationary per XCD (block b runs on XCD b % 8: observed, speed only).  With the panel-major order below, an XCD
-        // walks ~12 row panels and needs ALL gn weight tiles for each: the LM's gate/up operand is 10.6 MB against a 4 MiB L2, so
-        // every panel re-fetched the whole weight -- measured 850 MB of reads per launch for 54 MB of operands, 45 % of the
-        // family's memory-side traffic, and the launch ran at the fabric's rate (profiles/r05_pmc_traffic_by_shape_*.txt).  Here an
-        // XCD keeps gn / 8 weight tiles (1.3 MB) hot and every panel is read once per XCD: 8 x 43 + 10.6 MB.
-        const int npx = p.gn >> 3, b = (int)blockIdx.x, j = b >> 3;
-        pm = j / npx; pn = (b & 7) * npx + j % npx;
-        tile = pm * p.gn + pn; split = 0;
-    } else {
-        const int L = xcd_remap((int)blockIdx.x, tiles * p.ks);
-        tile = L % tiles; split = L / tiles;
-        pm = tile / p.gn; pn = tile % p.gn;
-    }
+    const TilePos tp = tile_decode<true>(p.gm, p.gn, p.ks, p.ng);
+    const int pm = tp.pm, pn = tp.pn;
     const int KTf = g.K >> 4;
-    const int kt0 = split * KTf / p.ks;
-    const int KT = (split + 1) * KTf / p.ks - kt0;                          // this workgroup's k16 steps (split-K, see splitk_store)
-    // waves 0,1 carry the A stage (chunks wave*6 .. +5 of 12), waves 2,3 the W stage
-    // norm-free chaining (kernels.h, rs_*): the row scales of this workgroup's 128 rows are formed here, while the first
-    // LDS-DMA stages are in flight, so that the epilogue finds them in LDS instead of starting with nine dependent loads per row
-    __shared__ float rs_rows[BM];
-    if (g.rs_ssq && tid < BM) {
-        int64_t m = (int64_t)pm * BM + tid;
-        m = m < g.M ? m : g.M - 1;
-        const float* sp = g.rs_ssq + m * g.rs_parts;
-        float ss = 0.f;
-        for (int p = 0; p < g.rs_parts; ++p) ss += sp[p];             // fixed order
-        rs_rows[tid] = 1.0f / sqrtf(ss / g.rs_dim + g.rs_eps);
-    }
-    const bool isA = wave < 2;
-    const int c0 = (wave & 1) * 6;
-    const char* base = isA ? reinterpret_cast<const char*>(g.A8) + (((int64_t)pm * KTf + kt0) * 12 + c0) * 1024
-                           : reinterpret_cast<const char*>(g.W8) + ((int64_t)pn * 4 * KTf + kt0) * 3072;
-    const uint32_t kstep = isA ? 12288u : 3072u;
-    uint32_t voff[6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        const int c = c0 + j;                                               // W chunk c = piece * 4 + n-tile
-        voff[j] = isA ? (uint32_t)(j * 1024 + lane * 16) : (uint32_t)(((c & 3) * KTf * 192 + (c >> 2) * 64 + lane) * 16);
-    }
-    const uint32_t lds0 = (uint32_t)(uintptr_t)smem_bf + (isA ? 0u : (uint32_t)(NST * STAGE * 16)) + (uint32_t)c0 * 1024u;
-#define X3Q_ISSUE(T, ST)                                                                         \
-    {                                                                                            \
-        const int t_ = (T) < KT ? (T) : KT - 1;                                                  \
-        const char* b_ = base + (int64_t)t_ * kstep;                                             \
-        _Pragma("unroll") for (int j = 0; j < 6; ++j) glds16(b_, voff[j], lds0 + (uint32_t)((ST) * STAGE * 16 + j * 1024)); \
-    }
+    const KRange kr = splitk_range(KTf, tp.split, p.ks);
+    const int kt0 = kr.kt0, KT = kr.KT;                                     // this workgroup's k16 steps (split-K, see splitk_store)
+    __shared__ float rs_rows[BM];                                           // formed while the first LDS-DMA stages are in flight
+    if (g.rs_ssq && tid < BM) rs_rows[tid] = rs_row_scale(g, pm, tid);
+    // a stage of an operand = 12 pieces, 6 per wave; W piece c = piece (c >> 2) of n-tile (c & 3) in PB order [n-tile][k16][piece][lane]
+    const DmaStage<6> dma = dma_stage<6>(
+        wave, lane, reinterpret_cast<const char*>(g.A8) + (((int64_t)pm * KTf + kt0) * 12 + (wave & 1) * 6) * 1024,
+        reinterpret_cast<const char*>(g.W8) + ((int64_t)pn * 4 * KTf + kt0) * 3072, 12288u, 3072u, (uint32_t)(uintptr_t)smem_bf,
+        (uint32_t)(uintptr_t)smem_bf + (uint32_t)(NST * STAGE * 16), [=](int c) { return (uint32_t)(((c & 3) * KTf * 192 + (c >> 2) * 64 + lane) * 16); });
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-#define X3Q_FRAGS(ST, FA, FW)                                                                    \
-    {                                                                                            \
-        const i32x4* Ac = As + (ST) * STAGE + (2 * wm) * 64 + lane;                              \
-        const i32x4* Wc = Ws + (ST) * STAGE + (2 * wn) * 64 + lane;                              \
-        _Pragma("unroll") for (int t = 0; t < 2; ++t)                                            \
-            _Pragma("unroll") for (int pc = 0; pc < 3; ++pc) {                                   \
-                FA[t][pc] = Ac[(pc * 4 + t) * 64];                                               \
-                FW[t][pc] = Wc[(pc * 4 + t) * 64];                                               \
-            }                                                                                    \
-    }
-#define X3Q_TERM(FA, FW, PW, PA)                        \
-    MELLOW_BF(FW[0][PW], FA[0][PA], acc[0][0])          \
-    MELLOW_BF(FW[0][PW], FA[1][PA], acc[0][1])          \
-    MELLOW_BF(FW[1][PW], FA[0][PA], acc[1][0])          \
-    MELLOW_BF(FW[1][PW], FA[1][PA], acc[1][1])
-#define X3Q_MFMAS(FA, FW) X3Q_TERM(FA, FW, 2, 0) X3Q_TERM(FA, FW, 0, 2) X3Q_TERM(FA, FW, 1, 1) X3Q_TERM(FA, FW, 1, 0) X3Q_TERM(FA, FW, 0, 1) X3Q_TERM(FA, FW, 0, 0)
-#define X3Q_SCHED()                                                                              \
-    _Pragma("unroll") for (int i_ = 0; i_ < 24; ++i_) {                                          \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                       \
-        if (i_ < 12) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                          \
-    }
+    TILE_ZERO_ACC22(acc)
     i32x4 fa0[2][3], fw0[2][3], fa1[2][3], fw1[2][3];
-    X3Q_ISSUE(0, 0)
-    X3Q_ISSUE(1, 1)
-    X3Q_ISSUE(2, 2)
+    dma_issue(dma, 0, KT, 0 * STAGE * 16);
+    dma_issue(dma, 1, KT, 1 * STAGE * 16);
+    dma_issue(dma, 2, KT, 2 * STAGE * 16);
     asm volatile("s_waitcnt vmcnt(6)" ::: "memory");                        // tiles 0 and 1 have landed
     __builtin_amdgcn_s_barrier();
-    X3Q_FRAGS(0, fa0, fw0)
+    X3_FRAGS(0, fa0, fw0)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                                           // stage 0 is free for tile 3
-#ifndef MELLOW_X3Q_VAR
-#define MELLOW_X3Q_VAR 8
-#endif
-    // developer variants (tools/ab_build.sh -DMELLOW_X3Q_VAR=bits): 1 no LDS-DMA in the loop (wrong), 2 no vmcnt wait (wrong),
-    // 4 no setprio, 8 LDS-DMA issued between the last 12 MFMAs instead of before the first
-#define X3Q_WAIT() if (MELLOW_X3Q_VAR & 2) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
+    // iteration T: the fragments of tile T + 1 (stage S1) are read under the first three terms; the LDS-DMA of tile T + 3 into
+    // stage S0 is issued piece by piece between the six half-terms of the last three (issued before the first MFMA it cost 5 %,
+    // tools/experiments/design_history_r03_r04.md)
+#define X3Q_WAIT() asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
 #define X3Q_ITER(T, S0, S1, FA, FW, FAN, FWN)                                                    \
     if ((T) < KT) {                                                                              \
-        if (!(MELLOW_X3Q_VAR & 9)) X3Q_ISSUE((T) + 3, S0)                                        \
-        if (!(MELLOW_X3Q_VAR & 4)) __builtin_amdgcn_s_setprio(2);                                \
-        X3Q_FRAGS(S1, FAN, FWN)                                                                  \
-        if (MELLOW_X3Q_VAR & 8) {                                                                \
-            X3Q_TERM(FA, FW, 2, 0) X3Q_TERM(FA, FW, 0, 2) X3Q_TERM(FA, FW, 1, 1)                 \
-            _Pragma("unroll") for (int i_ = 0; i_ < 12; ++i_) {                                  \
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                               \
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                               \
-            }                                                                                    \
-            __builtin_amdgcn_sched_barrier(0);                                                   \
-            const int t_ = (T) + 3 < KT ? (T) + 3 : KT - 1;                                      \
-            const char* b_ = base + (int64_t)t_ * kstep;                                         \
-            _Pragma("unroll") for (int j = 0; j < 6; ++j) {                                      \
-                glds16(b_, voff[j], lds0 + (uint32_t)((S0) * STAGE * 16 + j * 1024));            \
-                if (j == 0) { MELLOW_BF(FW[0][1], FA[0][0], acc[0][0]) MELLOW_BF(FW[0][1], FA[1][0], acc[0][1]) } \
-                if (j == 1) { MELLOW_BF(FW[1][1], FA[0][0], acc[1][0]) MELLOW_BF(FW[1][1], FA[1][0], acc[1][1]) } \
-                if (j == 2) { MELLOW_BF(FW[0][0], FA[0][1], acc[0][0]) MELLOW_BF(FW[0][0], FA[1][1], acc[0][1]) } \
-                if (j == 3) { MELLOW_BF(FW[1][0], FA[0][1], acc[1][0]) MELLOW_BF(FW[1][0], FA[1][1], acc[1][1]) } \
-                if (j == 4) { MELLOW_BF(FW[0][0], FA[0][0], acc[0][0]) MELLOW_BF(FW[0][0], FA[1][0], acc[0][1]) } \
-                if (j == 5) { MELLOW_BF(FW[1][0], FA[0][0], acc[1][0]) MELLOW_BF(FW[1][0], FA[1][0], acc[1][1]) } \
-                __builtin_amdgcn_sched_barrier(0);                                               \
-            }                                                                                    \
-        } else {                                                                                 \
-            X3Q_MFMAS(FA, FW)                                                                    \
-            X3Q_SCHED()                                                                          \
+        __builtin_amdgcn_s_setprio(2);                                                           \
+        X3_FRAGS(S1, FAN, FWN)                                                                   \
+        x3_terms(FA, FW, acc, 0, 3);                                                             \
+        _Pragma("unroll") for (int i_ = 0; i_ < 12; ++i_) {                                      \
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                   \
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                   \
         }                                                                                        \
-        if (!(MELLOW_X3Q_VAR & 4)) __builtin_amdgcn_s_setprio(0);                                \
+        __builtin_amdgcn_sched_barrier(0);                                                       \
+        const char* b_ = dma_step_base(dma, (T) + 3, KT);                                        \
+        _Pragma("unroll") for (int j = 0; j < 6; ++j) {                                          \
+            dma_piece(dma, b_, (S0) * STAGE * 16, j);                                            \
+            x3_half(FA, FW[j & 1], acc[j & 1], 3 + (j >> 1));                                    \
+            __builtin_amdgcn_sched_barrier(0);                                                   \
+        }                                                                                        \
+        __builtin_amdgcn_s_setprio(0);                                                           \
         X3Q_WAIT()                                                                               \
         __builtin_amdgcn_s_barrier();                                                            \
     }
-    // A wave whose 64 columns lie entirely beyond the weight's rows (the second half of the last column tile when N is an odd
-    // multiple of 64: N = 576 -> 1 wave pair in 10, N = 960 -> 1 in 16) keeps its loading duty and its barriers but issues no
-    // MFMA: the matrix pipe it would have kept busy with zeros goes to the other workgroup of the CU.
-    const bool idle = pn * BN + wn * 64 >= g.Nw;            // wave-uniform
+    const bool idle = wave_idle(pn, wn, g.Nw);
 #define X3Q_ITER_IDLE(T, S0)                                                                     \
     if ((T) < KT) {                                                                              \
-        X3Q_ISSUE((T) + 3, S0)                                                                   \
+        dma_issue(dma, (T) + 3, KT, (S0) * STAGE * 16);                                          \
         X3Q_WAIT()                                                                               \
         __builtin_amdgcn_s_barrier();                                                            \
     }
@@ -562,16 +454,12 @@ __global__ __launch_bounds__(256, 2) void gemm_x3q_kernel(const GemmBDev p) {
     }
 #undef X3Q_ITER_IDLE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                        // the clamped re-loads of the last tiles
-#undef X3Q_ISSUE
-#undef X3Q_FRAGS
-#undef X3Q_TERM
-#undef X3Q_MFMAS
-#undef X3Q_SCHED
 #undef X3Q_ITER
 #undef X3Q_WAIT
-    if (p.ks > 1) return splitk_store(p, acc, tile, split, tid);
+    if (p.ks > 1) return splitk_store(p, acc, tp.tile, tp.split, tid);
     gemm_epilogue<WN, EPI>(g, acc, pm, pn, wm, wn, lane, BM, BN, g.rs_ssq ? rs_rows : nullptr);   // (written before the main loop's barriers)
 }
+#undef X3_FRAGS
 
 // ---- "x3w": the K = 96 GEMMs of Swin stage 0 (M = 4096 rows per clip), weight-stationary and persistent ---------------------
 // A 128 x 128 tile of these GEMMs is six k16 steps: 5 us of matrix work behind a prologue (first stages from memory) and in front
@@ -584,14 +472,13 @@ __global__ __launch_bounds__(256, 2) void gemm_x3q_kernel(const GemmBDev p) {
 // MFMAs start behind them).  Four waves, wave tile 64 x 32, 72 KB of LDS: two workgroups per CU, which drift apart, so one's
 // epilogue runs under the other's MFMAs.  The same MFMAs in the same order per output element as the other x3 kernels.
 // vmcnt: the LDS-DMA loads of the four newest stages (3 per wave and stage) may stay in flight (loads complete in order among
-// loads; pending stores can only make the wait longer).
-#ifndef MELLOW_X3W_ABL
-#define MELLOW_X3W_ABL 0       // developer ablation (tools/ab_build.sh -DMELLOW_X3W_ABL=bits): 1 no output stores, 2 no MFMAs, 4 output stored column-tile-major (wrong results, timing only)
-#endif
+// loads; pending stores can only make the wait longer).  What bounds these launches is their output (ablations without stores,
+// without MFMAs, with column-tile-major stores: tools/experiments/r04_encoder_notes.md).
 template <bool GELU>
 __global__ __launch_bounds__(256, 2) void gemm_x3w_kernel(const GemmBDev p) {
     constexpr int KT = 6, NST = 6;                                          // element (panel, kt) of the A stream lives in stage kt
-    constexpr int ASTAGE = 3 * 4 * 64;                                      // i32x4 per A stage: [piece][32-row tile][lane]
+    constexpr int ASTAGE = X3_STAGE;                                        // i32x4 per A stage: [piece][32-row tile][lane]
+    static_assert((size_t)NST * ASTAGE * 16 == X3_LDS, "six A stages fill the LDS of the three-stage ring of both operands");
     extern __shared__ __attribute__((aligned(16))) i32x4 smem_bf[];
     i32x4* As = smem_bf;
     const GemmArgs& g = p.a;
@@ -643,20 +530,18 @@ __global__ __launch_bounds__(256, 2) void gemm_x3w_kernel(const GemmBDev p) {
     X3W_ISSUE(0, 4)
     X3W_ISSUE(0, 5)
     f32x16 acc[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+    TILE_ZERO_ACC2(acc)
+    // the A half of x3_frags (piece-major, the order this kernel was measured with)
 #define X3W_FRAGS(KTI, FA)                                                                       \
     {                                                                                            \
         const i32x4* Ac = As + (KTI) * ASTAGE + (2 * wm) * 64 + lane;                            \
         _Pragma("unroll") for (int pc = 0; pc < 3; ++pc) {                                       \
-            FA[0][pc] = Ac[(pc * 4) * 64];                                                       \
-            FA[1][pc] = Ac[(pc * 4 + 1) * 64];                                                   \
+            FA[0][pc] = x3_frag(Ac, 0, pc);                                                      \
+            FA[1][pc] = x3_frag(Ac, 1, pc);                                                      \
         }                                                                                        \
     }
-#define X3W_TERM(FA, FW, PW, PA) MELLOW_BF(FW[PW], FA[0][PA], acc[0]) MELLOW_BF(FW[PW], FA[1][PA], acc[1])
-#define X3W_MFMAS(FA, FW) X3W_TERM(FA, FW, 2, 0) X3W_TERM(FA, FW, 0, 2) X3W_TERM(FA, FW, 1, 1) X3W_TERM(FA, FW, 1, 0) X3W_TERM(FA, FW, 0, 1) X3W_TERM(FA, FW, 0, 0)
+    // one weight tile per wave: the six half-terms of a k16 tile (a loop over x3_half written out here gave another MFMA order)
+#define X3W_MFMAS(FA, FW) x3_halves(FA, FW, acc, 0, 6);
     // a STEP is two k16 tiles (24 MFMAs per barrier: with one tile per barrier the kernel ran at 146 / 199 us, the barrier and the
     // fragment-read latency of a 12-MFMA step being as long as its MFMAs); fragment sets are double-buffered per step
     i32x4 fa0[2][2][3], fa1[2][2][3];                                       // [k16 tile of the step][m-tile][piece]
@@ -673,12 +558,8 @@ __global__ __launch_bounds__(256, 2) void gemm_x3w_kernel(const GemmBDev p) {
         __builtin_amdgcn_s_setprio(2);                                                           \
         X3W_FRAGS((2 * (ST) + 2) % KT, FAN[0])                                                   \
         X3W_FRAGS((2 * (ST) + 3) % KT, FAN[1])                                                   \
-        if (!(MELLOW_X3W_ABL & 2)) {                                                             \
-            X3W_MFMAS(FA[0], wf[2 * (ST)])                                                       \
-            X3W_MFMAS(FA[1], wf[2 * (ST) + 1])                                                   \
-        } else {                                                                                 \
-            acc[0][0] += __int_as_float(FA[0][0][0][0] ^ FA[1][1][2][3]);                        \
-        }                                                                                        \
+        X3W_MFMAS(FA[0], wf[2 * (ST)])                                                           \
+        X3W_MFMAS(FA[1], wf[2 * (ST) + 1])                                                       \
         _Pragma("unroll") for (int i_ = 0; i_ < 24; ++i_) {                                      \
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                   \
             if (i_ < 12) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                      \
@@ -705,12 +586,11 @@ __global__ __launch_bounds__(256, 2) void gemm_x3w_kernel(const GemmBDev p) {
                             v[j] = acc[mi][4 * gq + j] + bias[gq][j];                            \
                             if (GELU) v[j] = gelu_erf(v[j]);                                     \
                         }                                                                        \
-                        if (MELLOW_X3W_ABL & 4) *reinterpret_cast<f32x4*>(g.C + ((int64_t)(pn % (g.N >> 6)) * g.M + m) * 64 + (col & 63)) = f32x4{v[0], v[1], v[2], v[3]}; \
-                        else if (!(MELLOW_X3W_ABL & 1) || v[0] == 1.2345f) *reinterpret_cast<f32x4*>(g.C + m * g.ldc + col) = f32x4{v[0], v[1], v[2], v[3]}; \
+                        *reinterpret_cast<f32x4*>(g.C + m * g.ldc + col) = f32x4{v[0], v[1], v[2], v[3]}; \
                     }                                                                            \
                 }                                                                                \
             }                                                                                    \
-            _Pragma("unroll") for (int r = 0; r < 16; ++r) acc[mi][r] = 0.f;                     \
+            TILE_ZERO_ACC(acc[mi])                                                               \
         }                                                                                        \
     }
     // three steps per panel: the two fragment sets swap roles from one panel to the next
@@ -724,14 +604,11 @@ __global__ __launch_bounds__(256, 2) void gemm_x3w_kernel(const GemmBDev p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                        // the clamped re-loads behind the last panel
 #undef X3W_ISSUE
 #undef X3W_FRAGS
-#undef X3W_TERM
 #undef X3W_MFMAS
 #undef X3W_ITER
 #undef X3W_EPILOGUE
 #undef X3W_PANEL
 }
-
-#undef MELLOW_BF
 
 // A fp32 [M][lda] -> APB: i32x4 index ((panel * K/16 + kt) * 12 + piece * 4 + tile) * 64 + lane, row = panel * 128 + tile * 32
 // + lane % 32, k = kt * 16 + (lane / 32) * 8 .. + 7; rows >= M are written as zeros (the buffer holds roundup(M, 128) rows)
@@ -761,18 +638,20 @@ void launch_split_rows_apb(const float* A, int64_t lda, int M, int K, void* out,
     const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
     hipLaunchKernelGGL(split_rows_apb_kernel, dim3(blocks), dim3(256), 0, s, A, lda, M, K, reinterpret_cast<i32x4*>(out));
 }
+// x3p / x3q: one workgroup per (tile, split) in X3_LDS of dynamic LDS, then the sum of the splits when there are any; xcd_own: the
+// kernel knows the XCD-ownership order (x3q)
+template <int EPI>
+static void launch_x3(void (*kernel)(const GemmBDev), const GemmArgs& a, bool xcd_own, hipStream_t s) {
+    GemmBDev d = tile_grid<GemmBDev>(a);
+    d.ks = splitk_for(a, d.gm * d.gn, a.K >> 4);
+    d.ng = (xcd_own && d.ks == 1 && tile_ng(d.gn)) ? 1 : 0;
+    set_max_dynamic_lds(reinterpret_cast<const void*>(kernel), X3_LDS);
+    hipLaunchKernelGGL(kernel, dim3(d.gm * d.gn * d.ks), dim3(256), X3_LDS, s, d);
+    if (d.ks > 1) hipLaunchKernelGGL((splitk_finish_kernel<EPI>), dim3(d.gm * d.gn), dim3(256), 0, s, d);
+}
 template <int EPI>
 static void launchq(const GemmArgs& a, hipStream_t s) {
-    GemmBDev d;
-    d.a = a;
-    d.gm = (a.M + 127) / 128;
-    d.gn = (a.Nw + 127) / 128;
-    d.ks = splitk_for(a, d.gm * d.gn, a.K >> 4);
-    d.ng = (d.ks == 1 && d.gn % 8 == 0 && d.gn >= 16) ? 1 : 0;
-    const size_t lds = (size_t)3 * (2 * 3 * 4 * 64) * 16;                              // 72 KiB
-    set_max_dynamic_lds(reinterpret_cast<const void*>(&gemm_x3q_kernel<EPI>), lds);
-    hipLaunchKernelGGL((gemm_x3q_kernel<EPI>), dim3(d.gm * d.gn * d.ks), dim3(256), lds, s, d);
-    if (d.ks > 1) hipLaunchKernelGGL((splitk_finish_kernel<EPI>), dim3(d.gm * d.gn), dim3(256), 0, s, d);
+    launch_x3<EPI>(gemm_x3q_kernel<EPI>, a, true, s);
 }
 // K = 96, plain LINEAR epilogue (bias, optional GELU, fp32 output): the weight-stationary persistent kernel
 static bool x3w_fits(const GemmArgs& a) {
@@ -786,7 +665,7 @@ static void launchw(const GemmArgs& a, hipStream_t s) {
     const int panels = (a.M + 127) / 128;
     d.gm = 512 / d.gn < panels ? 512 / d.gn : panels;                      // workgroups per column tile (two per CU in all)
     d.ks = 1;
-    const size_t lds = (size_t)(6 * (3 * 4 * 64)) * 16;                                 // 72 KiB
+    const size_t lds = X3_LDS;
     set_max_dynamic_lds(reinterpret_cast<const void*>(&gemm_x3w_kernel<false>), lds);
     set_max_dynamic_lds(reinterpret_cast<const void*>(&gemm_x3w_kernel<true>), lds);
     if (a.act == ACT_GELU) hipLaunchKernelGGL((gemm_x3w_kernel<true>), dim3(d.gm * d.gn), dim3(256), lds, s, d);
@@ -806,21 +685,12 @@ void launch_gemm_bf16x3_apb(const GemmArgs& a, hipStream_t s) {
 
 template <int EPI>
 static void launchbf(const GemmArgs& a, hipStream_t s) {
-    GemmBDev d;
-    d.a = a;
-    d.gm = (a.M + 127) / 128;
-    d.gn = (a.Nw + 127) / 128;
+    // shorter K: the 3-stage prologue costs more than it hides (K = 96: 77 vs 84 TF)
+    if (a.K % 16 == 0 && a.K >= 192) return launch_x3<EPI>(gemm_x3p_kernel<EPI>, a, false, s);
+    GemmBDev d = tile_grid<GemmBDev>(a);
     d.ks = 1;
-    if (a.K % 16 == 0 && a.K >= 192) {      // shorter K: the 3-stage prologue costs more than it hides (K = 96: 77 vs 84 TF)
-        const size_t lds = (size_t)3 * (2 * 3 * 4 * 64) * 16;                          // 72 KiB
-        set_max_dynamic_lds(reinterpret_cast<const void*>(&gemm_x3p_kernel<EPI>), lds);
-        d.ks = splitk_for(a, d.gm * d.gn, a.K >> 4);
-        hipLaunchKernelGGL((gemm_x3p_kernel<EPI>), dim3(d.gm * d.gn * d.ks), dim3(256), lds, s, d);
-        if (d.ks > 1) hipLaunchKernelGGL((splitk_finish_kernel<EPI>), dim3(d.gm * d.gn), dim3(256), 0, s, d);
-        return;
-    }
     const size_t lds = (size_t)2 * (2 * 4 * 64 + 3 * 4 * 64) * 16;                 // 40 KiB
-    hipLaunchKernelGGL((gemm_bf16x3f_kernel<EPI, 1>), dim3(d.gm * d.gn), dim3(256), lds, s, d);
+    hipLaunchKernelGGL((gemm_bf16x3f_kernel<EPI>), dim3(d.gm * d.gn), dim3(256), lds, s, d);
 }
 // fused variant: g.A (fp32, row-major, lda) + g.W8 (PB); K % 32 == 0; six partial products
 void launch_gemm_bf16x3_fused(const GemmArgs& a, hipStream_t s) {

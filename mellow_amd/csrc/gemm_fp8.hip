@@ -17,9 +17,11 @@
 //   AMX scales  [panel][s / 4][m-tile][lane = m % 32 + 32 j] uint32, byte s % 4 = E8M0 scale of block (2 s + j) of row m
 //   WMX data    [n-tile = n / 32][s][j][lane = n % 32 + 32 ((k / 16) % 2)]
 // so a k64 stage of a 128-row panel (8 KiB) or of a 128-column weight tile is eight contiguous 1-KiB pieces: both operands go
-// global -> LDS by LDS-DMA exactly like the f32x3 kernel's (gemm_bf16x3.hip, x3q), and the scale words of a tile are staged once.
+// global -> LDS by LDS-DMA exactly like the f32x3 kernel's (gemm_bf16x3.hip, x3q; the tile prologue and the stage descriptor of
+// both are gemm_tile.h), and the scale words of a tile are staged once.
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "gemm_tile.h"
 #include "kernels.h"
 
 namespace mellow {
@@ -101,11 +103,6 @@ struct GemmMxDev {
     GemmArgs a;
     int gm, gn, ng;
 };
-__device__ __forceinline__ void glds16_mx(const void* base, uint32_t voff, uint32_t lds_addr) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(lds_addr), "s"(base) : "memory");
-}
 // 128 x 128 tile, 4 waves (64 x 64 each: 4 accumulator tiles), one k64 step per stage (8 KiB per operand), ring of 3 stages filled
 // by LDS-DMA (waves 0, 1: the activation stage, waves 2, 3: the weight stage; four 1-KiB pieces per wave and step).  Per step and
 // wave: 8 ds_read_b128 feed 4 MFMAs of 64 cycles.  D[n][m] like every GEMM of the engine, so the epilogues are shared.
@@ -122,14 +119,8 @@ __global__ __launch_bounds__(256, 2) void gemm_mx8_kernel(const GemmMxDev p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
-    int pm, pn;
-    if (p.ng) {         // weight-stationary per XCD for wide outputs (gemm_bf16x3.hip: gemm_x3q_kernel)
-        const int npx = p.gn >> 3, b = (int)blockIdx.x, j = b >> 3;
-        pm = j / npx; pn = (b & 7) * npx + j % npx;
-    } else {
-        const int L = xcd_remap((int)blockIdx.x, p.gm * p.gn);
-        pm = L / p.gn; pn = L % p.gn;
-    }
+    const TilePos tp = tile_decode<false>(p.gm, p.gn, 1, p.ng);
+    const int pm = tp.pm, pn = tp.pn;
     const int KT = (int)(g.lda8 >> 6);                                     // k64 steps
     const int KQ = (KT + 3) >> 2;
     // scale words of this panel -> LDS (ordinary loads: they are complete before the first LDS-DMA piece is issued, so the
@@ -138,42 +129,17 @@ __global__ __launch_bounds__(256, 2) void gemm_mx8_kernel(const GemmMxDev p) {
         const uint32_t* src = g.a_sc + (int64_t)pm * KQ * 256;
         for (int i = tid; i < KQ * 256; i += 256) Sc[i] = src[i];
     }
-    if (g.rs_ssq && tid < BM) {
-        int64_t m = (int64_t)pm * BM + tid;
-        m = m < g.M ? m : g.M - 1;
-        const float* sp = g.rs_ssq + m * g.rs_parts;
-        float ss = 0.f;
-        for (int q = 0; q < g.rs_parts; ++q) ss += sp[q];                  // fixed order
-        rs_rows[tid] = 1.0f / sqrtf(ss / g.rs_dim + g.rs_eps);
-    }
+    if (g.rs_ssq && tid < BM) rs_rows[tid] = rs_row_scale(g, pm, tid);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const bool isA = wave < 2;
-    const int c0 = (wave & 1) * 4;                                         // pieces c0 .. c0 + 3 of the 8 of a stage
-    const char* base = isA ? reinterpret_cast<const char*>(g.A8) + ((int64_t)pm * KT * 8 + c0) * 1024
-                           : reinterpret_cast<const char*>(g.W8);
-    const uint32_t kstep = isA ? 8192u : 2048u;
-    uint32_t voff[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int c = c0 + j;                                              // W piece c = n-tile (c >> 1), half j (c & 1)
-        voff[j] = isA ? (uint32_t)(j * 1024 + lane * 16)
-                      : (uint32_t)((((int64_t)(pn * 4 + (c >> 1)) * KT * 2 + (c & 1)) * 64 + lane) * 16);
-    }
-    const uint32_t lds0 = (uint32_t)(uintptr_t)smem_mx + (isA ? 0u : (uint32_t)(NST * STAGE * 16)) + (uint32_t)c0 * 1024u;
-#define MX_ISSUE(T, ST)                                                                          \
-    {                                                                                            \
-        const int t_ = (T) < KT ? (T) : KT - 1;                                                  \
-        const char* b_ = base + (int64_t)t_ * kstep;                                             \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j) glds16_mx(b_, voff[j], lds0 + (uint32_t)((ST) * STAGE * 16 + j * 1024)); \
-    }
+    // a stage of an operand = 8 pieces, 4 per wave; W piece c = half (c & 1) of n-tile (c >> 1), addressed from the weight's start
+    const DmaStage<4> dma = dma_stage<4>(
+        wave, lane, reinterpret_cast<const char*>(g.A8) + ((int64_t)pm * KT * 8 + (wave & 1) * 4) * 1024, reinterpret_cast<const char*>(g.W8),
+        8192u, 2048u, (uint32_t)(uintptr_t)smem_mx, (uint32_t)(uintptr_t)smem_mx + (uint32_t)(NST * STAGE * 16),
+        [=](int c) { return (uint32_t)((((int64_t)(pn * 4 + (c >> 1)) * KT * 2 + (c & 1)) * 64 + lane) * 16); });
+#define MX_ISSUE(T, ST) dma_issue(dma, T, KT, (ST) * STAGE * 16);
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    const bool idle = pn * BN + wn * 64 >= g.Nw;            // wave-uniform: its 64 columns lie beyond the weight's rows
+    TILE_ZERO_ACC22(acc)
+    const bool idle = wave_idle(pn, wn, g.Nw);
     MX_ISSUE(0, 0)
     MX_ISSUE(1, 1)
     int sa0 = 0, sa1 = 0;
@@ -231,11 +197,8 @@ __global__ __launch_bounds__(256, 2) void gemm_mx8_kernel(const GemmMxDev p) {
 
 template <int EPI, bool C16 = false>
 static void launch8(const GemmArgs& a, hipStream_t s) {
-    GemmMxDev d;
-    d.a = a;
-    d.gm = (a.M + 127) / 128;
-    d.gn = (a.Nw + 127) / 128;
-    d.ng = (d.gn % 8 == 0 && d.gn >= 16) ? 1 : 0;
+    GemmMxDev d = tile_grid<GemmMxDev>(a);
+    d.ng = tile_ng(d.gn) ? 1 : 0;
     const int KT = (int)(a.lda8 >> 6), KQ = (KT + 3) / 4;
     const size_t lds = (size_t)2 * 3 * (2 * 4 * 64) * 16 + (size_t)KQ * 1024;          // 48 KiB of stages + the panel's scale words
     set_max_dynamic_lds(reinterpret_cast<const void*>(&gemm_mx8_kernel<EPI, C16>), 48 * 1024 + 24 * 1024);

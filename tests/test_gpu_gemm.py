@@ -30,7 +30,10 @@ import gemm_ref as G  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(1, 4, 32), (33, 68, 64), (127, 128, 96), (129, 132, 160), (129, 128, 192), (257, 576, 576), (70, 527, 64), (65, 64, 208)]
+SHAPES = [(1, 4, 32), (33, 68, 64), (127, 128, 96), (129, 132, 160), (129, 128, 192), (257, 576, 576), (70, 527, 64), (65, 64, 208),
+          # k16 steps against the six-step unroll of the LDS-DMA loop: three (kernel 17 at its minimum K, every look-ahead issue
+          # clamped), seven (one past a full trip, two row panels), fourteen (all three kernels; x3p off a multiple of six)
+          (33, 68, 48), (129, 132, 112), (65, 64, 224)]
 QKV_CASES = [(1, 1, 1, 0), (2, 33, 40, 0), (3, 129, 160, 0), (2, 97, 128, 64), (2, 389, 453, 256)]          # (B, T, Tmax, pos0)
 
 
