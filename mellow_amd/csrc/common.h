@@ -115,6 +115,14 @@ __device__ __forceinline__ float dec_lse_max(const float* __restrict__ cm, int n
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ float siluf_(float x) { return x / (1.0f + expf(-x)); }
+// softmax weights of every attention kernel: exp(x) = 2^(x * log2 e) on the hardware v_exp_f32 (x <= 0 there; ~1e-6 relative, far
+// inside the fp32 summation-order noise of a 64..700-key softmax); exp(-inf) = 0 exactly
+__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
+// four bf16 in two dwords (memory order), widened to fp32 (exact): the bf16 K/V pages and q/k/v rows of the fp8 mode
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float4 bf16x4_f32(u32x2 r) {
+    return make_float4(__uint_as_float(r[0] << 16), __uint_as_float(r[0] & 0xffff0000u), __uint_as_float(r[1] << 16), __uint_as_float(r[1] & 0xffff0000u));
+}
 
 // ---- fp32 = exact sum of three bf16 (gemm_bf16x3.hip) ------------------------------------------------------------------
 typedef int i32x4 __attribute__((ext_vector_type(4)));

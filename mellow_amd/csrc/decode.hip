@@ -53,9 +53,6 @@ __device__ __forceinline__ void kspan(int seq, int end) {
 #endif
 void set_kernel_debug_buffer(uint64_t* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_kdbg), &p, sizeof(p)); }
 
-// softmax weights: exp(x) = 2^(x*log2 e) on the hardware v_exp_f32 (x <= 0 here; ~1e-6 relative, far inside the fp32
-// summation-order noise of a 64..700-key softmax); exp(-inf) = 0 exactly
-__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
 #define MELLOW_BLK_EXIT(RB) if (BLK) { if (a.blk_live[RB] == 0) return; }   // BLK: compile-time (a run-time null test costs 0.26 us per launch)
 // streamed-once operands (weights, KV pages): non-temporal loads (`global_load_dwordx4 ... nt`).  Each of these lines is read
 // by exactly one workgroup per step, so keeping it in L2 buys nothing, and the nt policy shortens issue -> landed by ~18 %
@@ -396,16 +393,12 @@ __global__ __launch_bounds__(QKV_THREADS) void dec_qkv_kernel(const float* __res
 //     per-wave online softmax over an interleaved set of 4-key groups; partial (m, l, o) per split.
 //     Split sp owns key groups [sp*gs, (sp+1)*gs) (the last split: everything from sp*gs on, plus the new key).
 // ----------------------------------------------------------------------------------------------------
-#ifndef MELLOW_DA_WAVES
-#define MELLOW_DA_WAVES 8
-#define MELLOW_DA_G 7
-#endif
 #ifndef MELLOW_DA_MINW
 #define MELLOW_DA_MINW 4      // waves per SIMD the register allocation must allow: 4 = two 8-wave workgroups per CU (128 VGPRs), so that
 #endif                        // the 384 workgroups of a 64-row batch are resident together instead of in two rounds
-constexpr int DA_MINW = MELLOW_DA_WAVES == 8 || MELLOW_DA_WAVES == 4 ? MELLOW_DA_MINW : 1;
-constexpr int DA_WAVES = MELLOW_DA_WAVES;
-constexpr int DA_G = MELLOW_DA_G;   // 4-key groups in flight per wave: one chunk covers 2 * DA_WAVES * DA_G * 4 = 448 keys
+constexpr int DA_WAVES = 8;         // (4 and 16 waves: another summation order, no faster -- profiles/r06_decode_attn_ablation.txt)
+constexpr int DA_G = 7;             // 4-key groups in flight per wave: one chunk covers 2 * DA_WAVES * DA_G * 4 = 448 keys
+static_assert(DA_WAVES == 8, "the merge of the waves' partials reduces over 8-lane groups");
 #ifndef MELLOW_DA_G1
 #define MELLOW_DA_G1 5      // 5 of 7: 48.55 ms of decode per 63 steps; 2 / 3 / 4 / 7 (= everything up front): 49.35 / 49.15 / 49.0 / 49.75 (same box)
 #endif
@@ -422,19 +415,18 @@ constexpr int DA_G1 = MELLOW_DA_G1 < DA_G ? MELLOW_DA_G1 : DA_G;    // key group
 // Same box, fp8 mode, decode per 63 steps: B = 128 75.9 -> 72.4 ms, B = 32 43.9 -> 41.7; with the loads compiled out the two forms
 // cost the same (66.5 / 67.1): the loop is a dependent chain (scores -> max -> exp -> weights -> P V) more than an issue stream, and
 // what the matrix form wins is the chain's length and the registers (116 instead of 218 at one row block).
-#ifndef MELLOW_DA16_MFMA
-#define MELLOW_DA16_MFMA 1
-#endif
 constexpr int DA_GM = 8;            // key groups per wave and chunk of the matrix form: 32 keys = one MFMA tile
-#ifndef MELLOW_DA16_KNT
-#define MELLOW_DA16_KNT 0           // K tile loads plain: a lane's four 16-byte pieces share a 64-byte segment that four instructions touch, and a
-#endif                              // non-temporal line does not stay for the next one (same box, fp8 B = 128: 78.9 ms with nt, 72.5 without)
-// Measured and dropped: the tile as 32 consecutive keys loaded in 1 KiB runs and turned into the operand order through a swizzled
-// LDS image (72.8 against 72.5 ms: the LDS round trip costs what the coalescing gains).
+// Measured and dropped (profiles/r06_decode_attn_ablation.txt; the switch of the first is gone):
+//   * the K tile loads non-temporal: a lane's four 16-byte pieces share a 64-byte segment that four instructions touch, and a
+//     non-temporal line does not stay for the next one (same box, fp8 B = 128: 78.9 ms with nt, 72.5 without);
+//   * the tile as 32 consecutive keys loaded in 1 KiB runs and turned into the operand order through a swizzled LDS image (72.8
+//     against 72.5 ms: the LDS round trip costs what the coalescing gains).
 // Physical waves (template parameter NW): the eight chunk streams of a workgroup ("virtual waves": own weights region, own
 // partial in the merge) can run on 8 waves or, two after the other, on 4 -- the same arithmetic in the same order, so the
 // results are bit-identical and four 256-thread workgroups share a CU (the 768 workgroups of B = 128 resident together instead
 // of in 1.5 rounds).  Measured +-0 (fp8 B = 128, same box: 72.4 ms on 8 waves, 72.4-73.5 on 4): MELLOW_DA16_NW stays 8.
+// (The parameter outlived DESIGN.md 6v: without the loop over virtual waves the compiler lays the publish tail of the matrix form
+// out otherwise, 4 .. 5 instructions more; with it the kernel is the instruction stream the figures above were measured on.)
 #ifndef MELLOW_DA16_MINW
 #define MELLOW_DA16_MINW MELLOW_DA_MINW
 #endif
@@ -444,17 +436,9 @@ constexpr int DA_GM = 8;            // key groups per wave and chunk of the matr
 
 // KV16 (fp8 mode): the decode step reads and extends a bf16 SHADOW of the K/V pages (engine_lm.cpp: converted from the fp32
 // pages the prefill wrote, once per call): half the bytes of the step's largest stream.  The new key / value of the step itself
-// are used in fp32 (from LDS) and appended rounded to nearest even.  One 8-byte load per lane = 4 bf16 of one key.
-template <bool KV16>
-__device__ __forceinline__ float4 ld_kv(const float* page, int64_t elem) {
-    if constexpr (KV16) {
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-        const u32x2 r = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(reinterpret_cast<const uint16_t*>(page) + elem));
-        return make_float4(__uint_as_float(r[0] << 16), __uint_as_float(r[0] & 0xffff0000u), __uint_as_float(r[1] << 16), __uint_as_float(r[1] & 0xffff0000u));
-    } else {
-        return ldg_nt(reinterpret_cast<const float4*>(page + elem));
-    }
-}
+// are used in fp32 (from LDS) and appended rounded to nearest even.  Its loads are load_ktile / load_vgroup of the kernel; the
+// fp32 pages of the vector form go through ld_kv.
+__device__ __forceinline__ float4 ld_kv(const float* page, int64_t elem) { return ldg_nt(reinterpret_cast<const float4*>(page + elem)); }
 template <bool KV16>
 __device__ __forceinline__ void st_kv(float* page, int64_t elem, float v) {
     if constexpr (KV16) reinterpret_cast<__bf16*>(page)[elem] = static_cast<__bf16>(v);
@@ -468,7 +452,7 @@ __device__ __forceinline__ void st_kv(float* page, int64_t elem, float v) {
 //      (221 VGPRs, 0.7 ms of decode per 63 steps faster at B = 32); otherwise the first chunk is peeled by hand so that the kernel
 //      fits 128 VGPRs and two workgroups share a CU (B = 64: 384 workgroups resident together, 73.7 -> 71.2 ms)
 template <bool BLK, bool FUSED, bool ONE, bool KV16, int NW, int TS>
-__global__ __launch_bounds__(NW * 64, ONE ? 2 : (KV16 && MELLOW_DA16_MFMA && DA_MINW > 1 ? MELLOW_DA16_MINW : DA_MINW)) void dec_attn_kernel(float* __restrict__ k_cache, float* __restrict__ v_cache,
+__global__ __launch_bounds__(NW * 64, ONE ? 2 : (KV16 ? MELLOW_DA16_MINW : MELLOW_DA_MINW)) void dec_attn_kernel(float* __restrict__ k_cache, float* __restrict__ v_cache,
                                                                   const int32_t* __restrict__ d_pos_p, const float* __restrict__ pq_p,
                                                                   const float* __restrict__ xmidF_p, int Tmax_p, int gs_p, int rows_p,
                                                                   const DecArgs a) {
@@ -483,7 +467,7 @@ __global__ __launch_bounds__(NW * 64, ONE ? 2 : (KV16 && MELLOW_DA16_MFMA && DA_
     __shared__ __attribute__((aligned(16))) float ored[DA_WAVES * 3 * 64];
     __shared__ float mred[DA_WAVES * 3], lred[DA_WAVES * 3];
     __shared__ float snew_s[3];
-    constexpr bool MF = KV16 && MELLOW_DA16_MFMA != 0;                   // scores on the matrix pipe (comment at DA_GM)
+    constexpr bool MF = KV16;                                            // bf16 pages: scores on the matrix pipe (comment at DA_GM)
     __shared__ __attribute__((aligned(16))) float pl[MF ? DA_WAVES * 32 * 4 : 4];     // softmax weights [wave][key of the tile][head | pad]
     __shared__ __attribute__((aligned(16))) __bf16 qb[MF ? 10 * 64 : 8];               // q as bf16 triples [piece][head][dim] + a zero row
     constexpr int VPW = DA_WAVES / NW;                                   // virtual waves per physical wave (matrix form only)
@@ -551,7 +535,6 @@ __global__ __launch_bounds__(NW * 64, ONE ? 2 : (KV16 && MELLOW_DA16_MFMA && DA_
     // slowest wave.  So only the first DA_G1 key groups are requested before the prologue (enough bytes in flight to keep the
     // stream busy while it runs: slab sums, RoPE, two barriers); the rest is requested after it, and the score loop consumes
     // the groups in arrival order.
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     const int kk = lane & 31, hf = lane >> 5;                     // matrix form: lane -> (key of the 32-key tile, half of its dims)
     i32x4 kq[4];
     u32x2 vq[DA_GM];
@@ -561,7 +544,7 @@ __global__ __launch_bounds__(NW * 64, ONE ? 2 : (KV16 && MELLOW_DA16_MFMA && DA_
         const i32x4* kp = reinterpret_cast<const i32x4*>(reinterpret_cast<const uint16_t*>(kpage) + (int64_t)tc * 64 + hf * 32);
 #pragma unroll
         for (int st = 0; st < 4; ++st)
-            kq[st] = MELLOW_DA16_KNT ? __builtin_nontemporal_load(kp + st) : kp[st];
+            kq[st] = kp[st];
     };
     auto load_vgroup = [&](int g0, int u) {
         const int gi = mf_group(g0, u);
@@ -569,20 +552,20 @@ __global__ __launch_bounds__(NW * 64, ONE ? 2 : (KV16 && MELLOW_DA16_MFMA && DA_
         vq[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(reinterpret_cast<const uint16_t*>(vpage) + (int64_t)tc * 64 + quad * 4));
     };
     float4 k4[MF ? 1 : DA_G], v4[MF ? 1 : DA_G];
-    auto load_group = [&](int u) {
-        const int gi = gbeg + wave + u * DA_WAVES;
+    const int g_first = gbeg + wave;                              // the wave's first key group
+    auto load_group = [&](int g0, int u) {                        // slot u of the chunk that starts at group g0 (vector form)
+        const int gi = g0 + u * DA_WAVES;
         const int tc = min(gi * 4 + sub, Tmax - 1);               // inside the page; validity is decided later
-        k4[u] = ld_kv<KV16>(kpage, (int64_t)tc * 64 + quad * 4);
-        v4[u] = ld_kv<KV16>(vpage, (int64_t)tc * 64 + quad * 4);
+        k4[u] = ld_kv(kpage, (int64_t)tc * 64 + quad * 4);
+        v4[u] = ld_kv(vpage, (int64_t)tc * 64 + quad * 4);
     };
-    const int g_first_mf = gbeg + wave;                           // virtual wave wave + NW j starts at group g_first_mf + NW j
     if constexpr (MF) {
-        load_ktile(g_first_mf);
+        load_ktile(g_first);
 #pragma unroll
-        for (int u = 0; u < DA_GM / 2; ++u) load_vgroup(g_first_mf, u);
+        for (int u = 0; u < DA_GM / 2; ++u) load_vgroup(g_first, u);
     } else {
 #pragma unroll
-        for (int u = 0; u < DA_G1; ++u) load_group(u);
+        for (int u = 0; u < DA_G1; ++u) load_group(g_first, u);
     }
     __builtin_amdgcn_sched_barrier(0);
     kstamp(1, 1, dbg);
@@ -646,10 +629,10 @@ __global__ __launch_bounds__(NW * 64, ONE ? 2 : (KV16 && MELLOW_DA16_MFMA && DA_
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (MF) {
 #pragma unroll
-        for (int u = DA_GM / 2; u < DA_GM; ++u) load_vgroup(g_first_mf, u);
+        for (int u = DA_GM / 2; u < DA_GM; ++u) load_vgroup(g_first, u);
     } else {
 #pragma unroll
-        for (int u = DA_G1; u < DA_G; ++u) load_group(u);
+        for (int u = DA_G1; u < DA_G; ++u) load_group(g_first, u);
     }
     __builtin_amdgcn_sched_barrier(0);
     kstamp(1, 3, dbg);
@@ -716,14 +699,17 @@ _Pragma("unroll")                                                               
             l_run[hh] = l_run[hh] * alpha + lsum;                                                                        \
         }                                                                                                                \
     }
-    const int g_first = gbeg + wave, g_stop = gend;
+    const int g_stop = gend;
+    // a later chunk's groups, all at once.  The text of load_group, written out: as a loop over load_group (a lambda, an always-inline
+    // lambda, this macro around the lambda, a macro around a macro) every vector-form kernel comes out 7 .. 14 instructions
+    // shorter with other waits in its FIRST chunk, and the one-row-block kernel takes 220 .. 221 VGPRs instead of 218
 #define MELLOW_DA_RELOAD(g0)                                                                                             \
     {                                                                                                                    \
         _Pragma("unroll") for (int u = 0; u < DA_G; ++u) {                                                               \
             const int gi = (g0) + u * DA_WAVES;                                                                          \
             const int tc = min(gi * 4 + sub, Tmax - 1);                                                                  \
-            k4[u] = ld_kv<KV16>(kpage, (int64_t)tc * 64 + quad * 4);                                                    \
-            v4[u] = ld_kv<KV16>(vpage, (int64_t)tc * 64 + quad * 4);                                                    \
+            k4[u] = ld_kv(kpage, (int64_t)tc * 64 + quad * 4);                                                           \
+            v4[u] = ld_kv(vpage, (int64_t)tc * 64 + quad * 4);                                                           \
         }                                                                                                                \
         __builtin_amdgcn_sched_barrier(0);                                                                               \
     }
@@ -762,8 +748,7 @@ _Pragma("unroll")                                                               
 #pragma unroll
         for (int u = 0; u < DA_GM; ++u) {
             const float4 pp = plw[4 * u + sub];                        // the three heads' weights of key (u, sub): one address per 16 lanes
-            const float4 v = make_float4(__uint_as_float(vq[u][0] << 16), __uint_as_float(vq[u][0] & 0xffff0000u),
-                                         __uint_as_float(vq[u][1] << 16), __uint_as_float(vq[u][1] & 0xffff0000u));
+            const float4 v = bf16x4_f32(vq[u]);
             acc[0].x += pp.x * v.x; acc[0].y += pp.x * v.y; acc[0].z += pp.x * v.z; acc[0].w += pp.x * v.w;
             acc[1].x += pp.y * v.x; acc[1].y += pp.y * v.y; acc[1].z += pp.y * v.z; acc[1].w += pp.y * v.w;
             acc[2].x += pp.z * v.x; acc[2].y += pp.z * v.y; acc[2].z += pp.z * v.z; acc[2].w += pp.z * v.w;
@@ -803,7 +788,7 @@ _Pragma("unroll")                                                               
             }
 #pragma clang loop unroll(disable)
             for (int g0 = gbeg + vw; g0 < g_stop; g0 += DA_WAVES * DA_GM) {
-                if (g0 != g_first_mf) {          // every chunk but the first: load, then the same body
+                if (g0 != g_first) {             // every chunk but the first: load, then the same body
                     load_ktile(g0);
 #pragma unroll
                     for (int u = 0; u < DA_GM; ++u) load_vgroup(g0, u);
@@ -847,8 +832,6 @@ _Pragma("unroll")                                                               
     kstamp(1, 4, dbg && l_run[0] == l_run[0]);
     __syncthreads();
     kstamp(1, 5, dbg);
-    static_assert(DA_WAVES == 8 || DA_WAVES == 16 || DA_WAVES == 4, "the merge below reduces over 8-lane groups (8 waves) or serially");
-    if (DA_WAVES == 8)
 #pragma unroll
     for (int it = tid; it < 384; it += NW * 64) {      // (whole 8-lane groups: 384 and NW * 64 are multiples of 8)
         // item -> (pair = (head hh, dim quad dq), wave w): the 8 waves' partials of a pair sit in 8 adjacent lanes and are
@@ -883,37 +866,6 @@ _Pragma("unroll")                                                               
             if (dq == 0)      // (m, l) of this split: [head][row][split] pairs, so that the o_proj reads both splits of a row with one 16-byte load
                 *reinterpret_cast<float2*>(a.att_ml + (((int64_t)head * a.rows + b) * TS + sp) * 2) = make_float2(M, L);
         }
-    }
-    if (DA_WAVES != 8 && tid < 48) {
-        // thread -> (head hh, dim quad dq): merged float4 of the waves (+ the new key on the last split), serial form
-        const int hh = tid >> 4, dq = tid & 15;
-        const float snew = snew_s[hh];
-        float M = sp == TS - 1 ? snew : -INFINITY;   // the last split also owns the new key
-#pragma unroll
-        for (int w = 0; w < DA_WAVES; ++w) M = fmaxf(M, mred[w * 3 + hh]);
-        float L = 0.f;
-        float4 O = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (M > -INFINITY) {                 // an empty split (short context) publishes m = -inf, l = 0, o = 0
-            if (sp == TS - 1) {
-                const float pn = fast_exp(snew - M);
-                const float4 vn = *reinterpret_cast<const float4*>(vnew + dq * 4);
-                L = pn;
-                O = make_float4(pn * vn.x, pn * vn.y, pn * vn.z, pn * vn.w);
-            }
-#pragma unroll
-            for (int w = 0; w < DA_WAVES; ++w) {
-                const float f = fast_exp(mred[w * 3 + hh] - M);     // waves without keys: m = -inf -> factor 0
-                const float4 ow = *reinterpret_cast<const float4*>(ored + (w * 3 + hh) * 64 + dq * 4);
-                L += lred[w * 3 + hh] * f;
-                O.x += ow.x * f; O.y += ow.y * f; O.z += ow.z * f; O.w += ow.w * f;
-            }
-        }
-        const int head = 3 * g + hh, k = head * 64 + dq * 4;
-        const int rb = b >> 5, m = b & 31;
-        const int64_t o4 = ((((int64_t)sp * a.RB + rb) * 36 + (k >> 4)) * 2 + (m >> 4)) * 64 + (m & 15) + 16 * ((k >> 2) & 3);
-        reinterpret_cast<float4*>(a.attF16)[o4] = O;
-        if (dq == 0)
-            *reinterpret_cast<float2*>(a.att_ml + (((int64_t)head * a.rows + b) * TS + sp) * 2) = make_float2(M, L);
     }
     kstamp(1, 6, dbg);
     kspan(a.dbg_seq, 1);
@@ -2069,7 +2021,7 @@ void launch_dec_attn(const DecArgs& a, float* k_cache, float* v_cache, bool fuse
     auto launch = [&](auto blk, auto one_c) { with_bool(fused, [&](auto fused_c) { with_bool(a.kv16 != 0, [&](auto kv16) {
         constexpr bool ONE = one_c.value, KV16 = kv16.value;
         // bf16 pages, matrix form: MELLOW_DA16_NW physical waves from two row blocks on -- kernel comment at DA_GM
-        constexpr int NW = !KV16 ? DA_WAVES : MELLOW_DA16_MFMA && DA_WAVES == 8 && !ONE ? MELLOW_DA16_NW : DA_WAVES;
+        constexpr int NW = KV16 && !ONE ? MELLOW_DA16_NW : DA_WAVES;
         // the split count: ONE never meets another than DEC_TS, and the bf16 pages always run DEC_TS
         constexpr int TSM = ONE || KV16 ? DEC_TS : DEC_TS_MULTI;
         with_int<DEC_TS, TSM>(a.ts, [&](auto ts) {
@@ -2162,7 +2114,7 @@ __global__ __launch_bounds__(256) void compose_f64_kernel(const float* __restric
 void launch_compose_f64(const float* A, const float* B, float* C, int M, int N, int K, hipStream_t s) {
     hipLaunchKernelGGL(compose_f64_kernel, dim3((N + 15) / 16, (M + 15) / 16), dim3(256), 0, s, A, B, C, M, N, K);
 }
-int dec_attn_chunk_groups(bool kv16) { return DA_WAVES * (kv16 && MELLOW_DA16_MFMA ? DA_GM : DA_G); }
+int dec_attn_chunk_groups(bool kv16) { return DA_WAVES * (kv16 ? DA_GM : DA_G); }
 void launch_dec_oproj(const DecArgs& a, const float* Wp16, hipStream_t s, const float* wscale) {
 #ifdef MELLOW_OPROJ_ROWS
     const int rows = MELLOW_OPROJ_ROWS;

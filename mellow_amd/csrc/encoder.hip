@@ -499,9 +499,8 @@ void launch_rmsnorm(const float* in, float* out, int M, int C, const float* w, f
 //     kernel's dominant stream) and are widened on load; the arithmetic below is unchanged.
 __device__ __forceinline__ void wa_ld4(const float* base, int64_t elem, bool in16, float (&o)[4]) {
     if (in16) {
-        typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
-        const u32x2_ r = *reinterpret_cast<const u32x2_*>(reinterpret_cast<const uint16_t*>(base) + elem);
-        o[0] = __uint_as_float(r[0] << 16); o[1] = __uint_as_float(r[0] & 0xffff0000u); o[2] = __uint_as_float(r[1] << 16); o[3] = __uint_as_float(r[1] & 0xffff0000u);
+        const float4 r = bf16x4_f32(*reinterpret_cast<const u32x2*>(reinterpret_cast<const uint16_t*>(base) + elem));
+        o[0] = r.x; o[1] = r.y; o[2] = r.z; o[3] = r.w;
     } else {
         const float4 r = *reinterpret_cast<const float4*>(base + elem);
         o[0] = r.x; o[1] = r.y; o[2] = r.z; o[3] = r.w;
@@ -589,7 +588,7 @@ __global__ __launch_bounds__(256) void window_attention_mfma_kernel(const float*
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float pv = __builtin_amdgcn_exp2f((S[kt][qt][r] - mx) * 1.44269504088896340736f);
+                const float pv = fast_exp(S[kt][qt][r] - mx);
                 S[kt][qt][r] = pv;
                 sum += pv;
             }

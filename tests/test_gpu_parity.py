@@ -1335,7 +1335,7 @@ def test_fp8_decode_attention_chunks_and_key_splits_agree(synth_sd):
     decoded with 8 and with 400 reserved positions -- the second puts keys 0..395 into split 0 as TWO chunks per wave (rescale
     path, partly masked second tile) and leaves split 1 with the appended keys only.  Same arithmetic in another summation order;
     in this mode an e4m3 activation rounding downstream turns the 1e-7 into a flipped code here and there, so the logits of the
-    teacher-forced steps agree to 1.5e-2 .. 2.6e-2 relative rms (measured; the vector form of the kernel, -DMELLOW_DA16_MFMA=0,
+    teacher-forced steps agree to 1.5e-2 .. 2.6e-2 relative rms (measured; a build of that round with the vector form
     shows the same 1.5e-2 .. 2.6e-2 on the same box: the figure is the mode's, not the kernel's) -- asserted < 6e-2, with both runs
     at the mode's own distance (0.05 .. 0.18) from the fp32-accurate engine on the structured checkpoint.  A wrong rescale or mask
     would put O(1) errors into every row."""

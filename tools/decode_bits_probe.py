@@ -9,6 +9,10 @@ One side per process: MELLOW_HIP_LIB=path selects the library of a run.  It runs
 lm_decode_step calls at B = 3 and at B = 40 (two row blocks, the second with 8 rows: the BLK instantiations) on the engines below,
 which together reach every GEMV kernel of a decode layer in every weight mode, in the fused and in the five-launch layer, and stores
 each logits tensor as uint32 words.  The inputs are a seeded synthetic prefix and seeded tokens, the same on both sides.
+Those contexts stop near 393 keys, inside the first chunk of the decode attention (448 keys per split); so each engine and batch also
+runs a seeded 1000-position prefix -- beyond one chunk per split in every split count -- and, the fp8 engines,
+reserve=400 on the short prefix, which puts two 32-key tiles per wave into split 0; each again followed by the teacher-forced steps.
+The fp8 engines' lm_prefill logits are also what covers the MXFP8 output form of the prefill attention.
 `--compare` reports per engine, batch and step whether the two files are bit-equal, otherwise how many words differ and whether they
 differ in more than the sign of a zero; its exit status is 0 only if nothing but signs of zeros differs."""
 import argparse
@@ -28,6 +32,7 @@ ENGINES = [  # (name, precision, options)
     ("fp8 decode_fuse=0", "fp8", {"decode_fuse": 0}),
 ]
 BATCHES, STEPS, RESERVE = (3, 40), 4, 6
+LONG_T, RESERVE_2TILES = 1000, 400
 
 
 def run(out):
@@ -35,23 +40,28 @@ def run(out):
     from mellow_amd.engine import Engine
     rng = np.random.default_rng(11)
     prefix = (0.25 * rng.standard_normal((max(BATCHES), spec.PREFIX_LEN, spec.D_PROJ))).astype(np.float32)
+    long_prefix = (0.25 * np.random.default_rng(12).standard_normal((max(BATCHES), LONG_T, spec.D_PROJ))).astype(np.float32)
     res = {}
     sd = synth.make_state_dict(0)
     for name, precision, options in ENGINES:
         eng = Engine(device=0, precision=precision, options=options)
         eng.load_state_dict(sd)
         toks = rng.integers(1, eng.lm.vocab_size, size=(max(BATCHES), STEPS)).astype(np.int32)
+        runs = [("", prefix, RESERVE), (f"|T={LONG_T}", long_prefix, RESERVE)]
+        if precision == "fp8":
+            runs.append((f"|reserve={RESERVE_2TILES}", prefix, RESERVE_2TILES))
         for B in BATCHES:
-            logits = [eng.lm_prefill(prefix[:B], reserve=RESERVE).cpu().numpy()]
-            for i in range(STEPS):
-                logits.append(eng.lm_decode_step(toks[:B, i]).cpu().numpy())
-            for i, l in enumerate(logits):
-                res[f"{name}|B={B}|step={i}"] = np.ascontiguousarray(l).view(np.uint32)
-            print(f"{name:60s} B={B:2d}: {len(logits)} logits tensors {logits[-1].shape}, finite {all(np.isfinite(l).all() for l in logits)}", flush=True)
+            for tag, pre, reserve in runs:
+                logits = [eng.lm_prefill(pre[:B], reserve=reserve).cpu().numpy()]
+                for i in range(STEPS):
+                    logits.append(eng.lm_decode_step(toks[:B, i]).cpu().numpy())
+                for i, l in enumerate(logits):
+                    res[f"{name}|B={B}{tag}|step={i}"] = np.ascontiguousarray(l).view(np.uint32)
+                print(f"{name + tag:72s} B={B:2d}: {len(logits)} logits tensors {logits[-1].shape}, finite {all(np.isfinite(l).all() for l in logits)}", flush=True)
         eng.close()
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     np.savez(out, library=np.array(os.environ.get("MELLOW_HIP_LIB", "default")), **res)
-    print(f"wrote {out}: {len(res)} tensors", flush=True)
+    print(f"wrote {out}: {len(res)} tensors, {sum(v.size for v in res.values())} words", flush=True)
 
 
 def compare(pa, pb):

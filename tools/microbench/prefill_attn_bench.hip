@@ -1,7 +1,7 @@
 // Developer microbenchmark (GPU box), round 6: the LM prefill attention alone (B examples x 3 kv groups x 13 query tiles, T = 389
 // keys, Tmax = 512) on random q / K / V pages: us per launch, and a checksum of the output (variants that must be bit-identical
-// print the same one).  Build one binary per variant:
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DMELLOW_PAX_ABL=bits] -o tools/microbench/pab_<name>.bin tools/microbench/prefill_attn_bench.hip
+// print the same one).  Build one binary per variant (build.py's per-file flag of prefill_attn.hip included):
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-mfma-vgpr-form=1 [-DMELLOW_PAX_MINW=n] -o tools/microbench/pab_<name>.bin tools/microbench/prefill_attn_bench.hip
 #include "../../mellow_amd/csrc/prefill_attn.hip"
 #include <cstdio>
 #include <cstring>
@@ -39,7 +39,7 @@ int main(int argc, char** argv) {
             CK(hipMemcpy(ho.data(), o, nq * 4, hipMemcpyDeviceToHost));
             uint64_t cs = 0; double l1 = 0;
             for (size_t i = 0; i < nq; ++i) { uint32_t u; memcpy(&u, &ho[i], 4); cs = cs * 1099511628211ull + u; l1 += fabs(ho[i]); }
-            printf("B=%d %s abl=%d: avg %.1f us, min %.1f us, checksum %016llx, mean|o| %.6f\n", B, x3 == 2 ? "bf16" : x3 ? "x3" : "f32", MELLOW_PAX_ABL, sum / R * 1e3, best * 1e3,
+            printf("B=%d %s: avg %.1f us, min %.1f us, checksum %016llx, mean|o| %.6f\n", B, x3 == 2 ? "bf16" : x3 ? "x3" : "f32", sum / R * 1e3, best * 1e3,
                    (unsigned long long)cs, l1 / nq);
         }
         hipFree(q); hipFree(k); hipFree(v); hipFree(o); hipFree(o3);
