@@ -62,7 +62,7 @@ extern "C" {
  *  5: the attention taps on host data, mellow_debug_prefill_attn and mellow_debug_window_attn.  No existing symbol or struct
  *     changed; a binding that must also load a minor-4 library detects them by symbol lookup.  The GEMM epilogue tap
  *     mellow_debug_gemm_epi was added later under this same minor, detected by symbol lookup all the same, and so was the norm /
- *     hand-over tap mellow_debug_norm. */
+ *     hand-over tap mellow_debug_norm, and then the decode attention tap mellow_debug_dec_attn. */
 #define MELLOW_ABI_MINOR 5
 
 typedef struct mellow_engine mellow_engine_t;
@@ -645,6 +645,47 @@ int  mellow_debug_window_attn(mellow_engine_t* e, const float* qkv, int M, int C
 int  mellow_debug_norm(mellow_engine_t* e, int op, int form, const float* x, int M, int C, const float* w, const float* b, float eps,
                        const int32_t* row_map, int ntok, int n, int R, void* out, int64_t out_capacity, void* out_scales,
                        int64_t scales_capacity);
+/* Decode attention tap on HOST data (works on any engine, finalised or not): ONE call of launch_dec_attn and, when Wo is given,
+ * then ONE call of launch_dec_oproj (whose prologue merges the key splits) -- the launchers the decode step itself calls, on
+ * DecArgs the tap fills from buffers of its own.  rows = roundup(B, 32), RB = rows / 32; the slots B .. rows - 1 run on zeros.
+ *   slabs   host f32 [8][B][960] (fused 0: the split-K partial sums of the q/k/v projection, p = their sum) or [6][B][960] (fused 1)
+ *   ssq1    host f32 [B][8] (fused 0: rscale = 1 / sqrt(sum / 576 + eps)); NULL with fused 1
+ *   x_res   host f32 [B][576]: fused 0 x_new, the o_proj's residual; fused 1 x_mid
+ *   down    host f32 [4][B][576] (fused 1: x_new = x_mid + their sum, rscale from x_new); NULL with fused 0
+ *   rope_cur host f32 [64], cos then sin of the position, or NULL for row `pos` of the tables of mellow_host_rope_tables with
+ *           cfg.rope_theta, 64 dims, Tmax positions
+ *   k_pages / v_pages  host f32 [P][3][Tmax][64], P >= rows; kv16 != 0: rounded to bf16 on the device (launch_kv_to_bf16) and the
+ *           launch gets the bf16 pages
+ *   blk_live host i32 [RB] and row_of_slot host i32 [rows], or NULL (RB >= 2 only): a block with blk_live 0 and a slot with
+ *           row_of_slot -1 do not run; slot b reads and extends the pages of example row_of_slot[b]
+ *   Wo      host f32 [576][576] (x_mid' = x_new + att . Wo^T), or NULL: no o_proj launch
+ * d->ts must be what dec_key_splits gives for this RB and kv16 (2; or 1 from two row blocks on with fp32 pages); gs, the 4-key
+ * groups per key split, follows from ctx_end, ts and kv16 by the engine's own rule and is returned in *out_gs.
+ * Every output is filled with 0xFF bytes before the launches and returned whole and raw (capacities in bytes):
+ *   out_att   f32 [ts][RB][36][2][64][4] (F16-layout partials) + one more block [36][2][64][4]
+ *   out_ml    f32 [9][rows][ts][2]
+ *   out_k / out_v  the pages [P + 1][3][Tmax][64]: f32, or the 2-byte form with kv16 (kv_capacity: bytes of each)
+ *   out_xnew  f32 [rows + 32][576] (fused 0: what was sent, in rows < rows)
+ *   with Wo: out_xmid f32 [rows][576] (F32-layout, raw); out_x16 f32 [rows][576] (F16-layout, raw) or, with want_x3, the F3-32
+ *   image followed by the F3-16 image (rows * 576 * 6 bytes each); out_ssq f32 [rows + 32][40]
+ * Refused by name, nothing launched: B < 1; pos < 1 or pos >= Tmax; ctx_end <= pos or ctx_end > Tmax; Tmax < 2 or above
+ * cfg.max_positions; P < rows; ts not admissible; fused not 0 / 1; blk_live or row_of_slot at one row block; row_of_slot not
+ * one-to-one or outside [0, P); want_x3 without Wo; a null required pointer; eps not finite or negative; a capacity too small.
+ * Invalidates the decode state of an earlier prefill. */
+typedef struct mellow_dec_attn {
+    int32_t size;            /* sizeof(mellow_dec_attn_t) */
+    int32_t B, P;            /* batch slots in use, page sets in k_pages / v_pages */
+    int32_t pos, Tmax, ctx_end;
+    int32_t ts, fused, kv16;
+    int32_t want_x3;
+    float eps;
+} mellow_dec_attn_t;
+int  mellow_debug_dec_attn(mellow_engine_t* e, const mellow_dec_attn_t* d, const float* slabs, const float* ssq1, const float* x_res,
+                           const float* down, const float* rope_cur, const float* k_pages, const float* v_pages,
+                           const int32_t* blk_live, const int32_t* row_of_slot, const float* Wo, int32_t* out_gs, void* out_att,
+                           int64_t att_capacity, float* out_ml, int64_t ml_capacity, void* out_k, void* out_v, int64_t kv_capacity,
+                           float* out_xnew, int64_t xnew_capacity, void* out_xmid, int64_t xmid_capacity, void* out_x16,
+                           int64_t x16_capacity, float* out_ssq, int64_t ssq_capacity);
 /* The decode step's lm_head kernel on caller-supplied rows (dev): logits[B][vocab] = x[B][hidden] . lm_head^T with the engine's
  * own head weights (the e4m3 copy in MELLOW_PRECISION_FP8; act_fp8 != 0 then also quantises x inside the kernel: one scale per
  * batch row and 72-column slice, fp8 matrix pipe).  Invalidates the decode state of an earlier prefill. */

@@ -494,6 +494,161 @@ int mellow_debug_norm(mellow_engine_t* e, int op, int form, const float* x, int 
     return 0;
 }
 
+// ---- decode attention tap on host data (include/mellow_hip.h): one launch_dec_attn and, with Wo, one launch_dec_oproj on DecArgs
+// filled from buffers of the call's own ------------------------------------------------------------------------------------------------
+// host rows [n][B][width] -> device rows [n][rows][width], the slots B .. rows - 1 zero
+static int dec_tap_rows(mellow_engine* e, mellow_engine::Buf& b, const float* src, int n, int B, int rows, int width, size_t extra_rows = 0) {
+    std::vector<float> h(((size_t)n * rows + extra_rows) * width, 0.f);
+    for (int s = 0; s < n; ++s) memcpy(h.data() + (size_t)s * rows * width, src + (size_t)s * B * width, (size_t)B * width * 4);
+    if (extra_rows) memset(h.data() + (size_t)n * rows * width, 0xFF, extra_rows * width * 4);
+    return gemm_tap_buf(e, b, h.size() * 4, h.data());
+}
+// host rows [n][B][576] -> n F32-layout images of `rows` rows (common.h f32_idx with 72 k-tiles), the slots B .. rows - 1 zero
+static int dec_tap_f32_layout(mellow_engine* e, mellow_engine::Buf& b, const float* src, int n, int B, int rows) {
+    std::vector<float> h((size_t)n * rows * 576, 0.f);
+    for (int s = 0; s < n; ++s)
+        for (int r = 0; r < B; ++r)
+            for (int k = 0; k < 576; k += 4) {
+                const size_t f4 = ((size_t)(r >> 5) * 72 + (k >> 3)) * 64 + (r & 31) + 32 * ((k >> 2) & 1);
+                memcpy(h.data() + (size_t)s * rows * 576 + f4 * 4, src + ((size_t)s * B + r) * 576 + k, 16);
+            }
+    return gemm_tap_buf(e, b, h.size() * 4, h.data());
+}
+
+int mellow_debug_dec_attn(mellow_engine_t* e, const mellow_dec_attn_t* d, const float* slabs, const float* ssq1, const float* x_res,
+                          const float* down, const float* rope_cur, const float* k_pages, const float* v_pages, const int32_t* blk_live,
+                          const int32_t* row_of_slot, const float* Wo, int32_t* out_gs, void* out_att, int64_t att_capacity, float* out_ml,
+                          int64_t ml_capacity, void* out_k, void* out_v, int64_t kv_capacity, float* out_xnew, int64_t xnew_capacity,
+                          void* out_xmid, int64_t xmid_capacity, void* out_x16, int64_t x16_capacity, float* out_ssq, int64_t ssq_capacity) {
+    if (!e || !d) return fail("null argument");
+    if (d->size != (int32_t)sizeof(mellow_dec_attn_t)) return fail("size = %d is not sizeof(mellow_dec_attn_t) = %d", d->size, (int)sizeof(mellow_dec_attn_t));
+    const int B = d->B, P = d->P, pos = d->pos, Tmax = d->Tmax, ctx_end = d->ctx_end, ts = d->ts;
+    if (B < 1 || B > 1024) return fail("B = %d: 1 <= B <= 1024", B);
+    if (d->fused != 0 && d->fused != 1) return fail("fused must be 0 (slabs of the q/k/v launch) or 1 (slabs of the fused down + q/k/v launch): got %d", d->fused);
+    const bool fused = d->fused != 0, kv16 = d->kv16 != 0;
+    const int rows = rup(B, 32), RB = rows / 32;
+    if (Tmax < 2 || Tmax > e->cfg.max_positions) return fail("Tmax = %d is not a page length of the engine: 2 <= Tmax <= max_positions = %d", Tmax, e->cfg.max_positions);
+    if (pos < 1 || pos >= Tmax) return fail("pos = %d must lie in [1, Tmax = %d)", pos, Tmax);
+    if (ctx_end <= pos || ctx_end > Tmax) return fail("ctx_end = %d must lie in (pos = %d, Tmax = %d]", ctx_end, pos, Tmax);
+    if (P < rows || P > 4096) return fail("P = %d page sets: rows = %d <= P <= 4096", P, rows);
+    if ((int64_t)(P + 1) * 3 * Tmax * 64 > ((int64_t)1 << 28)) return fail("(P + 1) * 3 * Tmax * 64 = %lld page elements exceed the tap's 2^28", (long long)(P + 1) * 3 * Tmax * 64);
+    if (ts != dec_key_splits(RB, true) && (kv16 || ts != dec_key_splits(RB, false)))
+        return fail("ts = %d is not a key split count of RB = %d row blocks with %s pages (dec_key_splits: %d%s)", ts, RB, kv16 ? "bf16" : "fp32",
+                    dec_key_splits(RB, true), kv16 || dec_key_splits(RB, false) == dec_key_splits(RB, true) ? "" : ", or 1 in the f32x3 mode");
+    if ((blk_live || row_of_slot) && RB < 2) return fail("blk_live / row_of_slot exist from two row blocks on (RB = %d)", RB);
+    if (row_of_slot) {
+        std::vector<char> seen(P, 0);
+        for (int b = 0; b < rows; ++b) {
+            const int r = row_of_slot[b];
+            if (r == -1) continue;
+            if (r < 0 || r >= P || seen[r]) return fail("row_of_slot[%d] = %d is outside [0, P = %d) or taken twice", b, r, P);
+            seen[r] = 1;
+        }
+    }
+    if (d->want_x3 && !Wo) return fail("want_x3 without Wo: the pre-split images are written by the o_proj launch");
+    if (!slabs || !x_res || !k_pages || !v_pages || !out_gs) return fail("null argument: slabs, x_res, k_pages, v_pages and out_gs are required");
+    if (!fused && !ssq1) return fail("null argument: fused 0 needs ssq1");
+    if (fused && !down) return fail("null argument: fused 1 needs the down slabs");
+    if (!(d->eps >= 0.f && d->eps < INFINITY)) return fail("eps = %g must be finite and >= 0", d->eps);
+    // capacities, before anything is launched
+    const size_t n_x = (size_t)rows * 576, page_elems = (size_t)3 * Tmax * 64;
+    const size_t att_bytes = ((size_t)ts * n_x + 32 * 576) * 4, ml_bytes = (size_t)9 * rows * ts * 2 * 4;
+    const size_t kv_bytes = (size_t)(P + 1) * page_elems * (kv16 ? 2 : 4), xnew_bytes = (size_t)(rows + 32) * 576 * 4;
+    const size_t xmid_bytes = n_x * 4, x16_bytes = d->want_x3 ? 2 * n_x * 6 : n_x * 4, ssq_bytes = (size_t)(rows + 32) * 40 * 4;
+    if (!out_att || att_capacity < (int64_t)att_bytes) return fail("att_capacity %lld is below the %lld bytes this call returns (or out_att is null)", (long long)att_capacity, (long long)att_bytes);
+    if (!out_ml || ml_capacity < (int64_t)ml_bytes) return fail("ml_capacity %lld is below the %lld bytes this call returns (or out_ml is null)", (long long)ml_capacity, (long long)ml_bytes);
+    if (!out_k || !out_v || kv_capacity < (int64_t)kv_bytes) return fail("kv_capacity %lld is below the %lld bytes each page array takes (or out_k / out_v is null)", (long long)kv_capacity, (long long)kv_bytes);
+    if (!out_xnew || xnew_capacity < (int64_t)xnew_bytes) return fail("xnew_capacity %lld is below the %lld bytes this call returns (or out_xnew is null)", (long long)xnew_capacity, (long long)xnew_bytes);
+    if (Wo) {
+        if (!out_xmid || xmid_capacity < (int64_t)xmid_bytes) return fail("xmid_capacity %lld is below the %lld bytes this call returns (or out_xmid is null)", (long long)xmid_capacity, (long long)xmid_bytes);
+        if (!out_x16 || x16_capacity < (int64_t)x16_bytes) return fail("x16_capacity %lld is below the %lld bytes this call returns (or out_x16 is null)", (long long)x16_capacity, (long long)x16_bytes);
+        if (!out_ssq || ssq_capacity < (int64_t)ssq_bytes) return fail("ssq_capacity %lld is below the %lld bytes this call returns (or out_ssq is null)", (long long)ssq_capacity, (long long)ssq_bytes);
+    }
+    const int gs = dec_attn_split_groups(ctx_end, ts, kv16);
+    *out_gs = gs;
+
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    dec_prepare_lds_attributes();
+    e->cur_B = 0;                                     // the decode state of an earlier prefill is gone
+    mellow_engine::Buf bPq, bSsq1, bXin, bDown, bRope, bK, bV, bK16, bV16, bWords, bW, bWp, bAtt, bMl, bXnew, bXmid, bX16, bSsq;
+    CHK(dec_tap_rows(e, bPq, slabs, fused ? Q2_NPQ : DEC_KC_QKV, B, rows, 960));
+    std::vector<float> hr(64);
+    if (rope_cur) memcpy(hr.data(), rope_cur, 256);
+    else {
+        std::vector<float> hc((size_t)Tmax * 32), hs((size_t)Tmax * 32);
+        CHK(mellow_host_rope_tables(e->cfg.rope_theta, 64, Tmax, hc.data(), hs.data()));
+        memcpy(hr.data(), hc.data() + (size_t)pos * 32, 128);
+        memcpy(hr.data() + 32, hs.data() + (size_t)pos * 32, 128);
+    }
+    CHK(gemm_tap_buf(e, bRope, 256, hr.data()));
+    if (fused) {
+        CHK(dec_tap_f32_layout(e, bXin, x_res, 1, B, rows));
+        CHK(dec_tap_f32_layout(e, bDown, down, Q2_HC, B, rows));
+        CHK(gemm_tap_buf(e, bXnew, xnew_bytes, nullptr));
+    } else {
+        CHK(dec_tap_rows(e, bSsq1, ssq1, 1, B, rows, DEC_KC_QKV));
+        CHK(dec_tap_rows(e, bXnew, x_res, 1, B, rows, 576, 32));
+    }
+    // the pages: P sets from the caller and one of no example (0xFF bytes) behind them
+    auto pages = [&](mellow_engine::Buf& b32, mellow_engine::Buf& b16, const float* src) -> int {
+        CHK(gemm_tap_buf(e, b32, (size_t)(P + 1) * page_elems * 4, nullptr));
+        HIPCHK(hipMemcpyAsync(b32.p, src, (size_t)P * page_elems * 4, hipMemcpyHostToDevice, s));
+        if (kv16) {
+            CHK(gemm_tap_buf(e, b16, kv_bytes, nullptr));
+            launch_kv_to_bf16(b32.p, b16.p, (int64_t)((size_t)P * page_elems), s);
+        }
+        return 0;
+    };
+    CHK(pages(bK, bK16, k_pages));
+    CHK(pages(bV, bV16, v_pages));
+    // the device words: position | blk_live [RB] | row_of_slot [rows]
+    std::vector<int32_t> hw(1 + RB + rows, 1);
+    hw[0] = pos;
+    const bool blk = blk_live || row_of_slot;         // (the kernels read row_of_slot in their early-exit instantiation only)
+    if (blk_live) memcpy(hw.data() + 1, blk_live, (size_t)RB * 4);
+    if (row_of_slot) memcpy(hw.data() + 1 + RB, row_of_slot, (size_t)rows * 4);
+    CHK(gemm_tap_buf(e, bWords, hw.size() * 4, hw.data()));
+    int32_t* dw = reinterpret_cast<int32_t*>(bWords.p);
+    CHK(gemm_tap_buf(e, bAtt, att_bytes, nullptr));
+    CHK(gemm_tap_buf(e, bMl, ml_bytes, nullptr));
+    DecArgs a;
+    a.rows = rows; a.RB = RB; a.Tmax = Tmax; a.eps = d->eps; a.d_pos = dw; a.gs = gs; a.ts = ts; a.kv16 = kv16 ? 1 : 0;
+    a.rope_cur = bRope.p; a.ssq1 = bSsq1.p; a.pq = bPq.p;
+    a.xmidF = bXin.p; a.dslabF = bDown.p; a.slabF_stride4 = (int64_t)(n_x / 4); a.xnewR = bXnew.p;
+    a.attF16 = bAtt.p; a.att_ml = bMl.p;
+    a.blk_live = blk ? dw + 1 : nullptr; a.row_of_slot = row_of_slot ? dw + 1 + RB : nullptr;
+    if (Wo) {
+        CHK(gemm_tap_buf(e, bW, (size_t)576 * 576 * 4, Wo));
+        CHK(ensure(e, bWp, (size_t)576 * 576));
+        launch_pack_weight16(bW.p, 576, 576, bWp.p, s);
+        CHK(gemm_tap_buf(e, bXmid, xmid_bytes, nullptr));
+        CHK(gemm_tap_buf(e, bX16, x16_bytes, nullptr));
+        CHK(gemm_tap_buf(e, bSsq, ssq_bytes, nullptr));
+    }
+    launch_dec_attn(a, kv16 ? bK16.p : bK.p, kv16 ? bV16.p : bV.p, fused, s);
+    if (Wo) {
+        DecArgs o = a;
+        o.xmidF = bXmid.p; o.ssq = bSsq.p;
+        if (d->want_x3) { o.xmid3_32 = bX16.p; o.xmid3_16 = reinterpret_cast<char*>(bX16.p) + n_x * 6; }
+        else o.xmidF16 = bX16.p;
+        launch_dec_oproj(o, bWp.p, s);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    CHK(gemm_tap_fetch(out_att, att_capacity, bAtt, att_bytes, "att"));
+    CHK(gemm_tap_fetch(out_ml, ml_capacity, bMl, ml_bytes, "ml"));
+    CHK(gemm_tap_fetch(out_k, kv_capacity, kv16 ? bK16 : bK, kv_bytes, "kv"));
+    CHK(gemm_tap_fetch(out_v, kv_capacity, kv16 ? bV16 : bV, kv_bytes, "kv"));
+    CHK(gemm_tap_fetch(out_xnew, xnew_capacity, bXnew, xnew_bytes, "xnew"));
+    if (Wo) {
+        CHK(gemm_tap_fetch(out_xmid, xmid_capacity, bXmid, xmid_bytes, "xmid"));
+        CHK(gemm_tap_fetch(out_x16, x16_capacity, bX16, x16_bytes, "x16"));
+        CHK(gemm_tap_fetch(out_ssq, ssq_capacity, bSsq, ssq_bytes, "ssq"));
+    }
+    return 0;
+}
+
 // developer instrumentation (not part of the public header): one CSV line per profiled launch
 __attribute__((visibility("default"))) int mellow_dev_prof_dump(mellow_engine_t* e, const char* path) {
     if (!e || !path) return fail("bad argument");

@@ -439,6 +439,7 @@ struct RecordArgs {
 // B rows of pages and decode arena; the prefill workspaces hold prefill_B examples (0 = B: every row is prefilled itself)
 // (prefill_rows > 0: their row count itself, for a prefill that is not prefill_B x T rows)
 int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end = 0, int prefill_B = 0, size_t prefill_rows = 0);
+int dec_attn_split_groups(int ctx_end, int ts, bool kv16);      // DecArgs::gs of a context that ends at ctx_end
 static inline int prefix_page_len(int T) { return rup(T, 64); }      // positions per page of kprefix / vprefix (rounded as the pages are)
 int clear_page_tails(mellow_engine* e, int T, int t_end);
 LoopArgs loop_args(mellow_engine* e);

@@ -2,6 +2,15 @@
 // (A14), the lm taps and scoring.  The generation loop on top of it is engine_generate.cpp.
 #include "engine_internal.h"
 
+// key split of the decode attention (DecArgs::gs, 4-key groups per split): balanced at the END of the reserved context, rounded
+// down to whole passes of a workgroup when that costs at most 4 groups of imbalance.  ensure_lm and the tap mellow_debug_dec_attn.
+int dec_attn_split_groups(int ctx_end, int ts, bool kv16) {
+    const int ng_end = (ctx_end - 1 + 3) / 4, chunk = dec_attn_chunk_groups(kv16);
+    int gs = (ng_end + ts - 1) / ts;
+    if (gs > chunk && gs % chunk <= 4) gs -= gs % chunk;
+    return gs < 1 ? 1 : gs;
+}
+
 int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end, int prefill_B, size_t prefill_rows) {
     if (B > 1024) return fail("batch of %d exceeds the 1024 rows one pass takes (mellow_generate chunks larger batches itself; the decode state block is sized for 32 row blocks)", B);
     if (ctx_end <= 0 || ctx_end > Tmax) ctx_end = Tmax;      // last context length the call will reach (<= page capacity)
@@ -80,13 +89,8 @@ int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end, int prefill
         a.xmid3_32 = x3l ? (void*)(p + o_x3a) : nullptr; a.xmid3_16 = x3l ? (void*)(p + o_x3b) : nullptr; a.h3 = x3l ? (void*)(p + o_h3) : nullptr;
         a.dslabF = p + o_dslabF; a.slabF_stride4 = (int64_t)(n_x / 4); a.ssq1 = p + o_ssq1; a.rope_cur = p + o_rope;
         {
-            // key split of the decode attention: balanced at the END of the reserved context, rounded down to whole
-            // passes of a workgroup when that costs at most 4 groups of imbalance
-            const int ng_end = (ctx_end - 1 + 3) / 4, chunk = dec_attn_chunk_groups(e->opt.kv16);
             a.ts = dec_key_splits((int)RB, e->opt.kv16 || e->opt.mode != MELLOW_PRECISION_F32X3);
-            int gs = (ng_end + a.ts - 1) / a.ts;
-            if (gs > chunk && gs % chunk <= 4) gs -= gs % chunk;
-            gs = gs < 1 ? 1 : gs;
+            const int gs = dec_attn_split_groups(ctx_end, a.ts, e->opt.kv16);
             if (gs != a.gs) e->graphs.reset();     // the split is baked into captured launches
             a.gs = gs;
         }

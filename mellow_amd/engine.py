@@ -53,6 +53,11 @@ class GemmEpi(C.Structure):
                [(n, C.c_int32) for n in ("splitk_max", "no_x3w", "T", "Tmax", "pos0")]
 
 
+class DecAttn(C.Structure):
+    """mellow_dec_attn_t (include/mellow_hip.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("size", "B", "P", "pos", "Tmax", "ctx_end", "ts", "fused", "kv16", "want_x3")] + [("eps", C.c_float)]
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -64,7 +69,8 @@ _ADDED_UNDER_MINOR_4 = ("mellow_lm_score", "mellow_score", "mellow_generate_scor
 # symbols of minor 5 (the attention taps on host data): looked up the same way, so that a minor-4 library still loads
 _ADDED_UNDER_MINOR_5 = ("mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_generate_rules", "mellow_logit_rules_apply",
                         "mellow_generate_guidance", "mellow_guidance_apply", "mellow_generate_top_logprobs", "mellow_top_logprobs_apply",
-                        "mellow_debug_gemm_epi", "mellow_generate_filters", "mellow_sample_logits_filtered", "mellow_debug_norm")
+                        "mellow_debug_gemm_epi", "mellow_generate_filters", "mellow_sample_logits_filtered", "mellow_debug_norm",
+                        "mellow_debug_dec_attn")
 
 
 def load_library(path: Optional[str] = None):
@@ -128,6 +134,8 @@ def load_library(path: Optional[str] = None):
         "mellow_debug_gemm_f32": (ci, [vp, ci, vp, ci, ci, vp, ci, vp, ci, vp]),
         "mellow_debug_gemm_epi": (ci, [vp, P(GemmEpi), vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64]),
         "mellow_debug_norm": (ci, [vp, ci, ci, vp, ci, ci, vp, vp, cf, vp, ci, ci, ci, vp, i64, vp, i64]),
+        "mellow_debug_dec_attn": (ci, [vp, P(DecAttn), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, i64,
+                                       vp, i64, vp, i64]),
         "mellow_debug_prefill_attn": (ci, [vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp, i64]),
         "mellow_debug_window_attn": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, i64]),
         "mellow_debug_dec_head": (ci, [vp, vp, ci, ci, vp]),
@@ -172,7 +180,7 @@ EXPORTED_SYMBOLS = (
     "mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse", "mellow_generate_n", "mellow_generate_q",
     "mellow_generate_beam", "mellow_beam_select", "mellow_generate_rules", "mellow_logit_rules_apply", "mellow_generate_guidance", "mellow_guidance_apply", "mellow_generate_top_logprobs", "mellow_top_logprobs_apply", "mellow_generate_filters", "mellow_sample_logits_filtered", "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
     "mellow_prof_num_families", "mellow_prof_family_name", "mellow_prof_get", "mellow_last_phase_ms", "mellow_last_steps_enqueued", "mellow_last_row_repacks", "mellow_stft_is_fft", "mellow_prefill_parts", "mellow_abi_minor",
-    "mellow_resample", "mellow_engine_set_precision", "mellow_engine_set_option", "mellow_engine_describe", "mellow_debug_gemm_fp8", "mellow_debug_gemm_f32", "mellow_debug_gemm_epi", "mellow_debug_norm", "mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_debug_dec_head", "mellow_set_graph", "mellow_host_window_map", "mellow_host_pack_weight", "mellow_host_rope_tables",
+    "mellow_resample", "mellow_engine_set_precision", "mellow_engine_set_option", "mellow_engine_describe", "mellow_debug_gemm_fp8", "mellow_debug_gemm_f32", "mellow_debug_gemm_epi", "mellow_debug_norm", "mellow_debug_dec_attn", "mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_debug_dec_head", "mellow_set_graph", "mellow_host_window_map", "mellow_host_pack_weight", "mellow_host_rope_tables",
 )
 
 
@@ -1225,6 +1233,57 @@ class Engine:
         self._chk(self.lib.mellow_debug_norm(self.h, o, form, p(x), M, Cc, p(w), p(b), float(eps), p(rmap),
                                              0 if rmap is None else int(rmap.numel()), int(n), int(R), p(main), nbytes(main),
                                              p(out.get("scales")), nbytes(out.get("scales"))))
+        return out
+
+    def debug_dec_attn(self, slabs, x_res, k_pages, v_pages, pos: int, ctx_end: int, ts: int, fused: bool = False, kv16: bool = False,
+                       ssq1=None, down=None, rope_cur=None, eps: float = 1e-5, blk_live=None, row_of_slot=None, Wo=None,
+                       want_x3: bool = False) -> dict:
+        """One launch of the decode attention and, with Wo, one of the o_proj that merges its key splits (mellow_debug_dec_attn), on host
+        tensors: slabs [8 | 6][B][960], x_res [B][576] (fused: x_mid, else x_new), k / v pages [P][3][Tmax][64], ssq1 [B][8] (not fused),
+        down [4][B][576] (fused), rope_cur [64] or None, blk_live int32 [RB], row_of_slot int32 [rows], Wo [576][576].  -> dict of the
+        whole device outputs, which held 0xFF bytes before the launches: "gs" (4-key groups per split), "att" f32 [ts * rows * 576 + 32
+        * 576] (F16-layout partials + one block), "ml" f32 [9][rows][ts][2], "k" / "v" the pages [P + 1][3][Tmax][64] (f32, or int16
+        words with kv16), "xnew" f32 [rows + 32][576]; with Wo "xmid" f32 [rows * 576] (F32-layout), "x16" f32 [rows * 576] (F16-layout)
+        or with want_x3 int16 [2][rows * 576 * 3] (F3-32 image, F3-16 image), "ssq" f32 [rows + 32][40]."""
+        self._need("mellow_debug_dec_attn")
+        f32 = lambda t: None if t is None else torch.as_tensor(t).detach().cpu().contiguous().float()       # noqa: E731
+        i32 = lambda t: None if t is None else torch.as_tensor(t).detach().cpu().contiguous().to(torch.int32)       # noqa: E731
+        slabs, x_res, k_pages, v_pages, ssq1, down, rope_cur, Wo = (f32(t) for t in (slabs, x_res, k_pages, v_pages, ssq1, down, rope_cur, Wo))
+        blk_live, row_of_slot = i32(blk_live), i32(row_of_slot)
+        B = int(x_res.shape[0])
+        if k_pages.dim() != 4 or k_pages.shape[1] != 3 or k_pages.shape[3] != 64 or v_pages.shape != k_pages.shape:
+            raise ValueError(f"k {tuple(k_pages.shape)} / v {tuple(v_pages.shape)} are not pages [P][3][Tmax][64]")
+        Pn, Tmax = int(k_pages.shape[0]), int(k_pages.shape[2])
+        if tuple(slabs.shape) != (6 if fused else 8, B, 960) or tuple(x_res.shape) != (B, 576):
+            raise ValueError(f"slabs {tuple(slabs.shape)} / x_res {tuple(x_res.shape)} are not [{6 if fused else 8}][B][960] / [B][576]")
+        for name, t, shape in (("ssq1", ssq1, (B, 8)), ("down", down, (4, B, 576)), ("rope_cur", rope_cur, (64,)), ("Wo", Wo, (576, 576))):
+            if t is not None and tuple(t.shape) != shape:
+                raise ValueError(f"{name} {tuple(t.shape)} is not {shape}")
+        rows = (max(B, 1) + 31) // 32 * 32
+        for name, t, n in (("blk_live", blk_live, rows // 32), ("row_of_slot", row_of_slot, rows)):
+            if t is not None and t.numel() != n:
+                raise ValueError(f"{name} has {t.numel()} entries for {n}")
+        d = DecAttn()
+        d.size, d.B, d.P, d.pos, d.Tmax, d.ctx_end = C.sizeof(DecAttn), B, Pn, int(pos), Tmax, int(ctx_end)
+        d.ts, d.fused, d.kv16, d.want_x3, d.eps = int(ts), int(bool(fused)), int(bool(kv16)), int(bool(want_x3)), float(eps)
+        n_x, tsn = rows * 576, max(int(ts), 1)
+        out = {"att": torch.empty((tsn * n_x + 32 * 576,), dtype=torch.float32), "ml": torch.empty((9, rows, tsn, 2), dtype=torch.float32),
+               "k": torch.empty((Pn + 1, 3, Tmax, 64), dtype=torch.int16 if kv16 else torch.float32),
+               "xnew": torch.empty((rows + 32, 576), dtype=torch.float32)}
+        out["v"] = torch.empty_like(out["k"])
+        if Wo is not None:
+            out["xmid"] = torch.empty((n_x,), dtype=torch.float32)
+            out["x16"] = torch.empty((2, n_x * 3), dtype=torch.int16) if want_x3 else torch.empty((n_x,), dtype=torch.float32)
+            out["ssq"] = torch.empty((rows + 32, 40), dtype=torch.float32)
+        p = lambda t: None if t is None else _ptr(t)      # noqa: E731
+        nb = lambda k: 0 if k not in out else out[k].numel() * out[k].element_size()      # noqa: E731
+        gs = C.c_int32(0)
+        self._chk(self.lib.mellow_debug_dec_attn(self.h, C.byref(d), p(slabs), p(ssq1), p(x_res), p(down), p(rope_cur), p(k_pages),
+                                                 p(v_pages), p(blk_live), p(row_of_slot), p(Wo), C.cast(C.byref(gs), C.c_void_p),
+                                                 p(out["att"]), nb("att"), p(out["ml"]), nb("ml"), p(out["k"]), p(out["v"]), nb("k"),
+                                                 p(out["xnew"]), nb("xnew"), p(out.get("xmid")), nb("xmid"), p(out.get("x16")), nb("x16"),
+                                                 p(out.get("ssq")), nb("ssq")))
+        out["gs"] = int(gs.value)
         return out
 
     @staticmethod

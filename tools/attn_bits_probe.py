@@ -12,6 +12,9 @@ tests/attn_ref.py (imported, not copied):
     (variants 0 and 1);
   - PAST_CASES (B = 2) in variants 0 and 1, both forms: the launches for the queries from qpos0 on;
   - WINDOW_SHAPES with fp32 input in both forms and with bf16 input in the plain form (the tap has no other).
+  - the decode attention and its o_proj merge (debug_dec_attn) on the cases of tests/dec_attn_ref.py with both producers (fused 0 / 1):
+    partials, att_ml, the appended position of the pages, x_new, xmidF, xmidF16, ssq; and the F3 images on one case per
+    row-block count.  A library that predates the tap is reported and its side holds the other tensors only.
 The MXFP8 form of the prefill attention has no tap: the lm_prefill logits of the fp8 engines in tools/decode_bits_probe.py cover it.
 `--compare` is tools/gemm_bits_probe.py's: exit status 0 only if every word is equal."""
 import argparse
@@ -52,6 +55,21 @@ def run(out):
             c = R.window_case(windows, nH, nW, in16)
             for form in ((0,) if in16 else (0, 1)):      # (the tap has no APB form of the bf16-input kernel: the engine never launches it)
                 keep(f"window ({windows}, {nH}, {nW}) in16 {int(in16)} form {form}", eng.debug_window_attn(c["qkv"], c["bias"], c["mask"], in16=in16, out_form=form))
+    if hasattr(eng.lib, "mellow_debug_dec_attn"):
+        import dec_attn_ref as D
+        for cid in D.CASE_IDS:
+            c = D.case(cid)
+            for fused in (False, True):
+                i = D.inputs(cid, fused)
+                for x3 in ((False, True) if cid in ("b-B1-T512-pos224-end449-ts2-fp32", "d-B64-T512-pos447-end512-ts1-fp32") else (False,)):
+                    o = eng.debug_dec_attn(i["slabs"], i["x_mid"] if fused else i["x_new"], i["K"], i["V"], pos=c.pos, ctx_end=c.ctx_end, ts=c.ts,
+                                           fused=fused, kv16=c.kv16, ssq1=None if fused else i["ssq1"], down=i["down"] if fused else None,
+                                           rope_cur=i["rope_cur"], eps=i["eps"], Wo=i["Wo"], want_x3=x3)
+                    for name in ("att", "ml", "k", "v", "xnew", "xmid", "x16", "ssq"):      # (of the pages: position pos, the append)
+                        keep(f"decode {cid} fused {int(fused)} x3 {int(x3)} {name}", o[name][:, :, c.pos].contiguous() if name in ("k", "v") else o[name])
+        print(f"decode attention cases: {len(res)} tensors so far", flush=True)
+    else:
+        print("this library predates mellow_debug_dec_attn: no decode attention tensors on this side", flush=True)
     eng.close()
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     np.savez(out, library=np.array(os.environ.get("MELLOW_HIP_LIB", "default")), **res)
