@@ -1,7 +1,8 @@
-// Non-GEMM kernels of the audio encoder.  All are HBM-bound
+// Non-GEMM kernels of the audio encoder and, at the end of the file, the LM's prefix
+// assembly, row gathers and page clear.  Apart from the window attention all are HBM-bound
 // index-math kernels: permutations of the reference (reflect pad, bicubic resample + 4x256 fold,
-// cyclic shift + window partition, patch-merging gather, un-fold for the token-semantic head) are
-// address arithmetic on loads, never materialised copies.
+// un-fold for the token-semantic head) are address arithmetic on loads, never materialised copies.
+// The LayerNorm family (with the cyclic shift + window partition and the patch-merging gather) and the LM's RMSNorm are in norm.hip.
 #include <cstdlib>
 
 #include "common.h"
@@ -129,357 +130,6 @@ void launch_fold_patch_embed(const float* logmel_bn, int n_src, int src_frames, 
     const int64_t n_tokens = (int64_t)n_src * n_crops * 4096;
     hipLaunchKernelGGL(fold_patch_embed_kernel, dim3((unsigned)((n_tokens + 4 * PE_TPW - 1) / (4 * PE_TPW))), dim3(256), 0, s, logmel_bn,
                        src_frames, n_crops, crop_hop, crop_len, conv_w, conv_b, ln_w, ln_b, x0, n_tokens);
-}
-
-// ---- LayerNorm family: one wave per row, row kept in registers (C <= 1536) ------------------------------
-constexpr int LN_MAXV = 6;  // float4 per lane
-
-template <int MODE>  // 0: plain / row-map gather, 1: patch-merging gather
-__global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                                        int64_t M, int C, const float* __restrict__ w,
-                                                        const float* __restrict__ b,
-                                                        const int32_t* __restrict__ row_map, int ntok, int R,
-                                                        int Cin) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t m = (int64_t)blockIdx.x * 4 + wave;
-    if (m >= M) return;
-    const int nv = C >> 2;
-    const float* src_row = nullptr;
-    int64_t seg_base[4];
-    if (MODE == 0) {
-        int64_t src = m;
-        if (row_map) src = (m / ntok) * ntok + row_map[m % ntok];
-        src_row = in + src * C;
-    } else {
-        // output token (clip, i, j) of the (R/2)^2 grid gathers tokens (2i,2j), (2i+1,2j), (2i,2j+1), (2i+1,2j+1)
-        // in that order (reference htsat.py:488-492)
-        const int R2 = R >> 1;
-        const int64_t clip = m / (R2 * R2);
-        const int ij = (int)(m % (R2 * R2));
-        const int i = ij / R2, j = ij % R2;
-        const int64_t cb = clip * R * R;
-        seg_base[0] = (cb + (int64_t)(2 * i) * R + 2 * j) * Cin;
-        seg_base[1] = (cb + (int64_t)(2 * i + 1) * R + 2 * j) * Cin;
-        seg_base[2] = (cb + (int64_t)(2 * i) * R + 2 * j + 1) * Cin;
-        seg_base[3] = (cb + (int64_t)(2 * i + 1) * R + 2 * j + 1) * Cin;
-    }
-    float4 x[LN_MAXV];
-    float sum = 0.f;
-#pragma unroll
-    for (int q = 0; q < LN_MAXV; ++q) {
-        const int v = lane + 64 * q;
-        x[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (v < nv) {
-            if (MODE == 0) {
-                x[q] = reinterpret_cast<const float4*>(src_row)[v];
-            } else {
-                const int e = v * 4;
-                const int seg = e / Cin, c = e % Cin;
-                x[q] = *reinterpret_cast<const float4*>(in + seg_base[seg] + c);
-            }
-            sum += (x[q].x + x[q].y) + (x[q].z + x[q].w);
-        }
-    }
-    const float mean = wave_sum(sum) / (float)C;
-    float sq = 0.f;
-#pragma unroll
-    for (int q = 0; q < LN_MAXV; ++q) {
-        const int v = lane + 64 * q;
-        if (v < nv) {
-            const float a = x[q].x - mean, bb = x[q].y - mean, c = x[q].z - mean, d = x[q].w - mean;
-            sq += (a * a + bb * bb) + (c * c + d * d);
-        }
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)C + 1e-5f);
-    float4* dst = reinterpret_cast<float4*>(out + m * C);
-#pragma unroll
-    for (int q = 0; q < LN_MAXV; ++q) {
-        const int v = lane + 64 * q;
-        if (v < nv) {
-            const float4 ww = reinterpret_cast<const float4*>(w)[v];
-            const float4 bv = reinterpret_cast<const float4*>(b)[v];
-            float4 y;
-            y.x = (x[q].x - mean) * rstd * ww.x + bv.x;
-            y.y = (x[q].y - mean) * rstd * ww.y + bv.y;
-            y.z = (x[q].z - mean) * rstd * ww.z + bv.z;
-            y.w = (x[q].w - mean) * rstd * ww.w + bv.w;
-            dst[v] = y;
-        }
-    }
-}
-void launch_layernorm(const float* in, float* out, int M, int C, const float* w, const float* b,
-                      const int32_t* row_map, int ntok, hipStream_t s) {
-    hipLaunchKernelGGL((layernorm_kernel<0>), dim3((M + 3) / 4), dim3(256), 0, s, in, out, (int64_t)M, C, w, b,
-                       row_map, ntok, 0, 0);
-}
-void launch_merge_layernorm(const float* in, float* out, int n, int R, int C, const float* w, const float* b,
-                            hipStream_t s) {
-    const int64_t M = (int64_t)n * (R / 2) * (R / 2);
-    hipLaunchKernelGGL((layernorm_kernel<1>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, in, out, M, 4 * C, w, b,
-                       (const int32_t*)nullptr, 0, R, C);
-}
-
-// The row-map LayerNorm with its output pre-split in APB order (f32x3 mode: the consumer is an x3q GEMM, common.h).  Same
-// statistics as layernorm_kernel<0> bit for bit (same lane -> column mapping, same reduction order, same expression for y:
-// tests/test_gpu_norm.py decodes the image and holds it to the plain kernel's rows word for word);
-// a workgroup owns 32 consecutive OUTPUT rows: pass 1 gathers them (one row per wave at a time, coalesced), keeps them in LDS
-// and forms mean / rstd; pass 2 re-reads them from LDS in the (row % 32, k-half) order of an APB slot run, so that every store
-// instruction of a wave writes 1 KiB contiguous (the scheme of rmsnorm_apb_kernel below).  NQ = float4 per lane (C <= 256 NQ).
-// AMX = true (fp8 mode): the same rows, quantised to MXFP8 in the AMX image order of gemm_mx8_kernel (common.h: one scale per 32
-// columns; a lane of pass 2 holds 16 consecutive columns, its partner lane the other 16 of the block; pad blocks up to a whole
-// k64 step are written as zeros).
-template <int NQ, bool AMX>
-__global__ __launch_bounds__(256) void layernorm_apb_kernel(const float* __restrict__ in, i32x4* __restrict__ out, int64_t M, int C,
-                                                            const float* __restrict__ w, const float* __restrict__ b,
-                                                            const int32_t* __restrict__ row_map, int ntok, uint8_t* __restrict__ sc) {
-    extern __shared__ __attribute__((aligned(16))) float ln_rows_s[];
-    __shared__ float mu_s[32], rs_s[32];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nv = C >> 2, KT = C >> 4, RS = C + 4;
-    const int64_t m0 = (int64_t)blockIdx.x * 32;
-    float4 x[8][NQ];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        int64_t m = m0 + wave * 8 + i;
-        m = m < M ? m : M - 1;
-        int64_t src = m;
-        if (row_map) src = (m / ntok) * ntok + row_map[m % ntok];
-        const float4* sp = reinterpret_cast<const float4*>(in + src * C);
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int v = lane + 64 * q;
-            x[i][q] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (v < nv) x[i][q] = sp[v];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        float4* dst = reinterpret_cast<float4*>(ln_rows_s + (wave * 8 + i) * RS);
-        float sum = 0.f;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int v = lane + 64 * q;
-            if (v < nv) {
-                dst[v] = x[i][q];
-                sum += (x[i][q].x + x[i][q].y) + (x[i][q].z + x[i][q].w);
-            }
-        }
-        const float mean = wave_sum(sum) / (float)C;
-        float sq = 0.f;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int v = lane + 64 * q;
-            if (v < nv) {
-                const float a = x[i][q].x - mean, bb = x[i][q].y - mean, c = x[i][q].z - mean, d = x[i][q].w - mean;
-                sq += (a * a + bb * bb) + (c * c + d * d);
-            }
-        }
-        const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)C + 1e-5f);
-        if (lane == 0) { mu_s[wave * 8 + i] = mean; rs_s[wave * 8 + i] = rstd; }
-    }
-    __syncthreads();
-    const int ml = lane & 31;
-    const int64_t m = m0 + ml;
-    if (m >= M) return;
-    const float mean = mu_s[ml], rstd = rs_s[ml];
-    const int kh = lane >> 5;
-    if constexpr (AMX) {
-        const int KT64 = (C + 63) >> 6, KQ = (KT64 + 3) >> 2;
-        for (int kb = wave; kb < 2 * KT64; kb += 4) {
-            const int col = kb * 32 + kh * 16;
-            float y[16];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (col + 4 * q < C) {
-                    const float4 x0 = *reinterpret_cast<const float4*>(ln_rows_s + ml * RS + col + 4 * q);
-                    const float4 w0 = *reinterpret_cast<const float4*>(w + col + 4 * q), b0 = *reinterpret_cast<const float4*>(b + col + 4 * q);
-                    v.x = (x0.x - mean) * rstd * w0.x + b0.x;
-                    v.y = (x0.y - mean) * rstd * w0.y + b0.y;
-                    v.z = (x0.z - mean) * rstd * w0.z + b0.z;
-                    v.w = (x0.w - mean) * rstd * w0.w + b0.w;
-                }
-                y[4 * q] = v.x; y[4 * q + 1] = v.y; y[4 * q + 2] = v.z; y[4 * q + 3] = v.w;
-            }
-            amx_store16(out, sc, m, kb, KT64, KQ, y, kh);
-        }
-        return;
-    }
-    for (int kt = wave; kt < KT; kt += 4) {
-        const int col = kt * 16 + kh * 8;
-        const float4 x0 = *reinterpret_cast<const float4*>(ln_rows_s + ml * RS + col), x1 = *reinterpret_cast<const float4*>(ln_rows_s + ml * RS + col + 4);
-        const float4 w0 = *reinterpret_cast<const float4*>(w + col), w1 = *reinterpret_cast<const float4*>(w + col + 4);
-        const float4 b0 = *reinterpret_cast<const float4*>(b + col), b1 = *reinterpret_cast<const float4*>(b + col + 4);
-        float y[8];
-        y[0] = (x0.x - mean) * rstd * w0.x + b0.x;
-        y[1] = (x0.y - mean) * rstd * w0.y + b0.y;
-        y[2] = (x0.z - mean) * rstd * w0.z + b0.z;
-        y[3] = (x0.w - mean) * rstd * w0.w + b0.w;
-        y[4] = (x1.x - mean) * rstd * w1.x + b1.x;
-        y[5] = (x1.y - mean) * rstd * w1.y + b1.y;
-        y[6] = (x1.z - mean) * rstd * w1.z + b1.z;
-        y[7] = (x1.w - mean) * rstd * w1.w + b1.w;
-        apb_store8(out, m, kt * 2 + kh, KT, y);
-    }
-}
-// C % 16 == 0, C <= 768; out_apb holds roundup(M, 128) rows (rows >= M are left as they are: their products are never stored)
-void launch_layernorm_apb(const float* in, void* out_apb, int M, int C, const float* w, const float* b, const int32_t* row_map,
-                          int ntok, hipStream_t s, void* out_scales) {
-    const size_t lds = (size_t)32 * (C + 4) * sizeof(float);          // 98.8 KB at C = 768
-    const dim3 grid((M + 31) / 32), block(256);
-    i32x4* o = reinterpret_cast<i32x4*>(out_apb);
-    uint8_t* sc = reinterpret_cast<uint8_t*>(out_scales);
-#define MELLOW_LN_LAUNCH(NQ, AMX)                                                                                        \
-    do {                                                                                                                 \
-        set_max_dynamic_lds(reinterpret_cast<const void*>(&layernorm_apb_kernel<NQ, AMX>), 100 * 1024);                  \
-        hipLaunchKernelGGL((layernorm_apb_kernel<NQ, AMX>), grid, block, lds, s, in, o, (int64_t)M, C, w, b, row_map, ntok, sc); \
-    } while (0)
-    if (out_scales) {        // AMX image + scale bytes (fp8 mode)
-        if (C <= 256) MELLOW_LN_LAUNCH(1, true); else if (C <= 512) MELLOW_LN_LAUNCH(2, true); else MELLOW_LN_LAUNCH(3, true);
-    } else {
-        if (C <= 256) MELLOW_LN_LAUNCH(1, false); else if (C <= 512) MELLOW_LN_LAUNCH(2, false); else MELLOW_LN_LAUNCH(3, false);
-    }
-#undef MELLOW_LN_LAUNCH
-}
-
-// x^2 + y^2 + z^2 + w^2 of one float4 in ONE pinned form, fma(x, x, y y) + fma(z, z, w w).  Written as a plain expression the compiler
-// is free to contract it either way round, and it did: fma(x, x, y y) in rmsnorm_kernel, fma(y, y, x x) in rmsnorm_apb_kernel, so the
-// two kernels' 1/rms differed in the last place on a few rows in a hundred (tests/test_gpu_norm.py).  This is the form rmsnorm_kernel
-// compiled to before: its results are unchanged.
-__device__ __forceinline__ float sumsq4(const float4& v) {
-#pragma clang fp contract(off)
-    const float yy = v.y * v.y, ww = v.w * v.w;
-    return __builtin_fmaf(v.x, v.x, yy) + __builtin_fmaf(v.z, v.z, ww);
-}
-// LlamaRMSNorm (fp32): w * (x * rsqrt(mean(x^2) + eps))
-__global__ __launch_bounds__(256) void rmsnorm_kernel(const float* __restrict__ in, float* __restrict__ out, int64_t M,
-                                                      int C, const float* __restrict__ w, float eps) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t m = (int64_t)blockIdx.x * 4 + wave;
-    if (m >= M) return;
-    const int nv = C >> 2;
-    const float4* src = reinterpret_cast<const float4*>(in + m * C);
-    float4 x[LN_MAXV];
-    float ss = 0.f;
-#pragma unroll
-    for (int q = 0; q < LN_MAXV; ++q) {
-        const int v = lane + 64 * q;
-        x[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (v < nv) {
-            x[q] = src[v];
-            ss += sumsq4(x[q]);
-        }
-    }
-    const float r = 1.0f / sqrtf(wave_sum(ss) / (float)C + eps);
-    float4* dst = reinterpret_cast<float4*>(out + m * C);
-#pragma unroll
-    for (int q = 0; q < LN_MAXV; ++q) {
-        const int v = lane + 64 * q;
-        if (v < nv) {
-            const float4 ww = reinterpret_cast<const float4*>(w)[v];
-            float4 y;
-            y.x = __fmul_rn(ww.x, __fmul_rn(x[q].x, r));
-            y.y = __fmul_rn(ww.y, __fmul_rn(x[q].y, r));
-            y.z = __fmul_rn(ww.z, __fmul_rn(x[q].z, r));
-            y.w = __fmul_rn(ww.w, __fmul_rn(x[q].w, r));
-            dst[v] = y;
-        }
-    }
-}
-// w * (x * r) with each product rounded to fp32 on its own.  HIP's __fmul_rn is a plain product, so it may still be contracted with
-// what consumes it: split3's a - h (common.h) turned the last product into fma(w, x r, -h), and the three pieces then summed to
-// the 48-bit product rounded another way -- one unit in the last place off the plain kernel's row in about 7 % of the elements.
-// With contraction off inside this function the product carries no contract flag and stays a product.
-__device__ __forceinline__ float rms_scaled(float w, float x, float r) {
-#pragma clang fp contract(off)
-    const float xr = x * r;
-    return w * xr;
-}
-// the same arithmetic, output pre-split in APB order.  A workgroup owns 32 consecutive rows.  Pass 1 is the plain kernel's
-// statistic (same lane -> column mapping, sumsq4 and reduction order: the same 1/rms bit for bit), one row per wave at a time; pass 2
-// re-reads the rows (L2-hot) with lane = (row % 32, k-half), the order of an APB slot run, so every store instruction of a
-// wave writes 1 KiB contiguous (a first version that stored from the row-per-wave mapping scattered 16-byte pieces 12 KiB
-// apart and took 2.3x the time of the plain kernel)
-template <bool AMX>
-__global__ __launch_bounds__(256) void rmsnorm_apb_kernel(const float* __restrict__ in, i32x4* __restrict__ out, int64_t M,
-                                                          int C, const float* __restrict__ w, float eps, uint8_t* __restrict__ sc) {
-    // The 32 rows of the workgroup are staged in LDS by pass 1 (coalesced row reads) and re-read from there by pass 2 in the
-    // (row % 32, k-half) order of an APB slot run: a second pass over global memory in that order touches 32 cache lines per load
-    // instruction (22 us per launch at M = 12448; from LDS: see profiles/).  Row stride C + 4 floats: the sixteen lanes of a
-    // ds_read_b128 group then sit on sixteen different bank quads.
-    extern __shared__ __attribute__((aligned(16))) float rows_s[];
-    __shared__ float rs[32];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nv = C >> 2, KT = C >> 4, RS = C + 4;
-    const int64_t m0 = (int64_t)blockIdx.x * 32;
-    // all eight rows of the wave are loaded before the first reduction (rows past M: a clamped re-read, result unused)
-    float ss[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        int64_t m = m0 + wave * 8 + i;
-        m = m < M ? m : M - 1;
-        const float4* src = reinterpret_cast<const float4*>(in + m * C);
-        float4* dst = reinterpret_cast<float4*>(rows_s + (wave * 8 + i) * RS);
-        ss[i] = 0.f;
-#pragma unroll
-        for (int q = 0; q < LN_MAXV; ++q) {
-            const int v = lane + 64 * q;
-            if (v < nv) {
-                const float4 x = src[v];
-                dst[v] = x;
-                ss[i] += sumsq4(x);
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const float r = 1.0f / sqrtf(wave_sum(ss[i]) / (float)C + eps);
-        if (lane == 0) rs[wave * 8 + i] = r;
-    }
-    __syncthreads();
-    const int ml = lane & 31;
-    const int64_t m = m0 + ml;
-    if (m >= M) return;
-    const float r = rs[ml];
-    const int kh = lane >> 5;
-    if constexpr (AMX) {          // fp8 mode: the same values as MXFP8 in AMX order (see layernorm_apb_kernel)
-        const int KT64 = (C + 63) >> 6, KQ = (KT64 + 3) >> 2;
-        for (int kb = wave; kb < 2 * KT64; kb += 4) {
-            const int col = kb * 32 + kh * 16;
-            float y[16];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (col + 4 * q < C) {
-                    const float4 x0 = *reinterpret_cast<const float4*>(rows_s + ml * RS + col + 4 * q);
-                    const float4 w0 = *reinterpret_cast<const float4*>(w + col + 4 * q);
-                    v = make_float4(__fmul_rn(w0.x, __fmul_rn(x0.x, r)), __fmul_rn(w0.y, __fmul_rn(x0.y, r)), __fmul_rn(w0.z, __fmul_rn(x0.z, r)),
-                                    __fmul_rn(w0.w, __fmul_rn(x0.w, r)));
-                }
-                y[4 * q] = v.x; y[4 * q + 1] = v.y; y[4 * q + 2] = v.z; y[4 * q + 3] = v.w;
-            }
-            amx_store16(out, sc, m, kb, KT64, KQ, y, kh);
-        }
-        return;
-    }
-    for (int kt = wave; kt < KT; kt += 4) {
-        const int col = kt * 16 + kh * 8;
-        const float4 x0 = *reinterpret_cast<const float4*>(rows_s + ml * RS + col), x1 = *reinterpret_cast<const float4*>(rows_s + ml * RS + col + 4);
-        const float4 w0 = *reinterpret_cast<const float4*>(w + col), w1 = *reinterpret_cast<const float4*>(w + col + 4);
-        const float y[8] = {rms_scaled(w0.x, x0.x, r), rms_scaled(w0.y, x0.y, r), rms_scaled(w0.z, x0.z, r), rms_scaled(w0.w, x0.w, r),
-                            rms_scaled(w1.x, x1.x, r), rms_scaled(w1.y, x1.y, r), rms_scaled(w1.z, x1.z, r), rms_scaled(w1.w, x1.w, r)};
-        apb_store8(out, m, kt * 2 + kh, KT, y);
-    }
-}
-void launch_rmsnorm_apb(const float* in, void* out_apb, int M, int C, const float* w, float eps, hipStream_t s, void* out_scales) {
-    const size_t lds = (size_t)32 * (C + 4) * sizeof(float);          // 74 KB at C = 576: two workgroups per CU
-    set_max_dynamic_lds(reinterpret_cast<const void*>(&rmsnorm_apb_kernel<false>), 96 * 1024);
-    set_max_dynamic_lds(reinterpret_cast<const void*>(&rmsnorm_apb_kernel<true>), 96 * 1024);
-    if (out_scales) hipLaunchKernelGGL(rmsnorm_apb_kernel<true>, dim3((M + 31) / 32), dim3(256), lds, s, in, reinterpret_cast<i32x4*>(out_apb), (int64_t)M, C, w, eps, reinterpret_cast<uint8_t*>(out_scales));
-    else hipLaunchKernelGGL(rmsnorm_apb_kernel<false>, dim3((M + 31) / 32), dim3(256), lds, s, in, reinterpret_cast<i32x4*>(out_apb), (int64_t)M, C, w, eps, (uint8_t*)nullptr);
-}
-void launch_rmsnorm(const float* in, float* out, int M, int C, const float* w, float eps, hipStream_t s) {
-    hipLaunchKernelGGL(rmsnorm_kernel, dim3((M + 3) / 4), dim3(256), 0, s, in, out, (int64_t)M, C, w, eps);
 }
 
 // ---- A7 window attention core on the matrix pipe (v_mfma_f32_32x32x2_f32, exact fp32); reference htsat.py:301-327.  Inputs arrive in
