@@ -2,8 +2,8 @@
 // translation units share.  Not part of the C ABI (include/mellow_hip.h is).
 //   engine.cpp          errors, allocation helpers, create / destroy / fork / load_tensor, precision, profiler read-out
 //   engine_weights.cpp  mellow_engine_finalize: every reference checkpoint key -> device layouts (P / PB / P16 / e4m3, composed decode weights)
-//   engine_encoder.cpp  GEMM dispatch, front-end + HTSAT encoder (A1-A13), the taps mellow_logmel / mellow_encode / mellow_resample
-//   engine_lm.cpp       KV pages, LM prefill (A15), the decode step and its per-call mode, mellow_prefix / lm taps, scoring
+//   engine_encoder.cpp  the dense GEMM dispatch (run_gemm), front-end + HTSAT encoder (A1-A13; swin_block), the taps mellow_logmel / mellow_encode / mellow_resample
+//   engine_lm.cpp       KV pages, LM prefill (A15; plan, parts, prefill_layer), the decode step and its per-call mode, mellow_prefix / lm taps, scoring
 //   engine_generate.cpp the generation loop on top of it (A16): request + checks, passes, step graphs, the mellow_generate* entry points,
 //                       beam search (mellow_generate_beam, mellow_beam_select)
 //   engine_dev.cpp      developer entry points (GEMM timing / debug taps, kernel stamps)
@@ -403,30 +403,70 @@ void window_map_host(int R, int shift, int32_t* out);
 void pack_weight_host(const float* w, int N, int K, int NP, int KP, float* out);
 void rope_tables_host(float theta, int head_dim, int P, float* c, float* s);
 int alloc_state_words(mellow_engine* e);
+// `chain`: the stream the scope's launches go on (null: e->stream).  Records are read in enqueue order: profiling forces ONE chain.
 struct ProfScope {
     mellow_engine* e;
     ProfRec r;
     bool on;
-    ProfScope(mellow_engine* e_, int fam, double flops, double bytes) : e(e_), on(e_->prof_on) {
+    hipStream_t chain;
+    ProfScope(mellow_engine* e_, int fam, double flops, double bytes, hipStream_t chain_ = nullptr) : e(e_), on(e_->prof_on), chain(chain_ ? chain_ : e_->stream) {
         if (on) {
             r.fam = fam;
             r.flops = flops;
             r.bytes = bytes;
             r.a = next_event(e);
             r.b = next_event(e);
-            hipEventRecord(r.a, e->stream);
+            hipEventRecord(r.a, chain);
         }
     }
     ~ProfScope() {
         if (on) {
-            hipEventRecord(r.b, e->stream);
+            hipEventRecord(r.b, chain);
             e->prof.push_back(r);
         }
     }
 };
+// Forks the side streams stream2[0 .. n) off e->stream when it is made (`status`: what that returned); run() joins them back, and so
+// does the destructor if nothing has yet.  Once a side stream waits on ev_fork, EVERY exit of the forking function has to join -- an
+// early error return would leave side-stream launches running against buffers the caller's next call reuses or frees from e->stream.
+struct StreamFork {
+    mellow_engine* e; int n; bool joined; int status;
+    StreamFork(mellow_engine* e_, int n_) : e(e_), n(n_), joined(n_ <= 0), status(fork()) {}
+    StreamFork(const StreamFork&) = delete;
+    int fork() {
+        if (n > 0) HIPCHK(hipEventRecord(e->ev_fork, e->stream));
+        for (int i = 0; i < n; ++i) HIPCHK(hipStreamWaitEvent(e->stream2[i], e->ev_fork, 0));
+        return 0;
+    }
+    int run() {
+        if (joined) return 0;
+        joined = true;
+        for (int i = 0; i < n; ++i) {
+            HIPCHK(hipEventRecord(e->ev_join[i], e->stream2[i]));
+            HIPCHK(hipStreamWaitEvent(e->stream, e->ev_join[i], 0));
+        }
+        return 0;
+    }
+    ~StreamFork() { (void)run(); }
+};
 // engine_encoder.cpp
-int run_gemm(mellow_engine* e, const GemmArgs& a);
-int run_gemm_apb(mellow_engine* e, const GemmArgs& a, const void* a3, hipStream_t st = nullptr, const void* a3_scales = nullptr);
+// What a producer leaves for the GEMM that follows it: fp32 rows, or an image of K-long rows in the GEMM's operand format
+// and LDS order -- APB (three bf16 pieces, f32x3 mode; common.h) when scales is null, else AMX (MXFP8, fp8 mode) + its scale bytes.
+// `rows` beside an image: what the GEMM's A and the producer's fp32 output are given (null where the fp32 form does not exist).
+struct HandOver { float* rows = nullptr; char *image = nullptr, *scales = nullptr; int K = 0; };
+// the image of M rows x K at `base`: whole 128-row panels, and an AMX image's scale bytes live behind its data
+static inline HandOver image_region(void* base, int M, int K, bool amx, float* rows = nullptr) {
+    char* p = static_cast<char*>(base);
+    return HandOver{rows, p, amx ? p + (size_t)rup(M, 128) * rup(K, 64) : nullptr, K};
+}
+// g writes its output (also) as the image `out`: the epilogue's C3 fields
+static inline void hand_over_to(GemmArgs& g, const HandOver& out) {
+    g.C3 = out.image;
+    if (out.scales) { g.c3_fmt = 1; g.C3s = reinterpret_cast<uint8_t*>(out.scales); g.c3_kt64 = rup(out.K, 64) / 64; }
+}
+// One dense GEMM on `chain`, one profile record there.  `in` picks the kernel: an image the LDS-DMA kernel of its format, anything
+// else -- `{}` where no producer handed g.A over -- what the mode gives fp32 rows (main chain only).
+int run_gemm(mellow_engine* e, hipStream_t chain, const GemmArgs& g, const HandOver& in);
 GemmArgs lin(const float* A, int64_t lda, int M, const Packed& w, float* C, int64_t ldc, const float* bias);
 int run_encoder(mellow_engine* e, const float* wav, int n, int64_t n_samples, int want_logmel_only, int apply_bn, float* logmel_out);
 // engine_lm.cpp

@@ -1,5 +1,5 @@
-// The decoder LM: KV pages and decode workspaces, prefill (A15), the KV-cached decode step and its per-call mode, prefix assembly
-// (A14), the lm taps and scoring.  The generation loop on top of it is engine_generate.cpp.
+// The decoder LM: KV pages and decode workspaces, prefill (A15: a span's plan, its parts, one layer's launches, the fork / join around
+// them), the KV-cached decode step and its per-call mode, prefix assembly (A14), the lm taps and scoring.  The loop on top: engine_generate.cpp.
 #include "engine_internal.h"
 
 // key split of the decode attention (DecArgs::gs, 4-key groups per split): balanced at the END of the reserved context, rounded
@@ -225,149 +225,135 @@ int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec)
     return 0;
 }
 
-// The LM layers over positions [pos0, pos0 + rows) of B sequences (engine_internal.h, PrefillSpan): what run_prefill and
-// run_prefill_q are made of.  Nothing of the decode state is touched; every side stream is joined back into e->stream on return.
-static int run_prefill_span(mellow_engine* e, int B, const PrefillSpan& sp) {
-    hipStream_t s = e->stream;
-    const int NL = e->cfg.num_layers;
-    const int T = sp.rows, pos0 = sp.pos0, T_end = pos0 + T;                 // rows per sequence of every activation; keys [0, T_end)
-    const bool all_positions = sp.all_layers;
+// ---- the LM prefill: what a span decides (PrefillPlan), where its rows run (PrefillPart), what a layer launches (prefill_layer) ----
+struct PrefillPlan {
+    int T, pos0, T_end, Tmax;     // rows per sequence of every activation, their first position; keys [0, T_end); the kernels' page stride
+    bool all_layers, amx, apb, p16, fuse_norm, attn_x3, attn_bf16;
+    float *kpages, *vpages;       // layer 0, example 0 of what they write: the pages, their bf16 form (p16) or the prefix buffer
+    size_t lay, page;             // floats of one layer / of one example of it (halved for bf16 pages: two bytes per element)
+};
+struct PrefillPart {
+    hipStream_t chain;
+    int b0, B, M;                 // first example, examples, rows (B * T)
+    float *x, *q;                 // the part's rows of the span's input, of lm_q
+    HandOver xn, o, h;            // ... of lm_xn / lm_o / lm_h, and, APB or AMX, its panel-aligned region of lm_xn3 / lm_o3 / lm_h3
+    float *ssq_in, *ssq_mid;      // [row][9] sum-of-squares partials of the residual stream after down / after o_proj (fuse_norm)
+};
+static int prefill_plan(mellow_engine* e, int B, const PrefillSpan& sp, PrefillPlan& pl) {
+    pl.T = sp.rows; pl.pos0 = sp.pos0; pl.T_end = sp.pos0 + sp.rows; pl.all_layers = sp.all_layers;
     // to_prefix: the K/V of the B sequences go to the prefix buffer (page stride Tp), not to the pages -- a page of example b' would
     // lie inside the rows another example's copies are written to, and one parallel copy kernel cannot order those writes
     const bool fan = sp.to_prefix;
-    if (pos0 > 0 && (pos0 % 32 != 0 || fan || all_positions || e->opt.fp8 || e->opt.kv16 || B > e->kv_B))
-        return fail("internal: a prefill from position %d needs fp32 pages that hold the positions before it", pos0);
-    const int Tmax = fan ? prefix_page_len(e->cfg.prefix_len) : e->kv_Tmax;      // page stride the prefill kernels are given
-    const size_t lay = fan ? (size_t)B * 3 * Tmax * 64 : kv_layer_floats(e);    // floats of one layer of what they write
-    float *kbase = fan ? e->kprefix.p : e->kcache.p, *vbase = fan ? e->vprefix.p : e->vcache.p;
-    float *x = sp.x, *xn = e->lm_xn.p;
+    if (pl.pos0 > 0 && (pl.pos0 % 32 != 0 || fan || sp.all_layers || e->opt.fp8 || e->opt.kv16 || B > e->kv_B))
+        return fail("internal: a prefill from position %d needs fp32 pages that hold the positions before it", pl.pos0);
     // fp8 mode: the same producer -> consumer hand-over with AMX images (MXFP8, common.h) instead of APB ones: `amx`; the code below
     // says `apb` for "GEMM inputs leave their producers in operand format"
-    const bool amx = e->opt.fp8 && e->opt.fp8_prefill && e->opt.x3_apb && e->w.fp8_w.count(e->w.layers[0].qkv.p) != 0;
-    const bool apb = (e->opt.f32x3_terms && e->opt.x3_apb) || amx;        // option "x3_apb" = 0: the register-staged x3p kernel / the standalone quantiser (developer A/B)
-    // Split prefill (f32x3 mode): the batch is cut into independent parts (2 by default) that run the same launches on their own
-    // streams, so the tails and the fill / drain of one part's kernels are covered by another's (every buffer is indexed by row
-    // or by example, so a part is an offset; its pre-split operands get their own panel-aligned region).  Measured before it was
-    // built with two forked contexts (tools/half_chain_probe.py).  MELLOW_PREFILL_SPLIT=n: n parts (1 = one chain, at most 4).
-    if (apb && !e->prof_on && (e->prefill_parts > 1 || e->streams_probed)) CHK(ensure_prefill_streams(e));      // (may find that they would serialise: fewer parts)
-    int nh = (apb && !e->prof_on) ? e->prefill_parts : 1;
-    nh = nh < 1 ? 1 : (nh > 4 ? 4 : nh);
-    if (nh > B) nh = B;
-    int hb0[4], hB[4];
-    size_t prow[4];                                              // first row of each part's panel range
-    hipStream_t hs[4] = {s, e->stream2[0], e->stream2[1], e->stream2[2]};
-    for (int h = 0, b0 = 0, r = 0; h < nh; ++h) {
-        hb0[h] = b0; hB[h] = B / nh + (h < B % nh ? 1 : 0); prow[h] = (size_t)r;
-        b0 += hB[h]; r += rup(hB[h] * T, 128);
+    pl.amx = e->opt.fp8 && e->opt.fp8_prefill && e->opt.x3_apb && e->w.fp8_w.count(e->w.layers[0].qkv.p) != 0;
+    pl.apb = (e->opt.f32x3_terms && e->opt.x3_apb) || pl.amx;        // option "x3_apb" = 0: the register-staged x3p kernel / the standalone quantiser (developer A/B)
+    pl.p16 = pl.amx && e->kv16_direct;          // bf16 pages: the same element offsets, two bytes each
+    pl.fuse_norm = pl.apb && e->opt.prefill_fuse_norm;
+    pl.attn_x3 = (e->opt.f32x3_terms != 0 || pl.amx) && e->opt.x3_attn;      // option "x3_attn" = 0: f32x3 mode on the fp32 kernel (A/B)
+    pl.attn_bf16 = pl.amx && e->opt.fp8_attn_bf16;
+    // bf16 pages are never a fan-out's target: run_prefill / run_prefill_q refuse kv16 for one, and kv16_direct needs kv16
+    if (pl.p16 && fan) return fail("internal: a prefill to the prefix buffer needs fp32 K/V");
+    pl.Tmax = fan ? prefix_page_len(e->cfg.prefix_len) : e->kv_Tmax;
+    pl.kpages = pl.p16 ? e->kcache16.p : fan ? e->kprefix.p : e->kcache.p;
+    pl.vpages = pl.p16 ? e->vcache16.p : fan ? e->vprefix.p : e->vcache.p;
+    pl.page = (size_t)3 * pl.Tmax * 64 / (pl.p16 ? 2 : 1);
+    pl.lay = fan ? (size_t)B * pl.page : kv_layer_floats(e) / (pl.p16 ? 2 : 1);
+    return 0;
+}
+// Split prefill (f32x3 mode): the batch is cut into independent parts (2 by default) that run the same launches on their own
+// streams, so the tails and the fill / drain of one part's kernels are covered by another's (every buffer is indexed by row
+// or by example, so a part is an offset; its pre-split operands get their own panel-aligned region).  Measured before it was
+// built with two forked contexts (tools/half_chain_probe.py).  MELLOW_PREFILL_SPLIT=n: n parts (1 = one chain, at most 4).
+static int prefill_parts(mellow_engine* e, const PrefillPlan& pl, int B, float* x, PrefillPart* parts, int& nh) {
+    // The two invariants of a chain.  A span that is not APB is never split: its GEMMs share the quantiser's and the
+    // split-K buffers (run_gemm refuses them off the main chain).  Profiling forces one chain: records are read in enqueue order.
+    const bool may_split = pl.apb && !e->prof_on;
+    if (may_split && (e->prefill_parts > 1 || e->streams_probed)) CHK(ensure_prefill_streams(e));      // (may find that they would serialise: fewer parts)
+    nh = std::min(B, std::max(1, std::min(4, may_split ? e->prefill_parts : 1)));
+    size_t prow = 0;                                             // first row of the part's panel range
+    for (int h = 0, b0 = 0; h < nh; ++h) {
+        PrefillPart& p = parts[h];
+        p.chain = h ? e->stream2[h - 1] : e->stream; p.b0 = b0; p.B = B / nh + (h < B % nh ? 1 : 0); p.M = p.B * pl.T;
+        const int64_t r0 = (int64_t)b0 * pl.T;
+        // fp32 rows of the part; APB / AMX: also its pre-split operand region (6 bytes per element, whole 128-row panels)
+        auto rows_of = [&](float* rows, const mellow_engine::Buf& img, int K) { return pl.apb ? image_region(reinterpret_cast<char*>(img.p) + prow * K * 6, p.M, K, pl.amx, rows + r0 * K) : HandOver{rows + r0 * K}; };
+        p.x = x + r0 * 576; p.q = e->lm_q.p + r0 * 576;
+        p.xn = rows_of(e->lm_xn.p, e->lm_xn3, 576); p.o = rows_of(e->lm_o.p, e->lm_o3, 576); p.h = rows_of(e->lm_h.p, e->lm_h3, 1536);
+        p.ssq_in = pl.fuse_norm ? e->lm_ssq.p + prow * 9 : nullptr;
+        p.ssq_mid = pl.fuse_norm ? e->lm_ssq.p + e->lm_ssq.cap / 2 + prow * 9 : nullptr;    // second half of the buffer
+        b0 += p.B; prow += rup(p.M, 128);
     }
-    const bool split = nh > 1;
-    // Once the side streams wait on ev_fork, EVERY exit from this function has to join them back into `s` (an early error return
-    // inside the layer loop would otherwise leave launches of the side streams running against buffers the caller's next call
-    // reuses or frees from `s`): the guard joins in its destructor unless the normal path already has.
-    struct Join {
-        mellow_engine* e; hipStream_t* hs; int nh; bool done;
-        int run() {
-            if (done) return 0;
-            done = true;
-            for (int h = 1; h < nh; ++h) {
-                HIPCHK(hipEventRecord(e->ev_join[h - 1], hs[h]));
-                HIPCHK(hipStreamWaitEvent(hs[0], e->ev_join[h - 1], 0));
-            }
-            return 0;
-        }
-        ~Join() { (void)run(); }
-    } join{e, hs, nh, !split};
-    if (split) {
-        HIPCHK(hipEventRecord(e->ev_fork, s));
-        for (int h = 1; h < nh; ++h) HIPCHK(hipStreamWaitEvent(hs[h], e->ev_fork, 0));
+    return 0;
+}
+static void rmsnorm_to(mellow_engine* e, hipStream_t chain, const float* x, const HandOver& out, int M, const float* w) {
+    ProfScope ps(e, PF_NORM, 0, (out.image ? 2.5 : 2.0) * M * 576 * 4, chain);
+    if (out.image) launch_rmsnorm_apb(x, out.image, M, 576, w, e->cfg.rms_norm_eps, chain, out.scales);
+    else launch_rmsnorm(x, out.rows, M, 576, w, e->cfg.rms_norm_eps, chain);
+}
+// One layer of one part, on the part's chain.  f32x3 mode: every GEMM input of the layer is written by its producer already split
+// into three bf16 pieces, in the order the GEMM's LDS stage wants it (APB, common.h), and the GEMM stages both operands by LDS-DMA
+// (x3q); fp8 mode: the same with AMX images.
+static int prefill_layer(mellow_engine* e, const PrefillPlan& pl, const PrefillPart& p, int l) {
+    const LMLayerW& w = e->w.layers[l];
+    float *kc = pl.kpages + pl.lay * l + p.b0 * pl.page, *vc = pl.vpages + pl.lay * l + p.b0 * pl.page;
+    // norm-free chaining (fz): the residual stream leaves the o_proj / down GEMMs already pre-split together with its
+    // sum-of-squares partials (ssq_mid after o_proj, ssq_in after down); the GEMM that follows runs on the norm-folded
+    // weight and applies the row statistic to its accumulators -- 59 of the 60 normalisation launches of a prefill disappear
+    // (the first layer's input is the prefix, which has no producing GEMM: it keeps its launch)
+    const bool fz = pl.fuse_norm && w.gateup_f.p != nullptr;
+    const bool fz_in = fz && l > 0;       // this layer's input came out of the previous layer's down GEMM pre-split
+    auto with_rs = [&](GemmArgs& g, const float* ssq) { g.rs_ssq = ssq; g.rs_parts = 9; g.rs_dim = 576.f; g.rs_eps = e->cfg.rms_norm_eps; };
+    // x += ..., and under fz its image and statistic for the next GEMM
+    auto residual_out = [&](GemmArgs& g, float* ssq) { g.resid = p.x; g.ldr = 576; if (fz) { hand_over_to(g, p.xn); g.ssq_out = ssq; g.ssq_parts = 9; } };
+    if (!fz_in) rmsnorm_to(e, p.chain, p.x, p.xn, p.M, w.in_ln);
+    GemmArgs qkv;
+    qkv.A = p.xn.rows; qkv.lda = 576; qkv.M = p.M; qkv.K = 576; qkv.Wp = fz_in ? w.qkv_f.p : w.qkv.p; qkv.Nw = 960; qkv.N = 960;
+    qkv.epi = pl.pos0 > 0 ? EPI_QKV_ROPE_AT : EPI_QKV_ROPE; qkv.pos0 = pl.pos0;
+    if (fz_in) with_rs(qkv, p.ssq_in);
+    qkv.q_out = p.q; qkv.k_cache = kc; qkv.v_cache = vc; qkv.rope_cos = e->w.rope_cos; qkv.rope_sin = e->w.rope_sin;
+    qkv.T = pl.T; qkv.Tmax = pl.Tmax; qkv.q_heads = 9; qkv.kv_heads = 3; qkv.kv16 = pl.p16 ? 1 : 0;
+    CHK(run_gemm(e, p.chain, qkv, p.xn));
+    // The LAST layer only has to produce the final prefix row (nothing consumes the other rows' attention / MLP
+    // outputs; their K/V pages were just written above): it is finished by the decode kernels on B rows (finish_prefill).
+    if (l == e->cfg.num_layers - 1 && !pl.all_layers) return 0;
+    {
+        // causal QK^T + PV: 4*64 flops per (query,key) pair per head
+        ProfScope ps(e, PF_PREFILL_ATTN, 4.0 * 64 * 9 * (double)p.B * ((double)pl.T_end * (pl.T_end + 1) / 2 - (double)pl.pos0 * (pl.pos0 + 1) / 2), 0, p.chain);
+        if (pl.pos0 > 0) launch_prefill_attention_past(p.q, kc, vc, p.o.rows, p.o.image, p.B, pl.T_end, pl.Tmax, pl.pos0, pl.attn_x3, p.chain);
+        else launch_prefill_attention(p.q, kc, vc, p.o.rows, p.o.image, p.B, pl.T, pl.Tmax, pl.attn_x3, p.chain, p.o.scales, pl.attn_bf16, pl.p16);
     }
-    for (int l = 0; l < NL; ++l) {
-        const LMLayerW& w = e->w.layers[l];
-        bool last = false;
-        for (int h = 0; h < nh; ++h) {
-            hipStream_t st = hs[h];
-            const int64_t r0 = (int64_t)hb0[h] * T;
-            const int Mh = hB[h] * T, Bh = hB[h];
-            float* xh = x + r0 * 576;
-            float* xnh = xn + r0 * 576;
-            float* qh = e->lm_q.p + r0 * 576;
-            float* oh = e->lm_o.p + r0 * 576;
-            float* hh = e->lm_h.p + r0 * 1536;
-            const bool p16 = amx && e->kv16_direct;          // bf16 pages: the same element offsets, two bytes each
-            float* kc = p16 ? e->kcache16.p + (kv_layer_floats(e) * l + (size_t)hb0[h] * 3 * Tmax * 64) / 2
-                            : kbase + lay * l + (size_t)hb0[h] * 3 * Tmax * 64;
-            float* vc = p16 ? e->vcache16.p + (kv_layer_floats(e) * l + (size_t)hb0[h] * 3 * Tmax * 64) / 2
-                            : vbase + lay * l + (size_t)hb0[h] * 3 * Tmax * 64;
-            // pre-split operand regions of this half (6 bytes per element, whole 128-row panels)
-            char* xn3 = apb ? reinterpret_cast<char*>(e->lm_xn3.p) + prow[h] * 576 * 6 : nullptr;
-            char* o3 = apb ? reinterpret_cast<char*>(e->lm_o3.p) + prow[h] * 576 * 6 : nullptr;
-            char* h3 = apb ? reinterpret_cast<char*>(e->lm_h3.p) + prow[h] * 1536 * 6 : nullptr;
-            // fp8 mode: the same regions hold [AMX data: rows x K bytes | scale bytes: rows x ceil(K / 256) x 8]; rows of this part
-            char *xn3s = nullptr, *o3s = nullptr, *h3s = nullptr;
-            if (amx) {
-                xn3s = xn3 + (size_t)rup(Mh, 128) * 576; o3s = o3 + (size_t)rup(Mh, 128) * 576; h3s = h3 + (size_t)rup(Mh, 128) * 1536;
-            }
-            auto c3_amx = [&](GemmArgs& g, char* scales, int kt64) { if (amx) { g.c3_fmt = 1; g.C3s = reinterpret_cast<uint8_t*>(scales); g.c3_kt64 = kt64; } };
-            // norm-free chaining (fz): the residual stream leaves the o_proj / down GEMMs already pre-split together with its
-            // sum-of-squares partials (ssq_mid after o_proj, ssq_in after down); the GEMM that follows runs on the norm-folded
-            // weight and applies the row statistic to its accumulators -- 59 of the 60 normalisation launches of a prefill disappear
-            // (the first layer's input is the prefix, which has no producing GEMM: it keeps its launch)
-            const bool fz = apb && e->opt.prefill_fuse_norm && w.gateup_f.p != nullptr;
-            float* ssq_in = fz ? e->lm_ssq.p + prow[h] * 9 : nullptr;                       // [row][9], rows of this part
-            float* ssq_mid = fz ? e->lm_ssq.p + e->lm_ssq.cap / 2 + prow[h] * 9 : nullptr;    // second half of the buffer
-            auto with_rs = [&](GemmArgs& g, const float* ssq) { g.rs_ssq = ssq; g.rs_parts = 9; g.rs_dim = 576.f; g.rs_eps = e->cfg.rms_norm_eps; };
-            (void)ssq_mid;
-            // f32x3 mode: every GEMM input of the layer is written by its producer already split into three bf16 pieces, in the
-            // order the GEMM's LDS stage wants it (APB, common.h), and the GEMM stages both operands by LDS-DMA (x3q)
-            const bool fz_in = fz && l > 0;       // this layer's input came out of the previous layer's down GEMM pre-split
-            if (fz_in) {}
-            else if (apb) { ProfScope ps(e, PF_NORM, 0, 2.5 * Mh * 576 * 4); launch_rmsnorm_apb(xh, xn3, Mh, 576, w.in_ln, e->cfg.rms_norm_eps, st, xn3s); }
-            else { ProfScope ps(e, PF_NORM, 0, 2.0 * Mh * 576 * 4); launch_rmsnorm(xh, xnh, Mh, 576, w.in_ln, e->cfg.rms_norm_eps, st); }
-            {
-                GemmArgs g;
-                g.A = xnh; g.lda = 576; g.M = Mh; g.K = 576; g.Wp = fz_in ? w.qkv_f.p : w.qkv.p; g.Nw = 960; g.N = 960;
-                g.epi = pos0 > 0 ? EPI_QKV_ROPE_AT : EPI_QKV_ROPE; g.pos0 = pos0;
-                if (fz_in) with_rs(g, ssq_in);
-                g.q_out = qh; g.k_cache = kc; g.v_cache = vc; g.rope_cos = e->w.rope_cos; g.rope_sin = e->w.rope_sin;
-                g.T = T; g.Tmax = Tmax; g.q_heads = 9; g.kv_heads = 3; g.kv16 = p16 ? 1 : 0;
-                if (apb) CHK(run_gemm_apb(e, g, xn3, st, xn3s)); else CHK(run_gemm(e, g));
-            }
-            // The LAST layer only has to produce the final prefix row (nothing consumes the other rows' attention / MLP
-            // outputs; their K/V pages were just written above): it is finished below by the decode kernels on B rows.
-            if (l == NL - 1 && !all_positions) { last = true; continue; }
-            {
-                // causal QK^T + PV: 4*64 flops per (query,key) pair per head
-                ProfScope ps(e, PF_PREFILL_ATTN, 4.0 * 64 * 9 * (double)Bh * ((double)T_end * (T_end + 1) / 2 - (double)pos0 * (pos0 + 1) / 2), 0);
-                const bool attn_f32 = !e->opt.x3_attn;   // option "x3_attn" = 0: f32x3 mode on the fp32 kernel (A/B)
-                if (pos0 > 0) launch_prefill_attention_past(qh, kc, vc, oh, apb ? o3 : nullptr, Bh, T_end, Tmax, pos0, e->opt.f32x3_terms != 0 && !attn_f32, st);
-                else launch_prefill_attention(qh, kc, vc, oh, apb ? o3 : nullptr, Bh, T, Tmax, (e->opt.f32x3_terms != 0 || amx) && !attn_f32, st, o3s, amx && e->opt.fp8_attn_bf16, p16);
-            }
-            {
-                GemmArgs g = lin(oh, 576, Mh, w.o, xh, 576, nullptr);
-                g.resid = xh; g.ldr = 576;
-                if (fz) { g.C3 = xn3; g.ssq_out = ssq_mid; g.ssq_parts = 9; c3_amx(g, xn3s, 9); }
-                if (apb) CHK(run_gemm_apb(e, g, o3, st, o3s)); else CHK(run_gemm(e, g));
-            }
-            if (fz) {}
-            else if (apb) { ProfScope ps(e, PF_NORM, 0, 2.5 * Mh * 576 * 4); launch_rmsnorm_apb(xh, xn3, Mh, 576, w.post_ln, e->cfg.rms_norm_eps, st, xn3s); }
-            else { ProfScope ps(e, PF_NORM, 0, 2.0 * Mh * 576 * 4); launch_rmsnorm(xh, xnh, Mh, 576, w.post_ln, e->cfg.rms_norm_eps, st); }
-            {
-                GemmArgs g;
-                g.A = xnh; g.lda = 576; g.M = Mh; g.K = 576; g.Wp = fz ? w.gateup_f.p : w.gateup.p; g.Nw = 3072; g.N = 1536; g.C = hh; g.ldc = 1536;
-                g.epi = EPI_SWIGLU;
-                if (fz) with_rs(g, ssq_mid);
-                if (apb) { g.C3 = h3; c3_amx(g, h3s, 24); CHK(run_gemm_apb(e, g, xn3, st, xn3s)); } else CHK(run_gemm(e, g));
-            }
-            {
-                GemmArgs g = lin(hh, 1536, Mh, w.down, xh, 576, nullptr);
-                g.resid = xh; g.ldr = 576;
-                if (fz) { g.C3 = xn3; g.ssq_out = ssq_in; g.ssq_parts = 9; c3_amx(g, xn3s, 9); }
-                if (apb) CHK(run_gemm_apb(e, g, h3, st, h3s)); else CHK(run_gemm(e, g));
-            }
-        }
-        if (last) break;
-    }
-    CHK(join.run());
+    GemmArgs o = lin(p.o.rows, 576, p.M, w.o, p.x, 576, nullptr);
+    residual_out(o, p.ssq_mid);
+    CHK(run_gemm(e, p.chain, o, p.o));
+    if (!fz) rmsnorm_to(e, p.chain, p.x, p.xn, p.M, w.post_ln);
+    GemmArgs gu;
+    gu.A = p.xn.rows; gu.lda = 576; gu.M = p.M; gu.K = 576; gu.Wp = fz ? w.gateup_f.p : w.gateup.p; gu.Nw = 3072; gu.N = 1536; gu.C = p.h.rows; gu.ldc = 1536;
+    gu.epi = EPI_SWIGLU;
+    if (fz) with_rs(gu, p.ssq_mid);
+    hand_over_to(gu, p.h);
+    CHK(run_gemm(e, p.chain, gu, p.xn));
+    GemmArgs down = lin(p.h.rows, 1536, p.M, w.down, p.x, 576, nullptr);
+    residual_out(down, p.ssq_in);
+    CHK(run_gemm(e, p.chain, down, p.h));
+    return 0;
+}
+// The LM layers over positions [pos0, pos0 + rows) of B sequences (engine_internal.h, PrefillSpan): what run_prefill and
+// run_prefill_q are made of.  Nothing of the decode state is touched; every side stream is joined back into e->stream on return.
+// The loop is layer-major: the interleaving of the parts within a layer is the enqueue order.
+static int run_prefill_span(mellow_engine* e, int B, const PrefillSpan& sp) {
+    PrefillPlan plan;
+    PrefillPart parts[4];      // nh of them
+    int nh = 1;
+    CHK(prefill_plan(e, B, sp, plan));
+    CHK(prefill_parts(e, plan, B, sp.x, parts, nh));
+    StreamFork sides(e, nh - 1);
+    CHK(sides.status);
+    for (int l = 0; l < e->cfg.num_layers; ++l)
+        for (int h = 0; h < nh; ++h) CHK(prefill_layer(e, plan, parts[h], l));
+    CHK(sides.run());
     HIPCHK(hipGetLastError());
     return 0;
 }
