@@ -62,7 +62,8 @@ extern "C" {
  *  5: the attention taps on host data, mellow_debug_prefill_attn and mellow_debug_window_attn.  No existing symbol or struct
  *     changed; a binding that must also load a minor-4 library detects them by symbol lookup.  The GEMM epilogue tap
  *     mellow_debug_gemm_epi was added later under this same minor, detected by symbol lookup all the same, and so was the norm /
- *     hand-over tap mellow_debug_norm, and then the decode attention tap mellow_debug_dec_attn. */
+ *     hand-over tap mellow_debug_norm, and then the decode attention tap mellow_debug_dec_attn, and then the decode GEMV tap
+ *     mellow_debug_dec_gemv. */
 #define MELLOW_ABI_MINOR 5
 
 typedef struct mellow_engine mellow_engine_t;
@@ -686,6 +687,63 @@ int  mellow_debug_dec_attn(mellow_engine_t* e, const mellow_dec_attn_t* d, const
                            int64_t att_capacity, float* out_ml, int64_t ml_capacity, void* out_k, void* out_v, int64_t kv_capacity,
                            float* out_xnew, int64_t xnew_capacity, void* out_xmid, int64_t xmid_capacity, void* out_x16,
                            int64_t x16_capacity, float* out_ssq, int64_t ssq_capacity);
+/* Decode GEMV tap on HOST data (works on any engine, finalised or not): ONE call of ONE of the launchers that make up the rest of a
+ * decode layer and the step's final norm -- the launchers the decode step itself calls, on DecArgs the tap fills from buffers of
+ * its own.  rows = roundup(B, 32), RB = rows / 32; in the row-major operands the slots B .. rows - 1 run on zeros.
+ *   op 0  launch_dec_qkv:        the split-K q/k/v projection.  (kcd 0, first 1): the step's first launch, on x alone; it stages
+ *                                rope_cur from row pos + inc_pos of the tables and, with inc_pos, advances the position word.
+ *                                (kcd 8 = DEC_KC_DOWN, first 0): x_new = x + the sum of the down slabs.
+ *   op 1  launch_dec_gateup (form 0) / launch_dec_gateup3 (form 1): gate/up with the SwiGLU and its RMS factor
+ *   op 2  launch_dec_down:       the split-K down projection
+ *   op 3  launch_dec_qkv2 (form 0) / launch_dec_qkv2x3 (form 1): the down projection and the next q/k/v projection in one launch
+ *   op 4  launch_dec_final_norm: kcd 0 or 8; xnF, or with want_x3 the pre-split xn3
+ * Weights, logical row-major host f32, packed on the device by the routines the loader uses (launch_pack_weight; the 8 + 8 row
+ * gate/up interleave and launch_pack_weight16 / launch_pack_weight16n; launch_compose_f64, the [W' | Q] concatenation and the pack):
+ *   op 0: W = W' [960][576], the q/k/v weight with the norm weight folded in;   op 1: W = gate, W2 = up [1536][576], folded;
+ *   op 2: W = Wd [576][1536];   op 3: W = W' [960][576], W2 = Wd [576][1536];   op 4: W = the norm vector [576]
+ * Activations:
+ *   x       host f32 [B][576]: x_mid (ops 0, 4; op 3 form 0), sent in F32-layout
+ *   down    host f32 [8][B][576] with kcd 8 (ops 0, 4), NULL with kcd 0
+ *   h       host f32 [B][1536] (op 2; op 3 form 0), sent in F32-layout with 192 k-tiles
+ *   x_img   raw image of x_mid as a device kernel leaves it, whole (all `rows` rows): op 1 form 0 the F16-layout (rows * 576 * 4
+ *           bytes), op 1 form 1 the F3-16 triples, op 3 form 1 the F3-32 triples (rows * 576 * 6 bytes)
+ *   h_img   raw F3-32 image of h, 96 pairs (op 3 form 1: rows * 1536 * 6 bytes)
+ *   ssq     raw f32 [rows][40], the o_proj's sums of squares of x_mid (op 1; a row's 36 partials are summed, columns 36 .. 39 are not read)
+ *   rope_cos / rope_sin  host f32 [Tmax][32] (op 0 with first), or NULL for the tables of mellow_host_rope_tables
+ *   blk_live host i32 [RB] or NULL (RB >= 2 only): a block with blk_live 0 does not run (the f32x3 forms skip its stores)
+ * Every output the launch can write is filled with 0xFF bytes first and returned whole and raw (capacities in bytes):
+ *   out_pq    f32 [8][rows][960] + 32 rows   (ops 0, 3; op 3 owns the slabs 0 .. Q2_NPQ - 1 = 5 only)
+ *   out_down  f32 [8][rows * 576] F32-layout slabs + 32 * 576 floats   (ops 2, 3; op 3 owns the slabs 0 .. Q2_HC - 1 = 3 only)
+ *   out_ssq1  f32 [rows + 32][8];  out_xnew f32 [rows + 32][576];  out_rope f32 [128] (cos | sin, then 64 floats nobody owns);
+ *   out_pos   the position word after the launch   (op 0)
+ *   out_gu    f32 [rows * 1536 + 32 * 1536] (h in F32-layout with 192 k-tiles);  out_h3 the F3-32 image of h, 96 pairs, 6 bytes
+ *             per element of the same count (op 1; out_h3 form 1 only)
+ *   out_xn    [rows * 576 + 32 * 576] elements: f32 in F32-layout, or with want_x3 the F3-32 image, 6 bytes each   (op 4)
+ *   out_snap  i32 [64]: blk_snap [32] and 32 words nobody owns   (op 4 with blk_live)
+ *   out_q     f32 [960][1536] row-major: Q = W' . Wd as launch_compose_f64 rounded it   (op 3)
+ * Out of scope: the fp8 forms (wscale, a8, launch_dec_qkv2_w8), the lm_head (mellow_debug_dec_head), arg-max, compaction, sampling.
+ * Refused by name, nothing launched: op outside 0 .. 4; form outside 0 / 1, or form 1 with op 0, 2 or 4; B < 1 or B > 1024; kcd
+ * not 0 / 8, or with an op other than 0 / 4; op 0 with first != (kcd == 0); inc_pos without first; first / inc_pos with another
+ * op; with first: Tmax < 2 or above cfg.max_positions, pos < 0 or pos + inc_pos >= Tmax, one table without the other; tables
+ * without first; want_x3 with another op or with a vocabulary the streaming lm_head does not tile; blk_live at one row block; eps
+ * not finite or negative; a missing operand of the launch or one the launch does not take (W2, x, h, down, x_img, h_img, ssq); an
+ * image of another byte count; a null output or a capacity too small.  Invalidates the decode state of an earlier prefill. */
+typedef struct mellow_dec_gemv {
+    int32_t size;            /* sizeof(mellow_dec_gemv_t) */
+    int32_t op, form;
+    int32_t B;
+    int32_t kcd, first, inc_pos;
+    int32_t pos, Tmax;       /* op 0 with first */
+    int32_t want_x3;         /* op 4 */
+    float eps;
+} mellow_dec_gemv_t;
+int  mellow_debug_dec_gemv(mellow_engine_t* e, const mellow_dec_gemv_t* d, const float* W, const float* W2, const float* x,
+                           const float* down, const float* h, const void* x_img, int64_t x_img_bytes, const void* h_img,
+                           int64_t h_img_bytes, const float* ssq, const float* rope_cos, const float* rope_sin,
+                           const int32_t* blk_live, float* out_pq, int64_t pq_capacity, float* out_down, int64_t down_capacity,
+                           float* out_ssq1, int64_t ssq1_capacity, float* out_xnew, int64_t xnew_capacity, float* out_rope,
+                           int32_t* out_pos, float* out_gu, int64_t gu_capacity, void* out_h3, int64_t h3_capacity, void* out_xn,
+                           int64_t xn_capacity, int32_t* out_snap, float* out_q, int64_t q_capacity);
 /* The decode step's lm_head kernel on caller-supplied rows (dev): logits[B][vocab] = x[B][hidden] . lm_head^T with the engine's
  * own head weights (the e4m3 copy in MELLOW_PRECISION_FP8; act_fp8 != 0 then also quantises x inside the kernel: one scale per
  * batch row and 72-column slice, fp8 matrix pipe).  Invalidates the decode state of an earlier prefill. */

@@ -270,6 +270,14 @@ __device__ __forceinline__ F3Quad f3_split4(float4 y) {
     return q;
 }
 __device__ __forceinline__ unsigned dpp_xor1(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true); }
+// The quad as it goes to memory, for a producer that stores it as fp32 AND as triples.  __fmul_rn is a plain product to the compiler,
+// and under the default contraction mode split3's `a - float(h)` may be fused with the product that formed a into an fma on the
+// UNROUNDED product: the triple is then the split of a value that can differ from the stored fp32 word by its last bit (seen in
+// dec_gateup3_kernel on the z / w elements).  An empty asm operand is opaque to that fusion and costs no instruction.
+__device__ __forceinline__ float4 as_stored(float4 v) {
+    asm("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w));
+    return v;
+}
 // the neighbour's quad (lane ^ 1).  Both threads of a pair must be active.
 __device__ __forceinline__ F3Quad f3_partner(const F3Quad& q) {
     F3Quad o;
@@ -1508,7 +1516,7 @@ __global__ __launch_bounds__(GU3W * 64) void dec_gateup3_kernel(const float* __r
                 }
                 h[r] = __fmul_rn(siluf_(gv * r2), uv * r2);
             }
-            const float4 hv = make_float4(h[0], h[1], h[2], h[3]);
+            const float4 hv = as_stored(make_float4(h[0], h[1], h[2], h[3]));
             *(reinterpret_cast<float4*>(a.guF) + ((int64_t)rb * 192 + nt) * 64 + m + 32 * q) = hv;
             const F3Quad hq = f3_split4(hv), ho = f3_partner(hq);     // threads (q = 0, q = 1) of a row hold the halves of one slot
             if (q == 0) f3_store8(a.h3, f3_32_slot(rb, 96, m, 8 * nt), hq, ho);

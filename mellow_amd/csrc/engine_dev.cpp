@@ -503,14 +503,14 @@ static int dec_tap_rows(mellow_engine* e, mellow_engine::Buf& b, const float* sr
     if (extra_rows) memset(h.data() + (size_t)n * rows * width, 0xFF, extra_rows * width * 4);
     return gemm_tap_buf(e, b, h.size() * 4, h.data());
 }
-// host rows [n][B][576] -> n F32-layout images of `rows` rows (common.h f32_idx with 72 k-tiles), the slots B .. rows - 1 zero
-static int dec_tap_f32_layout(mellow_engine* e, mellow_engine::Buf& b, const float* src, int n, int B, int rows) {
-    std::vector<float> h((size_t)n * rows * 576, 0.f);
+// host rows [n][B][K] -> n F32-layout images of `rows` rows (common.h f32_idx with K / 8 k-tiles), the slots B .. rows - 1 zero
+static int dec_tap_f32_layout(mellow_engine* e, mellow_engine::Buf& b, const float* src, int n, int B, int rows, int K = 576) {
+    std::vector<float> h((size_t)n * rows * K, 0.f);
     for (int s = 0; s < n; ++s)
         for (int r = 0; r < B; ++r)
-            for (int k = 0; k < 576; k += 4) {
-                const size_t f4 = ((size_t)(r >> 5) * 72 + (k >> 3)) * 64 + (r & 31) + 32 * ((k >> 2) & 1);
-                memcpy(h.data() + (size_t)s * rows * 576 + f4 * 4, src + ((size_t)s * B + r) * 576 + k, 16);
+            for (int k = 0; k < K; k += 4) {
+                const size_t f4 = ((size_t)(r >> 5) * (K / 8) + (k >> 3)) * 64 + (r & 31) + 32 * ((k >> 2) & 1);
+                memcpy(h.data() + (size_t)s * rows * K + f4 * 4, src + ((size_t)s * B + r) * K + k, 16);
             }
     return gemm_tap_buf(e, b, h.size() * 4, h.data());
 }
@@ -645,6 +645,188 @@ int mellow_debug_dec_attn(mellow_engine_t* e, const mellow_dec_attn_t* d, const 
         CHK(gemm_tap_fetch(out_xmid, xmid_capacity, bXmid, xmid_bytes, "xmid"));
         CHK(gemm_tap_fetch(out_x16, x16_capacity, bX16, x16_bytes, "x16"));
         CHK(gemm_tap_fetch(out_ssq, ssq_capacity, bSsq, ssq_bytes, "ssq"));
+    }
+    return 0;
+}
+
+// ---- decode GEMV tap on host data (include/mellow_hip.h): one call of launch_dec_qkv, launch_dec_gateup / launch_dec_gateup3,
+// launch_dec_down, launch_dec_qkv2 / launch_dec_qkv2x3 or launch_dec_final_norm on DecArgs filled from buffers of the call's own;
+// the weights packed by the loader's routines (engine_weights.cpp) ------------------------------------------------------------------
+int mellow_debug_dec_gemv(mellow_engine_t* e, const mellow_dec_gemv_t* d, const float* W, const float* W2, const float* x,
+                          const float* down, const float* h, const void* x_img, int64_t x_img_bytes, const void* h_img,
+                          int64_t h_img_bytes, const float* ssq, const float* rope_cos, const float* rope_sin, const int32_t* blk_live,
+                          float* out_pq, int64_t pq_capacity, float* out_down, int64_t down_capacity, float* out_ssq1,
+                          int64_t ssq1_capacity, float* out_xnew, int64_t xnew_capacity, float* out_rope, int32_t* out_pos,
+                          float* out_gu, int64_t gu_capacity, void* out_h3, int64_t h3_capacity, void* out_xn, int64_t xn_capacity,
+                          int32_t* out_snap, float* out_q, int64_t q_capacity) {
+    if (!e || !d) return fail("null argument");
+    if (d->size != (int32_t)sizeof(mellow_dec_gemv_t)) return fail("size = %d is not sizeof(mellow_dec_gemv_t) = %d", d->size, (int)sizeof(mellow_dec_gemv_t));
+    const int op = d->op, form = d->form, B = d->B, kcd = d->kcd;
+    if (op < 0 || op > 4) return fail("op must be 0 (q/k/v), 1 (gate/up), 2 (down), 3 (fused down + q/k/v) or 4 (final norm): got %d", op);
+    if (form != 0 && form != 1) return fail("form must be 0 (the fp32 kernel) or 1 (the f32x3 kernel): got %d", form);
+    if (form == 1 && op != 1 && op != 3) return fail("op %d has the fp32 form only: the f32x3 forms are launch_dec_gateup3 (op 1) and launch_dec_qkv2x3 (op 3)", op);
+    if (B < 1 || B > 1024) return fail("B = %d: 1 <= B <= 1024", B);
+    const int rows = rup(B, 32), RB = rows / 32;
+    const bool k_op = op == 0 || op == 4;
+    if (k_op && kcd != 0 && kcd != DEC_KC_DOWN) return fail("kcd = %d: the down slabs a launch sums are 0 or DEC_KC_DOWN = %d", kcd, DEC_KC_DOWN);
+    if (!k_op && kcd != 0) return fail("kcd goes with ops 0 and 4 only");
+    const bool first = d->first != 0, inc_pos = d->inc_pos != 0;
+    if ((first || inc_pos) && op != 0) return fail("first / inc_pos go with op 0 only");
+    // the step's first q/k/v launch starts from a materialised x, every later one sums the down slabs (enqueue_decode_layer_range)
+    if (op == 0 && first != (kcd == 0)) return fail("op 0: first = %d with kcd = %d is no launch of a decode step (first goes with kcd 0, kcd %d with first 0)", (int)first, kcd, DEC_KC_DOWN);
+    if (inc_pos && !first) return fail("inc_pos without first: the position word advances in the step's first launch only");
+    if (d->want_x3 && op != 4) return fail("want_x3 goes with op 4 only");
+    if (d->want_x3 && !dec_head3r_fits(e->cfg.vocab_size)) return fail("want_x3: the streaming f32x3 lm_head does not tile vocab_size = %d, the engine never hands xn3 over", e->cfg.vocab_size);
+    if (blk_live && RB < 2) return fail("blk_live exists from two row blocks on (RB = %d)", RB);
+    if (!(d->eps >= 0.f && d->eps < INFINITY)) return fail("eps = %g must be finite and >= 0", d->eps);
+    const int Tmax = first ? d->Tmax : 2, pos = d->pos;
+    if (first) {
+        if (Tmax < 2 || Tmax > e->cfg.max_positions) return fail("Tmax = %d is not a page length of the engine: 2 <= Tmax <= max_positions = %d", Tmax, e->cfg.max_positions);
+        if (pos < 0 || pos + (int)inc_pos >= Tmax) return fail("pos = %d (+ inc_pos) must lie in [0, Tmax = %d)", pos, Tmax);
+        if ((rope_cos == nullptr) != (rope_sin == nullptr)) return fail("rope_cos and rope_sin go together");
+    } else if (rope_cos || rope_sin) return fail("RoPE tables without first: only the step's first q/k/v launch reads them");
+    const size_t n_x = (size_t)rows * 576, n_h = (size_t)rows * 1536;
+    // operands
+    if (!W) return fail("null argument: W");
+    if ((op == 1 || op == 3) && !W2) return fail("null argument: W2 (op 1 the up weight, op 3 the down weight)");
+    if (op != 1 && op != 3 && W2) return fail("W2 goes with ops 1 and 3 only");
+    const bool need_x = op == 0 || op == 4 || (op == 3 && form == 0), need_h = op == 2 || (op == 3 && form == 0);
+    if (need_x != (x != nullptr)) return fail(need_x ? "null argument: x" : "x is not an operand of this launch");
+    if (need_h != (h != nullptr)) return fail(need_h ? "null argument: h" : "h is not an operand of this launch");
+    if ((kcd != 0) != (down != nullptr)) return fail(kcd ? "null argument: down" : "down without kcd");
+    const size_t x_img_need = op == 1 ? (form ? n_x * 6 : n_x * 4) : (op == 3 && form == 1 ? n_x * 6 : 0);
+    const size_t h_img_need = op == 3 && form == 1 ? n_h * 6 : 0;
+    if ((x_img_need != 0) != (x_img != nullptr) || (x_img && x_img_bytes != (int64_t)x_img_need))
+        return fail("x_img: this launch takes %lld bytes there (got %lld)", (long long)x_img_need, x_img ? (long long)x_img_bytes : 0ll);
+    if ((h_img_need != 0) != (h_img != nullptr) || (h_img && h_img_bytes != (int64_t)h_img_need))
+        return fail("h_img: this launch takes %lld bytes there (got %lld)", (long long)h_img_need, h_img ? (long long)h_img_bytes : 0ll);
+    if ((op == 1) != (ssq != nullptr)) return fail(op == 1 ? "null argument: ssq" : "ssq goes with op 1 only");
+    // capacities, before anything is launched
+    const bool w_pq = op == 0 || op == 3, w_down = op == 2 || op == 3, w_x3 = op == 4 && d->want_x3;
+    const size_t pq_bytes = ((size_t)DEC_KC_QKV * rows + 32) * 960 * 4, down_bytes = ((size_t)DEC_KC_DOWN * n_x + 32 * 576) * 4;
+    const size_t ssq1_bytes = (size_t)(rows + 32) * DEC_KC_QKV * 4, xnew_bytes = (size_t)(rows + 32) * 576 * 4;
+    const size_t gu_bytes = (n_h + 32 * 1536) * 4, h3_bytes = (n_h + 32 * 1536) * 6, xn_bytes = (n_x + 32 * 576) * (w_x3 ? 6 : 4);
+    const size_t q_bytes = (size_t)960 * 1536 * 4;
+    auto cap = [&](bool wanted, const void* p, int64_t c, size_t bytes, const char* name) -> int {
+        if (wanted && (!p || c < (int64_t)bytes)) return fail("%s_capacity %lld is below the %lld bytes this call returns (or out_%s is null)", name, (long long)c, (long long)bytes, name);
+        return 0;
+    };
+    CHK(cap(w_pq, out_pq, pq_capacity, pq_bytes, "pq"));
+    CHK(cap(w_down, out_down, down_capacity, down_bytes, "down"));
+    CHK(cap(op == 0, out_ssq1, ssq1_capacity, ssq1_bytes, "ssq1"));
+    CHK(cap(op == 0, out_xnew, xnew_capacity, xnew_bytes, "xnew"));
+    if (op == 0 && (!out_rope || !out_pos)) return fail("null argument: out_rope (128 floats) and out_pos are required with op 0");
+    CHK(cap(op == 1, out_gu, gu_capacity, gu_bytes, "gu"));
+    CHK(cap(op == 1 && form == 1, out_h3, h3_capacity, h3_bytes, "h3"));
+    CHK(cap(op == 4, out_xn, xn_capacity, xn_bytes, "xn"));
+    if (op == 4 && blk_live && !out_snap) return fail("null argument: out_snap (64 words) is required with op 4 and blk_live");
+    CHK(cap(op == 3, out_q, q_capacity, q_bytes, "q"));
+
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    dec_prepare_lds_attributes();
+    e->cur_B = 0;                                     // the decode state of an earlier prefill is gone
+    mellow_engine::Buf bW, bW2, bWp, bWp2, bQ, bCat, bX, bH, bDown, bSsq, bWords, bCos, bSin, bRope, bPq, bSsq1, bXnew, bGu, bH3, bXn;
+    // the device words: position | blk_live [32] (zeros behind RB) | blk_snap [32] + 32 words nobody owns (0xFF bytes)
+    std::vector<int32_t> hw(1 + 32 + 64, -1);
+    hw[0] = pos;
+    for (int i = 0; i < 32; ++i) hw[1 + i] = blk_live && i < RB ? blk_live[i] : 0;
+    CHK(gemm_tap_buf(e, bWords, hw.size() * 4, hw.data()));
+    int32_t* dw = reinterpret_cast<int32_t*>(bWords.p);
+    DecArgs a;
+    a.rows = rows; a.RB = RB; a.Tmax = Tmax; a.eps = d->eps; a.d_pos = dw; a.first = first ? 1 : 0; a.inc_pos = inc_pos ? 1 : 0;
+    a.slabF_stride4 = (int64_t)(n_x / 4);
+    a.blk_live = blk_live ? dw + 1 : nullptr; a.blk_snap = dw + 33;
+    if (need_x) { CHK(dec_tap_f32_layout(e, bX, x, 1, B, rows)); a.xmidF = bX.p; }
+    if (need_h) { CHK(dec_tap_f32_layout(e, bH, h, 1, B, rows, 1536)); a.guF = bH.p; }
+    if (kcd) { CHK(dec_tap_f32_layout(e, bDown, down, DEC_KC_DOWN, B, rows)); a.dslabF = bDown.p; }
+    if (w_pq) { CHK(gemm_tap_buf(e, bPq, pq_bytes, nullptr)); a.pq = bPq.p; }
+    if (w_down) { CHK(gemm_tap_buf(e, bDown, down_bytes, nullptr)); a.dslabF = bDown.p; }
+    if (op == 0) {
+        CHK(gemm_tap_buf(e, bW, (size_t)960 * 576 * 4, W));
+        CHK(ensure(e, bWp, (size_t)1024 * 576));
+        launch_pack_weight(bW.p, 960, 576, 576, bWp.p, 1024, 576, s);
+        CHK(gemm_tap_buf(e, bSsq1, ssq1_bytes, nullptr));
+        CHK(gemm_tap_buf(e, bXnew, xnew_bytes, nullptr));
+        CHK(gemm_tap_buf(e, bRope, 128 * 4, nullptr));
+        a.ssq1 = bSsq1.p; a.xnewR = bXnew.p; a.rope_cur = bRope.p;
+        if (first) {
+            std::vector<float> hc, hs;
+            if (!rope_cos) {
+                hc.resize((size_t)Tmax * 32); hs.resize((size_t)Tmax * 32);
+                CHK(mellow_host_rope_tables(e->cfg.rope_theta, 64, Tmax, hc.data(), hs.data()));
+            }
+            CHK(gemm_tap_buf(e, bCos, (size_t)Tmax * 32 * 4, rope_cos ? rope_cos : hc.data()));
+            CHK(gemm_tap_buf(e, bSin, (size_t)Tmax * 32 * 4, rope_sin ? rope_sin : hs.data()));
+            a.rope_cos = bCos.p; a.rope_sin = bSin.p;
+        }
+        launch_dec_qkv(a, bWp.p, 72, kcd, s);
+    } else if (op == 1) {
+        std::vector<float> il;
+        interleave_gate_up8(W, W2, 1536, 576, il);
+        CHK(gemm_tap_buf(e, bW, il.size() * 4, il.data()));
+        CHK(ensure(e, bWp, il.size()));
+        if (form) launch_pack_weight16n(bW.p, 3072, 576, bWp.p, s);
+        else launch_pack_weight16(bW.p, 3072, 576, bWp.p, s);
+        CHK(gemm_tap_buf(e, bX, x_img_need, x_img));
+        CHK(gemm_tap_buf(e, bSsq, (size_t)rows * 40 * 4, ssq));
+        CHK(gemm_tap_buf(e, bGu, gu_bytes, nullptr));
+        a.ssq = bSsq.p; a.guF = bGu.p;
+        if (form) {
+            CHK(gemm_tap_buf(e, bH3, h3_bytes, nullptr));
+            a.xmid3_16 = bX.p; a.h3 = bH3.p;
+            launch_dec_gateup3(a, bWp.p, s);
+        } else {
+            a.xmidF16 = bX.p;
+            launch_dec_gateup(a, bWp.p, s);
+        }
+    } else if (op == 2) {
+        CHK(gemm_tap_buf(e, bW, (size_t)576 * 1536 * 4, W));
+        CHK(ensure(e, bWp, (size_t)640 * 1536));
+        launch_pack_weight(bW.p, 576, 1536, 1536, bWp.p, 640, 1536, s);
+        launch_dec_down(a, bWp.p, 192, s);
+    } else if (op == 3) {
+        CHK(gemm_tap_buf(e, bW, (size_t)960 * 576 * 4, W));
+        CHK(gemm_tap_buf(e, bW2, (size_t)576 * 1536 * 4, W2));
+        CHK(ensure(e, bQ, (size_t)960 * 1536));
+        CHK(ensure(e, bCat, (size_t)1024 * 2112));
+        CHK(ensure(e, bWp, (size_t)1024 * 2112));
+        CHK(ensure(e, bWp2, (size_t)640 * 1536));
+        launch_compose_f64(bW.p, bW2.p, bQ.p, 960, 1536, 576, s);
+        CHK(pack_qkv2_cat(e, bW.p, bQ.p, bCat.p, bWp.p));
+        launch_pack_weight(bW2.p, 576, 1536, 1536, bWp2.p, 640, 1536, s);
+        if (form) {
+            CHK(gemm_tap_buf(e, bX, x_img_need, x_img));
+            CHK(gemm_tap_buf(e, bH, h_img_need, h_img));
+            a.xmid3_32 = bX.p; a.h3 = bH.p;
+            launch_dec_qkv2x3(a, bWp.p, bWp2.p, s);
+        } else {
+            launch_dec_qkv2(a, bWp.p, bWp2.p, s);
+        }
+    } else {
+        CHK(gemm_tap_buf(e, bW, (size_t)576 * 4, W));
+        CHK(gemm_tap_buf(e, bXn, xn_bytes, nullptr));
+        if (w_x3) a.xn3 = bXn.p; else a.xnF = bXn.p;
+        launch_dec_final_norm(a, bW.p, kcd, s);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    if (w_pq) CHK(gemm_tap_fetch(out_pq, pq_capacity, bPq, pq_bytes, "pq"));
+    if (w_down) CHK(gemm_tap_fetch(out_down, down_capacity, bDown, down_bytes, "down"));
+    if (op == 0) {
+        CHK(gemm_tap_fetch(out_ssq1, ssq1_capacity, bSsq1, ssq1_bytes, "ssq1"));
+        CHK(gemm_tap_fetch(out_xnew, xnew_capacity, bXnew, xnew_bytes, "xnew"));
+        HIPCHK(hipMemcpy(out_rope, bRope.p, 128 * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(out_pos, dw, 4, hipMemcpyDeviceToHost));
+    }
+    if (op == 1) {
+        CHK(gemm_tap_fetch(out_gu, gu_capacity, bGu, gu_bytes, "gu"));
+        if (form) CHK(gemm_tap_fetch(out_h3, h3_capacity, bH3, h3_bytes, "h3"));
+    }
+    if (op == 3) CHK(gemm_tap_fetch(out_q, q_capacity, bQ, q_bytes, "q"));
+    if (op == 4) {
+        CHK(gemm_tap_fetch(out_xn, xn_capacity, bXn, xn_bytes, "xn"));
+        if (out_snap) HIPCHK(hipMemcpy(out_snap, dw + 33, 64 * 4, hipMemcpyDeviceToHost));
     }
     return 0;
 }

@@ -394,6 +394,11 @@ static_assert(std::is_copy_assignable<mellow_engine::Weights>::value && std::is_
 int ensure(mellow_engine* e, mellow_engine::Buf& b, size_t floats);
 int dev_alloc(mellow_engine* e, float** out, size_t floats);
 int upload(mellow_engine* e, float** out, const float* src, size_t floats, size_t alloc_floats = 0);
+// engine_weights.cpp: two packing steps of the decode weights that the loader and the tap mellow_debug_dec_gemv share.
+// il [2 I][H]: 16-row tile t = gate[8t .. 8t + 7] then up[8t .. 8t + 7] (the source of launch_pack_weight16 / 16n)
+void interleave_gate_up8(const float* g, const float* u, int I, int H, std::vector<float>& il);
+// device: cat [960][2112] = [F (960 x 576) | Q (960 x 1536)] row-major, then its P-layout [1024][2112] into out; enqueues only
+int pack_qkv2_cat(mellow_engine* e, const float* dF, const float* dQ, float* dCat, float* out);
 hipEvent_t next_event(mellow_engine* e);
 int tap(mellow_engine* e, const char* name, const float* src, int64_t n);
 std::vector<std::string> build_required(const mellow_config_t* cfg);

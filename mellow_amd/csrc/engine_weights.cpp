@@ -112,6 +112,20 @@ static int make_packed16(mellow_engine* e, const float* w, int N, int K, float**
     HIPCHK(hipStreamSynchronize(e->stream));
     return 0;
 }
+void interleave_gate_up8(const float* g, const float* u, int I, int H, std::vector<float>& il) {
+    il.resize((size_t)2 * I * H);
+    for (int t = 0; t < I / 8; ++t) {
+        memcpy(il.data() + (size_t)(2 * t) * 8 * H, g + (size_t)t * 8 * H, (size_t)8 * H * 4);
+        memcpy(il.data() + (size_t)(2 * t + 1) * 8 * H, u + (size_t)t * 8 * H, (size_t)8 * H * 4);
+    }
+}
+int pack_qkv2_cat(mellow_engine* e, const float* dF, const float* dQ, float* dCat, float* out) {
+    HIPCHK(hipMemcpy2DAsync(dCat, (size_t)2112 * 4, dF, (size_t)576 * 4, (size_t)576 * 4, 960, hipMemcpyDeviceToDevice, e->stream));
+    HIPCHK(hipMemcpy2DAsync(dCat + 576, (size_t)2112 * 4, dQ, (size_t)1536 * 4, (size_t)1536 * 4, 960, hipMemcpyDeviceToDevice, e->stream));
+    launch_pack_weight(dCat, 960, 2112, 2112, out, 1024, 2112, e->stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 static int pack_key(mellow_engine* e, const std::string& k, int N, int K, Packed* out) {
     const HostTensor* t = get(e, k);
     CHK(expect_shape(t, k, {N, K}));
@@ -342,11 +356,8 @@ extern "C" int mellow_engine_finalize(mellow_engine_t* e) {
                     HIPCHK(hipGetLastError());
                     CHK(make_dec_fp8(e, cmpCat.p, 32, (1536 / 8) * 64, 32, &w.q2h8, &w.q2h_sc));
                 } else {
-                    HIPCHK(hipMemcpy2DAsync(cmpCat.p, (size_t)2112 * 4, cmpF.p, (size_t)576 * 4, (size_t)576 * 4, 960, hipMemcpyDeviceToDevice, e->stream));
-                    HIPCHK(hipMemcpy2DAsync(cmpCat.p + 576, (size_t)2112 * 4, cmpQ.p, (size_t)1536 * 4, (size_t)1536 * 4, 960, hipMemcpyDeviceToDevice, e->stream));
                     CHK(dev_alloc(e, &w.qkv2, (size_t)1024 * 2112));
-                    launch_pack_weight(cmpCat.p, 960, 2112, 2112, w.qkv2, 1024, 2112, e->stream);
-                    HIPCHK(hipGetLastError());
+                    CHK(pack_qkv2_cat(e, cmpF.p, cmpQ.p, cmpCat.p, w.qkv2));
                     HIPCHK(hipStreamSynchronize(e->stream));
                 }
             }
@@ -366,11 +377,8 @@ extern "C" int mellow_engine_finalize(mellow_engine_t* e) {
             {
                 // 16-row tile t = gate[8t..8t+7] then up[8t..8t+7]: one workgroup of the decode gate/up kernel owns both
                 // halves of 8 hidden units and applies the SwiGLU in its epilogue
-                std::vector<float> il((size_t)2 * I * H);
-                for (int t = 0; t < I / 8; ++t) {
-                    memcpy(il.data() + (size_t)(2 * t) * 8 * H, gf.data() + (size_t)t * 8 * H, (size_t)8 * H * 4);
-                    memcpy(il.data() + (size_t)(2 * t + 1) * 8 * H, uf.data() + (size_t)t * 8 * H, (size_t)8 * H * 4);
-                }
+                std::vector<float> il;
+                interleave_gate_up8(gf.data(), uf.data(), I, H, il);
                 CHK(make_packed16(e, il.data(), 2 * I, H, &w.gu16));
                 if (e->opt.f32x3_terms && fuse && !e->opt.fp8_decode) CHK(make_packed16(e, il.data(), 2 * I, H, &w.gu16n, true));    // f32x3 layer kernels (row blocks >= dec_x3_min_rb)
             }

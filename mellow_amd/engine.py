@@ -58,6 +58,11 @@ class DecAttn(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("size", "B", "P", "pos", "Tmax", "ctx_end", "ts", "fused", "kv16", "want_x3")] + [("eps", C.c_float)]
 
 
+class DecGemv(C.Structure):
+    """mellow_dec_gemv_t (include/mellow_hip.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("size", "op", "form", "B", "kcd", "first", "inc_pos", "pos", "Tmax", "want_x3")] + [("eps", C.c_float)]
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -70,7 +75,7 @@ _ADDED_UNDER_MINOR_4 = ("mellow_lm_score", "mellow_score", "mellow_generate_scor
 _ADDED_UNDER_MINOR_5 = ("mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_generate_rules", "mellow_logit_rules_apply",
                         "mellow_generate_guidance", "mellow_guidance_apply", "mellow_generate_top_logprobs", "mellow_top_logprobs_apply",
                         "mellow_debug_gemm_epi", "mellow_generate_filters", "mellow_sample_logits_filtered", "mellow_debug_norm",
-                        "mellow_debug_dec_attn")
+                        "mellow_debug_dec_attn", "mellow_debug_dec_gemv")
 
 
 def load_library(path: Optional[str] = None):
@@ -136,6 +141,8 @@ def load_library(path: Optional[str] = None):
         "mellow_debug_norm": (ci, [vp, ci, ci, vp, ci, ci, vp, vp, cf, vp, ci, ci, ci, vp, i64, vp, i64]),
         "mellow_debug_dec_attn": (ci, [vp, P(DecAttn), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, i64,
                                        vp, i64, vp, i64]),
+        "mellow_debug_dec_gemv": (ci, [vp, P(DecGemv), vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp,
+                                       vp, vp, i64, vp, i64, vp, i64, vp, vp, i64]),
         "mellow_debug_prefill_attn": (ci, [vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp, i64]),
         "mellow_debug_window_attn": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, i64]),
         "mellow_debug_dec_head": (ci, [vp, vp, ci, ci, vp]),
@@ -180,7 +187,7 @@ EXPORTED_SYMBOLS = (
     "mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse", "mellow_generate_n", "mellow_generate_q",
     "mellow_generate_beam", "mellow_beam_select", "mellow_generate_rules", "mellow_logit_rules_apply", "mellow_generate_guidance", "mellow_guidance_apply", "mellow_generate_top_logprobs", "mellow_top_logprobs_apply", "mellow_generate_filters", "mellow_sample_logits_filtered", "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
     "mellow_prof_num_families", "mellow_prof_family_name", "mellow_prof_get", "mellow_last_phase_ms", "mellow_last_steps_enqueued", "mellow_last_row_repacks", "mellow_stft_is_fft", "mellow_prefill_parts", "mellow_abi_minor",
-    "mellow_resample", "mellow_engine_set_precision", "mellow_engine_set_option", "mellow_engine_describe", "mellow_debug_gemm_fp8", "mellow_debug_gemm_f32", "mellow_debug_gemm_epi", "mellow_debug_norm", "mellow_debug_dec_attn", "mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_debug_dec_head", "mellow_set_graph", "mellow_host_window_map", "mellow_host_pack_weight", "mellow_host_rope_tables",
+    "mellow_resample", "mellow_engine_set_precision", "mellow_engine_set_option", "mellow_engine_describe", "mellow_debug_gemm_fp8", "mellow_debug_gemm_f32", "mellow_debug_gemm_epi", "mellow_debug_norm", "mellow_debug_dec_attn", "mellow_debug_dec_gemv", "mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_debug_dec_head", "mellow_set_graph", "mellow_host_window_map", "mellow_host_pack_weight", "mellow_host_rope_tables",
 )
 
 
@@ -1284,6 +1291,66 @@ class Engine:
                                                  p(out["xnew"]), nb("xnew"), p(out.get("xmid")), nb("xmid"), p(out.get("x16")), nb("x16"),
                                                  p(out.get("ssq")), nb("ssq")))
         out["gs"] = int(gs.value)
+        return out
+
+    def debug_dec_gemv(self, op: int, B: int, W, W2=None, form: int = 0, x=None, down=None, h=None, x_img=None, h_img=None, ssq=None,
+                       kcd: int = 0, first: bool = False, inc_pos: bool = False, pos: int = 0, Tmax: int = 0, rope_cos=None, rope_sin=None,
+                       blk_live=None, want_x3: bool = False, eps: float = 1e-5) -> dict:
+        """One launch of a decode layer's q/k/v (op 0), gate/up (1), down (2), fused down + q/k/v (3) launcher or of the final norm (4)
+        on host tensors (mellow_debug_dec_gemv; form 1 = the f32x3 kernel of ops 1 and 3).  Weights logical row-major: op 0 W = W'
+        [960][576]; op 1 W / W2 = gate / up [1536][576]; op 2 W = Wd [576][1536]; op 3 W = W', W2 = Wd; op 4 W = the norm vector.  x
+        [B][576], down [8][B][576] (kcd 8), h [B][1536] row-major; x_img / h_img / ssq raw images of all rows (int16 words for the
+        F3 triples).  -> dict of the whole device outputs, which held 0xFF bytes before the launch: "pq" f32 [8 * rows + 32][960],
+        "down" f32 [8 * rows * 576 + 32 * 576] (F32-layout slabs), "ssq1" [rows + 32][8], "xnew" [rows + 32][576], "rope" [128], "pos",
+        "gu" f32 [(rows + 32) * 1536] (F32-layout, 192 k-tiles), "h3" int16 [(rows + 32) * 1536 * 3], "xn" f32 [(rows + 32) * 576] or
+        with want_x3 int16 [(rows + 32) * 576 * 3], "snap" int32 [64], "q" f32 [960][1536] -- those the op writes."""
+        self._need("mellow_debug_dec_gemv")
+        f32 = lambda t: None if t is None else torch.as_tensor(t).detach().cpu().contiguous().float()       # noqa: E731
+        raw = lambda t: None if t is None else torch.as_tensor(t).detach().cpu().contiguous()       # noqa: E731
+        W, W2, x, down, h, ssq, rope_cos, rope_sin = (f32(t) for t in (W, W2, x, down, h, ssq, rope_cos, rope_sin))
+        x_img, h_img = raw(x_img), raw(h_img)
+        blk_live = None if blk_live is None else torch.as_tensor(blk_live).detach().cpu().contiguous().to(torch.int32)
+        op, form, B = int(op), int(form), int(B)
+        rows = (max(B, 1) + 31) // 32 * 32
+        wshape = {0: ((960, 576), None), 1: ((1536, 576), (1536, 576)), 2: ((576, 1536), None), 3: ((960, 576), (576, 1536)), 4: ((576,), None)}
+        for name, t, shape in (("W", W, wshape.get(op, (None, None))[0]), ("W2", W2, wshape.get(op, (None, None))[1]), ("x", x, (B, 576)),
+                               ("down", down, (8, B, 576)), ("h", h, (B, 1536)), ("ssq", ssq, (rows, 40)), ("rope_cos", rope_cos, (int(Tmax), 32)),
+                               ("rope_sin", rope_sin, (int(Tmax), 32)), ("blk_live", blk_live, (rows // 32,))):
+            if t is not None and shape is not None and tuple(t.shape) != shape:
+                raise ValueError(f"{name} {tuple(t.shape)} is not {shape}")
+        d = DecGemv()
+        d.size, d.op, d.form, d.B, d.kcd, d.first, d.inc_pos = C.sizeof(DecGemv), op, form, B, int(kcd), int(bool(first)), int(bool(inc_pos))
+        d.pos, d.Tmax, d.want_x3, d.eps = int(pos), int(Tmax), int(bool(want_x3)), float(eps)
+        n_x, n_h = (rows + 32) * 576, (rows + 32) * 1536
+        out = {}
+        if op in (0, 3):
+            out["pq"] = torch.empty((8 * rows + 32, 960), dtype=torch.float32)
+        if op in (2, 3):
+            out["down"] = torch.empty((8 * rows * 576 + 32 * 576,), dtype=torch.float32)
+        if op == 0:
+            out["ssq1"] = torch.empty((rows + 32, 8), dtype=torch.float32)
+            out["xnew"] = torch.empty((rows + 32, 576), dtype=torch.float32)
+            out["rope"] = torch.empty((128,), dtype=torch.float32)
+            out["pos"] = torch.empty((1,), dtype=torch.int32)
+        if op == 1:
+            out["gu"] = torch.empty((n_h,), dtype=torch.float32)
+            if form:
+                out["h3"] = torch.empty((n_h * 3,), dtype=torch.int16)
+        if op == 3:
+            out["q"] = torch.empty((960, 1536), dtype=torch.float32)
+        if op == 4:
+            out["xn"] = torch.empty((n_x * 3,), dtype=torch.int16) if want_x3 else torch.empty((n_x,), dtype=torch.float32)
+            if blk_live is not None:
+                out["snap"] = torch.empty((64,), dtype=torch.int32)
+        p = lambda t: None if t is None else _ptr(t)      # noqa: E731
+        nbt = lambda t: 0 if t is None else t.numel() * t.element_size()      # noqa: E731
+        o, nb = (lambda k: p(out.get(k))), (lambda k: nbt(out.get(k)))      # noqa: E731
+        self._chk(self.lib.mellow_debug_dec_gemv(self.h, C.byref(d), p(W), p(W2), p(x), p(down), p(h), p(x_img), nbt(x_img), p(h_img), nbt(h_img),
+                                                 p(ssq), p(rope_cos), p(rope_sin), p(blk_live), o("pq"), nb("pq"), o("down"), nb("down"),
+                                                 o("ssq1"), nb("ssq1"), o("xnew"), nb("xnew"), o("rope"), o("pos"), o("gu"), nb("gu"),
+                                                 o("h3"), nb("h3"), o("xn"), nb("xn"), o("snap"), o("q"), nb("q")))
+        if "pos" in out:
+            out["pos"] = int(out["pos"][0])
         return out
 
     @staticmethod
