@@ -63,7 +63,7 @@ extern "C" {
  *     changed; a binding that must also load a minor-4 library detects them by symbol lookup.  The GEMM epilogue tap
  *     mellow_debug_gemm_epi was added later under this same minor, detected by symbol lookup all the same, and so was the norm /
  *     hand-over tap mellow_debug_norm, and then the decode attention tap mellow_debug_dec_attn, and then the decode GEMV tap
- *     mellow_debug_dec_gemv. */
+ *     mellow_debug_dec_gemv, and then the decode step-tail tap mellow_debug_dec_tail. */
 #define MELLOW_ABI_MINOR 5
 
 typedef struct mellow_engine mellow_engine_t;
@@ -721,7 +721,7 @@ int  mellow_debug_dec_attn(mellow_engine_t* e, const mellow_dec_attn_t* d, const
  *   out_xn    [rows * 576 + 32 * 576] elements: f32 in F32-layout, or with want_x3 the F3-32 image, 6 bytes each   (op 4)
  *   out_snap  i32 [64]: blk_snap [32] and 32 words nobody owns   (op 4 with blk_live)
  *   out_q     f32 [960][1536] row-major: Q = W' . Wd as launch_compose_f64 rounded it   (op 3)
- * Out of scope: the fp8 forms (wscale, a8, launch_dec_qkv2_w8), the lm_head (mellow_debug_dec_head), arg-max, compaction, sampling.
+ * Out of scope: the fp8 forms (wscale, a8, launch_dec_qkv2_w8); the lm_head, arg-max, compaction and row load have mellow_debug_dec_tail.
  * Refused by name, nothing launched: op outside 0 .. 4; form outside 0 / 1, or form 1 with op 0, 2 or 4; B < 1 or B > 1024; kcd
  * not 0 / 8, or with an op other than 0 / 4; op 0 with first != (kcd == 0); inc_pos without first; first / inc_pos with another
  * op; with first: Tmax < 2 or above cfg.max_positions, pos < 0 or pos + inc_pos >= Tmax, one table without the other; tables
@@ -744,6 +744,63 @@ int  mellow_debug_dec_gemv(mellow_engine_t* e, const mellow_dec_gemv_t* d, const
                            float* out_ssq1, int64_t ssq1_capacity, float* out_xnew, int64_t xnew_capacity, float* out_rope,
                            int32_t* out_pos, float* out_gu, int64_t gu_capacity, void* out_h3, int64_t h3_capacity, void* out_xn,
                            int64_t xn_capacity, int32_t* out_snap, float* out_q, int64_t q_capacity);
+/* Decode step-tail tap on HOST data (works on any engine, finalised or not): ONE call of ONE of the launchers that end a decode
+ * step -- the launchers the step itself calls, on DecArgs and LoopArgs the tap fills from buffers of its own.  rows = roundup(B, 32),
+ * RB = rows / 32.
+ *   op 0  launch_dec_lm_head:   form 0 the fp32 kernel (x host f32 [B][576], sent in F32-layout; the slots B .. rows - 1 run on
+ *                               zeros), form 1 the streaming f32x3 kernel (x_img = the raw F3-32 image of all `rows` rows, 36 pairs,
+ *                               rows * 576 * 6 bytes; DecArgs::x3 = DEC_X3_HEAD).  W = the logical head weight [V][576], packed on the
+ *                               device as the loader packs lm_head (launch_pack_weight into roundup(V, 128) rows, K8p = 72).
+ *                               want_logits: DecArgs::logits set or null; want_sum: DecArgs::cand_sum set or null; blk_live host i32
+ *                               [RB] or NULL (RB >= 2 only): a block with blk_live 0 stores nothing.
+ *   op 1  launch_dec_argmax on planted partials: cand_val f32 / cand_idx i32 / cand_sum f32 (or NULL) [B][V / 32]; write_x: gather
+ *                               row `token` of W = the embedding table [V][576] (the model ties it to the head) into the F32-layout
+ *                               row of the slot.  with_state 0: LoopArgs() -- the token only.  with_state 1: params {max_len,
+ *                               stop_id}, T0 and the position word `pos`, seen_stop i32 [rows], n_seen / arrive / ticket, blk_left +
+ *                               blk_live i32 [RB] (together, or both NULL), blk_snap i32 [RB] or NULL, row_of_slot i32 [rows] or
+ *                               NULL, with_logprob (LoopArgs::out_logprob; needs cand_sum); host_progress is a mapped host word of
+ *                               the call's own.
+ *   op 2  launch_dec_compact:   row_of_slot [rows], blk_live / blk_left [RB], seen_stop [rows], x host f32 [B][576] (sent in
+ *                               F32-layout), n_compactions
+ *   op 3  launch_dec_load_rows: x = the source rows host f32 [n_src][ld]; row_ids i32 [B] with T_last 0 (the kernel clamps an id
+ *                               to [0, n_src)), or NULL with T_last >= 1 (row b * T_last + T_last - 1)
+ * Every output the launch can write is filled with 0xFF bytes first and returned whole and raw (capacities in bytes):
+ *   out_logits    f32 [rows + 32][V]; out_cand_val f32 / out_cand_idx i32 / out_cand_sum f32 [rows + 32][V / 32] each   (op 0)
+ *   out_tokens    i32 [rows + 32]   (op 1)
+ *   out_record    i32 [rows][max_len], out_logprob f32 of the same shape (with_logprob), out_progress the host word   (op 1, with_state)
+ *   out_state     i32 words: seen_stop [rows + 32] | n_seen, arrive, ticket, n_compactions and 28 words nobody owns | blk_left [64] |
+ *                 blk_live [64] (the words RB .. 31 are sent as zeros, as the engine's are; 32 .. 63 nobody owns) | row_of_slot
+ *                 [rows + 32]; what the caller did not plant holds 0xFF bytes   (op 1 with_state, op 2)
+ *   out_x         f32 [rows * 576 + 32 * 576]: the residual rows in F32-layout   (ops 1, 2, 3)
+ * Out of scope: the fp8 forms (wscale, a8) have no argument here.
+ * Refused by name, nothing launched: op outside 0 .. 3; form outside 0 / 1, or form 1 with another op; B < 1 or B > 1024; V not a
+ * multiple of 32 in [32, 2^20], (rows + 32) * V above 2^28, or (form 1) a V the streaming kernel does not tile; a switch or scalar
+ * of another op that is not 0; blk_live / blk_left / blk_snap / row_of_slot at one row block; blk_live without blk_left or the
+ * reverse (op 1); with_logprob without cand_sum or without with_state; row_of_slot entries outside -1 .. rows - 1 or taken twice;
+ * max_len outside 1 .. 4096, T0 outside 0 .. 2^20, |pos| above 2^20; ld below 576 or no multiple of 4, n_src < 1 or n_src * ld above
+ * 2^26, T_last != 0 with row_ids, T_last < 1 or B * T_last > n_src without; a missing operand of the launch or one the launch does
+ * not take; an image of another byte count; a null output or a capacity too small.  Invalidates the decode state of an earlier
+ * prefill. */
+typedef struct mellow_dec_tail {
+    int32_t size;            /* sizeof(mellow_dec_tail_t) */
+    int32_t op, form;
+    int32_t B;
+    int32_t V;               /* ops 0 and 1: the vocabulary (n = V / 32 tiles) */
+    int32_t want_logits, want_sum;               /* op 0 */
+    int32_t write_x, with_state, with_logprob;   /* op 1 */
+    int32_t max_len, stop_id, T0, pos;           /* op 1 with with_state */
+    int32_t n_seen, arrive, ticket;              /* op 1 with with_state */
+    int32_t n_compactions;   /* op 2 */
+    int32_t ld, n_src, T_last;                   /* op 3 */
+} mellow_dec_tail_t;
+int  mellow_debug_dec_tail(mellow_engine_t* e, const mellow_dec_tail_t* d, const float* W, const float* x, const void* x_img,
+                           int64_t x_img_bytes, const int32_t* blk_live, const float* cand_val, const int32_t* cand_idx,
+                           const float* cand_sum, const int32_t* seen_stop, const int32_t* blk_left, const int32_t* blk_snap,
+                           const int32_t* row_of_slot, const int32_t* row_ids, float* out_logits, int64_t logits_capacity,
+                           float* out_cand_val, int32_t* out_cand_idx, float* out_cand_sum, int64_t cand_capacity,
+                           int32_t* out_tokens, int64_t tokens_capacity, int32_t* out_record, float* out_logprob,
+                           int64_t record_capacity, int32_t* out_state, int64_t state_capacity, uint64_t* out_progress, float* out_x,
+                           int64_t x_capacity);
 /* The decode step's lm_head kernel on caller-supplied rows (dev): logits[B][vocab] = x[B][hidden] . lm_head^T with the engine's
  * own head weights (the e4m3 copy in MELLOW_PRECISION_FP8; act_fp8 != 0 then also quantises x inside the kernel: one scale per
  * batch row and 72-column slice, fp8 matrix pipe).  Invalidates the decode state of an earlier prefill. */

@@ -1,6 +1,8 @@
 // Developer entry points (not used by the product path): GEMM timing and debug taps, profiler dump, kernel stamps.
 #include "engine_internal.h"
 
+#include <memory>
+
 extern "C" {
 
 // developer instrumentation (not part of the public header): time `iters` launches of one plain GEMM shape on
@@ -828,6 +830,230 @@ int mellow_debug_dec_gemv(mellow_engine_t* e, const mellow_dec_gemv_t* d, const 
         CHK(gemm_tap_fetch(out_xn, xn_capacity, bXn, xn_bytes, "xn"));
         if (out_snap) HIPCHK(hipMemcpy(out_snap, dw + 33, 64 * 4, hipMemcpyDeviceToHost));
     }
+    return 0;
+}
+
+// ---- decode step-tail tap on host data (include/mellow_hip.h): one call of launch_dec_lm_head, launch_dec_argmax, launch_dec_compact
+// or launch_dec_load_rows on DecArgs / LoopArgs filled from buffers of the call's own; the head weight packed as the loader packs
+// lm_head (engine_weights.cpp: launch_pack_weight into roundup(V, 128) rows) ------------------------------------------------------------
+namespace {
+// the int32 words a launch can rewrite, as the tap returns them (out_state): seen_stop [rows + 32] | n_seen, arrive, ticket,
+// n_compactions + 28 words nobody owns | blk_left [64] | blk_live [64] | row_of_slot [rows + 32]; behind them, on the device only,
+// what the launch reads: params {max_len, stop_id}, the position word + 29 words | blk_snap [32]
+struct TailWords {
+    int rows;
+    int seen() const { return 0; }
+    int scalars() const { return rows + 32; }
+    int left() const { return scalars() + 32; }
+    int live() const { return left() + 64; }
+    int slot() const { return live() + 64; }
+    int state_words() const { return slot() + rows + 32; }
+    int params() const { return state_words(); }
+    int pos() const { return params() + 2; }
+    int snap() const { return params() + 32; }
+    int total() const { return snap() + 32; }
+};
+}  // namespace
+
+int mellow_debug_dec_tail(mellow_engine_t* e, const mellow_dec_tail_t* d, const float* W, const float* x, const void* x_img,
+                          int64_t x_img_bytes, const int32_t* blk_live, const float* cand_val, const int32_t* cand_idx,
+                          const float* cand_sum, const int32_t* seen_stop, const int32_t* blk_left, const int32_t* blk_snap,
+                          const int32_t* row_of_slot, const int32_t* row_ids, float* out_logits, int64_t logits_capacity,
+                          float* out_cand_val, int32_t* out_cand_idx, float* out_cand_sum, int64_t cand_capacity, int32_t* out_tokens,
+                          int64_t tokens_capacity, int32_t* out_record, float* out_logprob, int64_t record_capacity, int32_t* out_state,
+                          int64_t state_capacity, uint64_t* out_progress, float* out_x, int64_t x_capacity) {
+    if (!e || !d) return fail("null argument");
+    if (d->size != (int32_t)sizeof(mellow_dec_tail_t)) return fail("size = %d is not sizeof(mellow_dec_tail_t) = %d", d->size, (int)sizeof(mellow_dec_tail_t));
+    const int op = d->op, form = d->form, B = d->B, V = d->V;
+    if (op < 0 || op > 3) return fail("op must be 0 (lm_head), 1 (arg-max), 2 (row repack) or 3 (row load): got %d", op);
+    if (form != 0 && form != 1) return fail("form must be 0 (the fp32 kernel) or 1 (the streaming f32x3 kernel): got %d", form);
+    if (form == 1 && op != 0) return fail("op %d has one form only: form 1 is the streaming f32x3 lm_head (op 0)", op);
+    if (B < 1 || B > 1024) return fail("B = %d: 1 <= B <= 1024", B);
+    const int rows = rup(B, 32), RB = rows / 32;
+    const bool head = op == 0, amax = op == 1, pack = op == 2, load = op == 3;
+    const bool state = amax && d->with_state != 0, lp_on = amax && d->with_logprob != 0, write_x = amax && d->write_x != 0;
+    // switches of another op
+    if (!head && (d->want_logits || d->want_sum)) return fail("want_logits / want_sum go with op 0 only");
+    if (!amax && (d->write_x || d->with_state || d->with_logprob)) return fail("write_x / with_state / with_logprob go with op 1 only");
+    if (!state && (d->max_len || d->stop_id || d->T0 || d->pos || d->n_seen || d->arrive || d->ticket))
+        return fail("max_len, stop_id, T0, pos, n_seen, arrive and ticket go with op 1 and with_state only");
+    if (!pack && d->n_compactions) return fail("n_compactions goes with op 2 only");
+    if (!load && (d->ld || d->n_src || d->T_last)) return fail("ld, n_src and T_last go with op 3 only");
+    if (!(head || amax) && V) return fail("V goes with ops 0 and 1 only");
+    if (head || amax) {
+        if (V < 32 || V % 32 != 0 || V > (1 << 20)) return fail("V = %d: the head and the arg-max tile the vocabulary in 32 columns (32 <= V <= 2^20, V %% 32 == 0)", V);
+        if ((int64_t)(rows + 32) * V > ((int64_t)1 << 28)) return fail("(rows + 32) * V = %lld elements exceed the tap's 2^28", (long long)(rows + 32) * V);
+    }
+    if (head && form == 1 && !dec_head3r_fits(V)) return fail("V = %d: the streaming f32x3 lm_head does not tile it (dec_head3r_fits)", V);
+    const int n = V / 32;
+    // operands
+    auto want = [&](bool needed, const void* p, const char* name) -> int {
+        if (needed && !p) return fail("null argument: %s", name);
+        if (!needed && p) return fail("%s is not an operand of this launch", name);
+        return 0;
+    };
+    CHK(want(head || write_x, W, "W"));
+    CHK(want((head && form == 0) || pack || load, x, "x"));
+    const size_t x_img_need = head && form == 1 ? (size_t)rows * 576 * 6 : 0;
+    if ((x_img_need != 0) != (x_img != nullptr) || (x_img && x_img_bytes != (int64_t)x_img_need))
+        return fail("x_img: this launch takes %lld bytes there (got %lld)", (long long)x_img_need, x_img ? (long long)x_img_bytes : 0ll);
+    CHK(want(amax, cand_val, "cand_val"));
+    CHK(want(amax, cand_idx, "cand_idx"));
+    if (cand_sum && !amax) return fail("cand_sum is not an operand of this launch");
+    if (lp_on && !cand_sum) return fail("with_logprob without cand_sum: the log-prob is merged from the head's partial sums");
+    if (lp_on && !state) return fail("with_logprob without with_state: the log-prob is written where the token record is");
+    CHK(want(state || pack, seen_stop, "seen_stop"));
+    if (pack && !row_of_slot) return fail("null argument: row_of_slot");
+    if (!(state || pack) && row_of_slot) return fail("row_of_slot is not an operand of this launch");
+    if (!(state || pack) && blk_left) return fail("blk_left is not an operand of this launch");
+    if (load || (amax && !state)) { if (blk_live) return fail("blk_live is not an operand of this launch"); }
+    if (pack && (!blk_live || !blk_left)) return fail("null argument: op 2 needs blk_live and blk_left");
+    if (state && (blk_live == nullptr) != (blk_left == nullptr)) return fail("blk_live and blk_left go together (LoopArgs: the count and the word it clears)");
+    if (blk_snap && !state) return fail("blk_snap is not an operand of this launch");
+    if ((blk_live || blk_left || blk_snap || row_of_slot) && RB < 2)
+        return fail("blk_live / blk_left / blk_snap / row_of_slot exist from two row blocks on (RB = %d)", RB);
+    if (row_ids && !load) return fail("row_ids is not an operand of this launch");
+    if (row_of_slot) {
+        std::vector<char> taken(rows, 0);
+        for (int b = 0; b < rows; ++b) {
+            const int r = row_of_slot[b];
+            if (r == -1) continue;
+            if (r < 0 || r >= rows || taken[r]) return fail("row_of_slot[%d] = %d is outside [0, rows = %d) or taken twice", b, r, rows);
+            taken[r] = 1;
+        }
+    }
+    const int max_len = state ? d->max_len : 0;
+    if (state) {
+        if (max_len < 1 || max_len > 4096) return fail("max_len = %d: 1 <= max_len <= 4096", max_len);
+        if (d->T0 < 0 || d->T0 > (1 << 20) || d->pos < -(1 << 20) || d->pos > (1 << 20)) return fail("T0 = %d / pos = %d: 0 <= T0 <= 2^20, |pos| <= 2^20", d->T0, d->pos);
+    }
+    int64_t ld = 0;
+    if (load) {
+        ld = d->ld;
+        if (ld < 576 || ld % 4 != 0) return fail("ld = %d: the rows are read as float4 (ld >= 576, ld %% 4 == 0)", d->ld);
+        if (d->n_src < 1 || (int64_t)d->n_src * ld > ((int64_t)1 << 26)) return fail("n_src = %d: 1 <= n_src and n_src * ld <= 2^26", d->n_src);
+        if (row_ids && d->T_last != 0) return fail("T_last = %d with row_ids: the ids address the rows (T_last 0)", d->T_last);
+        if (!row_ids && (d->T_last < 1 || (int64_t)B * d->T_last > d->n_src))
+            return fail("T_last = %d without row_ids: row b * T_last + T_last - 1 must exist (1 <= T_last, B * T_last <= n_src = %d)", d->T_last, d->n_src);
+    }
+    // capacities, before anything is launched
+    const TailWords tw{rows};
+    const size_t logits_bytes = (size_t)(rows + 32) * V * 4, cand_bytes = (size_t)(rows + 32) * n * 4, tokens_bytes = (size_t)(rows + 32) * 4;
+    const size_t record_bytes = (size_t)rows * max_len * 4, state_bytes = (size_t)tw.state_words() * 4, x_bytes = (size_t)(rows + 32) * 576 * 4;
+    auto cap = [&](bool wanted, const void* p, int64_t c, size_t bytes, const char* name, const char* cname) -> int {
+        if (wanted && (!p || c < (int64_t)bytes)) return fail("%s_capacity %lld is below the %lld bytes this call returns (or out_%s is null)", cname, (long long)c, (long long)bytes, name);
+        return 0;
+    };
+    CHK(cap(head, out_logits, logits_capacity, logits_bytes, "logits", "logits"));
+    CHK(cap(head, out_cand_val, cand_capacity, cand_bytes, "cand_val", "cand"));
+    CHK(cap(head, out_cand_idx, cand_capacity, cand_bytes, "cand_idx", "cand"));
+    CHK(cap(head, out_cand_sum, cand_capacity, cand_bytes, "cand_sum", "cand"));
+    CHK(cap(amax, out_tokens, tokens_capacity, tokens_bytes, "tokens", "tokens"));
+    CHK(cap(state, out_record, record_capacity, record_bytes, "record", "record"));
+    CHK(cap(lp_on, out_logprob, record_capacity, record_bytes, "logprob", "record"));
+    CHK(cap(state || pack, out_state, state_capacity, state_bytes, "state", "state"));
+    if (state && !out_progress) return fail("null argument: out_progress is required with with_state");
+    CHK(cap(!head, out_x, x_capacity, x_bytes, "x", "x"));
+
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    dec_prepare_lds_attributes();
+    e->cur_B = 0;                                     // the decode state of an earlier prefill is gone
+    mellow_engine::Buf bW, bWp, bX, bIn, bIds, bWords, bLogits, bCv, bCi, bCs, bTok, bRec, bLp;
+    DecArgs a;
+    a.rows = rows; a.RB = RB; a.slabF_stride4 = (int64_t)rows * 576 / 4;
+    // the device words (TailWords): 0xFF bytes wherever the caller planted nothing
+    std::vector<int32_t> hw(tw.total(), -1);
+    if (seen_stop) memcpy(hw.data() + tw.seen(), seen_stop, (size_t)rows * 4);
+    if (state) { hw[tw.scalars()] = d->n_seen; hw[tw.scalars() + 1] = d->arrive; hw[tw.scalars() + 2] = d->ticket; }
+    if (pack) hw[tw.scalars() + 3] = d->n_compactions;
+    auto blocks = [&](int at, const int32_t* src) { for (int i = 0; i < 32; ++i) hw[at + i] = i < RB ? src[i] : 0; };      // zeros behind RB, as the engine's
+    if (blk_left) blocks(tw.left(), blk_left);
+    if (blk_live) blocks(tw.live(), blk_live);
+    if (blk_snap) blocks(tw.snap(), blk_snap);
+    if (row_of_slot) memcpy(hw.data() + tw.slot(), row_of_slot, (size_t)rows * 4);
+    hw[tw.params()] = max_len; hw[tw.params() + 1] = d->stop_id; hw[tw.pos()] = d->pos;
+    CHK(gemm_tap_buf(e, bWords, hw.size() * 4, hw.data()));
+    int32_t* dw = reinterpret_cast<int32_t*>(bWords.p);
+    a.d_pos = dw + tw.pos();
+    struct HostFree { void operator()(void* p) const { (void)hipHostFree(p); } };
+    std::unique_ptr<unsigned long long, HostFree> h_prog;       // the mapped host word the last arrival publishes to
+    if (head) {
+        CHK(gemm_tap_buf(e, bW, (size_t)V * 576 * 4, W));
+        const int NP = rup(V, 128);
+        CHK(ensure(e, bWp, (size_t)NP * 576));
+        launch_pack_weight(bW.p, V, 576, 576, bWp.p, NP, 576, s);
+        if (form) { CHK(gemm_tap_buf(e, bX, x_img_need, x_img)); a.xn3 = bX.p; a.x3 = DEC_X3_HEAD; }
+        else { CHK(dec_tap_f32_layout(e, bX, x, 1, B, rows)); a.xnF = bX.p; }
+        CHK(gemm_tap_buf(e, bLogits, logits_bytes, nullptr));
+        CHK(gemm_tap_buf(e, bCv, cand_bytes, nullptr));
+        CHK(gemm_tap_buf(e, bCi, cand_bytes, nullptr));
+        CHK(gemm_tap_buf(e, bCs, cand_bytes, nullptr));
+        a.logits = d->want_logits ? bLogits.p : nullptr;
+        a.cand_val = bCv.p; a.cand_idx = reinterpret_cast<int32_t*>(bCi.p); a.cand_sum = d->want_sum ? bCs.p : nullptr;
+        a.blk_live = blk_live ? dw + tw.live() : nullptr;
+        launch_dec_lm_head(a, bWp.p, 72, V, s);
+    } else if (amax) {
+        CHK(gemm_tap_buf(e, bCv, (size_t)B * n * 4, cand_val));
+        CHK(gemm_tap_buf(e, bCi, (size_t)B * n * 4, cand_idx));
+        if (cand_sum) CHK(gemm_tap_buf(e, bCs, (size_t)B * n * 4, cand_sum));
+        if (write_x) CHK(gemm_tap_buf(e, bW, (size_t)V * 576 * 4, W));
+        CHK(gemm_tap_buf(e, bTok, tokens_bytes, nullptr));
+        CHK(gemm_tap_buf(e, bX, x_bytes, nullptr));
+        a.cand_val = bCv.p; a.cand_idx = reinterpret_cast<int32_t*>(bCi.p); a.cand_sum = cand_sum ? bCs.p : nullptr;
+        a.xmidF = bX.p;
+        LoopArgs lp;
+        if (state) {
+            CHK(gemm_tap_buf(e, bRec, record_bytes, nullptr));
+            if (lp_on) CHK(gemm_tap_buf(e, bLp, record_bytes, nullptr));
+            unsigned long long *hp = nullptr, *d_prog = nullptr;
+            HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&hp), 64, hipHostMallocMapped | hipHostMallocCoherent));
+            h_prog.reset(hp);
+            memset(hp, 0xFF, 64);
+            HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&d_prog), hp, 0));
+            lp.out_tokens = reinterpret_cast<int32_t*>(bRec.p); lp.params = dw + tw.params(); lp.seen_stop = dw + tw.seen();
+            lp.n_seen = dw + tw.scalars(); lp.arrive = dw + tw.scalars() + 1; lp.ticket = dw + tw.scalars() + 2;
+            if (blk_left) { lp.blk_left = dw + tw.left(); lp.blk_live = dw + tw.live(); }
+            if (blk_snap) lp.blk_snap = dw + tw.snap();
+            if (row_of_slot) lp.row_of_slot = dw + tw.slot();
+            lp.host_progress = d_prog; lp.T0 = d->T0;
+            if (lp_on) lp.out_logprob = bLp.p;
+        }
+        launch_dec_argmax(a, B, n, reinterpret_cast<int32_t*>(bTok.p), write_x ? bW.p : nullptr, write_x ? 1 : 0, lp, s);
+    } else if (pack) {
+        // x in F32-layout, in front of 32 rows of margin that hold 0xFF bytes
+        CHK(gemm_tap_buf(e, bX, x_bytes, nullptr));
+        CHK(dec_tap_f32_layout(e, bIn, x, 1, B, rows));
+        HIPCHK(hipMemcpyAsync(bX.p, bIn.p, (size_t)rows * 576 * 4, hipMemcpyDeviceToDevice, s));
+        a.xmidF = bX.p;
+        LoopArgs lp;
+        lp.seen_stop = dw + tw.seen(); lp.blk_left = dw + tw.left(); lp.blk_live = dw + tw.live(); lp.row_of_slot = dw + tw.slot();
+        lp.n_compactions = dw + tw.scalars() + 3;
+        launch_dec_compact(a, B, lp, s);
+    } else {
+        CHK(gemm_tap_buf(e, bIn, (size_t)d->n_src * ld * 4, x));
+        if (row_ids) CHK(gemm_tap_buf(e, bIds, (size_t)B * 4, row_ids));
+        CHK(gemm_tap_buf(e, bX, x_bytes, nullptr));
+        a.xmidF = bX.p;
+        launch_dec_load_rows(a, B, bIn.p, ld, row_ids ? reinterpret_cast<const int32_t*>(bIds.p) : nullptr, d->T_last, row_ids ? d->n_src : 0, s);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    if (head) {
+        CHK(gemm_tap_fetch(out_logits, logits_capacity, bLogits, logits_bytes, "logits"));
+        CHK(gemm_tap_fetch(out_cand_val, cand_capacity, bCv, cand_bytes, "cand"));
+        CHK(gemm_tap_fetch(out_cand_idx, cand_capacity, bCi, cand_bytes, "cand"));
+        CHK(gemm_tap_fetch(out_cand_sum, cand_capacity, bCs, cand_bytes, "cand"));
+        return 0;
+    }
+    if (amax) CHK(gemm_tap_fetch(out_tokens, tokens_capacity, bTok, tokens_bytes, "tokens"));
+    if (state) {
+        CHK(gemm_tap_fetch(out_record, record_capacity, bRec, record_bytes, "record"));
+        if (lp_on) CHK(gemm_tap_fetch(out_logprob, record_capacity, bLp, record_bytes, "record"));
+        *out_progress = *h_prog.get();
+    }
+    if (state || pack) CHK(gemm_tap_fetch(out_state, state_capacity, bWords, state_bytes, "state"));
+    CHK(gemm_tap_fetch(out_x, x_capacity, bX, x_bytes, "x"));
     return 0;
 }
 

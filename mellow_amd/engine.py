@@ -63,6 +63,13 @@ class DecGemv(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("size", "op", "form", "B", "kcd", "first", "inc_pos", "pos", "Tmax", "want_x3")] + [("eps", C.c_float)]
 
 
+class DecTail(C.Structure):
+    """mellow_dec_tail_t (include/mellow_hip.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("size", "op", "form", "B", "V", "want_logits", "want_sum", "write_x", "with_state", "with_logprob",
+                                         "max_len", "stop_id", "T0", "pos", "n_seen", "arrive", "ticket", "n_compactions", "ld", "n_src",
+                                         "T_last")]
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -75,7 +82,7 @@ _ADDED_UNDER_MINOR_4 = ("mellow_lm_score", "mellow_score", "mellow_generate_scor
 _ADDED_UNDER_MINOR_5 = ("mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_generate_rules", "mellow_logit_rules_apply",
                         "mellow_generate_guidance", "mellow_guidance_apply", "mellow_generate_top_logprobs", "mellow_top_logprobs_apply",
                         "mellow_debug_gemm_epi", "mellow_generate_filters", "mellow_sample_logits_filtered", "mellow_debug_norm",
-                        "mellow_debug_dec_attn", "mellow_debug_dec_gemv")
+                        "mellow_debug_dec_attn", "mellow_debug_dec_gemv", "mellow_debug_dec_tail")
 
 
 def load_library(path: Optional[str] = None):
@@ -143,6 +150,8 @@ def load_library(path: Optional[str] = None):
                                        vp, i64, vp, i64]),
         "mellow_debug_dec_gemv": (ci, [vp, P(DecGemv), vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp,
                                        vp, vp, i64, vp, i64, vp, i64, vp, vp, i64]),
+        "mellow_debug_dec_tail": (ci, [vp, P(DecTail), vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, i64, vp, vp,
+                                       i64, vp, i64, vp, vp, i64]),
         "mellow_debug_prefill_attn": (ci, [vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp, i64]),
         "mellow_debug_window_attn": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, i64]),
         "mellow_debug_dec_head": (ci, [vp, vp, ci, ci, vp]),
@@ -187,7 +196,7 @@ EXPORTED_SYMBOLS = (
     "mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse", "mellow_generate_n", "mellow_generate_q",
     "mellow_generate_beam", "mellow_beam_select", "mellow_generate_rules", "mellow_logit_rules_apply", "mellow_generate_guidance", "mellow_guidance_apply", "mellow_generate_top_logprobs", "mellow_top_logprobs_apply", "mellow_generate_filters", "mellow_sample_logits_filtered", "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
     "mellow_prof_num_families", "mellow_prof_family_name", "mellow_prof_get", "mellow_last_phase_ms", "mellow_last_steps_enqueued", "mellow_last_row_repacks", "mellow_stft_is_fft", "mellow_prefill_parts", "mellow_abi_minor",
-    "mellow_resample", "mellow_engine_set_precision", "mellow_engine_set_option", "mellow_engine_describe", "mellow_debug_gemm_fp8", "mellow_debug_gemm_f32", "mellow_debug_gemm_epi", "mellow_debug_norm", "mellow_debug_dec_attn", "mellow_debug_dec_gemv", "mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_debug_dec_head", "mellow_set_graph", "mellow_host_window_map", "mellow_host_pack_weight", "mellow_host_rope_tables",
+    "mellow_resample", "mellow_engine_set_precision", "mellow_engine_set_option", "mellow_engine_describe", "mellow_debug_gemm_fp8", "mellow_debug_gemm_f32", "mellow_debug_gemm_epi", "mellow_debug_norm", "mellow_debug_dec_attn", "mellow_debug_dec_gemv", "mellow_debug_dec_tail", "mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_debug_dec_head", "mellow_set_graph", "mellow_host_window_map", "mellow_host_pack_weight", "mellow_host_rope_tables",
 )
 
 
@@ -1351,6 +1360,83 @@ class Engine:
                                                  o("h3"), nb("h3"), o("xn"), nb("xn"), o("snap"), o("q"), nb("q")))
         if "pos" in out:
             out["pos"] = int(out["pos"][0])
+        return out
+
+    def debug_dec_tail(self, op: int, B: int, form: int = 0, V: int = 0, W=None, x=None, x_img=None, blk_live=None, want_logits: bool = False,
+                       want_sum: bool = False, cand_val=None, cand_idx=None, cand_sum=None, write_x: bool = False, state=None,
+                       with_logprob: bool = False, seen_stop=None, blk_left=None, blk_snap=None, row_of_slot=None, n_compactions: int = 0,
+                       row_ids=None, ld: int = 0, n_src: int = 0, T_last: int = 0) -> dict:
+        """One launch of the decode step's lm_head (op 0; form 1 = the streaming f32x3 kernel), arg-max (1), row repack (2) or row load
+        (3) launcher on host tensors (mellow_debug_dec_tail).  op 0: W [V][576] logical, x [B][576] (form 0) or x_img the raw F3-32
+        image of all rows (form 1, int16 words), blk_live [RB].  op 1: cand_val / cand_idx / cand_sum [B][V / 32], W = the embedding
+        table with write_x, state = None (LoopArgs()) or a dict {max_len, stop_id, T0, pos, n_seen, arrive, ticket} with seen_stop
+        [rows], blk_left / blk_live / blk_snap [RB], row_of_slot [rows].  op 2: row_of_slot, blk_live, blk_left, seen_stop, x [B][576],
+        n_compactions.  op 3: x = the source rows [n_src][ld], row_ids [B] or T_last.  -> dict of the whole device outputs, which held
+        0xFF bytes before the launch: "logits" f32 [rows + 32][V], "cand_val" f32 / "cand_idx" i32 / "cand_sum" f32 [rows + 32][V / 32];
+        "tokens" i32 [rows + 32], "record" i32 / "logprob" f32 [rows][max_len], "progress" (the published word as an int); "seen_stop"
+        [rows + 32], "n_seen", "arrive", "ticket", "n_compactions", "scalars" [32], "blk_left" / "blk_live" [64], "row_of_slot"
+        [rows + 32]; "x" f32 [(rows + 32) * 576] (F32-layout) -- those the op writes."""
+        self._need("mellow_debug_dec_tail")
+        f32 = lambda t: None if t is None else torch.as_tensor(t).detach().cpu().contiguous().float()       # noqa: E731
+        i32 = lambda t: None if t is None else torch.as_tensor(t).detach().cpu().contiguous().to(torch.int32)       # noqa: E731
+        W, x, cand_val, cand_sum = (f32(t) for t in (W, x, cand_val, cand_sum))
+        x_img = None if x_img is None else torch.as_tensor(x_img).detach().cpu().contiguous()
+        blk_live, cand_idx, seen_stop, blk_left, blk_snap, row_of_slot, row_ids = (i32(t) for t in (blk_live, cand_idx, seen_stop, blk_left,
+                                                                                                   blk_snap, row_of_slot, row_ids))
+        op, form, B, V = int(op), int(form), int(B), int(V)
+        rows = (max(B, 1) + 31) // 32 * 32
+        n = max(V, 0) // 32
+        src_shape = (int(n_src), int(ld)) if op == 3 else (B, 576)
+        for name, t, shape in (("W", W, (V, 576)), ("x", x, src_shape), ("cand_val", cand_val, (B, n)), ("cand_idx", cand_idx, (B, n)),
+                               ("cand_sum", cand_sum, (B, n)), ("blk_live", blk_live, (rows // 32,)), ("blk_left", blk_left, (rows // 32,)),
+                               ("blk_snap", blk_snap, (rows // 32,)), ("seen_stop", seen_stop, (rows,)), ("row_of_slot", row_of_slot, (rows,)),
+                               ("row_ids", row_ids, (B,))):
+            if t is not None and tuple(t.shape) != shape:
+                raise ValueError(f"{name} {tuple(t.shape)} is not {shape}")
+        st = dict(state or {})
+        d = DecTail()
+        d.size, d.op, d.form, d.B, d.V = C.sizeof(DecTail), op, form, B, V
+        d.want_logits, d.want_sum, d.write_x = int(bool(want_logits)), int(bool(want_sum)), int(bool(write_x))
+        d.with_state, d.with_logprob = int(state is not None), int(bool(with_logprob))
+        for k in ("max_len", "stop_id", "T0", "pos", "n_seen", "arrive", "ticket"):
+            setattr(d, k, int(st.pop(k, 0)))
+        if st:
+            raise ValueError(f"state has unknown keys {sorted(st)}")
+        d.n_compactions, d.ld, d.n_src, d.T_last = int(n_compactions), int(ld), int(n_src), int(T_last)
+        max_len = max(int(d.max_len), 0)
+        out = {}
+        if op == 0:
+            out["logits"] = torch.empty((rows + 32, max(V, 0)), dtype=torch.float32)
+            out["cand_val"] = torch.empty((rows + 32, n), dtype=torch.float32)
+            out["cand_idx"] = torch.empty((rows + 32, n), dtype=torch.int32)
+            out["cand_sum"] = torch.empty((rows + 32, n), dtype=torch.float32)
+        else:
+            out["x"] = torch.empty(((rows + 32) * 576,), dtype=torch.float32)
+        if op == 1:
+            out["tokens"] = torch.empty((rows + 32,), dtype=torch.int32)
+            if state is not None:
+                out["record"] = torch.empty((rows, max_len), dtype=torch.int32)
+                out["progress"] = torch.empty((1,), dtype=torch.int64)
+                if with_logprob:
+                    out["logprob"] = torch.empty((rows, max_len), dtype=torch.float32)
+        words = None
+        if (op == 1 and state is not None) or op == 2:
+            words = torch.empty((2 * (rows + 32) + 32 + 128,), dtype=torch.int32)
+        p = lambda t: None if t is None else _ptr(t)      # noqa: E731
+        nbt = lambda t: 0 if t is None else t.numel() * t.element_size()      # noqa: E731
+        o, nb = (lambda k: p(out.get(k))), (lambda k: nbt(out.get(k)))      # noqa: E731
+        self._chk(self.lib.mellow_debug_dec_tail(self.h, C.byref(d), p(W), p(x), p(x_img), nbt(x_img), p(blk_live), p(cand_val), p(cand_idx),
+                                                 p(cand_sum), p(seen_stop), p(blk_left), p(blk_snap), p(row_of_slot), p(row_ids),
+                                                 o("logits"), nb("logits"), o("cand_val"), o("cand_idx"), o("cand_sum"), nb("cand_val"),
+                                                 o("tokens"), nb("tokens"), o("record"), o("logprob"), nb("record"), p(words), nbt(words),
+                                                 o("progress"), o("x"), nb("x")))
+        if "progress" in out:
+            out["progress"] = int(out["progress"][0])
+        if words is not None:
+            at = rows + 32
+            out["seen_stop"], out["scalars"] = words[:at], words[at:at + 32]
+            out["n_seen"], out["arrive"], out["ticket"], out["n_compactions"] = (int(v) for v in words[at:at + 4])
+            out["blk_left"], out["blk_live"], out["row_of_slot"] = words[at + 32:at + 96], words[at + 96:at + 160], words[at + 160:]
         return out
 
     @staticmethod

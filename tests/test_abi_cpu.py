@@ -170,6 +170,41 @@ def test_decode_gemv_tap_is_declared_bound_and_refuses_without_a_device(lib):
         e.debug_dec_gemv(0, 1, None)
 
 
+def test_decode_tail_tap_is_declared_bound_and_refuses_without_a_device(lib):
+    hdr = open(os.path.join(ROOT, "include", "mellow_hip.h")).read()
+    name = "mellow_debug_dec_tail"
+    assert re.search(r"\bint\s+%s\s*\(" % name, hdr) and re.search(r"\}\s*mellow_dec_tail_t;", hdr)
+    assert name in E.EXPORTED_SYMBOLS and name in E._ADDED_UNDER_MINOR_5
+    assert lib.mellow_abi_minor() == 5          # added under the current minor: found by symbol lookup, not by the number
+    fn = getattr(lib, name)
+    assert fn.restype is ctypes.c_int and len(fn.argtypes) == 31 and fn.argtypes[-1] is ctypes.c_int64
+    # the binding's argument list is the header's: one entry per declared parameter, pointers as pointers (the descriptor typed)
+    decl = re.search(r"int\s+%s\s*\((.*?)\);" % name, hdr, re.S).group(1)
+    params = [a.strip() for a in decl.split(",")]
+    assert len(params) == len(fn.argtypes)
+    for a, t in zip(params, fn.argtypes):
+        if "mellow_dec_tail_t*" in a:
+            assert t._type_ is E.DecTail, (a, t)
+            continue
+        want = ctypes.c_void_p if "*" in a else ctypes.c_float if a.startswith("float") else ctypes.c_int64 if a.startswith("int64_t") else ctypes.c_int
+        assert t is want, (a, t)
+    # the descriptor of the binding is the header's: one 4-byte field per declared member, in the header's order
+    body = re.search(r"typedef struct mellow_dec_tail \{(.*?)\} mellow_dec_tail_t;", hdr, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    members = [(t, n.strip()) for t, names in re.findall(r"\b(int32_t|float)\s+([^;]+);", body) for n in names.split(",")]
+    assert members[0] == ("int32_t", "size")
+    assert [n for _, n in members] == [n for n, _ in E.DecTail._fields_]
+    assert all((ct is ctypes.c_float) == (t == "float") for (t, _), (_, ct) in zip(members, E.DecTail._fields_))
+    assert ctypes.sizeof(E.DecTail) == 4 * len(members)
+    # host code only: a null engine is refused before any device is touched
+    assert fn(*[None if (t is ctypes.c_void_p or hasattr(t, "contents")) else t(1) for t in fn.argtypes]) != 0
+    assert "null argument" in lib.mellow_last_error().decode()
+    e = object.__new__(E.Engine)
+    e.lib, e.h = type("OldLib", (), {})(), None
+    with pytest.raises(E.EngineError, match="predates mellow_debug_dec_tail"):
+        e.debug_dec_tail(0, 1)
+
+
 def test_required_keys_are_the_reference_state_dict_keys(lib):
     from mellow_amd import spec
     layout = spec.state_dict_layout()
