@@ -6,7 +6,8 @@
 //   engine_lm.cpp       KV pages, LM prefill (A15; plan, parts, prefill_layer), the decode step and its per-call mode, mellow_prefix / lm taps, scoring
 //   engine_generate.cpp the generation loop on top of it (A16): request + checks, passes, step graphs, the mellow_generate* entry points,
 //                       beam search (mellow_generate_beam, mellow_beam_select)
-//   engine_dev.cpp      developer entry points (GEMM timing / debug taps, kernel stamps)
+//   engine_dev.cpp      developer entry points (GEMM timing, the two GEMM accuracy / timing taps, profiler dump, kernel stamps)
+//   engine_taps.cpp     the launch taps on caller data (mellow_debug_*_attn, _gemm_epi, _norm, _dec_attn, _dec_gemv, _dec_tail): one call record
 // The engine object (below): `Options` + `Weights` are what a fork shares, each copied by one assignment; everything else is one
 // context's own -- stream, events, workspaces (`Buf` frees itself), KV pages, loop words, the decode-graph cache (`StepGraphs`).
 #pragma once
