@@ -20,8 +20,8 @@ PKG = os.path.dirname(HERE)
 LIBDIR = os.path.join(PKG, "lib")
 OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(LIBDIR, "libmellow_hip.so")
-SOURCES = ["gemm_f32.hip", "gemm_fp8.hip", "gemm_bf16x3.hip", "decode.hip", "prefill_attn.hip", "encoder.hip", "norm.hip", "stft_fft.hip", "sample.hip", "score.hip", "beam.hip", "logit_rules.hip", "guidance.hip", "top_logprobs.hip", "engine.cpp", "engine_weights.cpp", "engine_encoder.cpp", "engine_lm.cpp", "engine_generate.cpp", "engine_dev.cpp", "engine_taps.cpp"]
-HEADERS = ["common.h", "kernels.h", "step_tail.h", "gemm_epilogue.h", "gemm_tile.h", "engine_internal.h", os.path.join("..", "..", "include", "mellow_hip.h")]
+SOURCES = ["gemm_f32.hip", "gemm_fp8.hip", "gemm_bf16x3.hip", "dec_attn.hip", "dec_gemv.hip", "dec_tail.hip", "dec_weights.hip", "prefill_attn.hip", "encoder.hip", "norm.hip", "stft_fft.hip", "sample.hip", "score.hip", "beam.hip", "logit_rules.hip", "guidance.hip", "top_logprobs.hip", "engine.cpp", "engine_weights.cpp", "engine_encoder.cpp", "engine_lm.cpp", "engine_generate.cpp", "engine_dev.cpp", "engine_taps.cpp"]
+HEADERS = ["common.h", "kernels.h", "dec_common.h", "step_tail.h", "gemm_epilogue.h", "gemm_tile.h", "engine_internal.h", os.path.join("..", "..", "include", "mellow_hip.h")]
 ARCH = "gfx950"
 FLAGS = (["-DMELLOW_KDEBUG"] if os.environ.get("MELLOW_KDEBUG") else []) + os.environ.get("MELLOW_EXTRA_FLAGS", "").split() + ["-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable", "-x", "hip"]
@@ -49,10 +49,13 @@ VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
 FILE_FLAGS = {name: VGPR_FORM for name in os.environ.get("MELLOW_VGPR_FORM_FILES", "gemm_bf16x3.hip gemm_fp8.hip prefill_attn.hip encoder.hip").split()}
 # Kernel-argument preload (gfx950): the command processor writes the first dwords of a kernel's argument block into SGPRs while it
 # sets the dispatch up, so the first address computations of a launch do not wait for a scalar load from the argument buffer.
-# The decode kernels take their hot pointers as leading scalar arguments for this (decode.hip); measured on one kernel of the
+# The decode kernels take their hot pointers as leading scalar arguments for this (dec_*.hip); measured on one kernel of the
 # step (gate/up, 30 of 124 launches): 48.2-48.5 -> 47.65 ms of decode per 63 steps, 0.3 us per launch.  MELLOW_KERNARG_PRELOAD=0: off.
 KERNARG_PRELOAD = [] if os.environ.get("MELLOW_KERNARG_PRELOAD", "14") == "0" else ["-mllvm", "-amdgpu-kernarg-preload-count=" + os.environ.get("MELLOW_KERNARG_PRELOAD", "14")]
-FILE_FLAGS["decode.hip"] = FILE_FLAGS.get("decode.hip", []) + KERNARG_PRELOAD
+# every file cut from the former decode.hip, the load-time dec_weights.hip too: its kernels stay the instruction streams they were
+DECODE_FILES = ["dec_attn.hip", "dec_gemv.hip", "dec_tail.hip", "dec_weights.hip"]
+for _name in DECODE_FILES:
+    FILE_FLAGS[_name] = FILE_FLAGS.get(_name, []) + KERNARG_PRELOAD
 
 
 def build(force=False, verbose=False, out=None, objdir=None):

@@ -8,6 +8,9 @@
 //   MellowWrapper._generate_batch                         wrapper.py:197-249    -> mellow_generate
 #include "engine_internal.h"
 
+#include <mutex>
+#include <set>
+
 static thread_local std::string g_err;
 int fail(const char* fmt, ...) {
     char buf[1024];
@@ -18,6 +21,29 @@ int fail(const char* fmt, ...) {
     g_err = buf;
     return 1;
 }
+namespace mellow {
+// Dynamic LDS beyond 64 KiB has to be allowed per kernel function AND per device (an engine per GPU, pools of host threads):
+// remembered per (function, device) under a lock; the attribute call itself is cheap but not free on a per-step path.
+void set_max_dynamic_lds(const void* fn, size_t bytes) {
+    if (bytes <= 64 * 1024) return;
+    static std::mutex mu;
+    static std::set<std::pair<const void*, int>> done;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lk(mu);
+    if (done.insert({fn, dev}).second) {
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) fprintf(stderr, "mellow: hipFuncSetAttribute(max dynamic LDS %zu) failed: %s\n", bytes, hipGetErrorString(e));
+    }
+}
+// The launchers raise a kernel's dynamic-LDS limit on first use; a decode step is launched inside a stream capture, so the engine
+// calls this once per device beforehand (ensure_lm): every instantiation the launchers can pick (set_max_dynamic_lds skips those
+// within 64 KiB), named by the file that holds the family.
+void dec_prepare_lds_attributes() {
+    dec_gemv_prepare_lds();
+    dec_tail_prepare_lds();
+}
+}  // namespace mellow
 // ---- small helpers ---------------------------------------------------------------------------------------------
 int ensure(mellow_engine* e, mellow_engine::Buf& b, size_t floats) {
     if (b.cap >= floats) return 0;
@@ -437,7 +463,7 @@ int apply_options(mellow_engine* e) {
     // f32x3: six partial products (a2*b3, a3*b2, a3*b3 dropped: < 2^-23 |a*b| in total); measured error against an fp64 product is
     // identical to the nine-term form and slightly below the fp32 MFMA kernel's (tools/f32x3_check.py)
     e->opt.f32x3_terms = mode == MELLOW_PRECISION_F32X3 ? 6 : 0;
-    // f32x3 mode: the decode step's GEMM launches split their operands in registers and run on the bf16 pipe as well (decode.hip)
+    // f32x3 mode: the decode step's GEMM launches split their operands in registers and run on the bf16 pipe as well (dec_gemv.hip, dec_tail.hip)
     e->opt.dec_x3 = mode == MELLOW_PRECISION_F32X3 ? ((int)opt_val(e, "decode_x3") & DEC_X3_ALL) : 0;
     e->opt.dec_x3_min_rb = (int)opt_val(e, "decode_x3_min_rb") < 1 ? 1 : (int)opt_val(e, "decode_x3_min_rb");
     return 0;

@@ -29,6 +29,13 @@ int time_launches(hipStream_t s, int iters, const std::function<void()>& launch,
 }
 }  // namespace
 
+// the decode kernels' debug pointer: one copy per file that stamps (no relocatable device code), each behind its setter
+void mellow::set_kernel_debug_buffer(uint64_t* p) {
+    set_dec_attn_debug_buffer(p);
+    set_dec_gemv_debug_buffer(p);
+    set_dec_tail_debug_buffer(p);
+}
+
 extern "C" {
 
 // developer instrumentation (not part of the public header): time `iters` launches of one plain GEMM shape on

@@ -581,7 +581,7 @@ int mellow_generate_sampled(mellow_engine_t* e, const float* audio1, const float
 }
 
 // mellow_generate (do_sample = 0) or mellow_generate_sampled (do_sample != 0) plus the log-prob record: the same launches with the
-// head, the arg-max and the sampler in their LSE instantiations (decode.hip, sample.hip); tokens, lengths and steps are bit-identical
+// head, the arg-max and the sampler in their LSE instantiations (dec_tail.hip, sample.hip); tokens, lengths and steps are bit-identical
 int mellow_generate_scored(mellow_engine_t* e, const float* audio1, const float* audio2, int64_t n_samples, const int32_t* input_ids,
                            int B, int max_len, int do_sample, float top_p, float temperature, uint64_t seed, int32_t row_offset,
                            int stop_id, int ignore_stop, int32_t* out_tokens, float* out_logprob, int32_t* out_len, int32_t* out_steps,

@@ -416,7 +416,7 @@ int run_prefill_q(mellow_engine* e, int B, int Q, int T, int P, const RecordArgs
     return finish_prefill(e, N, T, e->lm_xq.p, reinterpret_cast<const int32_t*>(e->nseq_rows.p), N * Tt, rec);
 }
 
-// the 30 decode layers + head at position *d_pos (enqueue only; capture-safe).  5 launches per layer (decode.hip):
+// the 30 decode layers + head at position *d_pos (enqueue only; capture-safe).  5 launches per layer (dec_gemv.hip, dec_attn.hip):
 //   qkv split-K | attention (RMS scale, RoPE, KV append, key-split flash decoding) | o_proj (merge + residual) |
 //   gate/up | down split-K (RMS scale, SwiGLU); the down slabs are summed by the next layer's qkv/attention.
 int enqueue_decode_layer_range(mellow_engine* e, int B, int l_begin, int l_end, bool inc_pos) {
@@ -461,7 +461,8 @@ int enqueue_decode_layer_range(mellow_engine* e, int B, int l_begin, int l_end, 
           launch_dec_qkv(a, qkv.p, w.qkv_f.KP / 8, kcd, s, qkv.scale); }
         if (!(skip & 2))
         { ProfScope ps(e, PF_DECODE_ATTN, 4.0 * 64 * 9 * (double)B * (e->cur_pos + 1), 2.0 * (double)B * 3 * 64 * 4 * (e->cur_pos + 1));
-          launch_dec_attn(da(1), kc, vc, fused_in, s); }
+          if (!launch_dec_attn(da(1), kc, vc, fused_in, s))
+              return fail("decode attention launched with %d key splits at RB = %d", e->da.ts, e->da.RB); }
         if (!(skip & 4))
         { ProfScope ps(e, PF_SKINNY, 2.0 * Bp * 576.0 * 576.0, 576.0 * 576.0 * 4);
           launch_dec_oproj(da(2), o.p, s, o.scale); }
@@ -471,7 +472,7 @@ int enqueue_decode_layer_range(mellow_engine* e, int B, int l_begin, int l_end, 
           else launch_dec_gateup(da(3), gu.p, s, gu.scale); }
         const LMLayerW* nx = (l + 1 < l_end && !same_w) ? &e->w.layers[l + 1] : nullptr;
         if (nx && ((nx->qkv2 && fuse_rb) || nx->q2h8)) {
-            // the down projection of this layer and the q/k/v projection of the next one as one launch (decode.hip, dec_qkv2_kernel)
+            // the down projection of this layer and the q/k/v projection of the next one as one launch (dec_gemv.hip, dec_qkv2_kernel)
             if (!(skip & 16))
             { ProfScope ps(e, PF_SKINNY, 2.0 * Bp * (2112.0 * 960.0 + 1536.0 * 576.0), (2112.0 * 960.0 + 1536.0 * 576.0) * (nx->q2h8 ? 1 : 4));
               if (nx->q2h8) launch_dec_qkv2_w8(da(4), nx->qkv8, nx->qkv_sc, nx->q2h8, nx->q2h_sc, w.dn8, w.dn_sc, s);

@@ -539,7 +539,7 @@ int mellow_debug_dec_attn(mellow_engine_t* e, const mellow_dec_attn_t* d, const 
         CHK(t.scratch(dWp, (size_t)576 * 576));
         launch_pack_weight16(dW, 576, 576, dWp, s);
     }
-    launch_dec_attn(a, oK->p, oV->p, fused, s);
+    if (!launch_dec_attn(a, oK->p, oV->p, fused, s)) return fail("decode attention launched with %d key splits at RB = %d", a.ts, a.RB);
     if (Wo) {
         DecArgs o = a;
         o.xmidF = oXmid->p; o.ssq = oSsq->p;

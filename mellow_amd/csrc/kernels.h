@@ -123,9 +123,9 @@ double gemm_flops(const GemmArgs& a);
 
 // Allow `bytes` of dynamic LDS (> 64 KiB) for a kernel function on the CURRENT device: remembered per (function, device) under a
 // lock (an engine per GPU, pools of host threads), return code reported on stderr.  No-op up to 64 KiB.
-void set_max_dynamic_lds(const void* fn, size_t bytes);
+void set_max_dynamic_lds(const void* fn, size_t bytes);      // (engine.cpp)
 
-// ---- decode step (decode.hip) --------------------------------------------------------------------------------
+// ---- decode step (dec_attn.hip, dec_gemv.hip, dec_tail.hip; load-time weight forms: dec_weights.hip) -----------
 // split factors are compile-time so that partial-sum ("slab") loads are fully unrolled and issued together
 constexpr int DEC_KC_QKV = 8;    // qkv: 72 k-tiles = 8 chunks x 3 waves x 3  (30 x 8 = 240 workgroups <= 256 CUs)
 #ifndef MELLOW_DEC_KC_DOWN
@@ -192,7 +192,7 @@ struct DecArgs {
     // f32x3 layer kernels (row blocks >= the engine's threshold): x_mid pre-split by the o_proj for the fused down + q/k/v launch
     // (F3-32) and for gate/up (F3-16, replaces xmidF16), h pre-split by gate/up (F3-32, 96 pairs); null = the fp32 kernels
     void *xmid3_32 = nullptr, *xmid3_16 = nullptr, *h3 = nullptr;
-    void* xn3 = nullptr;           // f32x3 mode: the same pre-split (F3-32, decode.hip) instead of xnF; null = fp32 xnF
+    void* xn3 = nullptr;           // f32x3 mode: the same pre-split (F3-32, dec_common.h) instead of xnF; null = fp32 xnF
     // per-row-block early exit (reference stop rule, batches of more than one 32-row block): blk_live[rb] == 0 once every
     // row of block rb has produced the stop id -- its workgroups return at once.  Null = never skip (one block / fixed length).
     const int32_t* blk_live = nullptr;
@@ -204,10 +204,10 @@ struct DecArgs {
     // token record, its stop flag).  dec_compact_kernel repacks the rows that are still running into the lowest slots
     // whenever that empties a whole 32-row block.
     const int32_t* row_of_slot = nullptr;
-    int kv16 = 0;                  // fp8 mode: the K/V page pointers of launch_dec_attn address the bf16 shadow pages (decode.hip, KV16)
+    int kv16 = 0;                  // fp8 mode: the K/V page pointers of launch_dec_attn address the bf16 shadow pages (dec_attn.hip, KV16)
     int a8 = 0;                    // fp8 mode: launches that get e4m3 weights also quantise their activations (fp8 matrix pipe)
     int x3 = 0;                    // f32x3 mode: bit mask of the decode GEMM launches that run on the bf16 matrix pipe with operands split in
-                                   // registers (DEC_X3_*; decode.hip); 0 = the exact fp32 MFMA kernels
+                                   // registers (DEC_X3_*; dec_gemv.hip, dec_tail.hip); 0 = the exact fp32 MFMA kernels
     int dbg_seq = -1;              // -DMELLOW_KDEBUG builds: index of this launch in the step (span stamps of tools/kdebug.py), else unused
     float* logits = nullptr;       // [rows][vocab] (may be null)
     float* cand_val = nullptr; int32_t* cand_idx = nullptr;   // [rows][vocab/32]
@@ -221,8 +221,9 @@ struct DecArgs {
 // layout (launch_pack_dec_fp8: one 4-byte word per float4 slot) and wscale holds one factor per packed weight row
 void launch_dec_qkv(const DecArgs& a, const float* Wp_folded, int K8p, int kcd, hipStream_t s, const float* wscale = nullptr);
 void launch_pack_dec_fp8(const float* Wp, int tiles, int slots_per_tile, int rows_per_tile, void* out, float* scale, hipStream_t s);
-// fused = the projected values come from launch_dec_qkv2 (Q2_NPQ slabs; the attention also forms x_new from the down slabs)
-void launch_dec_attn(const DecArgs& a, float* k_cache, float* v_cache, bool fused, hipStream_t s);
+// fused = the projected values come from launch_dec_qkv2 (Q2_NPQ slabs; the attention also forms x_new from the down slabs).
+// false = nothing was launched: a.ts is a key-split count no instantiation serves (dec_key_splits never yields one)
+bool launch_dec_attn(const DecArgs& a, float* k_cache, float* v_cache, bool fused, hipStream_t s);
 // n fp32 values (n % 8 == 0) -> bf16, round to nearest even (the K/V shadow pages of the fp8 mode)
 void launch_kv_to_bf16(const float* src, void* dst, int64_t n, hipStream_t s);
 // mellow_generate_n: the prefix K/V of B examples, positions [0, T) of [layers][B][3][Tp][64], copied to the decode pages
@@ -236,6 +237,8 @@ void launch_dec_qkv2(const DecArgs& a, const float* Wq2, const float* Wd, hipStr
 // f32x3 forms for any number of row blocks (operands a.xmid3_32 / a.h3 / a.xmid3_16 pre-split by the o_proj / gate-up launches)
 void launch_dec_qkv2x3(const DecArgs& a, const float* Wq2, const float* Wd, hipStream_t s);
 void dec_prepare_lds_attributes();      // once per device, outside any stream capture: dynamic-LDS limits of the kernels above
+void dec_gemv_prepare_lds();            // ... its two parts: the instantiations dec_gemv.hip / dec_tail.hip launch with dynamic LDS
+void dec_tail_prepare_lds();
 void launch_dec_gateup3(const DecArgs& a, const float* Wp16n_folded_pairs, hipStream_t s);
 // the same launch on e4m3 weights: the unfused layer's q/k/v copy (72 k-tiles per n-tile), the composed W' Wd (192) and the
 // down copy, one scale per packed row each (launch_pack_dec_fp8)
@@ -394,10 +397,13 @@ void launch_dec_compact(const DecArgs& a, int B, const LoopArgs& loop, hipStream
 void launch_dec_load_rows(const DecArgs& a, int B, const float* in, int64_t ld, const int32_t* row_ids, int T_last,
                           int n_src /* rows of `in` that row_ids may address */, hipStream_t s);
 void launch_pack_weight16(const float* w, int N, int K, float* out, hipStream_t s);
-// the same 16-row tiles with eight consecutive k per lane (f32x3 gate/up, decode.hip P16N); K % 32 == 0
+// the same 16-row tiles with eight consecutive k per lane (f32x3 gate/up, dec_weights.hip P16N); K % 32 == 0
 void launch_pack_weight16n(const float* w, int N, int K, float* out, hipStream_t s);
 // developer instrumentation: device buffer of 64 uint64 slots stamped by workgroup 0 of the decode kernels (null = off)
-void set_kernel_debug_buffer(uint64_t* p);
+void set_kernel_debug_buffer(uint64_t* p);      // (engine_dev.cpp) every file's copy of the pointer, through its setter:
+void set_dec_attn_debug_buffer(uint64_t* p);
+void set_dec_gemv_debug_buffer(uint64_t* p);
+void set_dec_tail_debug_buffer(uint64_t* p);
 void set_gemm_debug_buffer(uint64_t* p);
 
 // ---- front-end ---------------------------------------------------------------------------------------

@@ -9,7 +9,7 @@
 //      integer mass) finds the boundary key; ties on that key are cut by index with a second select over the index (counts);
 //   4. Gumbel-max over the kept tokens: argmax (z + g), g = -log(-log u), u from Philox4x32-10 keyed by (seed) with counter
 //      (index / 4, step, global row, 0); ties to the lowest index.  Noise is only formed for kept tokens.
-// The loop variant then runs the step epilogue (step_tail.h) as dec_argmax_kernel (decode.hip) does, which it replaces in the step.
+// The loop variant then runs the step epilogue (step_tail.h) as dec_argmax_kernel (dec_tail.hip) does, which it replaces in the step.
 //
 // The filtered instantiation (FILT; include/mellow_hip.h, mellow_generate_filters) puts two more filters around step 3, in Hugging
 // Face's order top_k, top_p, min_p:

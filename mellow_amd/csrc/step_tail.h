@@ -1,5 +1,5 @@
 // The tail of a decode step, device side: what the kernels after the lm_head launch share (sample.hip, beam.hip, logit_rules.hip,
-// guidance.hip, top_logprobs.hip and the arg-max of decode.hip).  Everything here is inlined into its caller; the
+// guidance.hip, top_logprobs.hip and the arg-max of dec_tail.hip).  Everything here is inlined into its caller; the
 // helpers return values and take closures that capture by value, because a result written through a reference, or a local whose
 // address a closure holds, changed the instructions of the callers (DESIGN.md 6s has the per-kernel comparison).
 //   - the row tiling of the 1024-thread row kernels;

@@ -1,6 +1,6 @@
 """Plain torch / numpy reference for the decode attention launch and the o_proj launch that merges its key splits
 (tests/test_dec_attn_ref_cpu.py, tests/test_gpu_dec_attn.py).  Nothing here imports the engine: the float64 definition of the two
-launches, the layout codecs (transcribed from the layout COMMENTS of mellow_amd/csrc/decode.hip / common.h / kernels.h, not from
+launches, the layout codecs (transcribed from the layout COMMENTS of mellow_amd/csrc/dec_common.h / dec_attn.hip / common.h / kernels.h, not from
 their code), the merge of decoded partials, the seeded inputs, the case list and the tolerance rule.
 
 The two launches (dec_attn_ref):
@@ -17,7 +17,7 @@ tests/attn_ref.py:
 c, derived from the code before any GPU run.  attn_ref's 16 is 8 x 2: 8 for the hardware exp2 after a multiply by log2(e)
 (about 8 * 2^-23 relative where libm is within 1 ulp), 2 for the TWO exp factors a softmax weight of the prefill kernels is a
 product of (its own exp(s - m) and the rescale of the accumulator once per key tile), summation order included.  A weight of the
-decode path is a product of more such factors (mellow_amd/csrc/decode.hip):
+decode path is a product of more such factors (mellow_amd/csrc/dec_attn.hip):
     1            p = fast_exp(s - m_new) of its chunk                                  (MELLOW_DA_CHUNK / chunk_mf)
     n - 1        alpha = fast_exp(m_run - m_new), once per LATER chunk of its wave, n = chunks the longest split runs
     1            f = fast_exp(mw - M): the merge of the 8 waves' partials               (dec_attn_kernel, after the barrier)
@@ -35,7 +35,7 @@ import torch
 
 QH, KVH, HD, HID = 9, 3, 64, 576
 NPQ_UNFUSED, NPQ_FUSED, N_DOWN = 8, 6, 4       # DEC_KC_QKV, Q2_NPQ, Q2_HC of kernels.h: slabs of the two producers
-DA_WAVES, DA_G, DA_GM = 8, 7, 8                # decode.hip: waves, 4-key groups per wave and chunk (vector form / matrix form)
+DA_WAVES, DA_G, DA_GM = 8, 7, 8                # dec_attn.hip: waves, 4-key groups per wave and chunk (vector form / matrix form)
 F32, F64 = torch.float32, torch.float64
 
 

@@ -1,6 +1,6 @@
 """Plain torch / numpy reference for the q/k/v, gate/up, down, fused down + q/k/v and final-norm launches of a decode step
 (tests/test_dec_gemv_ref_cpu.py, tests/test_gpu_dec_gemv.py).  Nothing here imports the engine: the float64 definition of every
-launch, the layouts and the slab ownership (transcribed from the COMMENTS of mellow_amd/csrc/decode.hip and kernels.h, not from
+launch, the layouts and the slab ownership (transcribed from the COMMENTS of mellow_amd/csrc/dec_common.h, dec_gemv.hip and kernels.h, not from
 their code; the codecs of the 576-column images are those of tests/dec_attn_ref.py), the seeded inputs, the case list, the
 tolerance rule, an emulation of the tap's raw outputs in float32 (`emulate`: what the CPU test and its mutants feed to `check`)
 and the one function that judges a set of raw outputs (`check`: the GPU test hands it the tap's).

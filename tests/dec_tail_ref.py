@@ -1,7 +1,7 @@
 """Plain torch / numpy / Python reference for the launches that end a decode step: the lm_head (fp32 and streaming f32x3 form), the
 arg-max with the step epilogue, the row repack and the row load (tests/test_dec_tail_ref_cpu.py, tests/test_gpu_dec_tail.py).
 Nothing here imports the engine: the float64 definition of the head, an integer model of the step epilogue and of the repack
-(transcribed from the COMMENTS of mellow_amd/csrc/step_tail.h, kernels.h and decode.hip, not from their code; the codecs are those of
+(transcribed from the COMMENTS of mellow_amd/csrc/step_tail.h, kernels.h and dec_tail.hip, not from their code; the codecs are those of
 tests/dec_gemv_ref.py), the seeded inputs, the case list, the tolerance rules, an emulation of the tap's raw outputs (`emulate`: what
 the CPU test and its mutants feed to `check`) and the one function that judges a set of raw outputs (`check`: the GPU test hands it
 the tap's).

@@ -1298,7 +1298,7 @@ def test_fp8_decode_on_the_fp8_pipe_stays_near_the_fp32_activation_form(synth_sd
     ea = Engine(device=0, precision="fp8", options={"fp8_prefill": 0})
     ew.load_state_dict(synth_sd)
     ea.load_state_dict(synth_sd)
-    # ... and the fp8 mode's fused launch (down of layer l + q/k/v of layer l+1 on the e4m3 copy of W' Wd, decode.hip) against
+    # ... and the fp8 mode's fused launch (down of layer l + q/k/v of layer l+1 on the e4m3 copy of W' Wd, dec_gemv.hip) against
     # the five-launch layer on the same engine settings
     eu = Engine(device=0, precision="fp8", options={"decode_fuse": 0})
     eu.load_state_dict(synth_sd)
@@ -1329,7 +1329,7 @@ def test_fp8_decode_on_the_fp8_pipe_stays_near_the_fp32_activation_form(synth_sd
 
 
 def test_fp8_decode_attention_chunks_and_key_splits_agree(synth_sd):
-    """bf16-page decode attention (fp8 mode: scores on the matrix pipe, decode.hip at `DA_GM`): a wave walks its keys in chunks of
+    """bf16-page decode attention (fp8 mode: scores on the matrix pipe, dec_attn.hip at `DA_GM`): a wave walks its keys in chunks of
     one 32-key tile and rescales its running (m, l, o) between chunks, and the key range is cut into two splits at a boundary that
     follows the RESERVED context.  Every benchmarked configuration keeps a split inside one chunk; here the same 389-key prefix is
     decoded with 8 and with 400 reserved positions -- the second puts keys 0..395 into split 0 as TWO chunks per wave (rescale

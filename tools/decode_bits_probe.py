@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Developer tool (GPU box): the raw bits of the decode step's logits, for a comparison between two builds of the library
-(the GEMV kernels of decode.hip against the parent commit's).
+(the GEMV kernels of dec_gemv.hip against the parent commit's).
 
     python tools/decode_bits_probe.py --out FILE.npz
     python tools/decode_bits_probe.py --compare A.npz B.npz
