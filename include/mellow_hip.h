@@ -58,7 +58,8 @@ extern "C" {
  *     (repetition controls: logit rules inside the decode step), and then mellow_generate_guidance with its tap mellow_guidance_apply
  *     (contrastive guidance inside the decode step), and then mellow_generate_top_logprobs with its tap mellow_top_logprobs_apply
  *     (the k likeliest tokens of every step), and then mellow_generate_filters with its tap mellow_sample_logits_filtered (top_k and
- *     min_p inside the sampler) -- added while the minor was 5, detected by symbol lookup all the same.
+ *     min_p inside the sampler), and then mellow_generate_constraint with its tap mellow_constraint_apply (answers held to a phrase
+ *     set inside the decode step) -- added while the minor was 5, detected by symbol lookup all the same.
  *  5: the attention taps on host data, mellow_debug_prefill_attn and mellow_debug_window_attn.  No existing symbol or struct
  *     changed; a binding that must also load a minor-4 library detects them by symbol lookup.  The GEMM epilogue tap
  *     mellow_debug_gemm_epi was added later under this same minor, detected by symbol lookup all the same, and so was the norm /
@@ -350,6 +351,78 @@ int  mellow_generate_rules(mellow_engine_t* e, const mellow_logit_rules_t* rules
  * armed on the context (it uses the context's bias buffer).  Errors as above, and a null buffer, B <= 0 or ld outside [0, 8192]. */
 int  mellow_logit_rules_apply(mellow_engine_t* e, const mellow_logit_rules_t* rules, float* logits, int B, const int32_t* history, int ld,
                               const int32_t* hist_len, int stop_id, float* cand_val, int32_t* cand_idx, float* cand_sum);
+/* Constrained decoding: every answer of a call is held to a set of phrases (token-id sequences) on the device, inside the decode step --
+ * for the prefill's first token as for every decode step, and for every picker (arg-max, sampler, beam select).
+ *
+ * Constraint data.  Every answer row of the call has a root node in one shared trie arena:
+ *   node_first[n_nodes + 1]  offsets into the edge arrays: the edges of node u are [node_first[u], node_first[u + 1]);
+ *   node_flags[n_nodes]      bit 0 = terminal: a phrase ends here;
+ *   edge_token[n_edges], edge_child[n_edges];
+ *   row_root[n_rows]         n_rows = the row count N of the armed call's out_tokens;
+ *   then_free                0 or 1.
+ * The edges of a node are sorted by token, strictly ascending.  Every child > its parent, so the arena is acyclic.  A root is never
+ * terminal: there are no empty phrases.  n_nodes, n_edges and n_rows are at most 1 << 20 (n_nodes and n_rows at least 1).
+ *
+ * State of a row.  A row that has generated h[0 .. s) is in one of four kinds of state: a node index u >= 0, DEAD (-1), FREE (-2) or
+ * DONE (-3).  The state starts at row_root[row].  On token t the transition from u is:
+ *   1. if u has an edge for t: the child c -- with then_free and c terminal: FREE instead;
+ *   2. otherwise, if t == stop_id, stop_id >= 0 and u is terminal: DONE;
+ *   3. otherwise DEAD.
+ * DEAD, FREE and DONE absorb.  An edge wins over the stop rule.  The history is the row's GENERATED tokens, as for the rules: a beam
+ * row's history is its hypothesis, not its slot's past.
+ *
+ * Allowed set.  node u: the edge tokens of u, plus stop_id if u is terminal and stop_id >= 0.  DEAD, DONE: {stop_id} if stop_id >= 0,
+ * else empty.  FREE: everything.  An empty allowed set constrains nothing, so no row is ever banned whole.
+ *
+ * Effect on the row.  For a row whose allowed set is everything, or empty, the launch returns without touching it: the logits and the
+ * tile partials stay byte-identical to what the head (or the guidance, or the rules) left.  For any other row l[v] = -inf for every v
+ * outside the set; allowed values keep their bits; the row's tile partials are formed anew from the processed values (a tile banned
+ * whole has maximum -inf and sums to exactly 0).
+ *
+ * Order in the step: guidance, then rules, then the constraint, then top log-probs, then the picker.  A recorded log-prob
+ * (mellow_generate_scored, _n, _q, the lp table of mellow_generate_beam) and the top log-probs are those of the CONSTRAINED row: over
+ * the phrase set (with the stop id) they multiply along the trie to probabilities that sum to 1.  Two consequences: they are NOT the
+ * numbers mellow_score returns for the same answers; and min_new_tokens together with a set whose phrases are shorter can leave only
+ * banned tokens before the constraint runs -- as with the rules, a row in which every token is banned is the caller's error.
+ * A phrase that holds the stop id itself is followed like any other (the edge wins), so "phrase p, then stop" and a longer phrase
+ * "p, stop id, ..." are then one path: keep the stop id out of the phrases if the probabilities are to sum to 1.
+ * With then_free = 1 the set constrains only the start of an answer (a one-phrase set is a forced prefix): once a phrase is complete
+ * the row is FREE and continues unconstrained; without it a row that has completed a phrase may only continue along the trie or stop.
+ *
+ * mellow_generate_constraint arms the constraint for the NEXT mellow_generate* call on this context (mellow_generate, _sampled,
+ * _scored, _n, _q, _beam all honour it, in every precision, with and without armed rules, guidance, top log-probs and filters); NULL
+ * disarms.  That call takes it at entry and clears it whatever its outcome.  A fork has a constraint of its own, initially none.  The
+ * arrays (host or device memory) are copied into engine-owned buffers when the constraint is armed.  n_rows must equal the call's row
+ * count -- B, B * n, B * Q, B * k, or 2 P for a guided call, whose two rows of a pair carry the same root -- else the call fails; a
+ * call of more than 1024 rows advances through row_root pass by pass.  That a constraint is armed is part of the captured step's key,
+ * the trie's contents and counts are not.  A call without an armed constraint launches exactly what it launched before these symbols
+ * existed.
+ * Errors (host code, before any device is touched, in this order): a `size` other than sizeof(mellow_constraint_t); a negative count
+ * or one over its limit (and a null array, a then_free other than 0 or 1, a node_first that does not run from 0 to n_edges without
+ * decreasing); unsorted edges; a child <= its parent or out of range; a root out of range or terminal; a token outside [0, 49152).
+ * Then a null or unfinalized engine; then a vocabulary other than 49152 (the row tiling of the sampler).
+ * Added while the minor was 5 without raising it: a binding detects the two symbols by lookup. */
+typedef struct mellow_constraint {
+    int32_t size;                 /* sizeof(mellow_constraint_t) */
+    int32_t n_nodes;              /* 1 .. 1 << 20 */
+    int32_t n_edges;              /* 0 .. 1 << 20 */
+    const int32_t* node_first;    /* [n_nodes + 1] */
+    const int32_t* node_flags;    /* [n_nodes], bit 0 = terminal */
+    const int32_t* edge_token;    /* [n_edges] */
+    const int32_t* edge_child;    /* [n_edges] */
+    int32_t n_rows;               /* 1 .. 1 << 20: the rows of the armed call */
+    const int32_t* row_root;      /* [n_rows] */
+    int32_t then_free;            /* 0 or 1 */
+} mellow_constraint_t;
+int  mellow_generate_constraint(mellow_engine_t* e, const mellow_constraint_t* c);
+/* The same launch on caller data, no loop state (numeric tap); the arguments are those of mellow_logit_rules_apply, with
+ * c->n_rows == B: logits dev f32 [B][vocab], edited in place; history dev i32 [B][ld] (ld <= 8192) with hist_len dev i32 [B] tokens
+ * of every row; the row's state is its root advanced by one transition per history token, and goes to out_state dev i32 [B] (may be
+ * NULL).  cand_val / cand_idx / cand_sum (may be NULL) dev [B][vocab / 32] receive the tile partials of a constrained row; those of a
+ * row whose allowed set is everything, or empty, are left as they are, like its logits.  It works on copies of its own and leaves
+ * whatever is armed on the context as it is.  Errors as above, and a null buffer, B <= 0, c->n_rows != B or ld outside [0, 8192]. */
+int  mellow_constraint_apply(mellow_engine_t* e, const mellow_constraint_t* c, float* logits, int B, const int32_t* history, int ld,
+                             const int32_t* hist_len, int stop_id, float* cand_val, int32_t* cand_idx, float* cand_sum, int32_t* out_state);
 /* Contrastive (classifier-free) guidance: the step's distribution is contrasted with that of a NEGATIVE input on the device, inside
  * the decode step, between the lm_head and the rules launch / the kernel that picks the token -- for the prefill's first token as for
  * every decode step.

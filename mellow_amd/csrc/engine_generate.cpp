@@ -27,12 +27,15 @@ struct GenRequest {
     Guidance guide;                              // contrastive guidance (mellow_generate_guidance): likewise; rows 2p and 2p + 1 are then pair p
     TopLogprobs top;                             // top log-probs (mellow_generate_top_logprobs): likewise; the record [rows][max_len][k] advances with the passes
     SampleFilters filters;                       // top_k / min_p (mellow_generate_filters): likewise, the same for every pass
+    Constraint con;                              // constrained decoding (mellow_generate_constraint): likewise; the roots advance with the passes
+    int con_row0 = 0;                            // ... the first row of this pass among the roots of the call
     int rows() const { return examples * n * q; }
     // rows [r0, r0 + nb) of an n = 1, q = 1 request as a request of their own; a row's random stream follows its index in the whole call
     GenRequest pass(int r0, int nb, int text_len, int32_t* steps, float* ftm) const {
         GenRequest p = *this;
         p.audio1 += (size_t)r0 * n_samples; p.audio2 += (size_t)r0 * n_samples; p.input_ids += (size_t)r0 * text_len;
         p.examples = nb; p.row_offset += guide.on ? r0 >> 1 : r0;      // (guided: r0 is even, and the streams go by pair)
+        p.con_row0 += r0;
         p.out_tokens += (size_t)r0 * max_len;
         if (out_logprob) p.out_logprob += (size_t)r0 * max_len;
         if (top.k) { p.top.ids += (size_t)r0 * max_len * top.k; p.top.lp += (size_t)r0 * max_len * top.k; }
@@ -104,6 +107,66 @@ static int stage_rules(mellow_engine_t* e, const LogitRules& r, int stop_id) {
     memcpy(&w[RUL_THETA], &r.theta, 4);
     w[RUL_NGRAM] = (uint32_t)r.ngram; w[RUL_MIN_NEW] = (uint32_t)r.min_new; w[RUL_BIAS_ON] = r.bias ? 1u : 0u; w[RUL_STOP] = (uint32_t)stop_id;
     HIPCHK(hipMemcpyAsync(e->d_rparams, e->h_rparams, sizeof(e->h_rparams), hipMemcpyHostToDevice, e->stream));
+    return 0;
+}
+
+// `n` int32 words of host or device memory -> host memory
+static int fetch_words(int32_t* dst, const int32_t* src, size_t n) {
+    if (n == 0) return 0;
+    hipPointerAttribute_t at;
+    const bool on_device = hipPointerGetAttributes(&at, src) == hipSuccess && at.type == hipMemoryTypeDevice;
+    if (!on_device) {
+        (void)hipGetLastError();                  // a plain host pointer is not an error here
+        memcpy(dst, src, n * sizeof(int32_t));
+        return 0;
+    }
+    HIPCHK(hipMemcpy(dst, src, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// The value rules of a mellow_constraint_t, each once and in the order the header states (mellow_generate_constraint and
+// mellow_constraint_apply): host code only, no engine needed.  -> the arena as the kernel reads it (kernels.h ConstrainArgs::trie)
+// and the roots, in host memory.
+static int check_constraint(const mellow_constraint_t* c, std::vector<int32_t>* arena, std::vector<int32_t>* roots) {
+    if (c->size != (int32_t)sizeof(mellow_constraint_t))
+        return fail("mellow_constraint_t.size is %d, this library's struct has %d bytes", (int)c->size, (int)sizeof(mellow_constraint_t));
+    const int nn = c->n_nodes, ne = c->n_edges, nr = c->n_rows;
+    if (nn < 1 || ne < 0 || nr < 1 || nn > CON_MAX_COUNT || ne > CON_MAX_COUNT || nr > CON_MAX_COUNT)
+        return fail("constraint counts: n_nodes %d, n_rows %d must be 1 to %d and n_edges %d 0 to %d", nn, nr, CON_MAX_COUNT, ne, CON_MAX_COUNT);
+    if (!c->node_first || !c->node_flags || !c->row_root || (ne > 0 && (!c->edge_token || !c->edge_child))) return fail("constraint: null array");
+    if (c->then_free != 0 && c->then_free != 1) return fail("constraint: then_free must be 0 or 1 (got %d)", (int)c->then_free);
+    arena->assign((size_t)2 * nn + 1 + 2 * (size_t)ne, 0);
+    roots->assign((size_t)nr, 0);
+    int32_t *first = arena->data(), *flags = first + nn + 1, *tok = flags + nn, *child = tok + ne;
+    CHK(fetch_words(first, c->node_first, (size_t)nn + 1));
+    CHK(fetch_words(flags, c->node_flags, (size_t)nn));
+    CHK(fetch_words(tok, c->edge_token, (size_t)ne));
+    CHK(fetch_words(child, c->edge_child, (size_t)ne));
+    CHK(fetch_words(roots->data(), c->row_root, (size_t)nr));
+    if (first[0] != 0 || first[nn] != ne) return fail("constraint: node_first must run from 0 to n_edges = %d (got %d .. %d)", ne, (int)first[0], (int)first[nn]);
+    for (int u = 0; u < nn; ++u)
+        if (first[u + 1] < first[u]) return fail("constraint: node_first decreases at node %d", u);
+    for (int u = 0; u < nn; ++u)
+        for (int e = first[u] + 1; e < first[u + 1]; ++e)
+            if (tok[e] <= tok[e - 1]) return fail("constraint: the edges of node %d are not sorted by token, strictly ascending (%d after %d)", u, (int)tok[e], (int)tok[e - 1]);
+    for (int u = 0; u < nn; ++u)
+        for (int e = first[u]; e < first[u + 1]; ++e)
+            if (child[e] <= u || child[e] >= nn) return fail("constraint: node %d has child %d; every child is > its parent and < n_nodes = %d", u, (int)child[e], nn);
+    for (int r = 0; r < nr; ++r) {
+        const int u = (*roots)[r];
+        if (u < 0 || u >= nn) return fail("constraint: row_root[%d] = %d is outside [0, n_nodes = %d)", r, u, nn);
+        if (flags[u] & 1) return fail("constraint: row_root[%d] = node %d is terminal, a root never is (no empty phrase)", r, u);
+    }
+    for (int e = 0; e < ne; ++e)
+        if (tok[e] < 0 || tok[e] >= SAMPLE_MAX_V) return fail("constraint: edge token %d is outside the vocabulary [0, %d)", (int)tok[e], SAMPLE_MAX_V);
+    return 0;
+}
+
+// the value block a constraint launch reads, into `dst` (device)
+static int stage_constraint(mellow_engine_t* e, const Constraint& c, int stop_id, float* dst) {
+    uint32_t* w = e->h_cparams;
+    w[CON_STOP] = (uint32_t)stop_id; w[CON_THEN_FREE] = c.then_free ? 1u : 0u; w[CON_NODES] = (uint32_t)c.n_nodes; w[CON_EDGES] = (uint32_t)c.n_edges;
+    HIPCHK(hipMemcpyAsync(dst, e->h_cparams, sizeof(e->h_cparams), hipMemcpyHostToDevice, e->stream));
     return 0;
 }
 
@@ -185,6 +248,12 @@ static int check_request(mellow_engine_t* e, const GenRequest& r, int door) {
     if (r.rules.on) {
         if (e->cfg.vocab_size != SAMPLE_MAX_V) return fail("the logit rules are built for a vocabulary of %d (engine: %d)", SAMPLE_MAX_V, e->cfg.vocab_size);
         if (r.max_len > RULES_MAX_HIST) return fail("a call with logit rules takes max_len <= %d, the history one row stages (got %d)", RULES_MAX_HIST, r.max_len);
+    }
+    if (r.con.on) {
+        if (e->cfg.vocab_size != SAMPLE_MAX_V) return fail("the constraint kernel is built for a vocabulary of %d (engine: %d)", SAMPLE_MAX_V, e->cfg.vocab_size);
+        if (r.con.n_rows != r.rows())
+            return fail("a constraint is armed (mellow_generate_constraint) with n_rows = %d: this call has %d rows (B, B * n, B * Q, B * k, or both rows of every guided pair)",
+                        r.con.n_rows, r.rows());
     }
     return 0;
 }
@@ -347,6 +416,7 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
     m.guide = r.guide.on;               // dec_guidance_kernel combines the stored rows of a pair: the head stores them (apply_step_mode)
     m.top = r.top.k;                    // dec_top_logprobs_kernel reads the stored rows: the head stores them (apply_step_mode)
     m.filtered = r.filters.on;          // dec_sample_kernel in its filtered instantiation; the values travel in d_sparams
+    m.constrain = r.con.on;             // dec_constrain_kernel edits the stored rows: the head stores them (apply_step_mode)
     m.early_exit = !r.beam && (dev_dead || (!r.ignore_stop && e->da.RB > 1));
     // a guided call runs without migration (a pair's rows stay neighbours in slots 2p, 2p + 1); block exit stays: both rows of a
     // pair get the same token, so they finish at the same step, and a pair never straddles a 32-row block
@@ -370,6 +440,8 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
         CHK(ensure(e, e->rules_bias, SAMPLE_MAX_V));
         if (r.beam) CHK(ensure(e, e->rules_hist, (size_t)2 * B * max_len));
     }
+    // value block, roots and state of the pass: one buffer of fixed size, so a captured launch finds it where it was (StepGraphs::Key)
+    if (m.constrain) CHK(ensure(e, e->con_ws, CON_WORDS + (size_t)3 * CON_STATE_ROWS));
     // the pass runs in its mode; the taps' defaults are back on every way out (the taps never sample, record nor exit early)
     struct ModeScope { mellow_engine* e; ~ModeScope() { apply_step_mode(e, StepMode()); } } mode_scope{e};
     apply_step_mode(e, m);
@@ -379,6 +451,11 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
     }
     if (r.rules.on) CHK(stage_rules(e, r.rules, stop_id));
     if (r.guide.on) CHK(stage_guidance(e, r.guide.scale));
+    if (r.con.on) {
+        // the roots of this pass's rows go to the front of the pass's words; the state needs no clearing (step 0 writes the roots)
+        CHK(stage_constraint(e, r.con, stop_id, e->con_ws.p));
+        HIPCHK(hipMemcpyAsync(e->con_ws.p + CON_WORDS, e->con_roots.p + r.con_row0, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    }
     if (dev_dead) {
         HIPCHK(hipMemsetAsync(e->d_blk_left, 0, 96 * sizeof(int32_t), s));
     } else if (m.early_exit) {
@@ -498,7 +575,7 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
     return 0;
 }
 
-// What mellow_generate_rules / _guidance / _top_logprobs / _filters armed on the context serves ONE mellow_generate* call, whatever its outcome:
+// What mellow_generate_rules / _guidance / _top_logprobs / _filters / _constraint armed on the context serves ONE mellow_generate* call, whatever its outcome:
 // taken into that call's request, cleared on the context
 static void take_armed(mellow_engine_t* e, GenRequest& r) {
     if (!e) return;
@@ -506,6 +583,7 @@ static void take_armed(mellow_engine_t* e, GenRequest& r) {
     r.guide = e->guide_armed; e->guide_armed = Guidance();
     r.top = e->top_armed; e->top_armed = TopLogprobs();
     r.filters = e->filters_armed; e->filters_armed = SampleFilters();
+    r.con = e->con_armed; e->con_armed = Constraint();
 }
 
 // The reference's loop (wrapper.py:216-249) takes any number of examples.  One pass of the engine takes up to 1024 rows (32 row
@@ -636,6 +714,52 @@ int mellow_generate_rules(mellow_engine_t* e, const mellow_logit_rules_t* rules)
     LogitRules a;
     CHK(load_rules(e, rules, &a));
     e->rules_armed = a;
+    return 0;
+}
+
+int mellow_generate_constraint(mellow_engine_t* e, const mellow_constraint_t* c) {
+    std::vector<int32_t> arena, roots;
+    if (c) CHK(check_constraint(c, &arena, &roots));
+    if (!e || !e->finalized) return fail("engine not finalized");
+    e->con_armed = Constraint();
+    if (!c) return 0;
+    if (e->cfg.vocab_size != SAMPLE_MAX_V) return fail("the constraint kernel is built for a vocabulary of %d (engine: %d)", SAMPLE_MAX_V, e->cfg.vocab_size);
+    HIPCHK(hipSetDevice(e->device));
+    CHK(ensure(e, e->con_trie, arena.size()));
+    CHK(ensure(e, e->con_roots, roots.size()));
+    HIPCHK(hipMemcpyAsync(e->con_trie.p, arena.data(), arena.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->con_roots.p, roots.data(), roots.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));         // the host copies are free again on return
+    e->con_armed.on = true; e->con_armed.then_free = c->then_free != 0;
+    e->con_armed.n_nodes = c->n_nodes; e->con_armed.n_edges = c->n_edges; e->con_armed.n_rows = c->n_rows;
+    return 0;
+}
+
+// the constraint launch on caller data, on copies of its own: what is armed on the context stays
+int mellow_constraint_apply(mellow_engine_t* e, const mellow_constraint_t* c, float* logits, int B, const int32_t* history, int ld,
+                            const int32_t* hist_len, int stop_id, float* cand_val, int32_t* cand_idx, float* cand_sum, int32_t* out_state) {
+    std::vector<int32_t> arena, roots;
+    if (c) CHK(check_constraint(c, &arena, &roots));
+    if (!e || !e->finalized) return fail("engine not finalized");
+    if (!c || !logits || !hist_len || !cand_val || !cand_idx || B <= 0 || ld < 0 || (ld > 0 && !history)) return fail("bad argument");
+    if (c->n_rows != B) return fail("mellow_constraint_apply: the constraint has n_rows = %d for B = %d rows", (int)c->n_rows, B);
+    if (ld > RULES_MAX_HIST) return fail("mellow_constraint_apply takes histories of at most %d tokens (ld = %d)", RULES_MAX_HIST, ld);
+    if (e->cfg.vocab_size != SAMPLE_MAX_V) return fail("the constraint kernel is built for a vocabulary of %d (engine: %d)", SAMPLE_MAX_V, e->cfg.vocab_size);
+    HIPCHK(hipSetDevice(e->device));
+    CHK(ensure(e, e->con_tap, CON_WORDS + (size_t)B + arena.size()));
+    Constraint a;
+    a.on = true; a.then_free = c->then_free != 0; a.n_nodes = c->n_nodes; a.n_edges = c->n_edges; a.n_rows = B;
+    CHK(stage_constraint(e, a, stop_id, e->con_tap.p));
+    int32_t* ws = reinterpret_cast<int32_t*>(e->con_tap.p);
+    HIPCHK(hipMemcpyAsync(ws + CON_WORDS, roots.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(ws + CON_WORDS + B, arena.data(), arena.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    ConstrainArgs g;
+    g.logits = logits; g.ld = e->cfg.vocab_size; g.prm = reinterpret_cast<const uint32_t*>(ws); g.row_root = ws + CON_WORDS; g.trie = ws + CON_WORDS + B;
+    g.cand_val = cand_val; g.cand_idx = cand_idx; g.cand_sum = cand_sum;
+    g.hist = history; g.hist_ld = ld; g.hist_len = hist_len; g.out_state = out_state;
+    launch_dec_constrain(g, B, e->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->stream));
     return 0;
 }
 

@@ -142,6 +142,7 @@ struct StepMode {
     bool guide = false;          // contrastive guidance: dec_guidance_kernel after the head, before the rules launch (forces `logits` on; rows 2p, 2p + 1 are a pair)
     bool filtered = false;       // top_k / min_p: dec_sample_kernel in its filtered instantiation (needs `sample`)
     int top = 0;                 // k >= 1: dec_top_logprobs_kernel after the rules launch, before the picker (forces `logits` on; needs `logprob`)
+    bool constrain = false;      // constrained decoding: dec_constrain_kernel after the rules launch, before the top log-probs and the picker (forces `logits` on)
 };
 // The top log-probs record of one generation call (include/mellow_hip.h, mellow_generate_top_logprobs): armed on the context, taken
 // into the call's GenRequest at entry.  ids / lp are the caller's [rows][max_len][k], host or device.
@@ -170,6 +171,14 @@ struct LogitRules {
     float theta = 1.f;
     int ngram = 0, min_new = 0;
     bool bias = false;
+};
+
+// The constraint of one generation call (include/mellow_hip.h, mellow_generate_constraint): armed on the context, taken into the
+// call's GenRequest at entry.  The trie and the roots of all rows live in the context's con_trie / con_roots buffers.
+struct Constraint {
+    bool on = false;
+    bool then_free = false;
+    int n_nodes = 0, n_edges = 0, n_rows = 0;
 };
 
 // One execution context.  `opt` and `w` are what a fork shares with its parent (copied whole by mellow_engine_fork); the rest is its own.
@@ -244,7 +253,7 @@ struct mellow_engine {
     // d_params, the sampling parameters in d_sparams).  generate_pass (engine_generate.cpp) captures, ensure_lm invalidates.
     struct LOCAL StepGraphs {
         struct Key {
-            std::array<uintptr_t, 22> v{};       // all zero: no capture (a pass has at least one row)
+            std::array<uintptr_t, 25> v{};       // all zero: no capture (a pass has at least one row)
             static Key of(const mellow_engine* e, int B);      // from the engine as configured for the pass (below the engine)
             bool operator==(const Key& k) const { return v == k.v; }
         };
@@ -315,6 +324,13 @@ struct mellow_engine {
     // repetition controls, created on first use: the call's dense logit bias [vocab] (a copy: no caller pointer is ever captured),
     // and the ping-pong history of a beam call [2][rows][max_len] int32 (logit_rules.hip)
     Buf rules_bias, rules_hist;
+    Constraint con_armed;                      // mellow_generate_constraint: what the NEXT mellow_generate* call on this context takes (and clears)
+    // constrained decoding, created on first use (copies: no caller pointer is ever captured): the armed trie arena (kernels.h
+    // ConstrainArgs::trie) and the roots of all rows of the call; the words of a pass, of fixed size so that their address never
+    // changes -- value block [CON_WORDS] | roots of the pass's rows [1024] | state ping-pong [2][1024]; the tap's own copies --
+    // value block | roots | arena -- so that mellow_constraint_apply leaves what is armed as it is
+    Buf con_trie, con_roots, con_ws, con_tap;
+    uint32_t h_cparams[CON_WORDS] = {0};       // staging of the value block (kernels.h CON_*)
     StepMode mode;                             // what apply_step_mode last set (run_lm_head, loop_args and StepGraphs::Key::of read it)
     int32_t h_blk[64] = {0};                   // staging of d_blk_left[32] | d_blk_live[32]
     std::vector<int32_t> h_ident;              // staging of d_row_of_slot
@@ -386,7 +402,10 @@ inline mellow_engine::StepGraphs::Key mellow_engine::StepGraphs::Key::of(const m
                 (uintptr_t)e->mode.top,            // top log-probs: dec_top_logprobs_kernel in the step and its k (a launch argument); the head with its logits store
                 (uintptr_t)(e->mode.top ? e->top_ids.p : nullptr),           // ... its record: TopArgs
                 (uintptr_t)(e->mode.top ? e->top_lp.p : nullptr),
-                (uintptr_t)e->mode.filtered}};     // top_k / min_p: dec_sample_kernel's filtered instantiation (the values are in the SMP_* block)
+                (uintptr_t)e->mode.filtered,       // top_k / min_p: dec_sample_kernel's filtered instantiation (the values are in the SMP_* block)
+                (uintptr_t)e->mode.constrain,      // constrained decoding: dec_constrain_kernel in the step; the head with its logits store
+                (uintptr_t)(e->mode.constrain ? e->con_trie.p : nullptr),      // ... the trie arena: ConstrainArgs (its contents and counts are not baked in)
+                (uintptr_t)(e->mode.constrain ? e->con_ws.p : nullptr)}};      // ... value block, roots and state of the pass: ConstrainArgs
 }
 static_assert(!std::is_copy_constructible<mellow_engine::Buf>::value, "a Buf owns its device memory: it moves, it is never copied");
 static_assert(std::is_copy_assignable<mellow_engine::Weights>::value && std::is_copy_assignable<mellow_engine::Options>::value, "a fork copies these by assignment: no owning member (Buf, StepGraphs) belongs in them");
@@ -496,6 +515,8 @@ int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec)
 BeamArgs beam_args(mellow_engine* e, int N, int k);
 // the rules launch of a generation step on B rows, from the engine as apply_step_mode configured it (engine_lm.cpp)
 RulesArgs rules_args(mellow_engine* e, int B);
+// the constraint launch of a generation step on B rows, likewise
+ConstrainArgs constrain_args(mellow_engine* e, int B);
 // the guidance launch of a generation step, from the engine as apply_step_mode configured it (engine_lm.cpp)
 GuideArgs guide_args(mellow_engine* e);
 // the top log-probs launch of a generation step, from the engine as apply_step_mode configured it (engine_lm.cpp)

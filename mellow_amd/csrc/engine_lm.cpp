@@ -104,7 +104,7 @@ int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end, int prefill
 void apply_step_mode(mellow_engine* e, const StepMode& m) {
     e->mode = m;
     DecArgs& a = e->da;
-    e->mode.logits = m.logits || m.rules || m.guide || m.top > 0;   // the rules and the guidance edit the stored rows, the top log-probs read them
+    e->mode.logits = m.logits || m.rules || m.guide || m.top > 0 || m.constrain;   // the rules, the guidance and the constraint edit the stored rows, the top log-probs read them
     a.logits = e->mode.logits ? e->dlogits.p : nullptr;      // (off: generation's arg-max needs the candidates only, no 6 MB store per step)
     a.cand_sum = m.logprob ? e->cand_sum.p : nullptr;
     a.blk_live = m.early_exit ? e->d_blk_live : nullptr;
@@ -166,6 +166,24 @@ RulesArgs rules_args(mellow_engine* e, int B) {
     return g;
 }
 
+ConstrainArgs constrain_args(mellow_engine* e, int B) {
+    const LoopArgs lp = loop_args(e);
+    int32_t* ws = reinterpret_cast<int32_t*>(e->con_ws.p);
+    ConstrainArgs g;
+    g.logits = e->da.logits; g.ld = e->cfg.vocab_size; g.prm = reinterpret_cast<const uint32_t*>(ws);
+    g.trie = reinterpret_cast<const int32_t*>(e->con_trie.p); g.row_root = ws + CON_WORDS; g.state = ws + CON_WORDS + CON_STATE_ROWS;
+    g.cand_val = e->da.cand_val; g.cand_idx = e->da.cand_idx; g.cand_sum = e->da.cand_sum;
+    g.d_pos = e->d_pos; g.params = lp.params; g.T0 = lp.T0;
+    g.row_of_slot = lp.row_of_slot; g.blk_snap = lp.blk_snap;
+    if (e->mode.beam) {
+        const BeamArgs bm = beam_args(e, B, e->mode.beam);
+        g.parent_tab = bm.out_parent; g.token_tab = bm.out_token; g.N = B; g.k = e->mode.beam;
+    } else {
+        g.hist = lp.out_tokens;
+    }
+    return g;
+}
+
 GuideArgs guide_args(mellow_engine* e) {
     const LoopArgs lp = loop_args(e);
     GuideArgs g;
@@ -202,7 +220,11 @@ int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec)
         ProfScope ps(e, PF_MISC, 0, 2.0 * B * e->cfg.vocab_size * 4);
         launch_dec_logit_rules(rules_args(e, B), B, e->stream);
     }
-    if (e->mode.top && rec) {        // top log-probs: exactly the row the picker below reads, after the guidance and the rules
+    if (e->mode.constrain && rec) {  // constrained decoding: tokens outside the row's allowed set are banned after the rules, before the top log-probs and any picker
+        ProfScope ps(e, PF_MISC, 0, 2.0 * B * e->cfg.vocab_size * 4);
+        launch_dec_constrain(constrain_args(e, B), B, e->stream);
+    }
+    if (e->mode.top && rec) {        // top log-probs: exactly the row the picker below reads, after the guidance, the rules and the constraint
         ProfScope ps(e, PF_MISC, 0, 1.0 * B * e->cfg.vocab_size * 4);
         launch_dec_top_logprobs(top_args(e), B, e->stream);
     }

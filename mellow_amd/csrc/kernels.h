@@ -390,6 +390,45 @@ struct TopArgs {
     const int32_t* blk_snap = nullptr;
 };
 void launch_dec_top_logprobs(const TopArgs& g, int B, hipStream_t s);
+// Constrained decoding (constrain.hip; include/mellow_hip.h mellow_generate_constraint states the exact definition): one launch after
+// the rules launch and before the top log-probs and the picker.  Every row walks a trie of allowed phrases by ONE transition per step
+// (its state is one int), every token outside the state's allowed set is set to -inf and the row's tile partials are formed anew; a
+// row whose allowed set is everything, or empty, is not touched.  The trie is one arena of int32 words the kernel slices by the
+// counts of the value block, so a captured step serves any trie that lives in the same buffer:
+// trie = node_first [n_nodes + 1] | node_flags [n_nodes] | edge_token [n_edges] | edge_child [n_edges];
+// prm = {stop id, then_free, n_nodes, n_edges}.
+enum { CON_STOP = 0, CON_THEN_FREE, CON_NODES, CON_EDGES, CON_WORDS = 8 };
+enum { CON_DEAD = -1, CON_FREE = -2, CON_DONE = -3 };      // the states of a row that are no node
+constexpr int CON_MAX_COUNT = 1 << 20;   // nodes, edges and rows of one constraint
+constexpr int CON_STATE_ROWS = 1024;     // rows of one half of the state buffer: the rows of one pass
+struct ConstrainArgs {
+    float* logits = nullptr;             // [slots][ld] fp32, edited in place (ld = SAMPLE_MAX_V: the row tiling of the sampler)
+    int64_t ld = 0;
+    const uint32_t* prm = nullptr;       // device block of CON_WORDS words
+    const int32_t* trie = nullptr;       // the arena (above)
+    const int32_t* row_root = nullptr;   // [rows] the root node of every example row
+    float* cand_val = nullptr; int32_t* cand_idx = nullptr;   // [slots][ld / 32], rewritten for a constrained row
+    float* cand_sum = nullptr;           // [slots][ld / 32] or null
+    // the state of a row, one of two sources:
+    //   tap (hist_len != null): the root advanced once per token of hist [slots][hist_ld], hist_len [slots]; the result goes to out_state [slots];
+    //   loop: state [2][CON_STATE_ROWS] by example row; step s = *d_pos - T0 + 1 reads half (s - 1) & 1 of the parent row, advances it
+    //   by the token the last pick gave the row and writes half s & 1 (s = 0: the root).  Plain call: the parent is the row, the
+    //   token column s - 1 of the token record `hist` [rows][params[0]]; beam call (parent_tab != null): the select's tables
+    //   parent_tab / token_tab [params[0]][N], as the rules kernel resolves them
+    const int32_t* hist = nullptr;
+    int hist_ld = 0;
+    const int32_t* hist_len = nullptr;
+    int32_t* out_state = nullptr;
+    int32_t* state = nullptr;
+    const int32_t* d_pos = nullptr;
+    const int32_t* params = nullptr;     // device {max_len, stop_id} (LoopArgs::params)
+    int T0 = 0;
+    const int32_t* row_of_slot = nullptr;   // as in LoopArgs: logits and partials are addressed by slot, root, record and state by example
+    const int32_t* blk_snap = nullptr;
+    const int32_t* parent_tab = nullptr; const int32_t* token_tab = nullptr;
+    int N = 0, k = 1;
+};
+void launch_dec_constrain(const ConstrainArgs& g, int B, hipStream_t s);
 // after the arg-max of a step (early-exit mode only): if the rows that have not produced the stop id yet fit into fewer 32-row
 // blocks than are live, move them (their next-step residual rows) to the lowest slots, rewrite row_of_slot / blk_left / blk_live
 void launch_dec_compact(const DecArgs& a, int B, const LoopArgs& loop, hipStream_t s);

@@ -40,6 +40,13 @@ class LogitRules(C.Structure):
                 ("min_new_tokens", C.c_int32), ("logit_bias", C.c_void_p)]
 
 
+class Constraint(C.Structure):
+    """mellow_constraint_t (include/mellow_hip.h)"""
+    _fields_ = [("size", C.c_int32), ("n_nodes", C.c_int32), ("n_edges", C.c_int32), ("node_first", C.c_void_p),
+                ("node_flags", C.c_void_p), ("edge_token", C.c_void_p), ("edge_child", C.c_void_p), ("n_rows", C.c_int32),
+                ("row_root", C.c_void_p), ("then_free", C.c_int32)]
+
+
 class SampleFilters(C.Structure):
     """mellow_sample_filters_t (include/mellow_hip.h)"""
     _fields_ = [("size", C.c_int32), ("top_k", C.c_int32), ("min_p", C.c_float)]
@@ -82,7 +89,8 @@ _ADDED_UNDER_MINOR_4 = ("mellow_lm_score", "mellow_score", "mellow_generate_scor
 _ADDED_UNDER_MINOR_5 = ("mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_generate_rules", "mellow_logit_rules_apply",
                         "mellow_generate_guidance", "mellow_guidance_apply", "mellow_generate_top_logprobs", "mellow_top_logprobs_apply",
                         "mellow_debug_gemm_epi", "mellow_generate_filters", "mellow_sample_logits_filtered", "mellow_debug_norm",
-                        "mellow_debug_dec_attn", "mellow_debug_dec_gemv", "mellow_debug_dec_tail")
+                        "mellow_debug_dec_attn", "mellow_debug_dec_gemv", "mellow_debug_dec_tail", "mellow_generate_constraint",
+                        "mellow_constraint_apply")
 
 
 def load_library(path: Optional[str] = None):
@@ -125,6 +133,8 @@ def load_library(path: Optional[str] = None):
         "mellow_sample_logits_filtered": (ci, [vp, vp, ci, vp, ci, cf, cf, C.c_uint64, P(SampleFilters), vp]),
         "mellow_generate_rules": (ci, [vp, P(LogitRules)]),
         "mellow_logit_rules_apply": (ci, [vp, P(LogitRules), vp, ci, vp, ci, vp, ci, vp, vp, vp]),
+        "mellow_generate_constraint": (ci, [vp, P(Constraint)]),
+        "mellow_constraint_apply": (ci, [vp, P(Constraint), vp, ci, vp, ci, vp, ci, vp, vp, vp, vp]),
         "mellow_generate_guidance": (ci, [vp, cf]),
         "mellow_guidance_apply": (ci, [vp, cf, vp, ci, vp, vp, vp]),
         "mellow_generate_top_logprobs": (ci, [vp, ci, vp, vp]),
@@ -194,7 +204,7 @@ EXPORTED_SYMBOLS = (
     "mellow_engine_num_required", "mellow_engine_required_key", "mellow_generate", "mellow_generate_sampled", "mellow_sample_logits", "mellow_logmel",
     "mellow_encode", "mellow_prefix", "mellow_lm_prefill", "mellow_lm_decode_step", "mellow_argmax", "mellow_embed_tokens", "mellow_lm_forward_logits",
     "mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse", "mellow_generate_n", "mellow_generate_q",
-    "mellow_generate_beam", "mellow_beam_select", "mellow_generate_rules", "mellow_logit_rules_apply", "mellow_generate_guidance", "mellow_guidance_apply", "mellow_generate_top_logprobs", "mellow_top_logprobs_apply", "mellow_generate_filters", "mellow_sample_logits_filtered", "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
+    "mellow_generate_beam", "mellow_beam_select", "mellow_generate_rules", "mellow_logit_rules_apply", "mellow_generate_constraint", "mellow_constraint_apply", "mellow_generate_guidance", "mellow_guidance_apply", "mellow_generate_top_logprobs", "mellow_top_logprobs_apply", "mellow_generate_filters", "mellow_sample_logits_filtered", "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
     "mellow_prof_num_families", "mellow_prof_family_name", "mellow_prof_get", "mellow_last_phase_ms", "mellow_last_steps_enqueued", "mellow_last_row_repacks", "mellow_stft_is_fft", "mellow_prefill_parts", "mellow_abi_minor",
     "mellow_resample", "mellow_engine_set_precision", "mellow_engine_set_option", "mellow_engine_describe", "mellow_debug_gemm_fp8", "mellow_debug_gemm_f32", "mellow_debug_gemm_epi", "mellow_debug_norm", "mellow_debug_dec_attn", "mellow_debug_dec_gemv", "mellow_debug_dec_tail", "mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_debug_dec_head", "mellow_set_graph", "mellow_host_window_map", "mellow_host_pack_weight", "mellow_host_rope_tables",
 )
@@ -369,15 +379,23 @@ def has_question_axis(input_ids) -> bool:
 class _CallOptions:
     """What one generate() call arms before EVERY C call it makes (an armed record serves the next mellow_generate* call only): the
     rules struct or None (it keeps its bias vector alive), the guidance scale or None, the k of top_logprobs, the sampler's filters
-    struct (top_k / min_p of the draw) or None.  Built once per call and handed to the route that runs it; nothing of a call is kept
-    on the engine."""
-    __slots__ = ("rules", "guide", "top_k", "filters")
+    struct (top_k / min_p of the draw) or None, the constraint (_CallConstraint) or None.  Built once per call and handed to the route
+    that runs it; nothing of a call is kept on the engine."""
+    __slots__ = ("rules", "guide", "top_k", "filters", "constraint")
 
-    def __init__(self, rules, guide, top_k, filters=None):
-        self.rules, self.guide, self.top_k, self.filters = rules, guide, top_k, filters
+    def __init__(self, rules, guide, top_k, filters=None, constraint=None):
+        self.rules, self.guide, self.top_k, self.filters, self.constraint = rules, guide, top_k, filters, constraint
 
-    def arm(self, engine, top):
-        """arm the engine's context for its next C call; top = the rows of the top record that call fills (ids, log-probs), or None"""
+    def expand_constraint(self, examples: int, per_example: int):
+        """the route knows its rows: `per_example` consecutive answer rows of every example carry the example's root"""
+        if self.constraint is not None:
+            self.constraint.expand(examples, per_example)
+
+    def arm(self, engine, top, row0: int = 0, rows: Optional[int] = None):
+        """arm the engine's context for its next C call; top = the rows of the top record that call fills (ids, log-probs), or None;
+        rows [row0, row0 + rows) of the generate() call are the rows of that C call (the constraint arms their roots)"""
+        if self.constraint is not None:
+            engine._chk(engine.lib.mellow_generate_constraint(engine.h, C.byref(self.constraint.struct(row0, rows))))
         if self.rules is not None:
             engine._chk(engine.lib.mellow_generate_rules(engine.h, C.byref(self.rules)))
         if self.guide is not None:
@@ -386,6 +404,34 @@ class _CallOptions:
             engine._chk(engine.lib.mellow_generate_top_logprobs(engine.h, int(self.top_k), _ptr(top[0]), _ptr(top[1])))
         if self.filters is not None:
             engine._chk(engine.lib.mellow_generate_filters(engine.h, C.byref(self.filters)))
+
+
+class _CallConstraint:
+    """The constraint of one generate() call: the trie arrays of constraint.build_trie over the EXAMPLES' phrase sets (it keeps them
+    alive while a struct points at them) and, once the route has expanded them, the root of every answer row."""
+    __slots__ = ("trie", "then_free", "roots", "_struct")
+
+    def __init__(self, phrases_per_example, then_free: bool, vocab: int):
+        from .constraint import build_trie
+        self.trie = build_trie(phrases_per_example, vocab)
+        self.then_free, self.roots, self._struct = bool(then_free), None, None
+
+    def expand(self, examples: int, per_example: int):
+        ex = self.trie["row_root"]
+        if ex.shape[0] != int(examples):
+            raise ValueError(f"constraint holds {ex.shape[0]} phrase sets for {int(examples)} examples: one set per example")
+        self.roots = np.ascontiguousarray(np.repeat(ex, int(per_example)), dtype=np.int32)
+
+    def struct(self, row0: int = 0, rows: Optional[int] = None) -> "Constraint":
+        assert self.roots is not None, "the route has not expanded the constraint to its rows"
+        t = self.trie
+        rows = self.roots.shape[0] - row0 if rows is None else int(rows)
+        assert 0 <= row0 and row0 + rows <= self.roots.shape[0], (row0, rows, self.roots.shape)
+        self._struct = Constraint(size=C.sizeof(Constraint), n_nodes=t["node_flags"].shape[0], n_edges=t["edge_token"].shape[0],
+                                  node_first=t["node_first"].ctypes.data, node_flags=t["node_flags"].ctypes.data,
+                                  edge_token=t["edge_token"].ctypes.data, edge_child=t["edge_child"].ctypes.data, n_rows=rows,
+                                  row_root=self.roots.ctypes.data + 4 * int(row0), then_free=1 if self.then_free else 0)
+        return self._struct
 
 
 from .taps import DebugTaps      # noqa: E402  (behind the structures above, which its methods fill in)
@@ -558,7 +604,7 @@ class Engine(DebugTaps):
                  num_beams: Optional[int] = None, length_penalty: float = 1.0, repetition_penalty: float = 1.0,
                  no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, logit_bias=None, _arm_neutral_rules: bool = False,
                  guidance_scale: float = 1.0, negative=None, keep_negative_rows: bool = False, top_logprobs: int = 0,
-                 top_k: int = 0, min_p: float = 0.0):
+                 top_k: int = 0, min_p: float = 0.0, constraint=None, constraint_then_free: bool = False):
         """-> (tokens int32 [B, steps] on host, lengths [B], steps, first_token_ms)
         num_return_sequences = n > 1 (needs do_sample=True): n sampled answers per example from one encode and one prefill per
         example (mellow_generate_n).  Every array has B * n rows, row b * n + j = answer j of example b, and holds what this call
@@ -608,7 +654,17 @@ class Engine(DebugTaps):
         likeliest token's.  Seeds, row streams, num_return_sequences, question lists, repetition controls, guidance and the log-prob
         records (which stay unfiltered) work as without them.  ValueError without do_sample=True, with num_beams, for K < 0 or p
         outside [0, 1].  Both 0 (default; Hugging Face's top_k = 50 is not adopted): nothing is armed and the call is the one without
-        the keywords."""
+        the keywords.
+        constraint = a list parallel to the EXAMPLES of phrase sets, each a list of token-id lists: constrained decoding
+        (include/mellow_hip.h, mellow_generate_constraint; mellow_amd/constraint.py builds the trie).  Every answer of an example is
+        one of its phrases followed by the stop id: tokens that do not continue a phrase are banned on the device inside the decode
+        step, after the guidance and the repetition controls and before the top log-probs and whatever chooses the token, so the
+        recorded log-probs are those of the constrained distribution (over the phrase set they sum to 1) -- not the numbers score()
+        returns.  The engine expands the sets to the call's rows (num_return_sequences, questions, beams, both rows of a guided
+        pair).  constraint_then_free=True: the set constrains only the start of the answer, which continues freely once a phrase is
+        complete (a one-phrase set is a forced prefix).  ValueError for an empty set, an empty phrase, an id outside the vocabulary
+        or a list of another length than the examples.  None (default): nothing is armed and the call is the one without the
+        keywords."""
         import time
         t_in = time.perf_counter()
         nseq = int(num_return_sequences)
@@ -640,8 +696,12 @@ class Engine(DebugTaps):
             if negative is None:
                 raise ValueError(f"guidance_scale = {gscale} needs `negative` = (audio1, audio2, input_ids): the input to contrast with")
             self._need("mellow_generate_guidance")
+        con = None
+        if constraint is not None:
+            con = _CallConstraint(constraint, constraint_then_free, self.lm.vocab_size)
+            self._need("mellow_generate_constraint")
         opts = _CallOptions(self._make_rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, logit_bias, _arm_neutral_rules, int(max_len)),
-                            gscale if gscale != 1.0 else None, topk, filters)
+                            gscale if gscale != 1.0 else None, topk, filters, con)
         if num_beams is not None:
             if do_sample:
                 raise ValueError("num_beams and do_sample=True do not combine: beam search is deterministic")
@@ -665,6 +725,7 @@ class Engine(DebugTaps):
                                        bool(ignore_stop), _seed64(seed), int(row_offset), bool(return_logprobs), t_in, opts)
         a1, a2, ids = self._f32(audio1), self._f32(audio2), self._prompt_ids(input_ids)
         rows = slice(None)
+        opts.expand_constraint(a1.shape[0], 2 if opts.guide is not None else 1)      # (both rows of a guided pair carry the example's root)
         if opts.guide is not None:
             # rows 2i / 2i + 1 = example i / its negative
             n1, n2, nids = self._f32(negative[0]), self._f32(negative[1]), self._prompt_ids(negative[2])
@@ -698,12 +759,13 @@ class Engine(DebugTaps):
         self.last_first_token_host_ms = t_up + ftm
         return self._result(out, lens, steps, ftm, lp, top, rows)
 
-    def _generate_call(self, opts, top, fn, rows, *args):
-        """ONE generation C call fn(h, *args, lens, &steps, &first_token_ms) on `rows` answer rows, armed from the call's options with
-        the rows of the top record it fills (or None) -> (lengths int32 [rows], steps, first_token_ms)"""
+    def _generate_call(self, opts, top, fn, rows, *args, row0: int = 0):
+        """ONE generation C call fn(h, *args, lens, &steps, &first_token_ms) on `rows` answer rows -- rows [row0, row0 + rows) of the
+        generate() call -- armed from the call's options with the rows of the top record it fills (or None) -> (lengths int32 [rows],
+        steps, first_token_ms)"""
         lens = (C.c_int32 * rows)()
         steps, ftm = C.c_int32(0), C.c_float(0.0)
-        opts.arm(self, top)
+        opts.arm(self, top, row0, rows)
         self._chk(fn(self.h, *args, lens, C.byref(steps), C.byref(ftm)))
         return np.asarray(list(lens), dtype=np.int32), int(steps.value), float(ftm.value)
 
@@ -768,6 +830,35 @@ class Engine(DebugTaps):
             out["cand_sum"] = cs.cpu().numpy()
         return out
 
+    def constraint_apply(self, logits, history, hist_len, constraint, then_free: bool = False, stop_id: int = 0, with_sum: bool = True):
+        """The constraint on caller data (numeric tap, mellow_constraint_apply): logits [B][vocab], history int [B][ld], hist_len int
+        [B], constraint = per ROW a list of token-id lists -> dict of numpy arrays: "logits" [B][vocab] processed, "state" int32 [B]
+        the row's state after its history (a node of constraint.build_trie(constraint), or -1 DEAD / -2 FREE / -3 DONE), "cand_val" /
+        "cand_idx" / "cand_sum" [B][vocab / 32] the tile partials (with_sum=False: no "cand_sum").  The launch leaves a row whose
+        allowed set is everything, or empty, as it is, partials included: the partials start as those of the unprocessed rows (the
+        neutral rules tap forms them)."""
+        self._need("mellow_constraint_apply")
+        lg = self._f32(logits).clone()
+        B, V = lg.shape
+        h = self._i32(history).reshape(B, -1)
+        ln = self._i32(hist_len).reshape(-1)
+        if V != self.lm.vocab_size or ln.shape[0] != B:
+            raise ValueError(f"logits {tuple(lg.shape)}, history {tuple(h.shape)}, hist_len {tuple(ln.shape)} do not describe B rows of the vocabulary")
+        con = _CallConstraint(constraint, then_free, V)
+        con.expand(B, 1)
+        ld = int(h.shape[1])
+        before = self.logit_rules_apply(lg, np.zeros((B, 1), dtype=np.int32), np.zeros(B, dtype=np.int32), stop_id=-1, with_sum=with_sum)
+        cv, cx = self._f32(before["cand_val"]).clone(), self._i32(before["cand_idx"]).clone()
+        cs = self._f32(before["cand_sum"]).clone() if with_sum else None
+        st = torch.empty((B,), dtype=torch.int32, device=self.tdev)
+        self._sync_inputs()
+        self._chk(self.lib.mellow_constraint_apply(self.h, C.byref(con.struct(0, B)), _ptr(lg), B, _ptr(h) if ld else None, ld, _ptr(ln),
+                                                   int(stop_id), _ptr(cv), _ptr(cx), None if cs is None else _ptr(cs), _ptr(st)))
+        out = {"logits": lg.cpu().numpy(), "state": st.cpu().numpy(), "cand_val": cv.cpu().numpy(), "cand_idx": cx.cpu().numpy()}
+        if cs is not None:
+            out["cand_sum"] = cs.cpu().numpy()
+        return out
+
     def guidance_apply(self, logits, scale: float, with_sum: bool = True):
         """Contrastive guidance on caller data (numeric tap, mellow_guidance_apply): logits [2 * P][vocab], rows 2i / 2i + 1 the
         conditional and the negative row of pair i -> dict of numpy arrays: "logits" [2 * P][vocab], both rows of a pair holding g,
@@ -818,6 +909,7 @@ class Engine(DebugTaps):
         assert a2.shape == a1.shape and ids.shape == (B, spec.TEXT_LEN), (a1.shape, a2.shape, ids.shape)
         passes = plan_nseq_passes(B, nseq, row_offset)
         N = B * nseq
+        opts.expand_constraint(B, nseq)
         out = torch.empty((N, max_len), dtype=torch.int32, device=self.tdev)
         lp = torch.empty((N, max_len), dtype=torch.float32, device=self.tdev) if return_logprobs else None
         top = self._top_record(opts.top_k, N, max_len)
@@ -830,7 +922,7 @@ class Engine(DebugTaps):
             lens[r0:r1], steps, ftm = self._generate_call(
                 opts, None if top is None else (top[0][r0:r1], top[1][r0:r1]), self.lib.mellow_generate_n, r1 - r0,
                 _ptr(a1[lo:hi]), _ptr(a2[lo:hi]), ns, _ptr(ids[lo:hi]), hi - lo, nseq, max_len, 1, top_p, temperature, seed, off, stop_id,
-                1 if ignore_stop else 0, _ptr(out[r0:r1]), None if lp is None else _ptr(lp[r0:r1]))
+                1 if ignore_stop else 0, _ptr(out[r0:r1]), None if lp is None else _ptr(lp[r0:r1]), row0=r0)
             pass_steps.append(steps)
             if k == 0:
                 ftm0 = ftm
@@ -853,6 +945,7 @@ class Engine(DebugTaps):
         B, ns = a1.shape
         assert a2.shape == a1.shape and ids.shape == (B, spec.TEXT_LEN), (a1.shape, a2.shape, ids.shape)
         N = B * k
+        opts.expand_constraint(B, k)
         par = np.zeros((max_len, N), dtype=np.int32)
         tok = np.zeros((max_len, N), dtype=np.int32)
         lp = np.zeros((max_len, N), dtype=np.float32)
@@ -861,7 +954,7 @@ class Engine(DebugTaps):
         t_up = (time.perf_counter() - t_in) * 1e3
         steps, ftm = C.c_int32(0), C.c_float(0.0)
         vp = C.c_void_p
-        opts.arm(self, None)
+        opts.arm(self, None, 0, N)
         self._chk(self.lib.mellow_generate_beam(self.h, _ptr(a1), _ptr(a2), ns, _ptr(ids), B, k, max_len, stop_id, 1 if ignore_stop else 0,
                                                 vp(par.ctypes.data), vp(tok.ctypes.data), vp(lp.ctypes.data), vp(cum.ctypes.data),
                                                 C.byref(steps), C.byref(ftm)))
@@ -913,6 +1006,7 @@ class Engine(DebugTaps):
         if Q > 1 and self.precision == "fp8":
             raise ValueError('several questions per example are not available with precision="fp8": the bf16 K/V pages of that mode '
                              "have no fan-out (pass the pair once per question instead)")
+        opts.expand_constraint(B, Q)
         out = torch.empty((N, max_len), dtype=torch.int32, device=self.tdev)
         lp = torch.empty((N, max_len), dtype=torch.float32, device=self.tdev) if return_logprobs else None
         top = self._top_record(opts.top_k, N, max_len)

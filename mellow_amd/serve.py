@@ -73,7 +73,9 @@ class EnginePool:
         (audio1, audio2, input_ids, negative) brings its own; a guided batch counts its examples, not its rows, towards row_offset;
         top_logprobs=k with return_logprobs=True: seven values per batch, top_ids and top_logprobs [rows, steps, k] after logprobs;
         top_k / min_p with do_sample=True: the sampler's candidate filters, armed by each context for its own calls, the same for
-        every batch)."""
+        every batch; constraint / constraint_then_free: constrained decoding, armed by each context for its own calls -- the list of
+        phrase sets is parallel to a batch's examples and goes to every batch as it is, so the batches then hold equally many
+        examples)."""
         kws = [kw] * len(batches)
         if kw.get("do_sample"):
             off, kws = int(kw.get("row_offset", 0)), []

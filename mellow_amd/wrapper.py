@@ -40,6 +40,14 @@ list that holds the pair once per question.  Not combined with num_return_sequen
 Extension: `score(examples, candidates)` returns the teacher-forced log-probability of given answer strings and
 `choose(examples, candidates)` the index of the likeliest one (multiple-choice ranking, re-ranking of sampled answers); the LM
 head of that path reduces its logits to log-softmax statistics on the fly (include/mellow_hip.h mellow_score).
+Extension (keyword-only): `generate(..., choices=[...])` holds every answer to a set of phrases -- the labels of a classification set,
+the options of a multiple-choice question -- by constrained decoding: inside the captured decode step every token that does not
+continue one of the phrases is banned before the token is chosen (include/mellow_hip.h mellow_generate_constraint,
+mellow_amd/constraint.py), so the answer IS one of the phrases and, with return_logprobs=True, its log-prob is that of the constrained
+distribution, a probability over the phrase set.  One decode serves any number of phrases (`choose()` runs one teacher-forced row
+per candidate), and it combines with do_sample, num_return_sequences, question lists, num_beams (the k likeliest labels with their
+probabilities from one decode), guidance and the repetition keywords.  `choices_then="free"` constrains only the start of the answer
+(a one-phrase set is a forced answer prefix).
 Deviations: `tqdm` progress output is not produced; the B>1/steps==1 mis-shape and B==1/steps==1 crash of
 reference wrapper.py:251-253 are not reproduced (one string per example is always returned).
 """
@@ -343,7 +351,7 @@ class MellowWrapper:
                  num_return_sequences: int = 1, num_beams: int = 1, length_penalty: float = 1.0, repetition_penalty: float = 1.0,
                  no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, suppress_tokens: Optional[Sequence[int]] = None,
                  logit_bias: Optional[dict] = None, guidance_scale: float = 1.0, negative_examples=None, top_logprobs: int = 0,
-                 top_k: int = 0, min_p: float = 0.0):
+                 top_k: int = 0, min_p: float = 0.0, choices=None, choices_then: str = "stop"):
         r"""Produces text response for the given audio files and text prompts
         examples: (list<list>) each example is [audio path 1, audio path 2, text prompt]; the text prompt may be a list or tuple of
                      prompts, several questions about the one pair of clips (module docstring).  If any example has a list, the
@@ -409,6 +417,22 @@ class MellowWrapper:
                      parallelism (the values are per call and the same on every rank).  ValueError without do_sample=True, with
                      num_beams > 1, for K < 0 or p outside [0, 1].  Both 0 (default -- Hugging Face's top_k = 50 is not adopted):
                      the call without the keywords.
+        choices: a list of strings -- the same phrase set for every example -- or a list parallel to `examples` of lists of strings:
+                     every answer is exactly one of its example's phrases (with a list of prompts: every answer of the example),
+                     followed by the stop token.  The phrases are tokenised with `tokenizer.encode(text)`, as `choose()` tokenises
+                     its candidates, and enforced on the device inside the decode step: a token that does not continue a phrase
+                     cannot be chosen, whatever chooses it (arg-max, sampler, beam select), after the guidance and the repetition
+                     keywords.  With return_logprobs=True the log-probs are those of the constrained distribution: over the phrase
+                     set they sum to 1, and they are not what `score` returns.  With num_beams=k and num_return_sequences=m the
+                     result is the m likeliest phrases with their probabilities from one decode.  Works with every other keyword
+                     and under data parallelism (the sets are sliced with the shard and must be the same on every rank).
+                     ValueError for an empty set or an empty string, a per-example list of another length than `examples`, a
+                     phrase of more than max_len - 1 tokens (the stop token needs a place; max_len with choices_then="free"), or,
+                     with num_beams, num_return_sequences greater than the number of distinct phrases of some example.  min_new_tokens
+                     larger than a phrase can leave no allowed token: that stays the caller's error.  None (default): the call
+                     without the keyword.
+        choices_then: "stop" (default): the answer ends after its phrase.  "free": the set constrains only the start of the answer,
+                     which then continues freely up to max_len; a one-phrase set is a forced answer prefix ("The difference is").
 
         With `data_parallel=True` (or MELLOW_DATA_PARALLEL=1) under an initialised torch.distributed group (one process per
         GPU, every rank calling with the same examples) the examples are sharded contiguously over the ranks, each rank ingests
@@ -430,9 +454,11 @@ class MellowWrapper:
         engine_kw = dict(rules_kw, **self._top_request(top_logprobs, return_logprobs, k))
         filters_kw = self._filters_request(top_k, min_p, do_sample, k)
         engine_kw.update(filters_kw)
+        choices_kw = self._choices_request(choices, choices_then, len(examples), max_len, k, nseq)
+        engine_kw.update(choices_kw)
         if k > 1:
             return self._generate_beams(examples, audio_paths1, audio_paths2, text_prompts, max_len, stop_token, audio_resample,
-                                        do_sample, return_logprobs, k, nseq, float(length_penalty), rules_kw)
+                                        do_sample, return_logprobs, k, nseq, float(length_penalty), dict(rules_kw, **choices_kw))
         if nseq > 1 and not do_sample:
             raise ValueError("num_return_sequences > 1 needs do_sample=True: greedy answers of one example are all the same")
         if nseq > 1024:
@@ -463,6 +489,9 @@ class MellowWrapper:
                                  for k, v in rules_kw.items())).encode()
         if filters_kw:    # likewise
             extra += repr(("filters", filters_kw["top_k"], filters_kw["min_p"])).encode()
+        if choices_kw and world > 1:    # likewise: the sets of ALL examples, before the shard is cut
+            from .constraint import constraint_digest
+            extra += repr(("choices", constraint_digest(choices_kw["constraint"]), choices_kw["constraint_then_free"])).encode()
         lo, hi = 0, n
         if world > 1:
             from .dist import shard_range
@@ -475,6 +504,8 @@ class MellowWrapper:
         else:
             audio1 = audio2 = torch.zeros((0, 1))
             ids = torch.zeros((0, spec.TEXT_LEN), dtype=torch.int64)
+        if choices_kw:                  # the sets follow their examples into the shard
+            engine_kw["constraint"] = choices_kw["constraint"][lo:hi]
         if negatives is not None:       # (one rank: lo, hi = 0, n)
             if negatives == "silence":      # the examples' own prompts over all-zero clips: nothing is read
                 neg = (torch.zeros_like(audio1), torch.zeros_like(audio2), ids)
@@ -486,6 +517,60 @@ class MellowWrapper:
         return self._generate_batch(audio1, audio2, ids, entry_length=max_len, top_p=top_p,
                                     temperature=temperature, stop_token=stop_token, n_total=n, do_sample=do_sample,
                                     seed=seed, row_offset=lo * nseq, return_logprobs=return_logprobs, nseq=nseq, engine_kw=engine_kw)
+
+    def _choices_request(self, choices, choices_then, n_examples, max_len, k, nseq):
+        """The keyword rules of choices / choices_then -> the keywords for Engine.generate ({} for None: the call without them):
+        constraint = per example the list of its phrases' token ids, constraint_then_free."""
+        if choices_then not in ("stop", "free"):
+            raise ValueError(f"choices_then must be 'stop' or 'free', got {choices_then!r}")
+        if choices is None:
+            return {}
+        if isinstance(choices, str):
+            raise ValueError("choices is a list of strings, or a list parallel to the examples of lists of strings")
+        choices = list(choices)
+        if len(choices) == 0:
+            raise ValueError("choices is an empty set: a constrained answer needs at least one phrase")
+        if all(isinstance(c, str) for c in choices):
+            per_example = [choices] * int(n_examples)
+        else:
+            if any(isinstance(c, str) for c in choices):
+                raise ValueError("choices mixes strings and lists: give one flat list of strings, or one list of strings per example")
+            per_example = [list(c) for c in choices]
+            if len(per_example) != int(n_examples):
+                raise ValueError(f"choices holds {len(per_example)} phrase sets for {int(n_examples)} examples: one list per example")
+        cache, done, sets = {}, {}, []
+        for i, phrases in enumerate(per_example):
+            if id(phrases) in done:          # the one flat list of every example: tokenised once, and one object for the trie builder
+                sets.append(done[id(phrases)])
+                continue
+            if len(phrases) == 0:
+                raise ValueError(f"choices[{i}] is an empty set: a constrained answer needs at least one phrase")
+            row = []
+            for text in phrases:
+                if not isinstance(text, str):
+                    raise TypeError(f"a choice must be a string, got {type(text).__name__}")
+                if text not in cache:
+                    cache[text] = [int(t) for t in self.tokenizer.encode(text)]       # the convention of _candidate_ids
+                if text == "" or not cache[text]:
+                    raise ValueError(f"choices[{i}] holds an empty string (or one without tokens): every phrase needs at least one token")
+                row.append(cache[text])
+            done[id(phrases)] = row
+            sets.append(row)
+        free = choices_then == "free"
+        longest = max(len(p) for row in sets for p in row)
+        room = int(max_len) if free else int(max_len) - 1
+        if longest > room:
+            raise ValueError(f"the longest phrase of choices has {longest} tokens: max_len = {int(max_len)} holds phrases of at most {room}"
+                             + ("" if free else " (the stop token needs a place)"))
+        if k > 1:
+            for i, row in enumerate(sets):
+                distinct = len({tuple(p) for p in row})
+                if nseq > distinct:
+                    raise ValueError(f"num_return_sequences = {nseq} exceeds the {distinct} distinct phrases of choices[{i}]: a constrained "
+                                     "beam search has no more finite hypotheses than that")
+        from .constraint import check_constraint
+        check_constraint(sets)
+        return dict(constraint=sets, constraint_then_free=free)
 
     @staticmethod
     def _filters_request(top_k, min_p, do_sample, k):
