@@ -59,7 +59,9 @@ extern "C" {
  *     (contrastive guidance inside the decode step), and then mellow_generate_top_logprobs with its tap mellow_top_logprobs_apply
  *     (the k likeliest tokens of every step), and then mellow_generate_filters with its tap mellow_sample_logits_filtered (top_k and
  *     min_p inside the sampler), and then mellow_generate_constraint with its tap mellow_constraint_apply (answers held to a phrase
- *     set inside the decode step) -- added while the minor was 5, detected by symbol lookup all the same.
+ *     set inside the decode step), and then mellow_set_vocab_bytes and mellow_generate_stop_strings with its tap
+ *     mellow_stop_strings_apply (answers end at a string, matched on bytes inside the decode step) -- added while the minor was 5,
+ *     detected by symbol lookup all the same.
  *  5: the attention taps on host data, mellow_debug_prefill_attn and mellow_debug_window_attn.  No existing symbol or struct
  *     changed; a binding that must also load a minor-4 library detects them by symbol lookup.  The GEMM epilogue tap
  *     mellow_debug_gemm_epi was added later under this same minor, detected by symbol lookup all the same, and so was the norm /
@@ -423,6 +425,66 @@ int  mellow_generate_constraint(mellow_engine_t* e, const mellow_constraint_t* c
  * whatever is armed on the context as it is.  Errors as above, and a null buffer, B <= 0, c->n_rows != B or ld outside [0, 8192]. */
 int  mellow_constraint_apply(mellow_engine_t* e, const mellow_constraint_t* c, float* logits, int B, const int32_t* history, int ld,
                              const int32_t* hist_len, int stop_id, float* cand_val, int32_t* cand_idx, float* cand_sum, int32_t* out_state);
+/* Stop strings: an answer ends once its TEXT contains one of a call's strings, decided on the device inside the decode step -- on the
+ * bytes of the generated tokens, so a string that lies across a token boundary or inside a token is found -- for every picker
+ * (arg-max, sampler, beam select).
+ *
+ * Vocabulary bytes.  An engine gets one byte string per token id: tok_off[V + 1] int32, starting at 0 and never decreasing, and
+ * tok_bytes[tok_off[V]] uint8, V = 49152.  A token has at most 256 bytes and may be empty.  mellow_set_vocab_bytes copies the table
+ * (host arrays) to the device.  It belongs to the SHARED engine state, like the weights: set once on any context, seen by the engine
+ * and every fork of it.  Setting it again replaces it; never while a call runs on any context.
+ * Errors (host code, before any device is touched, in this order): a null array; n_tokens other than 49152; offsets that do not start
+ * at 0 or that decrease; a token of more than 256 bytes (the message names the token id and its length).  Then a null or unfinalized
+ * engine; then a vocabulary other than 49152.
+ *
+ * Stop strings of a call: 1 to 16 byte strings of 1 to 64 bytes each, string j = str_bytes[str_off[j] .. str_off[j + 1]) (host
+ * arrays, copied when armed).
+ *
+ * Text and hit.  The text of a row that has generated h[0 .. s) is X(s) = bytes(h[0]) | ... | bytes(h[s - 1]).  The row is HIT at s
+ * iff some stop string is a substring of X(s).  The hit is sticky and is maintained step by step from a fixed-size state, the flag
+ * and the last 63 bytes of the text:  hit(s) = hit(s - 1), or a stop string occurs in tail63(X(s - 1)) | bytes(h[s - 1]).  The
+ * history is the row's GENERATED tokens, as for the rules and the constraint: a beam row's history is its hypothesis, not its slot's
+ * past.  An id outside [0, 49152) in a history (the tap) has no bytes.
+ *
+ * Effect on the row.  A hit row gets l[stop_id] = 0.0f and l[v] = -inf for every other v, and its per-32-column tile partials are
+ * formed anew: the stop id's tile gets value 0.0, index stop_id and sum exactly 1.0, every other tile value -inf, its lowest index and
+ * sum exactly 0.  Every picker then takes the stop id, and the row ends through the EXISTING stop rule, one step after the token that
+ * completed the match; loop control, tickets, block exit and row migration are untouched.  The launch returns without touching the
+ * logits or the partials of a row that is not hit: they stay byte-identical.
+ *
+ * Order in the step: guidance, rules, constraint, stop strings, top log-probs, picker.  The launch overwrites rather than
+ * intersects, so it wins over both earlier stages: over min_new_tokens (which only keeps the stop TOKEN out; Hugging Face behaves the
+ * same way) and over an armed constraint.  It can never leave a row banned whole.
+ * Log-probs: the recorded log-prob of the forced stop token is exactly zero (lp == 0.0f; the greedy form records -log 1.0f, which is the
+ * zero with the sign bit set), those of the tokens before it are the ones of the same
+ * call without stop strings, so a sum of log-probs runs over the answer up to the end of the token that completed the match.  A top
+ * log-probs record at the forced step holds (stop_id, 0.0) first.
+ *
+ * mellow_generate_stop_strings arms the strings for the NEXT mellow_generate* call on this context (mellow_generate, _sampled,
+ * _scored, _n, _q, _beam all honour it, in every precision, with and without armed rules, guidance, constraint, top log-probs and
+ * filters); NULL disarms.  That call takes them at entry and clears them whatever its outcome.  A fork has strings of its own,
+ * initially none.  That strings are armed is part of the captured step's key; their contents are not: they sit in fixed buffers.  A
+ * call without armed strings launches exactly what it launched before these symbols existed.
+ * Errors (in this order): a `size` other than sizeof(mellow_stop_strings_t); a count outside 1..16 (and a null array); a string length
+ * outside 1..64; a null or unfinalized engine; a vocabulary other than 49152; no vocabulary bytes set; and, at the armed call, a
+ * stop_id outside [0, 49152) -- mellow_generate_beam with ignore_stop is one such case, it knows no stop token.
+ * Added while the minor was 5 without raising it: a binding detects the three symbols by lookup. */
+int  mellow_set_vocab_bytes(mellow_engine_t* e, const int32_t* tok_off, const uint8_t* tok_bytes, int32_t n_tokens);
+typedef struct mellow_stop_strings {
+    int32_t size;                 /* sizeof(mellow_stop_strings_t) */
+    int32_t n_strings;            /* 1 .. 16 */
+    const int32_t* str_off;       /* [n_strings + 1], from 0; every string 1 .. 64 bytes */
+    const uint8_t* str_bytes;     /* [str_off[n_strings]] */
+} mellow_stop_strings_t;
+int  mellow_generate_stop_strings(mellow_engine_t* e, const mellow_stop_strings_t* strings);
+/* The same launch on caller data, no loop state (numeric tap); the arguments and conventions are those of mellow_constraint_apply:
+ * logits dev f32 [B][vocab], edited in place; history dev i32 [B][ld] (ld <= 8192) with hist_len dev i32 [B] tokens of every row; the
+ * row's state is the empty text advanced once per history token, and its hit flag, 0 or 1, goes to out_hit dev i32 [B] (may be NULL).
+ * cand_val / cand_idx / cand_sum (may be NULL) dev [B][vocab / 32] receive the tile partials of a hit row; those of a row that is not
+ * hit are left as they are, like its logits.  It works on copies of its own and leaves what is armed on the context alone.  Errors as
+ * above, and a null buffer, B <= 0, ld outside [0, 8192] or a stop_id outside [0, 49152). */
+int  mellow_stop_strings_apply(mellow_engine_t* e, const mellow_stop_strings_t* strings, float* logits, int B, const int32_t* history, int ld,
+                               const int32_t* hist_len, int stop_id, float* cand_val, int32_t* cand_idx, float* cand_sum, int32_t* out_hit);
 /* Contrastive (classifier-free) guidance: the step's distribution is contrasted with that of a NEGATIVE input on the device, inside
  * the decode step, between the lm_head and the rules launch / the kernel that picks the token -- for the prefill's first token as for
  * every decode step.

@@ -20,7 +20,7 @@ PKG = os.path.dirname(HERE)
 LIBDIR = os.path.join(PKG, "lib")
 OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(LIBDIR, "libmellow_hip.so")
-SOURCES = ["gemm_f32.hip", "gemm_fp8.hip", "gemm_bf16x3.hip", "dec_attn.hip", "dec_gemv.hip", "dec_tail.hip", "dec_weights.hip", "prefill_attn.hip", "encoder.hip", "norm.hip", "stft_fft.hip", "sample.hip", "score.hip", "beam.hip", "logit_rules.hip", "constrain.hip", "guidance.hip", "top_logprobs.hip", "engine.cpp", "engine_weights.cpp", "engine_encoder.cpp", "engine_lm.cpp", "engine_generate.cpp", "engine_dev.cpp", "engine_taps.cpp"]
+SOURCES = ["gemm_f32.hip", "gemm_fp8.hip", "gemm_bf16x3.hip", "dec_attn.hip", "dec_gemv.hip", "dec_tail.hip", "dec_weights.hip", "prefill_attn.hip", "encoder.hip", "norm.hip", "stft_fft.hip", "sample.hip", "score.hip", "beam.hip", "logit_rules.hip", "constrain.hip", "stop_strings.hip", "guidance.hip", "top_logprobs.hip", "engine.cpp", "engine_weights.cpp", "engine_encoder.cpp", "engine_lm.cpp", "engine_generate.cpp", "engine_dev.cpp", "engine_taps.cpp"]
 HEADERS = ["common.h", "kernels.h", "dec_common.h", "step_tail.h", "gemm_epilogue.h", "gemm_tile.h", "engine_internal.h", os.path.join("..", "..", "include", "mellow_hip.h")]
 ARCH = "gfx950"
 FLAGS = (["-DMELLOW_KDEBUG"] if os.environ.get("MELLOW_KDEBUG") else []) + os.environ.get("MELLOW_EXTRA_FLAGS", "").split() + ["-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",

@@ -29,6 +29,7 @@ struct GenRequest {
     SampleFilters filters;                       // top_k / min_p (mellow_generate_filters): likewise, the same for every pass
     Constraint con;                              // constrained decoding (mellow_generate_constraint): likewise; the roots advance with the passes
     int con_row0 = 0;                            // ... the first row of this pass among the roots of the call
+    StopStrings stop;                            // stop strings (mellow_generate_stop_strings): likewise, the same for every pass
     int rows() const { return examples * n * q; }
     // rows [r0, r0 + nb) of an n = 1, q = 1 request as a request of their own; a row's random stream follows its index in the whole call
     GenRequest pass(int r0, int nb, int text_len, int32_t* steps, float* ftm) const {
@@ -170,6 +171,49 @@ static int stage_constraint(mellow_engine_t* e, const Constraint& c, int stop_id
     return 0;
 }
 
+// The value rules of a mellow_stop_strings_t, each once and in the order the header states (mellow_generate_stop_strings and
+// mellow_stop_strings_apply): host code only, no engine needed.  -> the strings as a call carries them.
+static int check_stop_strings(const mellow_stop_strings_t* s, StopStrings* out) {
+    if (s->size != (int32_t)sizeof(mellow_stop_strings_t))
+        return fail("mellow_stop_strings_t.size is %d, this library's struct has %d bytes", (int)s->size, (int)sizeof(mellow_stop_strings_t));
+    if (s->n_strings < 1 || s->n_strings > STS_MAX_STRINGS) return fail("stop strings: a call takes 1 to %d strings (got %d)", STS_MAX_STRINGS, (int)s->n_strings);
+    if (!s->str_off || !s->str_bytes) return fail("stop strings: null array");
+    *out = StopStrings();
+    for (int j = 0; j < s->n_strings; ++j) {
+        const int64_t m = (int64_t)s->str_off[j + 1] - s->str_off[j];
+        if (m < 1 || m > STS_MAX_STR_LEN) return fail("stop strings: string %d has %lld bytes, a string has 1 to %d", j, (long long)m, STS_MAX_STR_LEN);
+        memcpy(out->bytes + out->off[j], s->str_bytes + s->str_off[j], (size_t)m);
+        out->off[j + 1] = out->off[j] + (int32_t)m;
+    }
+    for (int j = s->n_strings; j < STS_MAX_STRINGS; ++j) out->off[j + 1] = out->off[j];
+    out->on = true; out->n = s->n_strings;
+    return 0;
+}
+
+// what an engine must be for a stop-strings launch, each rule once
+static int check_stop_engine(mellow_engine_t* e) {
+    if (e->cfg.vocab_size != SAMPLE_MAX_V) return fail("the stop-strings kernel is built for a vocabulary of %d (engine: %d)", SAMPLE_MAX_V, e->cfg.vocab_size);
+    if (!e->w.vocab_bytes || !e->w.vocab_bytes->set) return fail("stop strings need the vocabulary's bytes: call mellow_set_vocab_bytes first");
+    return 0;
+}
+static int check_stop_id(int stop_id, bool never_stops) {
+    if (stop_id < 0 || stop_id >= SAMPLE_MAX_V || never_stops)
+        return fail("stop strings end a row through the stop token: stop_id = %d%s is no token of the vocabulary [0, %d)", stop_id,
+                    never_stops ? " under ignore_stop (a beam call then knows no stop token)" : "", SAMPLE_MAX_V);
+    return 0;
+}
+
+// the block a stop-strings launch reads, into `dst` (device)
+static int stage_stop_strings(mellow_engine_t* e, const StopStrings& st, int stop_id, float* dst) {
+    uint32_t* w = e->h_stopblk;       // (a member: alive until the copy has run)
+    memset(w, 0, sizeof(e->h_stopblk));
+    w[STS_STOP] = (uint32_t)stop_id; w[STS_COUNT] = (uint32_t)st.n;
+    for (int j = 0; j <= STS_MAX_STRINGS; ++j) w[STS_OFF + j] = (uint32_t)st.off[j];
+    memcpy(w + STS_WORDS, st.bytes, sizeof(st.bytes));
+    HIPCHK(hipMemcpyAsync(dst, e->h_stopblk, sizeof(e->h_stopblk), hipMemcpyHostToDevice, e->stream));
+    return 0;
+}
+
 // the value block a guidance launch reads
 static int stage_guidance(mellow_engine_t* e, float scale) {
     memcpy(&e->h_gparams[GDN_SCALE], &scale, 4);
@@ -254,6 +298,10 @@ static int check_request(mellow_engine_t* e, const GenRequest& r, int door) {
         if (r.con.n_rows != r.rows())
             return fail("a constraint is armed (mellow_generate_constraint) with n_rows = %d: this call has %d rows (B, B * n, B * Q, B * k, or both rows of every guided pair)",
                         r.con.n_rows, r.rows());
+    }
+    if (r.stop.on) {
+        CHK(check_stop_engine(e));
+        CHK(check_stop_id(r.stop_id, r.beam && r.ignore_stop));
     }
     return 0;
 }
@@ -417,6 +465,7 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
     m.top = r.top.k;                    // dec_top_logprobs_kernel reads the stored rows: the head stores them (apply_step_mode)
     m.filtered = r.filters.on;          // dec_sample_kernel in its filtered instantiation; the values travel in d_sparams
     m.constrain = r.con.on;             // dec_constrain_kernel edits the stored rows: the head stores them (apply_step_mode)
+    m.stop = r.stop.on;                 // dec_stop_strings_kernel overwrites the stored rows it hits: the head stores them (apply_step_mode)
     m.early_exit = !r.beam && (dev_dead || (!r.ignore_stop && e->da.RB > 1));
     // a guided call runs without migration (a pair's rows stay neighbours in slots 2p, 2p + 1); block exit stays: both rows of a
     // pair get the same token, so they finish at the same step, and a pair never straddles a 32-row block
@@ -442,6 +491,8 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
     }
     // value block, roots and state of the pass: one buffer of fixed size, so a captured launch finds it where it was (StepGraphs::Key)
     if (m.constrain) CHK(ensure(e, e->con_ws, CON_WORDS + (size_t)3 * CON_STATE_ROWS));
+    // block and state of the pass, likewise of fixed size
+    if (m.stop) CHK(ensure(e, e->stop_ws, STS_BLOCK_WORDS + (size_t)2 * STS_STATE_ROWS * STS_ROW_WORDS));
     // the pass runs in its mode; the taps' defaults are back on every way out (the taps never sample, record nor exit early)
     struct ModeScope { mellow_engine* e; ~ModeScope() { apply_step_mode(e, StepMode()); } } mode_scope{e};
     apply_step_mode(e, m);
@@ -455,6 +506,11 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
         // the roots of this pass's rows go to the front of the pass's words; the state needs no clearing (step 0 writes the roots)
         CHK(stage_constraint(e, r.con, stop_id, e->con_ws.p));
         HIPCHK(hipMemcpyAsync(e->con_ws.p + CON_WORDS, e->con_roots.p + r.con_row0, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    }
+    if (r.stop.on) {
+        // every row starts from the empty text, not hit (step 0 writes that state too: the clearing covers rows that never run it)
+        CHK(stage_stop_strings(e, r.stop, stop_id, e->stop_ws.p));
+        HIPCHK(hipMemsetAsync(e->stop_ws.p + STS_BLOCK_WORDS, 0, (size_t)2 * STS_STATE_ROWS * STS_ROW_WORDS * sizeof(uint32_t), s));
     }
     if (dev_dead) {
         HIPCHK(hipMemsetAsync(e->d_blk_left, 0, 96 * sizeof(int32_t), s));
@@ -575,7 +631,7 @@ static int generate_pass(mellow_engine_t* e, const GenRequest& r) {
     return 0;
 }
 
-// What mellow_generate_rules / _guidance / _top_logprobs / _filters / _constraint armed on the context serves ONE mellow_generate* call, whatever its outcome:
+// What mellow_generate_rules / _guidance / _top_logprobs / _filters / _constraint / _stop_strings armed on the context serves ONE mellow_generate* call, whatever its outcome:
 // taken into that call's request, cleared on the context
 static void take_armed(mellow_engine_t* e, GenRequest& r) {
     if (!e) return;
@@ -584,6 +640,7 @@ static void take_armed(mellow_engine_t* e, GenRequest& r) {
     r.top = e->top_armed; e->top_armed = TopLogprobs();
     r.filters = e->filters_armed; e->filters_armed = SampleFilters();
     r.con = e->con_armed; e->con_armed = Constraint();
+    r.stop = e->stop_armed; e->stop_armed = StopStrings();
 }
 
 // The reference's loop (wrapper.py:216-249) takes any number of examples.  One pass of the engine takes up to 1024 rows (32 row
@@ -758,6 +815,64 @@ int mellow_constraint_apply(mellow_engine_t* e, const mellow_constraint_t* c, fl
     g.cand_val = cand_val; g.cand_idx = cand_idx; g.cand_sum = cand_sum;
     g.hist = history; g.hist_ld = ld; g.hist_len = hist_len; g.out_state = out_state;
     launch_dec_constrain(g, B, e->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+// The vocabulary's byte table, checked whole in host code and copied into the engine's shared holder (engine_internal.h VocabBytes).
+int mellow_set_vocab_bytes(mellow_engine_t* e, const int32_t* tok_off, const uint8_t* tok_bytes, int32_t n_tokens) {
+    if (!tok_off || !tok_bytes) return fail("mellow_set_vocab_bytes: null array");
+    if (n_tokens != SAMPLE_MAX_V) return fail("mellow_set_vocab_bytes: n_tokens = %d, the table holds the %d tokens of the vocabulary", (int)n_tokens, SAMPLE_MAX_V);
+    if (tok_off[0] != 0) return fail("mellow_set_vocab_bytes: tok_off must start at 0 (got %d)", (int)tok_off[0]);
+    for (int t = 0; t < n_tokens; ++t) {
+        const int64_t m = (int64_t)tok_off[t + 1] - tok_off[t];
+        if (m < 0) return fail("mellow_set_vocab_bytes: tok_off decreases at token %d", t);
+        if (m > STS_MAX_TOKEN_BYTES) return fail("mellow_set_vocab_bytes: token %d has %lld bytes, a token has at most %d", t, (long long)m, STS_MAX_TOKEN_BYTES);
+    }
+    if (!e || !e->finalized) return fail("engine not finalized");
+    if (e->cfg.vocab_size != SAMPLE_MAX_V) return fail("the stop-strings kernel is built for a vocabulary of %d (engine: %d)", SAMPLE_MAX_V, e->cfg.vocab_size);
+    HIPCHK(hipSetDevice(e->device));
+    VocabBytes& vb = *e->w.vocab_bytes;
+    if (!vb.off) HIPCHK(hipMalloc(&vb.off, ((size_t)SAMPLE_MAX_V + 1) * sizeof(int32_t)));
+    if (!vb.bytes) HIPCHK(hipMalloc(&vb.bytes, (size_t)SAMPLE_MAX_V * STS_MAX_TOKEN_BYTES));
+    HIPCHK(hipMemcpyAsync(vb.off, tok_off, ((size_t)n_tokens + 1) * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    if (tok_off[n_tokens] > 0) HIPCHK(hipMemcpyAsync(vb.bytes, tok_bytes, (size_t)tok_off[n_tokens], hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));         // the caller's arrays are free again on return, and every context's stream finds the table
+    vb.set = true;
+    return 0;
+}
+
+int mellow_generate_stop_strings(mellow_engine_t* e, const mellow_stop_strings_t* strings) {
+    StopStrings st;
+    if (strings) CHK(check_stop_strings(strings, &st));
+    if (!e || !e->finalized) return fail("engine not finalized");
+    e->stop_armed = StopStrings();
+    if (!strings) return 0;
+    CHK(check_stop_engine(e));
+    e->stop_armed = st;
+    return 0;
+}
+
+// the stop-strings launch on caller data, on a block of its own: what is armed on the context stays
+int mellow_stop_strings_apply(mellow_engine_t* e, const mellow_stop_strings_t* strings, float* logits, int B, const int32_t* history, int ld,
+                              const int32_t* hist_len, int stop_id, float* cand_val, int32_t* cand_idx, float* cand_sum, int32_t* out_hit) {
+    StopStrings st;
+    if (strings) CHK(check_stop_strings(strings, &st));
+    if (!e || !e->finalized) return fail("engine not finalized");
+    if (!strings || !logits || !hist_len || !cand_val || !cand_idx || B <= 0 || ld < 0 || (ld > 0 && !history)) return fail("bad argument");
+    if (ld > RULES_MAX_HIST) return fail("mellow_stop_strings_apply takes histories of at most %d tokens (ld = %d)", RULES_MAX_HIST, ld);
+    CHK(check_stop_engine(e));
+    CHK(check_stop_id(stop_id, false));
+    HIPCHK(hipSetDevice(e->device));
+    CHK(ensure(e, e->stop_tap, STS_BLOCK_WORDS));
+    CHK(stage_stop_strings(e, st, stop_id, e->stop_tap.p));
+    StopStrArgs g;
+    g.logits = logits; g.ld = e->cfg.vocab_size; g.blk = reinterpret_cast<const uint32_t*>(e->stop_tap.p);
+    g.tok_off = e->w.vocab_bytes->off; g.tok_bytes = e->w.vocab_bytes->bytes;
+    g.cand_val = cand_val; g.cand_idx = cand_idx; g.cand_sum = cand_sum;
+    g.hist = history; g.hist_ld = ld; g.hist_len = hist_len; g.out_hit = out_hit;
+    launch_dec_stop_strings(g, B, e->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(e->stream));
     return 0;

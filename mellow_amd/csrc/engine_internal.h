@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <unordered_map>
 #include <string>
 #include <thread>
@@ -143,6 +144,7 @@ struct StepMode {
     bool filtered = false;       // top_k / min_p: dec_sample_kernel in its filtered instantiation (needs `sample`)
     int top = 0;                 // k >= 1: dec_top_logprobs_kernel after the rules launch, before the picker (forces `logits` on; needs `logprob`)
     bool constrain = false;      // constrained decoding: dec_constrain_kernel after the rules launch, before the top log-probs and the picker (forces `logits` on)
+    bool stop = false;           // stop strings: dec_stop_strings_kernel after the constraint launch, before the top log-probs and the picker (forces `logits` on)
 };
 // The top log-probs record of one generation call (include/mellow_hip.h, mellow_generate_top_logprobs): armed on the context, taken
 // into the call's GenRequest at entry.  ids / lp are the caller's [rows][max_len][k], host or device.
@@ -179,6 +181,25 @@ struct Constraint {
     bool on = false;
     bool then_free = false;
     int n_nodes = 0, n_edges = 0, n_rows = 0;
+};
+
+// The stop strings of one generation call (include/mellow_hip.h, mellow_generate_stop_strings): armed on the context, taken into the
+// call's GenRequest at entry.  Small and of fixed size, so the strings themselves travel with the record.
+struct StopStrings {
+    bool on = false;
+    int n = 0;
+    int32_t off[STS_MAX_STRINGS + 1] = {0};
+    uint8_t bytes[STS_MAX_STRINGS * STS_MAX_STR_LEN] = {0};
+};
+// The vocabulary's byte table (mellow_set_vocab_bytes): one holder per engine, shared by its forks as the weights are, so that a
+// table set on any context is seen by all.  The buffers have their full size from the first call on -- tok_off [49152 + 1], tok_bytes
+// [49152 * 256] -- so a captured launch finds them where they were when the table is replaced.
+struct VocabBytes {
+    int32_t* off = nullptr;
+    uint8_t* bytes = nullptr;
+    bool set = false;
+    VocabBytes() = default; VocabBytes(const VocabBytes&) = delete; VocabBytes& operator=(const VocabBytes&) = delete;
+    ~VocabBytes() { if (off) (void)hipFree(off); if (bytes) (void)hipFree(bytes); }
 };
 
 // One execution context.  `opt` and `w` are what a fork shares with its parent (copied whole by mellow_engine_fork); the rest is its own.
@@ -248,12 +269,13 @@ struct mellow_engine {
         DecW head_w() const { return head8 ? DecW{head8, head_sc} : DecW{lm_head.p, nullptr}; }
         std::unordered_map<const float*, void*> bf_w;   // fp32 packed pointer -> PB copy
         std::unordered_map<const float*, Fp8W> fp8_w;
+        std::shared_ptr<VocabBytes> vocab_bytes;     // created by finalize; a fork shares the holder, so what any context sets all see
     };
     // The captured decode step and what it was captured with: the graphs bake buffer addresses in (max_len / stop id travel in
     // d_params, the sampling parameters in d_sparams).  generate_pass (engine_generate.cpp) captures, ensure_lm invalidates.
     struct LOCAL StepGraphs {
         struct Key {
-            std::array<uintptr_t, 25> v{};       // all zero: no capture (a pass has at least one row)
+            std::array<uintptr_t, 29> v{};       // all zero: no capture (a pass has at least one row)
             static Key of(const mellow_engine* e, int B);      // from the engine as configured for the pass (below the engine)
             bool operator==(const Key& k) const { return v == k.v; }
         };
@@ -331,6 +353,12 @@ struct mellow_engine {
     // value block | roots | arena -- so that mellow_constraint_apply leaves what is armed as it is
     Buf con_trie, con_roots, con_ws, con_tap;
     uint32_t h_cparams[CON_WORDS] = {0};       // staging of the value block (kernels.h CON_*)
+    StopStrings stop_armed;                    // mellow_generate_stop_strings: what the NEXT mellow_generate* call on this context takes (and clears)
+    // stop strings, created on first use and of fixed size so that their address never changes: the words of a pass -- value block
+    // and string bytes [STS_BLOCK_WORDS] | state ping-pong [2][1024][STS_ROW_WORDS]; the tap's own block, so that
+    // mellow_stop_strings_apply leaves what is armed as it is
+    Buf stop_ws, stop_tap;
+    uint32_t h_stopblk[STS_BLOCK_WORDS] = {0}; // staging of the block (kernels.h STS_*)
     StepMode mode;                             // what apply_step_mode last set (run_lm_head, loop_args and StepGraphs::Key::of read it)
     int32_t h_blk[64] = {0};                   // staging of d_blk_left[32] | d_blk_live[32]
     std::vector<int32_t> h_ident;              // staging of d_row_of_slot
@@ -405,7 +433,11 @@ inline mellow_engine::StepGraphs::Key mellow_engine::StepGraphs::Key::of(const m
                 (uintptr_t)e->mode.filtered,       // top_k / min_p: dec_sample_kernel's filtered instantiation (the values are in the SMP_* block)
                 (uintptr_t)e->mode.constrain,      // constrained decoding: dec_constrain_kernel in the step; the head with its logits store
                 (uintptr_t)(e->mode.constrain ? e->con_trie.p : nullptr),      // ... the trie arena: ConstrainArgs (its contents and counts are not baked in)
-                (uintptr_t)(e->mode.constrain ? e->con_ws.p : nullptr)}};      // ... value block, roots and state of the pass: ConstrainArgs
+                (uintptr_t)(e->mode.constrain ? e->con_ws.p : nullptr),        // ... value block, roots and state of the pass: ConstrainArgs
+                (uintptr_t)e->mode.stop,           // stop strings: dec_stop_strings_kernel in the step; the head with its logits store
+                (uintptr_t)(e->mode.stop ? e->stop_ws.p : nullptr),            // ... block and state of the pass: StopStrArgs (the strings are not baked in)
+                (uintptr_t)(e->mode.stop && e->w.vocab_bytes ? e->w.vocab_bytes->off : nullptr),      // ... the vocabulary's byte table: StopStrArgs
+                (uintptr_t)(e->mode.stop && e->w.vocab_bytes ? e->w.vocab_bytes->bytes : nullptr)}};
 }
 static_assert(!std::is_copy_constructible<mellow_engine::Buf>::value, "a Buf owns its device memory: it moves, it is never copied");
 static_assert(std::is_copy_assignable<mellow_engine::Weights>::value && std::is_copy_assignable<mellow_engine::Options>::value, "a fork copies these by assignment: no owning member (Buf, StepGraphs) belongs in them");
@@ -517,6 +549,8 @@ BeamArgs beam_args(mellow_engine* e, int N, int k);
 RulesArgs rules_args(mellow_engine* e, int B);
 // the constraint launch of a generation step on B rows, likewise
 ConstrainArgs constrain_args(mellow_engine* e, int B);
+// the stop-strings launch of a generation step on B rows, likewise
+StopStrArgs stop_str_args(mellow_engine* e, int B);
 // the guidance launch of a generation step, from the engine as apply_step_mode configured it (engine_lm.cpp)
 GuideArgs guide_args(mellow_engine* e);
 // the top log-probs launch of a generation step, from the engine as apply_step_mode configured it (engine_lm.cpp)

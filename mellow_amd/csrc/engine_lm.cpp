@@ -104,7 +104,8 @@ int ensure_lm(mellow_engine* e, int B, int T, int Tmax, int ctx_end, int prefill
 void apply_step_mode(mellow_engine* e, const StepMode& m) {
     e->mode = m;
     DecArgs& a = e->da;
-    e->mode.logits = m.logits || m.rules || m.guide || m.top > 0 || m.constrain;   // the rules, the guidance and the constraint edit the stored rows, the top log-probs read them
+    // the rules, the guidance, the constraint and the stop strings edit the stored rows, the top log-probs read them
+    e->mode.logits = m.logits || m.rules || m.guide || m.top > 0 || m.constrain || m.stop;
     a.logits = e->mode.logits ? e->dlogits.p : nullptr;      // (off: generation's arg-max needs the candidates only, no 6 MB store per step)
     a.cand_sum = m.logprob ? e->cand_sum.p : nullptr;
     a.blk_live = m.early_exit ? e->d_blk_live : nullptr;
@@ -184,6 +185,24 @@ ConstrainArgs constrain_args(mellow_engine* e, int B) {
     return g;
 }
 
+StopStrArgs stop_str_args(mellow_engine* e, int B) {
+    const LoopArgs lp = loop_args(e);
+    uint32_t* ws = reinterpret_cast<uint32_t*>(e->stop_ws.p);
+    StopStrArgs g;
+    g.logits = e->da.logits; g.ld = e->cfg.vocab_size; g.blk = ws; g.state = ws + STS_BLOCK_WORDS;
+    g.tok_off = e->w.vocab_bytes->off; g.tok_bytes = e->w.vocab_bytes->bytes;
+    g.cand_val = e->da.cand_val; g.cand_idx = e->da.cand_idx; g.cand_sum = e->da.cand_sum;
+    g.d_pos = e->d_pos; g.params = lp.params; g.T0 = lp.T0;
+    g.row_of_slot = lp.row_of_slot; g.blk_snap = lp.blk_snap;
+    if (e->mode.beam) {
+        const BeamArgs bm = beam_args(e, B, e->mode.beam);
+        g.parent_tab = bm.out_parent; g.token_tab = bm.out_token; g.N = B; g.k = e->mode.beam;
+    } else {
+        g.hist = lp.out_tokens;
+    }
+    return g;
+}
+
 GuideArgs guide_args(mellow_engine* e) {
     const LoopArgs lp = loop_args(e);
     GuideArgs g;
@@ -224,7 +243,11 @@ int run_lm_head(mellow_engine* e, int B, int pending_kcd, const RecordArgs* rec)
         ProfScope ps(e, PF_MISC, 0, 2.0 * B * e->cfg.vocab_size * 4);
         launch_dec_constrain(constrain_args(e, B), B, e->stream);
     }
-    if (e->mode.top && rec) {        // top log-probs: exactly the row the picker below reads, after the guidance, the rules and the constraint
+    if (e->mode.stop && rec) {       // stop strings: a row whose text holds one becomes the one-hot row of the stop id, whatever the earlier launches left
+        ProfScope ps(e, PF_MISC, 0, 1.0 * B * e->cfg.vocab_size * 4);
+        launch_dec_stop_strings(stop_str_args(e, B), B, e->stream);
+    }
+    if (e->mode.top && rec) {        // top log-probs: exactly the row the picker below reads, after the guidance, the rules, the constraint and the stop strings
         ProfScope ps(e, PF_MISC, 0, 1.0 * B * e->cfg.vocab_size * 4);
         launch_dec_top_logprobs(top_args(e), B, e->stream);
     }

@@ -408,6 +408,7 @@ extern "C" int mellow_engine_finalize(mellow_engine_t* e) {
         CHK(upload(e, &e->w.rope_sin, s.data(), s.size()));
     }
     CHK(alloc_state_words(e));
+    e->w.vocab_bytes = std::make_shared<VocabBytes>();      // empty until mellow_set_vocab_bytes; every fork shares this holder
     e->host.clear();
     e->finalized = true;
     return 0;

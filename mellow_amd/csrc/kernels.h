@@ -429,6 +429,45 @@ struct ConstrainArgs {
     int N = 0, k = 1;
 };
 void launch_dec_constrain(const ConstrainArgs& g, int B, hipStream_t s);
+// Stop strings (stop_strings.hip; include/mellow_hip.h mellow_generate_stop_strings states the exact definition): one launch after the
+// constraint launch and before the top log-probs and the picker.  Every row carries the hit flag and the last 63 bytes of its generated
+// text; a step appends the bytes of the ONE token the last pick gave the row and looks for every stop string in tail | token bytes.  A
+// hit row becomes the one-hot row of the stop id (its tile partials formed anew); a row that is not hit is not touched.
+// blk = {stop id, n_strings, str_off [STS_MAX_STRINGS + 1]} padded to STS_WORDS words, then the strings' bytes [STS_MAX_STRINGS *
+// STS_MAX_STR_LEN]: fixed size, so a captured step serves any strings.
+constexpr int STS_MAX_STRINGS = 16, STS_MAX_STR_LEN = 64, STS_MAX_TOKEN_BYTES = 256;
+constexpr int STS_TAIL = STS_MAX_STR_LEN - 1;           // bytes of text a row keeps: a match that ends in the next token starts inside them
+enum { STS_STOP = 0, STS_COUNT, STS_OFF, STS_WORDS = 32 };
+constexpr int STS_BLOCK_WORDS = STS_WORDS + STS_MAX_STRINGS * STS_MAX_STR_LEN / 4;      // value block and string bytes
+constexpr int STS_ROW_WORDS = 18;        // state of a row: hit | tail length | 64 bytes, the first `tail length` of which are the tail
+constexpr int STS_STATE_ROWS = 1024;     // rows of one half of the state buffer: the rows of one pass
+struct StopStrArgs {
+    float* logits = nullptr;             // [slots][ld] fp32, a hit row is overwritten (ld = SAMPLE_MAX_V: the row tiling of the sampler)
+    int64_t ld = 0;
+    const uint32_t* blk = nullptr;       // device block of STS_BLOCK_WORDS words (above)
+    const int32_t* tok_off = nullptr;    // [ld + 1] the vocabulary's byte table (mellow_set_vocab_bytes)
+    const uint8_t* tok_bytes = nullptr;
+    float* cand_val = nullptr; int32_t* cand_idx = nullptr;   // [slots][ld / 32], rewritten for a hit row
+    float* cand_sum = nullptr;           // [slots][ld / 32] or null
+    // the state of a row, one of two sources:
+    //   tap (hist_len != null): the empty text advanced once per token of hist [slots][hist_ld], hist_len [slots]; the flag goes to out_hit [slots];
+    //   loop: state [2][STS_STATE_ROWS][STS_ROW_WORDS] by example row; step s = *d_pos - T0 + 1 reads half (s - 1) & 1 of the parent
+    //   row, advances it by the token the last pick gave the row and writes half s & 1 (s = 0: the empty text).  Parent and token
+    //   are resolved as the constraint kernel resolves them (ConstrainArgs)
+    const int32_t* hist = nullptr;
+    int hist_ld = 0;
+    const int32_t* hist_len = nullptr;
+    int32_t* out_hit = nullptr;
+    uint32_t* state = nullptr;
+    const int32_t* d_pos = nullptr;
+    const int32_t* params = nullptr;     // device {max_len, stop_id} (LoopArgs::params)
+    int T0 = 0;
+    const int32_t* row_of_slot = nullptr;   // as in LoopArgs: logits and partials are addressed by slot, record and state by example
+    const int32_t* blk_snap = nullptr;
+    const int32_t* parent_tab = nullptr; const int32_t* token_tab = nullptr;
+    int N = 0, k = 1;
+};
+void launch_dec_stop_strings(const StopStrArgs& g, int B, hipStream_t s);
 // after the arg-max of a step (early-exit mode only): if the rows that have not produced the stop id yet fit into fewer 32-row
 // blocks than are live, move them (their next-step residual rows) to the lowest slots, rewrite row_of_slot / blk_left / blk_live
 void launch_dec_compact(const DecArgs& a, int B, const LoopArgs& loop, hipStream_t s);

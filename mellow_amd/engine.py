@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -45,6 +45,11 @@ class Constraint(C.Structure):
     _fields_ = [("size", C.c_int32), ("n_nodes", C.c_int32), ("n_edges", C.c_int32), ("node_first", C.c_void_p),
                 ("node_flags", C.c_void_p), ("edge_token", C.c_void_p), ("edge_child", C.c_void_p), ("n_rows", C.c_int32),
                 ("row_root", C.c_void_p), ("then_free", C.c_int32)]
+
+
+class StopStrings(C.Structure):
+    """mellow_stop_strings_t (include/mellow_hip.h)"""
+    _fields_ = [("size", C.c_int32), ("n_strings", C.c_int32), ("str_off", C.c_void_p), ("str_bytes", C.c_void_p)]
 
 
 class SampleFilters(C.Structure):
@@ -90,7 +95,7 @@ _ADDED_UNDER_MINOR_5 = ("mellow_debug_prefill_attn", "mellow_debug_window_attn",
                         "mellow_generate_guidance", "mellow_guidance_apply", "mellow_generate_top_logprobs", "mellow_top_logprobs_apply",
                         "mellow_debug_gemm_epi", "mellow_generate_filters", "mellow_sample_logits_filtered", "mellow_debug_norm",
                         "mellow_debug_dec_attn", "mellow_debug_dec_gemv", "mellow_debug_dec_tail", "mellow_generate_constraint",
-                        "mellow_constraint_apply")
+                        "mellow_constraint_apply", "mellow_set_vocab_bytes", "mellow_generate_stop_strings", "mellow_stop_strings_apply")
 
 
 def load_library(path: Optional[str] = None):
@@ -135,6 +140,9 @@ def load_library(path: Optional[str] = None):
         "mellow_logit_rules_apply": (ci, [vp, P(LogitRules), vp, ci, vp, ci, vp, ci, vp, vp, vp]),
         "mellow_generate_constraint": (ci, [vp, P(Constraint)]),
         "mellow_constraint_apply": (ci, [vp, P(Constraint), vp, ci, vp, ci, vp, ci, vp, vp, vp, vp]),
+        "mellow_set_vocab_bytes": (ci, [vp, vp, vp, C.c_int32]),
+        "mellow_generate_stop_strings": (ci, [vp, P(StopStrings)]),
+        "mellow_stop_strings_apply": (ci, [vp, P(StopStrings), vp, ci, vp, ci, vp, ci, vp, vp, vp, vp]),
         "mellow_generate_guidance": (ci, [vp, cf]),
         "mellow_guidance_apply": (ci, [vp, cf, vp, ci, vp, vp, vp]),
         "mellow_generate_top_logprobs": (ci, [vp, ci, vp, vp]),
@@ -204,7 +212,7 @@ EXPORTED_SYMBOLS = (
     "mellow_engine_num_required", "mellow_engine_required_key", "mellow_generate", "mellow_generate_sampled", "mellow_sample_logits", "mellow_logmel",
     "mellow_encode", "mellow_prefix", "mellow_lm_prefill", "mellow_lm_decode_step", "mellow_argmax", "mellow_embed_tokens", "mellow_lm_forward_logits",
     "mellow_lm_score", "mellow_score", "mellow_generate_scored", "mellow_debug_dec_head_lse", "mellow_generate_n", "mellow_generate_q",
-    "mellow_generate_beam", "mellow_beam_select", "mellow_generate_rules", "mellow_logit_rules_apply", "mellow_generate_constraint", "mellow_constraint_apply", "mellow_generate_guidance", "mellow_guidance_apply", "mellow_generate_top_logprobs", "mellow_top_logprobs_apply", "mellow_generate_filters", "mellow_sample_logits_filtered", "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
+    "mellow_generate_beam", "mellow_beam_select", "mellow_generate_rules", "mellow_logit_rules_apply", "mellow_generate_constraint", "mellow_constraint_apply", "mellow_set_vocab_bytes", "mellow_generate_stop_strings", "mellow_stop_strings_apply", "mellow_generate_guidance", "mellow_guidance_apply", "mellow_generate_top_logprobs", "mellow_top_logprobs_apply", "mellow_generate_filters", "mellow_sample_logits_filtered", "mellow_debug_enable_taps", "mellow_debug_tap", "mellow_prof_enable", "mellow_prof_reset",
     "mellow_prof_num_families", "mellow_prof_family_name", "mellow_prof_get", "mellow_last_phase_ms", "mellow_last_steps_enqueued", "mellow_last_row_repacks", "mellow_stft_is_fft", "mellow_prefill_parts", "mellow_abi_minor",
     "mellow_resample", "mellow_engine_set_precision", "mellow_engine_set_option", "mellow_engine_describe", "mellow_debug_gemm_fp8", "mellow_debug_gemm_f32", "mellow_debug_gemm_epi", "mellow_debug_norm", "mellow_debug_dec_attn", "mellow_debug_dec_gemv", "mellow_debug_dec_tail", "mellow_debug_prefill_attn", "mellow_debug_window_attn", "mellow_debug_dec_head", "mellow_set_graph", "mellow_host_window_map", "mellow_host_pack_weight", "mellow_host_rope_tables",
 )
@@ -303,6 +311,56 @@ def check_sample_filters(top_k=0, min_p=0.0):
     return k, p
 
 
+STOP_MAX_STRINGS, STOP_MAX_STR_LEN, STOP_MAX_TOKEN_BYTES = 16, 64, 256      # what mellow_generate_stop_strings / mellow_set_vocab_bytes take
+
+
+def check_stop_strings(stop_strings) -> List[bytes]:
+    """The value rules of stop_strings (the C entry repeats them): a list of 1 to 16 byte strings of 1 to 64 bytes each.  -> the
+    strings as bytes objects."""
+    if isinstance(stop_strings, (str, bytes, bytearray)) or stop_strings is None:
+        raise ValueError("stop_strings is a list of byte strings")
+    out = []
+    for b in stop_strings:
+        if isinstance(b, str) or not isinstance(b, (bytes, bytearray, memoryview, np.ndarray)):
+            raise ValueError(f"a stop string is a bytes object (encode text as UTF-8), got {type(b).__name__}")
+        out.append(bytes(b))
+    if not 1 <= len(out) <= STOP_MAX_STRINGS:
+        raise ValueError(f"stop_strings holds {len(out)} strings: a call takes 1 to {STOP_MAX_STRINGS}")
+    for j, b in enumerate(out):
+        if not 1 <= len(b) <= STOP_MAX_STR_LEN:
+            raise ValueError(f"stop string {j} has {len(b)} bytes: a string has 1 to {STOP_MAX_STR_LEN}")
+    return out
+
+
+def check_vocab_bytes(offsets, data, vocab: int):
+    """The value rules of a vocabulary byte table (the C entry repeats them) -> (offsets int32 [vocab + 1], data uint8)."""
+    off = np.ascontiguousarray(np.asarray(offsets), dtype=np.int64).reshape(-1)
+    dat = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else np.asarray(data, dtype=np.uint8)).reshape(-1)
+    if off.shape[0] != int(vocab) + 1:
+        raise ValueError(f"vocabulary bytes: {off.shape[0]} offsets, the table has vocab + 1 = {int(vocab) + 1}")
+    if off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != dat.shape[0]:
+        raise ValueError("vocabulary bytes: the offsets start at 0, never decrease and end at the number of bytes")
+    ln = np.diff(off)
+    if ln.size and int(ln.max()) > STOP_MAX_TOKEN_BYTES:
+        t = int(ln.argmax())
+        raise ValueError(f"vocabulary bytes: token {t} has {int(ln[t])} bytes, a token has at most {STOP_MAX_TOKEN_BYTES}")
+    return off.astype(np.int32), dat
+
+
+class _CallStopStrings:
+    """The stop strings of one generate() call as the arrays of mellow_stop_strings_t (it keeps them alive while the struct points
+    at them)."""
+    __slots__ = ("strings", "off", "data", "struct")
+
+    def __init__(self, stop_strings):
+        self.strings = check_stop_strings(stop_strings)
+        self.off = np.zeros(len(self.strings) + 1, dtype=np.int32)
+        self.off[1:] = np.cumsum([len(b) for b in self.strings])
+        self.data = np.frombuffer(b"".join(self.strings), dtype=np.uint8).copy()
+        self.struct = StopStrings(size=C.sizeof(StopStrings), n_strings=len(self.strings), str_off=self.off.ctypes.data,
+                                  str_bytes=self.data.ctypes.data)
+
+
 BEAM_MAX_K = 8                 # beams per example mellow_generate_beam takes
 BEAM_STAGE_ROWS = 65536        # B * k * max_len its K/V staging takes (1.5 GB per tensor)
 
@@ -379,12 +437,12 @@ def has_question_axis(input_ids) -> bool:
 class _CallOptions:
     """What one generate() call arms before EVERY C call it makes (an armed record serves the next mellow_generate* call only): the
     rules struct or None (it keeps its bias vector alive), the guidance scale or None, the k of top_logprobs, the sampler's filters
-    struct (top_k / min_p of the draw) or None, the constraint (_CallConstraint) or None.  Built once per call and handed to the route
-    that runs it; nothing of a call is kept on the engine."""
-    __slots__ = ("rules", "guide", "top_k", "filters", "constraint")
+    struct (top_k / min_p of the draw) or None, the constraint (_CallConstraint) or None, the stop strings (_CallStopStrings) or None.
+    Built once per call and handed to the route that runs it; nothing of a call is kept on the engine."""
+    __slots__ = ("rules", "guide", "top_k", "filters", "constraint", "stop")
 
-    def __init__(self, rules, guide, top_k, filters=None, constraint=None):
-        self.rules, self.guide, self.top_k, self.filters, self.constraint = rules, guide, top_k, filters, constraint
+    def __init__(self, rules, guide, top_k, filters=None, constraint=None, stop=None):
+        self.rules, self.guide, self.top_k, self.filters, self.constraint, self.stop = rules, guide, top_k, filters, constraint, stop
 
     def expand_constraint(self, examples: int, per_example: int):
         """the route knows its rows: `per_example` consecutive answer rows of every example carry the example's root"""
@@ -396,6 +454,8 @@ class _CallOptions:
         rows [row0, row0 + rows) of the generate() call are the rows of that C call (the constraint arms their roots)"""
         if self.constraint is not None:
             engine._chk(engine.lib.mellow_generate_constraint(engine.h, C.byref(self.constraint.struct(row0, rows))))
+        if self.stop is not None:
+            engine._chk(engine.lib.mellow_generate_stop_strings(engine.h, C.byref(self.stop.struct)))
         if self.rules is not None:
             engine._chk(engine.lib.mellow_generate_rules(engine.h, C.byref(self.rules)))
         if self.guide is not None:
@@ -604,7 +664,7 @@ class Engine(DebugTaps):
                  num_beams: Optional[int] = None, length_penalty: float = 1.0, repetition_penalty: float = 1.0,
                  no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, logit_bias=None, _arm_neutral_rules: bool = False,
                  guidance_scale: float = 1.0, negative=None, keep_negative_rows: bool = False, top_logprobs: int = 0,
-                 top_k: int = 0, min_p: float = 0.0, constraint=None, constraint_then_free: bool = False):
+                 top_k: int = 0, min_p: float = 0.0, constraint=None, constraint_then_free: bool = False, stop_strings=None):
         """-> (tokens int32 [B, steps] on host, lengths [B], steps, first_token_ms)
         num_return_sequences = n > 1 (needs do_sample=True): n sampled answers per example from one encode and one prefill per
         example (mellow_generate_n).  Every array has B * n rows, row b * n + j = answer j of example b, and holds what this call
@@ -664,7 +724,17 @@ class Engine(DebugTaps):
         pair).  constraint_then_free=True: the set constrains only the start of the answer, which continues freely once a phrase is
         complete (a one-phrase set is a forced prefix).  ValueError for an empty set, an empty phrase, an id outside the vocabulary
         or a list of another length than the examples.  None (default): nothing is armed and the call is the one without the
-        keywords."""
+        keywords.
+        stop_strings = a list of 1 to 16 byte strings of 1 to 64 bytes: an answer ends once its text -- the concatenated bytes of
+        its generated tokens, from the table of set_vocab_bytes -- contains one of them (include/mellow_hip.h,
+        mellow_generate_stop_strings).  The match runs on the device inside the decode step, after the guidance, the repetition
+        controls and the constraint and before the top log-probs and whatever chooses the token: the step after the token that
+        completed a match, the row's only choice is the stop id (recorded log-prob exactly 0.0; it wins over min_new_tokens and over
+        a constraint), so the row ends through the usual stop rule and a log-prob sum runs over the answer up to the end of the
+        matching token.  Works on every route (sampling, num_return_sequences, questions, beams, guidance).  ValueError for an
+        empty list, more than 16 strings or a string of 0 or more than 64 bytes; EngineError without set_vocab_bytes, or when the
+        call knows no stop token (num_beams with ignore_stop).  None (default): nothing is armed and the call is the one without
+        the keyword."""
         import time
         t_in = time.perf_counter()
         nseq = int(num_return_sequences)
@@ -700,8 +770,12 @@ class Engine(DebugTaps):
         if constraint is not None:
             con = _CallConstraint(constraint, constraint_then_free, self.lm.vocab_size)
             self._need("mellow_generate_constraint")
+        stop = None
+        if stop_strings is not None:
+            stop = _CallStopStrings(stop_strings)
+            self._need("mellow_generate_stop_strings")
         opts = _CallOptions(self._make_rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, logit_bias, _arm_neutral_rules, int(max_len)),
-                            gscale if gscale != 1.0 else None, topk, filters, con)
+                            gscale if gscale != 1.0 else None, topk, filters, con, stop)
         if num_beams is not None:
             if do_sample:
                 raise ValueError("num_beams and do_sample=True do not combine: beam search is deterministic")
@@ -855,6 +929,45 @@ class Engine(DebugTaps):
         self._chk(self.lib.mellow_constraint_apply(self.h, C.byref(con.struct(0, B)), _ptr(lg), B, _ptr(h) if ld else None, ld, _ptr(ln),
                                                    int(stop_id), _ptr(cv), _ptr(cx), None if cs is None else _ptr(cs), _ptr(st)))
         out = {"logits": lg.cpu().numpy(), "state": st.cpu().numpy(), "cand_val": cv.cpu().numpy(), "cand_idx": cx.cpu().numpy()}
+        if cs is not None:
+            out["cand_sum"] = cs.cpu().numpy()
+        return out
+
+    def set_vocab_bytes(self, offsets, data):
+        """The byte string of every token id, for stop_strings (mellow_set_vocab_bytes): offsets int [vocab + 1] from 0, never
+        decreasing; data = the tokens' bytes back to back (bytes or uint8 array), token i = data[offsets[i] : offsets[i + 1]], at
+        most 256 bytes, possibly none.  mellow_amd/stop_strings.py vocab_bytes builds the pair from a tokenizer.  The table
+        belongs to the engine's shared state: set once on the engine or any fork, it serves all of them.  Setting it again replaces
+        it -- never while a call runs on any context."""
+        self._need("mellow_set_vocab_bytes")
+        off, dat = check_vocab_bytes(offsets, data, self.lm.vocab_size)
+        if dat.shape[0] == 0:
+            dat = np.zeros(1, dtype=np.uint8)
+        self._chk(self.lib.mellow_set_vocab_bytes(self.h, C.c_void_p(off.ctypes.data), C.c_void_p(dat.ctypes.data), int(off.shape[0] - 1)))
+
+    def stop_strings_apply(self, logits, history, hist_len, stop_strings, stop_id: int = 0, with_sum: bool = True):
+        """The stop strings on caller data (numeric tap, mellow_stop_strings_apply): logits [B][vocab], history int [B][ld], hist_len
+        int [B], stop_strings = a list of byte strings -> dict of numpy arrays: "logits" [B][vocab] processed, "hit" int32 [B] (1:
+        the text of the row's history holds a stop string), "cand_val" / "cand_idx" / "cand_sum" [B][vocab / 32] the tile partials
+        (with_sum=False: no "cand_sum").  The launch leaves a row that is not hit as it is, partials included: the partials start as
+        those of the unprocessed rows (the neutral rules tap forms them)."""
+        self._need("mellow_stop_strings_apply")
+        lg = self._f32(logits).clone()
+        B, V = lg.shape
+        h = self._i32(history).reshape(B, -1)
+        ln = self._i32(hist_len).reshape(-1)
+        if V != self.lm.vocab_size or ln.shape[0] != B:
+            raise ValueError(f"logits {tuple(lg.shape)}, history {tuple(h.shape)}, hist_len {tuple(ln.shape)} do not describe B rows of the vocabulary")
+        st = _CallStopStrings(stop_strings)
+        ld = int(h.shape[1])
+        before = self.logit_rules_apply(lg, np.zeros((B, 1), dtype=np.int32), np.zeros(B, dtype=np.int32), stop_id=-1, with_sum=with_sum)
+        cv, cx = self._f32(before["cand_val"]).clone(), self._i32(before["cand_idx"]).clone()
+        cs = self._f32(before["cand_sum"]).clone() if with_sum else None
+        hit = torch.empty((B,), dtype=torch.int32, device=self.tdev)
+        self._sync_inputs()
+        self._chk(self.lib.mellow_stop_strings_apply(self.h, C.byref(st.struct), _ptr(lg), B, _ptr(h) if ld else None, ld, _ptr(ln),
+                                                     int(stop_id), _ptr(cv), _ptr(cx), None if cs is None else _ptr(cs), _ptr(hit)))
+        out = {"logits": lg.cpu().numpy(), "hit": hit.cpu().numpy(), "cand_val": cv.cpu().numpy(), "cand_idx": cx.cpu().numpy()}
         if cs is not None:
             out["cand_sum"] = cs.cpu().numpy()
         return out

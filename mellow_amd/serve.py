@@ -75,7 +75,8 @@ class EnginePool:
         top_k / min_p with do_sample=True: the sampler's candidate filters, armed by each context for its own calls, the same for
         every batch; constraint / constraint_then_free: constrained decoding, armed by each context for its own calls -- the list of
         phrase sets is parallel to a batch's examples and goes to every batch as it is, so the batches then hold equally many
-        examples)."""
+        examples; stop_strings: the byte strings an answer ends at, armed by each context for its own calls, the same for every batch
+        -- the vocabulary's byte table is shared engine state: Engine.set_vocab_bytes on any one context serves the pool)."""
         kws = [kw] * len(batches)
         if kw.get("do_sample"):
             off, kws = int(kw.get("row_offset", 0)), []

@@ -48,6 +48,11 @@ distribution, a probability over the phrase set.  One decode serves any number o
 per candidate), and it combines with do_sample, num_return_sequences, question lists, num_beams (the k likeliest labels with their
 probabilities from one decode), guidance and the repetition keywords.  `choices_then="free"` constrains only the start of the answer
 (a one-phrase set is a forced answer prefix).
+Extension (keyword-only): `generate(..., stop_strings=[...])` ends an answer once its text contains one of the strings ("the first
+sentence", "up to the first newline").  The match runs on the device inside the captured decode step, on the bytes of the generated
+tokens (include/mellow_hip.h mellow_generate_stop_strings, mellow_amd/stop_strings.py), so a string that lies across a token
+boundary or inside a token is found, the row stops one step after the token that completed it, and no step after the cut is paid
+for or counted in `logprob`.  The returned text is cut at the string (`include_stop_str_in_output=True` keeps it).
 Deviations: `tqdm` progress output is not produced; the B>1/steps==1 mis-shape and B==1/steps==1 crash of
 reference wrapper.py:251-253 are not reproduced (one string per example is always returned).
 """
@@ -351,7 +356,8 @@ class MellowWrapper:
                  num_return_sequences: int = 1, num_beams: int = 1, length_penalty: float = 1.0, repetition_penalty: float = 1.0,
                  no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, suppress_tokens: Optional[Sequence[int]] = None,
                  logit_bias: Optional[dict] = None, guidance_scale: float = 1.0, negative_examples=None, top_logprobs: int = 0,
-                 top_k: int = 0, min_p: float = 0.0, choices=None, choices_then: str = "stop"):
+                 top_k: int = 0, min_p: float = 0.0, choices=None, choices_then: str = "stop", stop_strings=None,
+                 include_stop_str_in_output: bool = False):
         r"""Produces text response for the given audio files and text prompts
         examples: (list<list>) each example is [audio path 1, audio path 2, text prompt]; the text prompt may be a list or tuple of
                      prompts, several questions about the one pair of clips (module docstring).  If any example has a list, the
@@ -433,6 +439,23 @@ class MellowWrapper:
                      without the keyword.
         choices_then: "stop" (default): the answer ends after its phrase.  "free": the set constrains only the start of the answer,
                      which then continues freely up to max_len; a one-phrase set is a forced answer prefix ("The difference is").
+        stop_strings: a string or a list of 1 to 16 strings of 1 to 64 bytes each (as UTF-8): an answer ends once its text contains
+                     one of them (`stop` of OpenAI and vLLM, `stop_strings` of Hugging Face).  The match runs on the device inside
+                     the decode step, on the bytes of the generated tokens: a string across a token boundary or inside a token is
+                     found.  The step after the token that completed a match the row's only choice is the stop token (log-prob
+                     exactly 0.0), whatever chooses it, so the row ends as at any stop token; this wins over min_new_tokens (as in
+                     Hugging Face) and over `choices`.  The table of the vocabulary's bytes is built from the tokenizer on first use
+                     (mellow_amd/stop_strings.py vocab_bytes), kept on the wrapper and handed to the engine once.  The text is cut
+                     at the start of the first match -- the occurrence that ends first, on equal end the one that starts first --
+                     after the cut at `<|endoftext|>`.  With return_logprobs=True every dict gains "stop_reason", the matched
+                     string or None, and `logprob` sums over the answer up to the end of the token that completed the match (the
+                     forced stop token adds 0.0).  Works with every other keyword and under data parallelism (the strings are per
+                     call and must be the same on every rank).  ValueError for an empty list or an empty string, more than 16
+                     strings, a string over 64 bytes, or a vocabulary token over 256 bytes.  A tokenizer whose `decode(ids)` is
+                     not the concatenation of its per-token texts (one that cleans up spaces, say) can make the device stop where
+                     the host text shows no match: that text is returned uncut, with "stop_reason" None.  None (default): the
+                     call without the keyword.
+        include_stop_str_in_output: keep the matched string at the end of the text (cut at its end, not its start).
 
         With `data_parallel=True` (or MELLOW_DATA_PARALLEL=1) under an initialised torch.distributed group (one process per
         GPU, every rank calling with the same examples) the examples are sharded contiguously over the ranks, each rank ingests
@@ -456,17 +479,22 @@ class MellowWrapper:
         engine_kw.update(filters_kw)
         choices_kw = self._choices_request(choices, choices_then, len(examples), max_len, k, nseq)
         engine_kw.update(choices_kw)
+        stop_kw, stop_texts = self._stop_request(stop_strings)
+        engine_kw.update(stop_kw)
+        # a call with stop strings is the same call, its texts cut at the first stop string on the way out
+        finish = (lambda res: self._cut_results(res, stop_texts, bool(include_stop_str_in_output))) if stop_kw else (lambda res: res)
         if k > 1:
-            return self._generate_beams(examples, audio_paths1, audio_paths2, text_prompts, max_len, stop_token, audio_resample,
-                                        do_sample, return_logprobs, k, nseq, float(length_penalty), dict(rules_kw, **choices_kw))
+            return finish(self._generate_beams(examples, audio_paths1, audio_paths2, text_prompts, max_len, stop_token, audio_resample,
+                                               do_sample, return_logprobs, k, nseq, float(length_penalty),
+                                               dict(rules_kw, **choices_kw, **stop_kw)))
         if nseq > 1 and not do_sample:
             raise ValueError("num_return_sequences > 1 needs do_sample=True: greedy answers of one example are all the same")
         if nseq > 1024:
             raise ValueError(f"num_return_sequences = {nseq} exceeds the 1024 answer rows one pass of the engine takes")
         rank, world = self._dp()
         if any(isinstance(tp, (list, tuple)) for tp in text_prompts):
-            return self._generate_questions(audio_paths1, audio_paths2, text_prompts, max_len, top_p, temperature, stop_token,
-                                            audio_resample, do_sample, seed, return_logprobs, nseq, engine_kw)
+            return finish(self._generate_questions(audio_paths1, audio_paths2, text_prompts, max_len, top_p, temperature, stop_token,
+                                                   audio_resample, do_sample, seed, return_logprobs, nseq, engine_kw))
         if return_logprobs and world > 1:
             raise NotImplementedError("generate(return_logprobs=True) is not sharded over data-parallel ranks: call it on one rank (or with data_parallel off)")
         n = len(examples)
@@ -492,6 +520,9 @@ class MellowWrapper:
         if choices_kw and world > 1:    # likewise: the sets of ALL examples, before the shard is cut
             from .constraint import constraint_digest
             extra += repr(("choices", constraint_digest(choices_kw["constraint"]), choices_kw["constraint_then_free"])).encode()
+        if stop_kw:       # likewise
+            from .stop_strings import stop_strings_digest
+            extra += repr(("stop_strings", stop_strings_digest(stop_kw["stop_strings"]))).encode()
         lo, hi = 0, n
         if world > 1:
             from .dist import shard_range
@@ -514,9 +545,46 @@ class MellowWrapper:
                        self.preprocess_audio([e[1] for e in negatives], resample=audio_resample),
                        self.preprocess_text([e[2] for e in negatives])["input_ids"])
             engine_kw.update(guidance_scale=gscale, negative=neg)
-        return self._generate_batch(audio1, audio2, ids, entry_length=max_len, top_p=top_p,
-                                    temperature=temperature, stop_token=stop_token, n_total=n, do_sample=do_sample,
-                                    seed=seed, row_offset=lo * nseq, return_logprobs=return_logprobs, nseq=nseq, engine_kw=engine_kw)
+        return finish(self._generate_batch(audio1, audio2, ids, entry_length=max_len, top_p=top_p,
+                                           temperature=temperature, stop_token=stop_token, n_total=n, do_sample=do_sample,
+                                           seed=seed, row_offset=lo * nseq, return_logprobs=return_logprobs, nseq=nseq, engine_kw=engine_kw))
+
+    def _stop_request(self, stop_strings):
+        """The keyword rules of stop_strings -> ({} for None: the call without it, else the keyword for Engine.generate; the strings
+        as text).  The first call with strings builds the vocabulary's byte table and hands it to the engine."""
+        if stop_strings is None:
+            return {}, []
+        texts = [stop_strings] if isinstance(stop_strings, str) else list(stop_strings)
+        if len(texts) == 0:
+            raise ValueError("stop_strings is an empty list: give at least one string (None is off)")
+        for t in texts:
+            if not isinstance(t, str):
+                raise TypeError(f"a stop string must be a string, got {type(t).__name__}")
+            if t == "":
+                raise ValueError("stop_strings holds an empty string: every text contains it")
+        from .engine import check_stop_strings
+        raw = check_stop_strings([t.encode("utf-8") for t in texts])
+        if getattr(self, "_vocab_bytes", None) is None:
+            from .stop_strings import vocab_bytes
+            table = vocab_bytes(self.tokenizer, int(self.model.lm.vocab_size))
+            self.model.set_vocab_bytes(*table)
+            self._vocab_bytes = table
+        return dict(stop_strings=raw), texts
+
+    @staticmethod
+    def _cut_results(res, stop_texts, include):
+        """every text of a generate() result -- strings or the dicts of return_logprobs=True, flat or nested per example -- cut by
+        stop_strings.cut_text; a dict gains "stop_reason", the matched string or None"""
+        from .stop_strings import cut_text
+
+        def one(r):
+            if isinstance(r, list):
+                return [one(x) for x in r]
+            if isinstance(r, dict):
+                text, why = cut_text(r["text"], stop_texts, include)
+                return dict(r, text=text, stop_reason=why)
+            return cut_text(r, stop_texts, include)[0]
+        return one(res)
 
     def _choices_request(self, choices, choices_then, n_examples, max_len, k, nseq):
         """The keyword rules of choices / choices_then -> the keywords for Engine.generate ({} for None: the call without them):
